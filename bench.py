@@ -1,20 +1,24 @@
 #!/usr/bin/env python
 """bench.py -- impressions/s (encode + score) of the xnrs hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic MIND-shaped impressions whose
 token tensors are ALREADY RESIDENT in HBM: encode H history + C candidate news per impression with
 the NRMS news encoder, one user vector, C dot-product scores (ParentRec._forward,
 xnrs/models/components/parent.py:31-34), eval mode, no dedup.  Workload = BASELINE.json configs[2]
 at the reference's shipped token shape (config/mind_small_NRMS.yml): B=512, H=50, C=5, S=50, D=768,
-16 heads, E=256.  configs[1] (news encoder only, 1024 news) is reported under "extra".
+16 heads, E=256.  configs[1] (news encoder only, 1024 news) is reported under "extra" (--full).
 
 N>1: one process per GPU (launched by torch.distributed.run), impressions sharded by user, no
 data-path collective (weak scaling: every rank owns a full B=512 batch); the barrier/MAX reduction
 around the timed region is the only communication.
 
-The JSON line also carries
+A plain run sets up, runs W warm-up and K timed steps, writes the scores of the last timed step under
+--dump-outputs DIR (the inputs are seeded: the same arguments give the same inputs), and prints one JSON
+line (value, ms_per_step = milliseconds per timed step, dtype, config, whole_path).  Everything else is
+measured with --full only (--no-cpu-baseline / --no-extra drop parts of it); with --full the JSON line
+also carries
   roofline     : the dominant kernel (the fused Q/K/V projection, an fp32-MFMA GEMM) -- algorithmic
                  FLOPs per launch / its average launch duration, measured with HIP events inside
                  the timed region (xnrs_profile_* in include/xnrs_hip.h), against the 157.3 TFLOP/s
@@ -964,16 +968,78 @@ def train_scaling(args, device, rank, world, dist_on):
             "loss_finite": bool(torch.isfinite(fn()).item())}
 
 
+def qkv_roofline(prof, w, gemm_mode):
+    """--full: roofline entry of the dominant kernel (the fused Q/K/V projection) from the launch timer that ran during the
+    timed steps (`prof` = hip.profile_read() of stage 0)."""
+    mode_products = GEMM_MODES[gemm_mode][1]
+    q_ms, q_n, q_fl = prof["qkv_gemm"]
+    ach = (q_fl / max(q_n, 1)) / (q_ms / max(q_n, 1) * 1e-3) / 1e12 if q_n else 0.0
+    # `traffic` cannot be measured in this run (PMC counters need rocprofv3 around the process): it is read from the
+    # committed PMC summary of the SAME kernel and launch shape and labelled with where and when that was taken
+    # The counters were taken on ONE launch shape -- a full 65 500-row pass -- so `traffic` sits next to the algorithmic
+    # bytes of THAT launch (`traffic_launch`), not next to the mean over this run's mixed launches; null when the file
+    # does not say which launch it measured.
+    traffic, traffic_source = None, None
+    for tname in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json"):
+        tpath = os.path.join(ROOT, "profiles", tname)
+        if os.path.exists(tpath):
+            tj = json.load(open(tpath))
+            launch = tj.get("qkv_launch") or ({"rows": 65500, "grid_threads": 2359296} if "65 500-row pass" in str(tj.get("kernel")) else None)
+            if launch is None:
+                continue
+            traffic = tj.get("qkv_gemm_hbm_bytes_per_launch")
+            traffic_source = {"file": "profiles/" + tname, "commit": tj.get("commit"), "date": tj.get("date"),
+                              "kernel": tj.get("kernel"), "method": tj.get("method", "rocprofv3 --pmc, FETCH_SIZE x2 + WRITE_SIZE, separate passes"),
+                              "traffic_launch": dict(launch, alg_bytes=tj.get("algorithmic_bytes_per_launch"),
+                                                     note="the counters belong to this launch shape: compare `traffic` with ITS "
+                                                          "alg_bytes; roofline.alg_bytes_per_launch is the mean over this run's launches "
+                                                          "(the last pass of every call is shorter)")}
+            break
+    # modes 1/2 issue `mode_products` bf16 MFMA products per algorithmic fp32 product: achieved = issued
+    # matrix flops against the dense bf16 peak
+    return {"bound": "mfma", "achieved": ach * mode_products,
+            "peak": FP32_MFMA_PEAK_TFLOPS if gemm_mode == 0 else BF16_MFMA_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": ach * mode_products / (FP32_MFMA_PEAK_TFLOPS if gemm_mode == 0 else BF16_MFMA_PEAK_TFLOPS),
+            "traffic": traffic if gemm_mode == 0 else None,
+            "traffic_source": traffic_source if gemm_mode == 0 else None,
+            "alg_bytes_per_launch": (q_fl / max(q_n, 1)) / (6.0 * w["D"] * w["D"]) * (4 * w["D"] + 12 * w["D"]),
+            "kernel": ("gemm_f32_kernel<2,2,...> (fused Q/K/V projection)" if gemm_mode == 0 else
+                       f"gemm_split_kernel<{4 - gemm_mode},...> (fused Q/K/V projection)"),
+            "alg_tflops": ach,
+            "launches_timed": q_n, "avg_launch_ms": q_ms / max(q_n, 1),
+            "alg_flops_per_launch": q_fl / max(q_n, 1)}
+
+
+def dump_outputs(d, arrays, rank=0):
+    """--dump-outputs: `arrays` ({name: tensor}, what a caller of the timed path receives) as d/<name>.npy in float32
+    (d/<name>_rank<r>.npy on rank r > 0), 64 MB at most in all."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes > 64 MB"
+    for k, a in host.items():
+        np.save(os.path.join(d, k + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline of the dominant kernel (launch timer on during the timed "
+                         "steps), the fully-live batch, the gather roofline, the CPU baseline with its parity check and the "
+                         "extras; off (default): set up, warm up, time the steps, write --dump-outputs, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the scores of the last timed step as DIR/scores.npy (float32; "
+                         "rank r > 0: DIR/scores_rank<r>.npy)")
     ap.add_argument("--gemm-mode", type=int, default=0, choices=(0, 1, 2),
                     help="arithmetic of the forward GEMMs for the HEADLINE line: 0 exact fp32 MFMA (default), "
-                         "1 bf16x3 split, 2 bf16x2 split; the default run reports modes 1 and 2 under extra")
+                         "1 bf16x3 split, 2 bf16x2 split; a --full run reports modes 1 and 2 under extra")
     ap.add_argument("--train", choices=("nrms", "standard", "naml"), default=None,
                     help="time the data-parallel GRAD step instead (BASELINE configs[3]: impressions sharded over the "
                          "ranks, global in-batch InfoNCE through a differentiable all-gather, one flat RCCL gradient "
@@ -1046,47 +1112,32 @@ def main():
     model, sd = build_model(w, device)
     hist, cand = make_inputs(w, device, seed=1000 + rank)  # each rank = its own shard of users
 
+    last = {}
+
+    def fn():
+        last["scores"] = step(model, hist, cand)
+        return last["scores"]
+
     with torch.no_grad():
-        fn = lambda: step(model, hist, cand)  # noqa: E731
-        # warm-up outside the profiled region, then profile ONLY the dominant kernel (stage 0) live
+        # warm-up outside the profiled region; with --full, profile ONLY the dominant kernel (stage 0) live
         for _ in range(args.warmup):
             fn()
         torch.cuda.synchronize()
-        hip.profile_enable(1)
+        if args.full:
+            hip.profile_enable(1)
         dt = timed(fn, args.steps, 0, dist_on)
-        prof = hip.profile_read()
-        hip.profile_enable(0)
-        scores = fn()
-        torch.cuda.synchronize()
+        if args.full:
+            prof = hip.profile_read()
+            hip.profile_enable(0)
+        scores = last["scores"]  # what the last timed step computed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": scores}, rank)
 
     n_gpus = world
     ms_per_step = dt / args.steps * 1e3
     value = n_gpus * w["B"] * args.steps / dt
 
     if rank == 0:
-        q_ms, q_n, q_fl = prof["qkv_gemm"]
-        ach = (q_fl / max(q_n, 1)) / (q_ms / max(q_n, 1) * 1e-3) / 1e12 if q_n else 0.0
-        # `traffic` cannot be measured in this run (PMC counters need rocprofv3 around the process): it is read from the
-        # committed PMC summary of the SAME kernel and launch shape and labelled with where and when that was taken
-        # The counters were taken on ONE launch shape -- a full 65 500-row pass -- so `traffic` sits next to the algorithmic
-        # bytes of THAT launch (`traffic_launch`), not next to the mean over this run's mixed launches; null when the file
-        # does not say which launch it measured.
-        traffic, traffic_source = None, None
-        for tname in ("r04_traffic.json", "r03_traffic.json", "r02_traffic.json"):
-            tpath = os.path.join(ROOT, "profiles", tname)
-            if os.path.exists(tpath):
-                tj = json.load(open(tpath))
-                launch = tj.get("qkv_launch") or ({"rows": 65500, "grid_threads": 2359296} if "65 500-row pass" in str(tj.get("kernel")) else None)
-                if launch is None:
-                    continue
-                traffic = tj.get("qkv_gemm_hbm_bytes_per_launch")
-                traffic_source = {"file": "profiles/" + tname, "commit": tj.get("commit"), "date": tj.get("date"),
-                                  "kernel": tj.get("kernel"), "method": tj.get("method", "rocprofv3 --pmc, FETCH_SIZE x2 + WRITE_SIZE, separate passes"),
-                                  "traffic_launch": dict(launch, alg_bytes=tj.get("algorithmic_bytes_per_launch"),
-                                                         note="the counters belong to this launch shape: compare `traffic` with ITS "
-                                                              "alg_bytes; roofline.alg_bytes_per_launch is the mean over this run's launches "
-                                                              "(the last pass of every call is shorter)")}
-                break
         out = {
             "metric": "impressions/sec (encode+score) on MIND-shaped batches",
             "value": value,
@@ -1112,20 +1163,6 @@ def main():
                                            "applied once per news behind the additive pooling instead of once per token (exact "
                                            "algebra, recomputed inside every timed step; extra.per_token_out_projection = the "
                                            "reference's order)" if fold_on() else "the reference's (XNRS_FOLD_OUT=0)")},
-            # modes 1/2 issue `mode_products` bf16 MFMA products per algorithmic fp32 product: achieved = issued
-            # matrix flops against the dense bf16 peak
-            "roofline": {"bound": "mfma", "achieved": ach * mode_products,
-                         "peak": FP32_MFMA_PEAK_TFLOPS if args.gemm_mode == 0 else BF16_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s",
-                         "frac": ach * mode_products / (FP32_MFMA_PEAK_TFLOPS if args.gemm_mode == 0 else BF16_MFMA_PEAK_TFLOPS),
-                         "traffic": traffic if args.gemm_mode == 0 else None,
-                         "traffic_source": traffic_source if args.gemm_mode == 0 else None,
-                         "alg_bytes_per_launch": (q_fl / max(q_n, 1)) / (6.0 * w["D"] * w["D"]) * (4 * w["D"] + 12 * w["D"]),
-                         "kernel": ("gemm_f32_kernel<2,2,...> (fused Q/K/V projection)" if args.gemm_mode == 0 else
-                                    f"gemm_split_kernel<{4 - args.gemm_mode},...> (fused Q/K/V projection)"),
-                         "alg_tflops": ach,
-                         "launches_timed": q_n, "avg_launch_ms": q_ms / max(q_n, 1),
-                         "alg_flops_per_launch": q_fl / max(q_n, 1)},
             # executed FLOPs (out-projection folded behind the pooling unless XNRS_FOLD_OUT=0); `reference_order_tflops` prices
             # the same impressions at the FLOPs of the reference's operation order -- it is NOT a utilisation figure
             "whole_path": {"alg_tflops": impression_flops(w, fold_on()) * value / n_gpus / 1e12,
@@ -1137,7 +1174,9 @@ def main():
                            "alg_gbs": impression_bytes(w) * value / n_gpus / 1e9,
                            "frac_hbm": impression_bytes(w) * value / n_gpus / 1e9 / HBM_PEAK_GBS},
         }
-        if n_gpus == 1:
+        if args.full:
+            out["roofline"] = qkv_roofline(prof, w, args.gemm_mode)
+        if n_gpus == 1 and args.full:
             # the same step on a batch with EVERY history slot live: no all-zero news rows anywhere, so the dominant GEMM
             # multiplies random data throughout (the section-8d batch above has ~45 % all-zero rows, on which the chip
             # holds a higher clock); a few steps, same live hipEvent timing
@@ -1160,7 +1199,7 @@ def main():
                 "note": "same step, every history slot live (no all-zero news rows)"}
             out["roofline_gather"] = gather_roofline(device)
         cpu_sample = None
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             cb, ref = cpu_baseline(w, sd)
             out["cpu_baseline"] = cb
             # parity spot-check of the benchmarked model on the CPU sample (same weights)
@@ -1173,7 +1212,7 @@ def main():
             cpu_sample = (b, ref)
         else:
             out["cpu_baseline"] = None
-        if n_gpus == 1 and not args.no_extra:
+        if n_gpus == 1 and args.full and not args.no_extra:
             with torch.no_grad():
                 out["extra"] = {"news_encoder_only_1024": news_only_extra(device)}
                 hip.profile_enable(hip.PROFILE_ALL)

@@ -186,6 +186,9 @@ def test_fold_cache_is_bitwise_neutral_and_follows_weight_updates(shape):
     enc, _ = build(S, D, h, 64, 4242)
     x, m = synth.token_block(synth.rng_for(4243), 1, 300, S, D, min_len=1, full_pad_prob=0.1)
     x, m = x.to(DEV), m.to(DEV)
+    # start from an empty table: entries of earlier tests' models can fill it to its cap, and the cap clears the whole table
+    # -- between this forward's fc1 entry and its head entry when the fc1 entry is the 65th
+    hip.invalidate_fold_cache()
     with torch.no_grad():
         y_cached, _ = enc((x, m))
         key = (id(enc.att), id(enc.pooler))

@@ -10,7 +10,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -6 $OUT/tests.log
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout -k 10 800 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+timeout -k 10 800 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 python3 - <<PY
 import json
 d=json.load(open('$OUT/bench.json'))

@@ -20,6 +20,6 @@ done
 python3 $R/tools/summarize_prof.py $OUT > $OUT/summary.txt 2>&1
 grep -v "at::native\|rocclr\|^void  " $OUT/summary.txt
 # the same command the bench line comes from, under the kernel tracer
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $OUT/bench_trace.log 2>&1 || { echo "bench trace failed"; tail -5 $OUT/bench_trace.log; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $OUT/bench_trace.log 2>&1 || { echo "bench trace failed"; tail -5 $OUT/bench_trace.log; }
 tail -1 $OUT/bench_trace.log | cut -c1-900
 find $OUT/bench_trace -name "*kernel_stats.csv" | head -1 | xargs -I{} sh -c 'head -12 {}' 

@@ -1,10 +1,10 @@
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+OUT=${1:?usage: tools/gpu_r4_e.sh <output dir>}; mkdir -p "$OUT"
 python -m pytest tests -m gpu -q 2>&1 | tail -n 8
-python bench.py --no-cpu-baseline > gpurun_out/r4_bench2.json 2> gpurun_out/r4_bench2.err; tail -c 300 gpurun_out/r4_bench2.err
+python bench.py --full --no-cpu-baseline > "$OUT/r4_bench2.json" 2> "$OUT/r4_bench2.err"; tail -c 300 "$OUT/r4_bench2.err"
 python3 - <<PY
 import json
-d=json.load(open('gpurun_out/r4_bench2.json'))
+d=json.load(open('$OUT/r4_bench2.json'))
 print('value', round(d['value']), 'ms', round(d['ms_per_step'],2), 'roofline', round(d['roofline']['frac'],3))
 e=d['extra']
 print({k: round(v,3) for k,v in e['stage_ms_per_step'].items() if v})

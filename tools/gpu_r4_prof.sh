@@ -9,12 +9,12 @@ cd $R
 timeout -k 10 600 python -m pytest tests -m gpu -q > $OUT/tests.log 2>&1; echo "tests rc=$?"; tail -n 2 $OUT/tests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 1
 timeout -k 10 300 python3 tools/soak_determinism.py 25 2>&1 | grep -v amdgpu.ids | tee $OUT/soak_determinism.txt
-timeout -k 10 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$?"
 for t in nrms standard naml; do
   timeout -k 10 300 python bench.py --train $t --steps 20 --warmup 5 >> $OUT/bench_train_lines.json 2>> $OUT/bench.err
 done
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 $R/bench.py --no-extra --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_trace.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 $R/bench.py --full --no-extra --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_trace.err
 python3 $R/tools/trace_summary.py $OUT/bench_trace > $OUT/bench_kernel_trace_summary.txt 2>&1
 for m in nrms standard naml; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$m -- python3 $R/tools/prof_train.py 6 $m > $OUT/trace_$m.log 2>&1 || { echo "trace $m failed"; tail -n 3 $OUT/trace_$m.log; }

@@ -37,7 +37,7 @@ buf = io.StringIO()
 with redirect_stdout(buf):
     trace_summary.main(os.path.join(src, "bench_trace"))
 with open(os.path.join(dst, f"{rnd}_bench_kernel_trace_summary.txt"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra   (MI355X)\n"
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra   (MI355X)\n"
             "# per (kernel, grid) durations from the kernel trace; grid = threads.  The Q/K/V projection is gemm_f32_kernel<2,2,...> at grid 2359296\n"
             "# (9216 workgroups = 512 row tiles x 18 column tiles of one 65 500-row pass).\n")
     f.write(buf.getvalue())
