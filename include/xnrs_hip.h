@@ -472,6 +472,51 @@ int32_t xnrs_get_gemm_mode(void);
  * pooling; XNRS_FOLD_TRAIN must not change between a training forward and its backward). */
 int32_t xnrs_reload_knobs(void);
 
+/* ---- BilinScoring / FCScoring (scoring.py:41-102), u:(B,E), c:(B,N,E) -> s:(B,N) --------------------------
+ * Factorised: bilinear v_b = W[0]^T u^_b (one GEMM per call), s = v_b . c^_bn + bias, with u^ / c^ = u / ||u||, c / ||c||
+ * when normalize (no epsilon, scoring.py:58-60) and u / c otherwise; MLP (hidden H, tanh): q_b = W1u u_b + b1 (once per
+ * impression), p_bn = W1c c_bn, s = w2 . tanh(q_b + p_bn) + b2, where W1 = [W1u | W1c] is fc1.weight (H, 2E).
+ * w: nn.Bilinear weight (1,E,E); w1 (H,2E), w2 (1,H); every bias nullable (bias=False).  `saved`
+ * (xnrs_*_scoring_saved_bytes) is written by the forward and read by the backward: bilinear v [| u^], MLP q | p.
+ * Backward: every gradient output nullable, and only what is asked for is computed (an input-gradient pass launches no
+ * weight-gradient product and the other way round); dw1 is written as [dW1u | dW1c] into its (H, 2E) rows.  All sums in
+ * a fixed order (no atomics).  Launches: forward <= 3, backward <= 6.  B == 0 or N == 0: nothing to score (no launch;
+ * a backward writes zero weight gradients).  B > 2^31 - 1 or B*N >= 2^31: XNRS_EUNSUPPORTED. */
+size_t xnrs_bilinear_scoring_saved_bytes(int64_t B, int32_t E, int32_t normalize);
+int32_t xnrs_bilinear_scoring_fwd(const float *u, const float *c, const float *w, const float *bias, float *s, int64_t B,
+                                  int32_t N, int32_t E, int32_t normalize, void *saved, size_t saved_bytes, void *stream);
+size_t xnrs_bilinear_scoring_bwd_workspace_bytes(int64_t B, int32_t E, int32_t normalize);
+int32_t xnrs_bilinear_scoring_bwd(const float *u, const float *c, const float *w, const void *saved, size_t saved_bytes,
+                                  const float *ds, float *du, float *dc, float *dw, float *dbias, int64_t B, int32_t N,
+                                  int32_t E, int32_t normalize, void *ws, size_t ws_bytes, void *stream);
+size_t xnrs_mlp_scoring_saved_bytes(int64_t B, int32_t N, int32_t H);
+int32_t xnrs_mlp_scoring_fwd(const float *u, const float *c, const float *w1, const float *b1, const float *w2,
+                             const float *b2, float *s, int64_t B, int32_t N, int32_t E, int32_t H, void *saved,
+                             size_t saved_bytes, void *stream);
+size_t xnrs_mlp_scoring_bwd_workspace_bytes(int64_t B, int32_t N, int32_t H);
+int32_t xnrs_mlp_scoring_bwd(const float *u, const float *c, const float *w1, const float *w2, const void *saved,
+                             size_t saved_bytes, const float *ds, float *du, float *dc, float *dw1, float *db1, float *dw2,
+                             float *db2, int64_t B, int32_t N, int32_t E, int32_t H, void *ws, size_t ws_bytes,
+                             void *stream);
+/* p:(rows,H) = c:(rows,E) . W1c^T -- the news-side half of fc1 (evaluation: once per epoch over the news table) */
+int32_t xnrs_mlp_scoring_news_proj(const float *c, int64_t rows, int32_t E, const float *w1, int32_t H, float *p,
+                                   void *stream);
+/* Evaluation against news vectors pre-encoded once per epoch (as xnrs_score_csr), u:(n_sess,E):
+ *   xnrs_score_csr_bilinear: r[e] = relu?(v[sess[e]] . vecs[rows[e]] + bias), v = u W[0] (one GEMM into ws)
+ *   xnrs_score_csr_mlp:      r[e] = relu?(w2 . tanh(q[sess[e]] + P[rows[e]]) + b2), q = u W1u^T + b1 (one GEMM into ws),
+ *                            P = xnrs_mlp_scoring_news_proj of the table
+ * ws: xnrs_score_csr_scorer_workspace_bytes(n_sess, E) (bilinear) / (n_sess, H) (MLP).  A normalised bilinear scorer
+ * passes vectors normalised with xnrs_l2_normalize_rows. */
+size_t xnrs_score_csr_scorer_workspace_bytes(int64_t n_sess, int32_t width);
+int32_t xnrs_score_csr_bilinear(const float *vecs, const int32_t *cand_rows, const int32_t *cand_sess, const float *u,
+                                int64_t n_sess, const float *w, const float *bias, float *r, int64_t n_cand, int32_t E,
+                                int32_t relu, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_score_csr_mlp(const float *P, const int32_t *cand_rows, const int32_t *cand_sess, const float *u,
+                           int64_t n_sess, const float *w1, const float *b1, const float *w2, const float *b2, float *r,
+                           int64_t n_cand, int32_t E, int32_t H, int32_t relu, void *ws, size_t ws_bytes, void *stream);
+/* y[r,:] = x[r,:] / ||x[r,:]|| (no epsilon, scoring.py:20-22); y may equal x */
+int32_t xnrs_l2_normalize_rows(const float *x, float *y, int64_t rows, int32_t E, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -733,3 +733,87 @@ class _DotScoring(torch.autograd.Function):
 
 def dot_scoring(u, c, normalize):
     return _DotScoring.apply(u, c, normalize)
+
+
+class _BilinScoring(torch.autograd.Function):
+    """BilinScoring (scoring.py:41-66): backward G_b = sum_n g_bn c^_bn, dW[0] = U^^T G, du^_b = W[0] G_b, dc^_bn = g_bn v_b,
+    dbias = sum g (then through the normalisation when it is on)."""
+
+    @staticmethod
+    def forward(ctx, u, c, w, b, normalize):
+        from . import ops
+        with torch.no_grad():
+            s, saved = ops.bilinear_scoring_forward(u, c, w, b, normalize, keep=True)
+        ctx.save_for_backward(hip.dev_f32(u, "user vector"), hip.dev_f32(c, "candidate vectors"), hip.dev_f32(w, "bilinear weight"),
+                              saved)
+        ctx.normalize = bool(normalize)
+        ctx.has_bias = b is not None
+        ctx.u_shape = tuple(u.shape)
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        u, c, w, saved = ctx.saved_tensors
+        ds = hip.dev_f32(ds, "ds")
+        B, N, E = c.shape
+        wanted = _wanted_inputs(ctx, [True, True, True, ctx.has_bias, False], 0)
+        need = [n and k for n, k in zip(ctx.needs_input_grad, wanted)]
+        du = torch.empty(ctx.u_shape, dtype=torch.float32, device=c.device) if need[0] else None
+        dc = torch.empty_like(c) if need[1] else None
+        dw = torch.empty_like(w) if need[2] else None
+        db = torch.empty((1,), dtype=torch.float32, device=c.device) if (ctx.has_bias and need[3]) else None
+        l = hip.lib()
+        nws = l.xnrs_bilinear_scoring_bwd_workspace_bytes(B, E, int(ctx.normalize))
+        ws = hip.workspace(c.device, nws)
+        hip.check(l.xnrs_bilinear_scoring_bwd(hip.ptr(u), hip.ptr(c), hip.ptr(w), hip.ptr(saved), saved.numel(), hip.ptr(ds),
+                                              hip.ptr(du), hip.ptr(dc), hip.ptr(dw), hip.ptr(db), B, N, E, int(ctx.normalize),
+                                              hip.ptr(ws), nws, hip.stream_ptr(c.device)), "xnrs_bilinear_scoring_bwd")
+        return du, dc, dw, db, None
+
+
+def bilinear_scoring(u, c, w, b, normalize):
+    return _BilinScoring.apply(u, c, w, b, normalize)
+
+
+class _MlpScoring(torch.autograd.Function):
+    """FCScoring with tanh (scoring.py:69-102), factorised: delta_bn = g_bn w2 (1 - t^2), dw2 = sum g t, db2 = sum g,
+    db1 = sum delta, dW1 = [sum_b Delta_b (x) u_b | sum_bn delta_bn (x) c_bn], du_b = W1u^T Delta_b, dc_bn = W1c^T delta_bn
+    (Delta_b = sum_n delta_bn)."""
+
+    @staticmethod
+    def forward(ctx, u, c, w1, b1, w2, b2):
+        from . import ops
+        with torch.no_grad():
+            s, saved = ops.mlp_scoring_forward(u, c, w1, b1, w2, b2, keep=True)
+        ctx.save_for_backward(hip.dev_f32(u, "user vector"), hip.dev_f32(c, "candidate vectors"), hip.dev_f32(w1, "fc1 weight"),
+                              hip.dev_f32(w2, "fc2 weight"), saved)
+        ctx.has_b1, ctx.has_b2 = b1 is not None, b2 is not None
+        ctx.u_shape = tuple(u.shape)
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        u, c, w1, w2, saved = ctx.saved_tensors
+        ds = hip.dev_f32(ds, "ds")
+        B, N, E = c.shape
+        H = w1.shape[0]
+        wanted = _wanted_inputs(ctx, [True, True, True, ctx.has_b1, True, ctx.has_b2], 0)
+        need = [n and k for n, k in zip(ctx.needs_input_grad, wanted)]
+        dev = c.device
+        du = torch.empty(ctx.u_shape, dtype=torch.float32, device=dev) if need[0] else None
+        dc = torch.empty_like(c) if need[1] else None
+        dw1 = torch.empty_like(w1) if need[2] else None
+        db1 = torch.empty((H,), dtype=torch.float32, device=dev) if (ctx.has_b1 and need[3]) else None
+        dw2 = torch.empty_like(w2) if need[4] else None
+        db2 = torch.empty((1,), dtype=torch.float32, device=dev) if (ctx.has_b2 and need[5]) else None
+        l = hip.lib()
+        nws = l.xnrs_mlp_scoring_bwd_workspace_bytes(B, N, H)
+        ws = hip.workspace(dev, nws)
+        hip.check(l.xnrs_mlp_scoring_bwd(hip.ptr(u), hip.ptr(c), hip.ptr(w1), hip.ptr(w2), hip.ptr(saved), saved.numel(), hip.ptr(ds),
+                                         hip.ptr(du), hip.ptr(dc), hip.ptr(dw1), hip.ptr(db1), hip.ptr(dw2), hip.ptr(db2), B, N, E, H,
+                                         hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_mlp_scoring_bwd")
+        return du, dc, dw1, db1, dw2, db2
+
+
+def mlp_scoring(u, c, w1, b1, w2, b2):
+    return _MlpScoring.apply(u, c, w1, b1, w2, b2)

@@ -548,6 +548,33 @@ hipError_t launch_score_csr(const float* vecs, const int32_t* rows, const int32_
 hipError_t launch_rank_metrics(const float* score, const float* target, const int64_t* off, float* out, int64_t B,
                                hipStream_t stream);
 
+// ---------------------------------------------------------------- bilinear / MLP scorers (scorers.hip; scoring.py:41-102)
+// one row-major block of a fixed-order column sum: out[j] = sum_r X[r * ld + j], j < ncol (out nullable: skipped)
+struct ColSumSeg {
+  const float* X;
+  int64_t ld;
+  int64_t rows;
+  int ncol;
+  float* out;
+};
+hipError_t launch_colsum_segments(const ColSumSeg* segs, int n_segs, hipStream_t stream);  // up to 3 non-empty: one launch
+hipError_t launch_l2_normalize_rows(const float* x, float* y, int64_t rows, int E, hipStream_t stream);
+// du = (duh - uh (uh . duh)) / ||u||, per row
+hipError_t launch_l2_normalize_bwd(const float* u, const float* uh, const float* duh, float* du, int64_t rows, int E,
+                                   hipStream_t stream);
+hipError_t launch_bilinear_pair_fwd(const float* v, const float* c, const float* bias, float* s, int64_t B, int N, int E,
+                                    int normalize, hipStream_t stream);
+hipError_t launch_bilinear_pair_bwd(const float* v, const float* c, const float* g, float* dc, float* G, int64_t B, int N, int E,
+                                    int normalize, hipStream_t stream);
+hipError_t launch_mlp_pair_fwd(const float* q, const float* p, const float* w2, const float* b2, float* s, int64_t B, int N, int H,
+                               hipStream_t stream);
+hipError_t launch_mlp_pair_bwd(const float* q, const float* p, const float* w2, const float* g, float* delta, float* Delta,
+                               float* dw2_part, int64_t B, int N, int H, hipStream_t stream);
+hipError_t launch_score_csr_bilinear(const float* vecs, const int32_t* rows, const int32_t* sess, const float* v, const float* bias,
+                                     float* r, int64_t n, int E, int relu, hipStream_t stream);
+hipError_t launch_score_csr_mlp(const float* P, const int32_t* rows, const int32_t* sess, const float* q, const float* w2,
+                                const float* b2, float* r, int64_t n, int H, int relu, hipStream_t stream);
+
 // ---------------------------------------------------------------- in-batch InfoNCE (training.py:433-472)
 // ws: (B*E + 4*B + 1) floats = normalised embeddings | 1/norm | num | den | L_i | 1/(count+1e-8); kept for the backward
 hipError_t launch_infonce_fwd(const float* x, const int64_t* lab, int64_t B, int E, float temperature, float* loss, float* ws,

@@ -101,7 +101,16 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
     news table is encoded in slices (one all-gather of the vectors), every rank scores a contiguous block of the sessions
     (distributed.shard_range) and ONE fp64 all-reduce adds the metric sums -- every rank returns the same dict, equal to the
     single-process result up to the order of that final sum.  (The reference's test loop is one process, batch size 1:
-    training.py:194-243.)"""
+    training.py:194-243.)
+
+    Impressions are scored by the model's own scorer (`model.rec_model`) through its two evaluation hooks: prepare_csr(vecs)
+    once per epoch over the (all-gathered) news table, score_csr(table, rows, sess, u, relu) per batch.  A scorer without
+    them raises NotImplementedError."""
+    scorer = getattr(model, "rec_model", None)
+    prepare, score = getattr(scorer, "prepare_csr", None), getattr(scorer, "score_csr", None)
+    if prepare is None or score is None:
+        raise NotImplementedError(f"evaluate(): the scorer {type(scorer).__name__} has no CSR scoring path (prepare_csr / "
+                                  "score_csr); scoring it with a plain dot product would report another model's metrics")
     rank, world, on = _dist_rank_world(distributed)
     if on:
         from .distributed import shard_range
@@ -110,6 +119,7 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
     else:
         vecs, hm = encode_news_table(model, store)
         s_lo, s_hi = 0, len(behaviors)
+    table = prepare(vecs)  # once per epoch: the scorer's news-side work (identity for the plain dot product)
     batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
     dev = vecs.device
     sums = torch.zeros(len(METRIC_NAMES), dtype=torch.float64, device=dev)
@@ -120,7 +130,7 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
         h = vecs[hist.long()]            # (B, l_hist, E) row gather of pre-encoded vectors (data movement only)
         m = hm[hist.long()]
         u = model.encode_user(h, m)
-        r = score_csr(vecs, rows, csess, u, relu=True)
+        r = score(table, rows, csess, u, relu=True)
         sums += rank_metrics(r, targets, off).double().sum(0)
     mean = sharded_mean(sums, n, on)
     out = {k: float(v) for k, v in zip(METRIC_NAMES, mean.tolist())}

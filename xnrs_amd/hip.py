@@ -38,6 +38,10 @@ SYMBOLS = (
     "xnrs_seq_encoder_fwd_train_rows", "xnrs_seq_encoder_bwd_rows", "xnrs_seq_encoder_saved_qkv_offset",
     "xnrs_fold_head_weights_workspace_bytes", "xnrs_fold_head_weights",
     "xnrs_build_id", "xnrs_row_lists_workspace_bytes", "xnrs_build_row_lists", "xnrs_set_status_word", "xnrs_status_string",
+    "xnrs_bilinear_scoring_saved_bytes", "xnrs_bilinear_scoring_fwd", "xnrs_bilinear_scoring_bwd_workspace_bytes",
+    "xnrs_bilinear_scoring_bwd", "xnrs_mlp_scoring_saved_bytes", "xnrs_mlp_scoring_fwd", "xnrs_mlp_scoring_bwd_workspace_bytes",
+    "xnrs_mlp_scoring_bwd", "xnrs_mlp_scoring_news_proj", "xnrs_score_csr_scorer_workspace_bytes", "xnrs_score_csr_bilinear",
+    "xnrs_score_csr_mlp", "xnrs_l2_normalize_rows",
 )
 POOL_NONE = -1
 PROFILE_STAGES = ("qkv_gemm", "attention_core", "out_gemm", "fc1_tanh_gemm", "pool", "head_gemms", "news_fused",
@@ -225,6 +229,32 @@ def lib():
     l.xnrs_set_status_word.argtypes = [p]
     l.xnrs_status_string.restype = C.c_char_p
     l.xnrs_status_string.argtypes = [i32]
+    l.xnrs_bilinear_scoring_saved_bytes.restype = sz
+    l.xnrs_bilinear_scoring_saved_bytes.argtypes = [i64, i32, i32]
+    l.xnrs_bilinear_scoring_fwd.restype = i32
+    l.xnrs_bilinear_scoring_fwd.argtypes = [p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
+    l.xnrs_bilinear_scoring_bwd_workspace_bytes.restype = sz
+    l.xnrs_bilinear_scoring_bwd_workspace_bytes.argtypes = [i64, i32, i32]
+    l.xnrs_bilinear_scoring_bwd.restype = i32
+    l.xnrs_bilinear_scoring_bwd.argtypes = [p, p, p, p, sz, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
+    l.xnrs_mlp_scoring_saved_bytes.restype = sz
+    l.xnrs_mlp_scoring_saved_bytes.argtypes = [i64, i32, i32]
+    l.xnrs_mlp_scoring_fwd.restype = i32
+    l.xnrs_mlp_scoring_fwd.argtypes = [p, p, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
+    l.xnrs_mlp_scoring_bwd_workspace_bytes.restype = sz
+    l.xnrs_mlp_scoring_bwd_workspace_bytes.argtypes = [i64, i32, i32]
+    l.xnrs_mlp_scoring_bwd.restype = i32
+    l.xnrs_mlp_scoring_bwd.argtypes = [p, p, p, p, p, sz, p, p, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
+    l.xnrs_mlp_scoring_news_proj.restype = i32
+    l.xnrs_mlp_scoring_news_proj.argtypes = [p, i64, i32, p, i32, p, p]
+    l.xnrs_score_csr_scorer_workspace_bytes.restype = sz
+    l.xnrs_score_csr_scorer_workspace_bytes.argtypes = [i64, i32]
+    l.xnrs_score_csr_bilinear.restype = i32
+    l.xnrs_score_csr_bilinear.argtypes = [p, p, p, p, i64, p, p, p, i64, i32, i32, p, sz, p]
+    l.xnrs_score_csr_mlp.restype = i32
+    l.xnrs_score_csr_mlp.argtypes = [p, p, p, p, i64, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
+    l.xnrs_l2_normalize_rows.restype = i32
+    l.xnrs_l2_normalize_rows.argtypes = [p, p, i64, i32, p]
     if l.xnrs_abi_version() != 6:
         raise XnrsHipError("libxnrs_hip.so ABI version mismatch; rebuild it")
     _lib = l

@@ -148,8 +148,9 @@ def install(force: bool = False) -> bool:
     full.__class__ = type("_FullModels", (_Mirror,), {"__getattr__": lambda self, item: full_getattr(item)})
 
     def make_model(cfg):
-        """xnrs/models/make_model.py:15-56 on the HIP path; a model or scorer outside the path (NPA, CAUM, LSTUR, bilinear /
-        fc scoring) is built by the REFERENCE's own make_model on stock torch, exactly as before the install."""
+        """xnrs/models/make_model.py:15-56 on the HIP path (dot, bilin and fc scorers); a model or scorer outside the path
+        (NPA, CAUM, LSTUR, smallNAML, CAUMScoring) is built by the REFERENCE's own make_model on stock torch, exactly as
+        before the install."""
         try:
             return assemblies.make_model(cfg)
         except NotImplementedError:

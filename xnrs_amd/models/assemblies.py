@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .blocks import AdditiveAttention, DotScoring, MaskedMean, MultiHeadAttention, ParentRec, TextEncoder, UserEncoder
+from .blocks import AdditiveAttention, BilinScoring, DotScoring, FCScoring, MaskedMean, MultiHeadAttention, ParentRec, TextEncoder, UserEncoder
 
 CFG_BIAS = "cfg.bias"  # marker: the tower takes bias=cfg.bias (otherwise the constructor default True)
 
@@ -205,18 +205,29 @@ _MODELS = {"standard": StandardRec, "base": BaseRec, "mean": MeanRec, "NRMS": NR
 # reference models / scorers that are NOT on the path BASELINE.json names: they keep
 # running on the reference's own stock-torch classes
 _OUT_OF_SCOPE_MODELS = ("smallNAML", "NPA", "LSTUR", "CAUM")
-_OUT_OF_SCOPE_SCORING = ("bilin", "fc", "CAUMScoring")
+_OUT_OF_SCOPE_SCORING = ("CAUMScoring",)
+
+
+def _scorer(cfg) -> nn.Module:
+    """make_model.py:20-32: emb_dim = cfg.total_emb_dim, bias = cfg.bias, the MLP's hidden size emb_dim // 2."""
+    if cfg.scoring == 'dot':
+        return DotScoring()
+    if cfg.scoring == 'bilin':
+        return BilinScoring(cfg.total_emb_dim, bias=cfg.bias)
+    if cfg.scoring == 'fc':
+        return FCScoring(cfg.total_emb_dim, hidden_dim=cfg.total_emb_dim // 2, bias=cfg.bias)
+    raise ValueError(f'invalid value for cfg.scoring: {cfg.scoring}')
 
 
 def make_model(cfg):
     """xnrs/models/make_model.py:15-56: same cfg keys (scoring, model, ...), same ValueError on unknown names
-    ('nonlin' included: its class does not exist in the reference either, make_model.py:25-26)."""
+    ('nonlin' included: its class does not exist in the reference either, make_model.py:25-26).  The scorer is built
+    first, as the reference does: under the same torch.manual_seed every parameter starts at the reference's value."""
     if cfg.scoring in _OUT_OF_SCOPE_SCORING or cfg.model in _OUT_OF_SCOPE_MODELS:
         what = f"cfg.scoring={cfg.scoring!r}" if cfg.scoring in _OUT_OF_SCOPE_SCORING else f"cfg.model={cfg.model!r}"
-        raise NotImplementedError(f"{what} is outside the MI355X hot path (dot scorer; NRMS / standard / base / mean / "
-                                  "NAML); use the reference's torch implementation for it")
-    if cfg.scoring != 'dot':
-        raise ValueError(f'invalid value for cfg.scoring: {cfg.scoring}')
+        raise NotImplementedError(f"{what} is outside the MI355X hot path (dot / bilin / fc scorers; NRMS / standard / base / "
+                                  "mean / NAML); use the reference's torch implementation for it")
+    scorer = _scorer(cfg)
     if cfg.model not in _MODELS:
         raise ValueError(f'invalid value for cfg.model: {cfg.model}')
-    return _MODELS[cfg.model](cfg, DotScoring())
+    return _MODELS[cfg.model](cfg, scorer)

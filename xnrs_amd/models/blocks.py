@@ -178,6 +178,9 @@ class UserEncoder(_Tower):
         return ops.user_encoder(self.dropout(x), m, self, return_weights)
 
 
+# Scorers.  Besides forward, each one answers the evaluation epoch's two questions (xnrs_amd.evaluation.evaluate): what to do
+# ONCE per epoch with the table of pre-encoded news vectors (prepare_csr), and how to score impressions given as CSR
+# candidate lists against that table (score_csr(table, rows, sess, u, relu)).
 class DotScoring(nn.Module):
     """Reference: xnrs/models/components/scoring.py:6-23.  u:(B,1,D), c:(B,N,D) -> (B,N,1)."""
 
@@ -187,6 +190,64 @@ class DotScoring(nn.Module):
 
     def forward(self, u: torch.Tensor, c: torch.Tensor):
         return ops.dot_scoring(u, c, self.normalize)
+
+    def prepare_csr(self, vecs: torch.Tensor) -> torch.Tensor:
+        return ops.l2_normalize_rows(vecs) if self.normalize else vecs
+
+    def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
+        from ..evaluation import score_csr
+        return score_csr(table, rows, sess, ops.l2_normalize_rows(u) if self.normalize else u, relu=relu)
+
+
+class BilinScoring(nn.Module):
+    """Reference: scoring.py:41-66.  nn.Bilinear(E, E, 1, bias) registered as `bilin`; u:(B,1,E), c:(B,N,E) -> (B,N,1) =
+    u^ W[0] c^ + bias (u^, c^ L2-normalised when `normalize`).  Factorised: v_b = W[0]^T u^_b once per impression, then one
+    dot product per pair (xnrs_bilinear_scoring_fwd)."""
+
+    def __init__(self, emb_dim: int, normalize: bool = False, bias: bool = True):
+        super().__init__()
+        self.bilin = nn.Bilinear(in1_features=emb_dim, in2_features=emb_dim, out_features=1, bias=bias)
+        self.normalize = normalize
+
+    def forward(self, u: torch.Tensor, c: torch.Tensor):
+        return ops.bilinear_scoring(u, c, self)
+
+    def prepare_csr(self, vecs: torch.Tensor) -> torch.Tensor:
+        return ops.l2_normalize_rows(vecs) if self.normalize else vecs
+
+    def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
+        u = ops.l2_normalize_rows(u) if self.normalize else u
+        return ops.score_csr_bilinear(table, rows, sess, u, self.bilin.weight, self.bilin.bias, relu=relu)
+
+
+def _is_tanh(activation) -> bool:
+    import torch.nn.functional as F
+    return activation is torch.tanh or activation is F.tanh or isinstance(activation, nn.Tanh)
+
+
+class FCScoring(nn.Module):
+    """Reference: scoring.py:69-102.  fc1 = Linear(2E, H, bias), fc2 = Linear(H, 1, bias) over [u repeated N times, c]:
+    s = fc2(tanh(fc1([u, c]))).  Factorised with W1 = [W1u | W1c]: q_b = W1u u_b + b1 once per impression, p_bn = W1c c_bn,
+    s = w2 . tanh(q_b + p_bn) + b2 (xnrs_mlp_scoring_fwd).  The HIP path implements tanh only (torch.tanh, F.tanh, nn.Tanh());
+    any other activation raises NotImplementedError here."""
+
+    def __init__(self, emb_dim: int, hidden_dim: int, activation=torch.tanh, bias: bool = True):
+        super().__init__()
+        if not _is_tanh(activation):
+            raise NotImplementedError(f"FCScoring activation {activation!r}: the HIP scorer implements tanh only "
+                                      "(torch.tanh, torch.nn.functional.tanh, nn.Tanh())")
+        self.fc1 = nn.Linear(in_features=2 * emb_dim, out_features=hidden_dim, bias=bias)
+        self.fc2 = nn.Linear(in_features=hidden_dim, out_features=1, bias=bias)
+        self.activation = activation
+
+    def forward(self, u: torch.Tensor, c: torch.Tensor):
+        return ops.mlp_scoring(u, c, self)
+
+    def prepare_csr(self, vecs: torch.Tensor) -> torch.Tensor:
+        return ops.mlp_news_proj(vecs, self.fc1.weight)  # P = vecs W1c^T: the news-side projection, once per epoch
+
+    def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
+        return ops.score_csr_mlp(table, rows, sess, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, relu=relu)
 
 
 # ------------------------------------------------------------------------------------------- bi-encoder shell

@@ -1,2 +1,2 @@
 """Import-path mirror of xnrs.models.components.scoring (implementation: xnrs_amd/models/blocks.py)."""
-from ..blocks import DotScoring  # noqa: F401
+from ..blocks import BilinScoring, DotScoring, FCScoring  # noqa: F401

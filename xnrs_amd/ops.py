@@ -328,6 +328,148 @@ def dot_scoring_forward(u: torch.Tensor, c: torch.Tensor, normalize: bool = Fals
     return r
 
 
+def _scorer_inputs(u: torch.Tensor, c: torch.Tensor):
+    u = hip.dev_f32(u, "user vector")
+    c = hip.dev_f32(c, "candidate vectors")
+    if c.dim() != 3:
+        raise RuntimeError(f"candidate vectors: expected (B, N, E), got {tuple(c.shape)}")
+    B, N, E = c.shape
+    if u.numel() != B * E or u.shape[-1] != E:
+        raise RuntimeError(f"user vector {tuple(u.shape)} does not match candidates {tuple(c.shape)}: expected ({B}, 1, {E})")
+    return u, c, B, N, E
+
+
+def _saved(device, nbytes: int, keep: bool):
+    """Activations a training forward hands to its backward (their own buffer), or the per-stream scratch (inference)."""
+    if keep:
+        return torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=device)
+    return hip.workspace(device, nbytes)
+
+
+def bilinear_scoring(u: torch.Tensor, c: torch.Tensor, scorer):
+    """BilinScoring.forward (scoring.py:52-66).  u:(B,1,E), c:(B,N,E) -> (B,N,1)."""
+    w, b = scorer.bilin.weight, scorer.bilin.bias
+    if _needs_grad(u, c, w, b):
+        from . import autograd
+        return autograd.bilinear_scoring(u, c, w, b, scorer.normalize)
+    return bilinear_scoring_forward(u, c, w, b, scorer.normalize)[0]
+
+
+def bilinear_scoring_forward(u, c, w, b, normalize: bool, keep: bool = False):
+    """-> (scores (B,N,1), saved buffer for the backward)."""
+    u, c, B, N, E = _scorer_inputs(u, c)
+    w = hip.dev_f32(w, "bilinear weight")
+    if tuple(w.shape) != (1, E, E):
+        raise RuntimeError(f"bilinear weight {tuple(w.shape)} does not match the embedding size {E}: expected (1, {E}, {E})")
+    b = None if b is None else hip.dev_f32(b, "bilinear bias")
+    s = torch.empty((B, N, 1), dtype=torch.float32, device=c.device)
+    l = hip.lib()
+    nbytes = l.xnrs_bilinear_scoring_saved_bytes(B, E, int(normalize))
+    saved = _saved(c.device, nbytes, keep)
+    if B * N > 0:
+        hip.check(l.xnrs_bilinear_scoring_fwd(hip.ptr(u), hip.ptr(c), hip.ptr(w), hip.ptr(b), hip.ptr(s), B, N, E, int(normalize),
+                                              hip.ptr(saved), nbytes, hip.stream_ptr(c.device)), "xnrs_bilinear_scoring_fwd")
+    return s, saved
+
+
+def mlp_scoring(u: torch.Tensor, c: torch.Tensor, scorer):
+    """FCScoring.forward (scoring.py:93-102) with activation tanh.  u:(B,1,E), c:(B,N,E) -> (B,N,1)."""
+    fc1, fc2 = scorer.fc1, scorer.fc2
+    if _needs_grad(u, c, fc1, fc2):
+        from . import autograd
+        return autograd.mlp_scoring(u, c, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+    return mlp_scoring_forward(u, c, fc1.weight, fc1.bias, fc2.weight, fc2.bias)[0]
+
+
+def _mlp_weights(E, w1, b1, w2, b2):
+    w1 = hip.dev_f32(w1, "fc1 weight")
+    H = w1.shape[0]
+    if w1.dim() != 2 or w1.shape[1] != 2 * E:
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied (fc1 weight {tuple(w1.shape)}, input width {2 * E})")
+    w2 = hip.dev_f32(w2, "fc2 weight")
+    if tuple(w2.shape) != (1, H):
+        raise RuntimeError(f"fc2 weight {tuple(w2.shape)} does not match the hidden size {H}: expected (1, {H})")
+    b1 = None if b1 is None else hip.dev_f32(b1, "fc1 bias")
+    b2 = None if b2 is None else hip.dev_f32(b2, "fc2 bias")
+    return w1, b1, w2, b2, H
+
+
+def mlp_scoring_forward(u, c, w1, b1, w2, b2, keep: bool = False):
+    """-> (scores (B,N,1), saved buffer q | p for the backward)."""
+    u, c, B, N, E = _scorer_inputs(u, c)
+    w1, b1, w2, b2, H = _mlp_weights(E, w1, b1, w2, b2)
+    s = torch.empty((B, N, 1), dtype=torch.float32, device=c.device)
+    l = hip.lib()
+    nbytes = l.xnrs_mlp_scoring_saved_bytes(B, N, H)
+    saved = _saved(c.device, nbytes, keep)
+    if B * N > 0:
+        hip.check(l.xnrs_mlp_scoring_fwd(hip.ptr(u), hip.ptr(c), hip.ptr(w1), hip.ptr(b1), hip.ptr(w2), hip.ptr(b2), hip.ptr(s),
+                                         B, N, E, H, hip.ptr(saved), nbytes, hip.stream_ptr(c.device)), "xnrs_mlp_scoring_fwd")
+    return s, saved
+
+
+def l2_normalize_rows(x: torch.Tensor):
+    """x / ||x|| along the last dim (no epsilon, scoring.py:20-22), as a new tensor."""
+    x = hip.dev_f32(x, "vectors")
+    y = torch.empty_like(x)
+    E = x.shape[-1]
+    hip.check(hip.lib().xnrs_l2_normalize_rows(hip.ptr(x), hip.ptr(y), x.numel() // max(E, 1), E, hip.stream_ptr(x.device)),
+              "xnrs_l2_normalize_rows")
+    return y
+
+
+def mlp_news_proj(vecs: torch.Tensor, w1: torch.Tensor):
+    """P = vecs . W1c^T: the candidate half of FCScoring's fc1 over a whole news table (once per evaluation epoch)."""
+    vecs = hip.dev_f32(vecs, "news vectors")
+    E = vecs.shape[-1]
+    w1 = hip.dev_f32(w1, "fc1 weight")
+    if w1.dim() != 2 or w1.shape[1] != 2 * E:
+        raise RuntimeError(f"fc1 weight {tuple(w1.shape)} does not match news vectors of width {E}")
+    H = w1.shape[0]
+    rows = vecs.numel() // E
+    P = torch.empty((rows, H), dtype=torch.float32, device=vecs.device)
+    hip.check(hip.lib().xnrs_mlp_scoring_news_proj(hip.ptr(vecs), rows, E, hip.ptr(w1), H, hip.ptr(P), hip.stream_ptr(vecs.device)),
+              "xnrs_mlp_scoring_news_proj")
+    return P
+
+
+def score_csr_bilinear(vecs, cand_rows, cand_sess, u, w, b, relu: bool = True):
+    """r[e] = relu?(u[sess[e]] W[0] vecs[rows[e]] + bias) against a pre-encoded news table."""
+    vecs = hip.dev_f32(vecs, "news vectors")
+    E = vecs.shape[1]
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    w = hip.dev_f32(w, "bilinear weight")
+    b = None if b is None else hip.dev_f32(b, "bilinear bias")
+    n, n_sess = cand_rows.numel(), u.shape[0]
+    r = torch.empty((n,), dtype=torch.float32, device=vecs.device)
+    l = hip.lib()
+    nbytes = l.xnrs_score_csr_scorer_workspace_bytes(n_sess, E)
+    ws = hip.workspace(vecs.device, nbytes)
+    hip.check(l.xnrs_score_csr_bilinear(hip.ptr(vecs), hip.ptr(cand_rows), hip.ptr(cand_sess), hip.ptr(u), n_sess, hip.ptr(w),
+                                        hip.ptr(b), hip.ptr(r), n, E, int(relu), hip.ptr(ws), nbytes, hip.stream_ptr(vecs.device)),
+              "xnrs_score_csr_bilinear")
+    return r
+
+
+def score_csr_mlp(P, cand_rows, cand_sess, u, w1, b1, w2, b2, relu: bool = True):
+    """r[e] = relu?(w2 . tanh(W1u u[sess[e]] + b1 + P[rows[e]]) + b2), P = mlp_news_proj(table)."""
+    P = hip.dev_f32(P, "projected news table")
+    E = w1.shape[1] // 2
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    w1, b1, w2, b2, H = _mlp_weights(E, w1, b1, w2, b2)
+    if P.shape[-1] != H:
+        raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
+    n, n_sess = cand_rows.numel(), u.shape[0]
+    r = torch.empty((n,), dtype=torch.float32, device=P.device)
+    l = hip.lib()
+    nbytes = l.xnrs_score_csr_scorer_workspace_bytes(n_sess, H)
+    ws = hip.workspace(P.device, nbytes)
+    hip.check(l.xnrs_score_csr_mlp(hip.ptr(P), hip.ptr(cand_rows), hip.ptr(cand_sess), hip.ptr(u), n_sess, hip.ptr(w1), hip.ptr(b1),
+                                   hip.ptr(w2), hip.ptr(b2), hip.ptr(r), n, E, H, int(relu), hip.ptr(ws), nbytes,
+                                   hip.stream_ptr(P.device)), "xnrs_score_csr_mlp")
+    return r
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
