@@ -33,11 +33,80 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(l, s), f"libxnrs_hip.so does not export {s}"
 
 
+def header_prototypes():
+    """{name: (return type, parameter count)} by a plain split of the header text, independent of hip.parse_header."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xnrs_hip.h")).read(), flags=re.S)
+    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+    return {name: (" ".join(ret.split()), 0 if args.strip() == "void" else args.count(",") + 1)
+            for ret, name, args in re.findall(r"([A-Za-z_][\w\s*]*?)\b(xnrs_\w+)\s*\(([^)]*)\)\s*;", text)}
+
+
+def test_every_prototype_is_bound_with_its_arity_and_return_type():
+    protos = header_prototypes()
+    assert sorted(protos) == header_symbols()
+    rets = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+    l = hip.lib()
+    for name, (ret, n_args) in protos.items():
+        f = getattr(l, name)
+        assert f.argtypes is not None and len(f.argtypes) == n_args, name
+        assert f.restype is rets[ret], (name, ret, f.restype)
+
+
+def test_struct_layout_matches_the_c_compiler(tmp_path):
+    """sizeof and every field offset of every header struct, as gcc lays them out, against the ctypes classes."""
+    import subprocess
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xnrs_hip.h")).read(), flags=re.S)
+    assert sorted(hip.STRUCTS) == sorted(re.findall(r"\}\s*(xnrs_\w+)\s*;", text))
+    lines = []
+    for cname, S in hip.STRUCTS.items():
+        lines.append(f'  printf("{cname} sizeof %zu\\n", sizeof({cname}));')
+        lines += [f'  printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));' for f, _ in S._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xnrs_hip.h"\nint main(void) {\n' + "\n".join(lines)
+                   + "\n  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    c = {(s, f): int(n) for s, f, n in (line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True,
+                                                                               check=True).stdout.splitlines())}
+    for cname, S in hip.STRUCTS.items():
+        assert ctypes.sizeof(S) == c[cname, "sizeof"], cname
+        for f, _ in S._fields_:
+            assert getattr(S, f).offset == c[cname, f], (cname, f)
+
+
+def test_header_parser_on_a_snippet():
+    """Comments, a #define right before a prototype, multi-declarator struct fields, (void), void and const char * returns."""
+    consts, structs, protos = hip.parse_header(
+        "#define XNRS_X (-3) /* note */\ntypedef struct {\n  const float *a, *b; /* c */\n  int64_t n;\n} xnrs_pair_args;\n"
+        "void xnrs_g(void);\n#define XNRS_Y 1\nconst char *xnrs_h(const xnrs_pair_args *p, double *d, uint64_t s, float f);\n")
+    assert consts == {"X": -3, "Y": 1}
+    S = structs["xnrs_pair_args"]
+    assert S.__name__ == "PairArgs" and S._fields_ == [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("n", ctypes.c_int64)]
+    assert protos["xnrs_g"] == (None, [])
+    ret, args = protos["xnrs_h"]
+    assert ret is ctypes.c_char_p and args[0]._type_ is S and args[1:] == [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_float]
+    assert len(hip.PROFILE_STAGES) == hip.parse_header(open(hip.HEADER_PATH).read())[0]["PROFILE_STAGES"]
+
+
+@pytest.mark.parametrize("snippet", [
+    "int32_t xnrs_f(long long n);",
+    "long long xnrs_f(void);",
+    "int32_t xnrs_f(const xnrs_unknown_params *p);",
+    "typedef struct {\n  long long n;\n} xnrs_s;",
+    "typedef int32_t xnrs_handle;",
+])
+def test_header_parser_refuses_types_it_cannot_map(snippet):
+    with pytest.raises(hip.XnrsHipError):
+        hip.parse_header(snippet)
+
+
 def test_abi_version_and_error_strings():
     l = hip.lib()
     import re
     want = int(re.search(r"#define XNRS_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "xnrs_hip.h")).read()).group(1))
-    assert l.xnrs_abi_version() == want == 6
+    assert l.xnrs_abi_version() == want == hip.ABI_VERSION == 6
     assert b"divisible" in l.xnrs_error_string(-2)
     assert l.xnrs_error_string(0) == b"ok"
 

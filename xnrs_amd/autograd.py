@@ -8,8 +8,6 @@ through HIP kernels; torch only routes gradients between the Functions.
 from __future__ import annotations
 
 import os
-
-import ctypes as C
 from typing import List, Optional
 
 import torch
@@ -73,10 +71,6 @@ def _param_structs(cfg: _Cfg, params: List[Optional[torch.Tensor]]):
         keep += ts
         i += 4
     return ap, pp, hp, keep
-
-
-def _ref(s):
-    return None if s is None else C.byref(s)
 
 
 #: forward and backward over the unmasked token rows only (exact; include/xnrs_hip.h: xnrs_seq_encoder_fwd_train_live /
@@ -285,7 +279,7 @@ def _train_fold(l, cfg, params, ap, pp, dev):
     b1f = torch.empty((cfg.A,), dtype=torch.float32, device=dev)
     nws = l.xnrs_fold_weights_workspace_bytes(cfg.D, cfg.A)
     ws = hip.workspace(dev, nws)
-    hip.check(l.xnrs_fold_weights(C.byref(ap), C.byref(pp), cfg.D, hip.ptr(w1f), hip.ptr(b1f), hip.ptr(ws), nws, hip.stream_ptr(dev)),
+    hip.check(l.xnrs_fold_weights(hip.ref(ap), hip.ref(pp), cfg.D, hip.ptr(w1f), hip.ptr(b1f), hip.ptr(ws), nws, hip.stream_ptr(dev)),
               "xnrs_fold_weights")
     _TRAIN_FOLDS[key] = (w1f, b1f)
     return w1f, b1f
@@ -351,9 +345,9 @@ class _SeqEncode(torch.autograd.Function):
         if live is not None or qkv_shared is not None:
             lists = hip.RowLists(_addr(live), _addr(live_src), n_live, _addr(kv), _addr(kv_src), n_kv, qkv_shared,
                                  _addr(counts), None, hip.DQKV_OWN)
-        hip.check(l.xnrs_seq_encoder_fwd_train_rows(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n, L, D, _ref(ap), cfg.pool_kind,
-                                                    _ref(pp), _ref(hp), hip.ptr(y), hip.ptr(a), hip.ptr(hm), hip.ptr(saved),
-                                                    nsaved, _ref(lists), hip.stream_ptr(dev)),
+        hip.check(l.xnrs_seq_encoder_fwd_train_rows(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n, L, D, hip.ref(ap), cfg.pool_kind,
+                                                    hip.ref(pp), hip.ref(hp), hip.ptr(y), hip.ptr(a), hip.ptr(hm), hip.ptr(saved),
+                                                    nsaved, hip.ref(lists), hip.stream_ptr(dev)),
                   "xnrs_seq_encoder_fwd_train_rows")
         ctx.row_lists = (live, live_src, n_live, kv, kv_src, n_kv, counts)
         ctx.qkv_shared = qkv_shared
@@ -447,9 +441,9 @@ class _SeqEncode(torch.autograd.Function):
         if live is not None or ctx.qkv_shared is not None or mode != hip.DQKV_OWN:
             lists = hip.RowLists(_addr(live), _addr(live_src), n_live, _addr(kv), _addr(kv_src), n_kv, ctx.qkv_shared,
                                  _addr(counts), _addr(image), mode)
-        hip.check(l.xnrs_seq_encoder_bwd_rows(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n, L, D, _ref(ap), cfg.pool_kind, _ref(pp),
-                                              _ref(hp), hip.ptr(saved), ctx.nsaved, hip.ptr(dy), hip.ptr(dx), _ref(ga),
-                                              _ref(gp), _ref(gh), _ref(lists), hip.ptr(ws), nws,
+        hip.check(l.xnrs_seq_encoder_bwd_rows(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n, L, D, hip.ref(ap), cfg.pool_kind, hip.ref(pp),
+                                              hip.ref(hp), hip.ptr(saved), ctx.nsaved, hip.ptr(dy), hip.ptr(dx), hip.ref(ga),
+                                              hip.ref(gp), hip.ref(gh), hip.ref(lists), hip.ptr(ws), nws,
                                               hip.stream_ptr(dev)), "xnrs_seq_encoder_bwd_rows")
         return (None, dx, None, None, *_sum_with_group(ctx, grads))
 

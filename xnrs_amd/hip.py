@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+import weakref
 from typing import Optional
 
 import torch
@@ -16,78 +18,82 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 #: XNRS_HIP_LIB: another build of the same sources (diagnostic builds of tools/, e.g. libxnrs_hip_stamps.so); never a fallback
 LIB_PATH = os.environ.get("XNRS_HIP_LIB") or os.path.join(_HERE, "libxnrs_hip.so")
 
-ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
-POOL_ADDITIVE, POOL_MEAN = 0, 1
-
-#: every symbol include/xnrs_hip.h declares (checked by tests/test_abi.py against the header text)
-SYMBOLS = (
-    "xnrs_abi_version", "xnrs_error_string", "xnrs_linear_fwd", "xnrs_mha_workspace_bytes", "xnrs_mha_fwd",
-    "xnrs_additive_workspace_bytes", "xnrs_additive_attention_fwd", "xnrs_masked_mean_fwd", "xnrs_collapse_mask",
-    "xnrs_text_encoder_workspace_bytes", "xnrs_text_encoder_fwd", "xnrs_user_encoder_workspace_bytes",
-    "xnrs_user_encoder_fwd", "xnrs_dot_scoring_fwd", "xnrs_profile_enable", "xnrs_profile_read",
-    "xnrs_set_gemm_mode", "xnrs_get_gemm_mode", "xnrs_reload_knobs",
-    "xnrs_text_encoder_unpadded_workspace_bytes", "xnrs_text_encoder_fwd_unpadded",
-    "xnrs_seq_encoder_saved_bytes", "xnrs_seq_encoder_fwd_train", "xnrs_seq_encoder_fwd_train_live",
-    "xnrs_seq_encoder_bwd_workspace_bytes",
-    "xnrs_seq_encoder_bwd", "xnrs_seq_encoder_bwd_live", "xnrs_linear_bwd_workspace_bytes", "xnrs_linear_bwd",
-    "xnrs_embedding_linear_bwd_workspace_bytes", "xnrs_embedding_linear_bwd", "xnrs_dot_scoring_bwd", "xnrs_dot_scoring_norm_bwd",
-    "xnrs_assemble_train_batch", "xnrs_assemble_eval_batch", "xnrs_score_csr", "xnrs_rank_metrics", "xnrs_gather_rows",
-    "xnrs_infonce_saved_bytes", "xnrs_infonce_fwd", "xnrs_infonce_bwd", "xnrs_train_fold_enabled",
-    "xnrs_fold_weights_workspace_bytes", "xnrs_fold_weights",
-    "xnrs_text_encoder_compact_workspace_bytes", "xnrs_text_encoder_fwd_compact",
-    "xnrs_seq_encoder_fwd_train_rows", "xnrs_seq_encoder_bwd_rows", "xnrs_seq_encoder_saved_qkv_offset",
-    "xnrs_fold_head_weights_workspace_bytes", "xnrs_fold_head_weights",
-    "xnrs_build_id", "xnrs_row_lists_workspace_bytes", "xnrs_build_row_lists", "xnrs_set_status_word", "xnrs_status_string",
-    "xnrs_bilinear_scoring_saved_bytes", "xnrs_bilinear_scoring_fwd", "xnrs_bilinear_scoring_bwd_workspace_bytes",
-    "xnrs_bilinear_scoring_bwd", "xnrs_mlp_scoring_saved_bytes", "xnrs_mlp_scoring_fwd", "xnrs_mlp_scoring_bwd_workspace_bytes",
-    "xnrs_mlp_scoring_bwd", "xnrs_mlp_scoring_news_proj", "xnrs_score_csr_scorer_workspace_bytes", "xnrs_score_csr_bilinear",
-    "xnrs_score_csr_mlp", "xnrs_l2_normalize_rows",
-)
-POOL_NONE = -1
-PROFILE_STAGES = ("qkv_gemm", "attention_core", "out_gemm", "fc1_tanh_gemm", "pool", "head_gemms", "news_fused",
-                  "bwd_dw_gemms", "bwd_dx_gemms", "bwd_attention_core")
-PROFILE_ALL = (1 << len(PROFILE_STAGES)) - 1
+#: the C ABI this module binds: read once at import, the single source of the prototypes, structs and constants below
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "xnrs_hip.h")
 
 
 class XnrsHipError(RuntimeError):
     pass
 
 
-class MhaParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")] + [
-        ("n_heads", C.c_int32), ("scaled", C.c_int32), ("dropout_p", C.c_float), ("seed", C.c_uint64), ("seed_dev", C.c_void_p)]
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "float": C.c_float}
 
 
-class AdditiveParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2")] + [("hidden", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("w1_folded", "b1_folded")]
+def _ctype(decl: str, structs: dict, what: str, ret: bool = False):
+    """ctypes type of one C type in the header's closed set; anything else is an error, never a guess."""
+    words = decl.replace("*", " * ").split()
+    stars = words.count("*")
+    base = " ".join(w for w in words if w not in ("*", "const"))
+    if stars == 0 and (base in _SCALARS or base == "void" and ret):
+        return _SCALARS.get(base)
+    if stars == 1 and base in structs:
+        return C.POINTER(structs[base])
+    if stars == 1 and base == "char" and ret:
+        return C.c_char_p
+    if stars >= 1 and re.fullmatch(r"[A-Za-z_]\w*( [A-Za-z_]\w*)*", base) and not base.startswith("xnrs_"):
+        return C.c_void_p
+    raise XnrsHipError(f"xnrs_hip.h: no ctypes type for {decl.strip()!r} in {what}")
 
 
-class HeadParams(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("w0", "b0", "w2", "b2")] + [("out_features", C.c_int32), ("activation", C.c_int32)] + [
-        (n, C.c_void_p) for n in ("w0_folded", "b0_rowvec")]
+def parse_header(text: str):
+    """C header text -> ({XNRS_ name without the prefix: int}, {C struct name: Structure}, {function: (restype, argtypes)})."""
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {n: int(v) for n, v in re.findall(r"^\s*#\s*define\s+XNRS_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", code, re.M)}
+    # the declarations as a C compiler sees them: no C++ linkage block, no preprocessor lines
+    code = re.sub(r"^\s*#\s*ifdef\s+__cplusplus\b.*?^\s*#\s*endif\b", "", code, flags=re.M | re.S)
+    code = "\n".join(line for line in code.splitlines() if not line.lstrip().startswith("#"))
+    structs = {}
+
+    def read_struct(m):
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in m[1].split(";"))):  # `const float *wq, *bq;`, `int32_t n;`
+            d = re.fullmatch(r"([\w ]+?) *(\*? *\w+(?: *, *\*? *\w+)*)", decl)
+            if d is None:
+                raise XnrsHipError(f"xnrs_hip.h: cannot read field {decl!r} of {m[2]}")
+            fields += [(v.strip(" *"), C.c_void_p if "*" in v else _ctype(d[1], {}, m[2])) for v in d[2].split(",")]
+        py_name = "".join(w.capitalize() for w in m[2].split("_")[1:])
+        structs[m[2]] = type(py_name, (C.Structure,), {"_fields_": fields, "__doc__": f"{m[2]} (include/xnrs_hip.h)"})
+        return ""
+
+    code = re.sub(r"\btypedef\s+struct\s*\{(.*?)\}\s*(xnrs_\w+)\s*;", read_struct, code, flags=re.S)
+    protos = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in code.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(xnrs_\w+) ?\((.*)\)", stmt)
+        if m is None:
+            raise XnrsHipError(f"xnrs_hip.h: unrecognised declaration {stmt!r}")
+        args = [] if m[3].strip() == "void" else [re.sub(r"(?<=[\s*])\w+$", "", a.strip()) for a in m[3].split(",")]
+        protos[m[2]] = (_ctype(m[1], structs, m[2], ret=True), [_ctype(a, structs, m[2]) for a in args])
+    return consts, structs, protos
 
 
-class RowLists(C.Structure):
-    """xnrs_row_lists: the unmasked token rows and the token rows of the non-empty news (include/xnrs_hip.h)."""
-    _fields_ = [("live_rows", C.c_void_p), ("live_src_rows", C.c_void_p), ("n_live", C.c_int64),
-                ("kv_rows", C.c_void_p), ("kv_src_rows", C.c_void_p), ("n_kv", C.c_int64), ("qkv_shared", C.c_void_p),
-                ("counts_dev", C.c_void_p), ("dqkv_image", C.c_void_p), ("dqkv_mode", C.c_int32)]
+with open(HEADER_PATH) as _f:
+    _CONSTANTS, STRUCTS, PROTOTYPES = parse_header(_f.read())
+#: every function the header declares
+SYMBOLS = tuple(PROTOTYPES)
+ABI_VERSION = _CONSTANTS["ABI_VERSION"]
+#: the header's XNRS_ACT_*, XNRS_POOL_*, XNRS_DQKV_*, XNRS_STATUS_* and XNRS_GEMM_* codes, without the prefix (hip.ACT_RELU, ...)
+globals().update({k: v for k, v in _CONSTANTS.items() if k.startswith(("ACT_", "POOL_", "DQKV_", "STATUS_", "GEMM_"))})
+MhaParams, AdditiveParams, HeadParams, RowLists, MhaGrads, AdditiveGrads, HeadGrads = (STRUCTS["xnrs_" + n] for n in (
+    "mha_params", "additive_params", "head_params", "row_lists", "mha_grads", "additive_grads", "head_grads"))
+PROFILE_STAGES = ("qkv_gemm", "attention_core", "out_gemm", "fc1_tanh_gemm", "pool", "head_gemms", "news_fused",
+                  "bwd_dw_gemms", "bwd_dx_gemms", "bwd_attention_core")
+PROFILE_ALL = (1 << len(PROFILE_STAGES)) - 1
 
 
-DQKV_OWN, DQKV_DEFER, DQKV_MERGE = 0, 1, 2
-
-
-class MhaGrads(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")]
-
-
-class AdditiveGrads(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2")]
-
-
-class HeadGrads(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("w0", "b0", "w2", "b2")]
+def ref(s):
+    """A struct argument: byref(s), or NULL for None."""
+    return None if s is None else C.byref(s)
 
 
 _lib = None
@@ -103,166 +109,15 @@ def lib():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C xnrs_amd/csrc`).  xnrs_amd has no non-HIP fallback.")
     l = C.CDLL(LIB_PATH)
-    p, i32, i64, sz, f = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
-    l.xnrs_abi_version.restype = i32
-    l.xnrs_abi_version.argtypes = []
-    l.xnrs_error_string.restype = C.c_char_p
-    l.xnrs_error_string.argtypes = [i32]
-    l.xnrs_linear_fwd.restype = i32
-    l.xnrs_linear_fwd.argtypes = [p, p, i32, p, p, p, i64, i32, i32, i32, p]
-    l.xnrs_mha_workspace_bytes.restype = sz
-    l.xnrs_mha_workspace_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_mha_fwd.restype = i32
-    l.xnrs_mha_fwd.argtypes = [p, p, C.POINTER(MhaParams), p, i64, i32, i32, p, sz, p]
-    l.xnrs_additive_workspace_bytes.restype = sz
-    l.xnrs_additive_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    l.xnrs_additive_attention_fwd.restype = i32
-    l.xnrs_additive_attention_fwd.argtypes = [p, p, C.POINTER(AdditiveParams), p, p, i64, i32, i32, p, sz, p]
-    l.xnrs_masked_mean_fwd.restype = i32
-    l.xnrs_masked_mean_fwd.argtypes = [p, p, p, i64, i32, i32, p]
-    l.xnrs_collapse_mask.restype = i32
-    l.xnrs_collapse_mask.argtypes = [p, p, i64, i32, p]
-    l.xnrs_text_encoder_workspace_bytes.restype = sz
-    l.xnrs_text_encoder_workspace_bytes.argtypes = [i64, i32, i32, i32, i32, i32, i32, i32, i64]
-    l.xnrs_text_encoder_fwd.restype = i32
-    l.xnrs_text_encoder_fwd.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                        C.POINTER(HeadParams), p, p, i64, p, sz, p]
-    l.xnrs_text_encoder_unpadded_workspace_bytes.restype = sz
-    l.xnrs_text_encoder_unpadded_workspace_bytes.argtypes = [i64, i64, i32, i32, i32, i32, i32, i32]
-    l.xnrs_text_encoder_fwd_unpadded.restype = i32
-    l.xnrs_text_encoder_fwd_unpadded.argtypes = [p, p, i64, i32, i32, p, p, i64, C.POINTER(MhaParams),
-                                                 C.POINTER(AdditiveParams), C.POINTER(HeadParams), p, p, p, sz, p]
-    l.xnrs_user_encoder_workspace_bytes.restype = sz
-    l.xnrs_user_encoder_workspace_bytes.argtypes = [i64, i32, i32, i32, i32, i32, i32]
-    l.xnrs_user_encoder_fwd.restype = i32
-    l.xnrs_user_encoder_fwd.argtypes = [p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                        C.POINTER(HeadParams), p, p, p, sz, p]
-    l.xnrs_dot_scoring_fwd.restype = i32
-    l.xnrs_dot_scoring_fwd.argtypes = [p, p, p, i64, i32, i32, i32, p]
-    l.xnrs_seq_encoder_saved_bytes.restype = sz
-    l.xnrs_seq_encoder_saved_bytes.argtypes = [i64, i32, i32, i32, i32, i32, i32, i32]
-    l.xnrs_seq_encoder_fwd_train.restype = i32
-    l.xnrs_seq_encoder_fwd_train.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                             C.POINTER(HeadParams), p, p, p, p, sz, p]
-    l.xnrs_seq_encoder_fwd_train_live.restype = i32
-    l.xnrs_seq_encoder_fwd_train_live.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                                  C.POINTER(HeadParams), p, p, p, p, sz, p, p, i64, p]
-    l.xnrs_seq_encoder_bwd_workspace_bytes.restype = sz
-    l.xnrs_seq_encoder_bwd_workspace_bytes.argtypes = [i64, i32, i32, i32, i32, i32, i32, i32]
-    l.xnrs_seq_encoder_bwd.restype = i32
-    l.xnrs_seq_encoder_bwd.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                       C.POINTER(HeadParams), p, sz, p, p, C.POINTER(MhaGrads), C.POINTER(AdditiveGrads),
-                                       C.POINTER(HeadGrads), p, sz, p]
-    l.xnrs_seq_encoder_bwd_live.restype = i32
-    l.xnrs_seq_encoder_bwd_live.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                            C.POINTER(HeadParams), p, sz, p, p, C.POINTER(MhaGrads), C.POINTER(AdditiveGrads),
-                                            C.POINTER(HeadGrads), p, p, i64, p, sz, p]
-    l.xnrs_seq_encoder_saved_qkv_offset.restype = sz
-    l.xnrs_seq_encoder_saved_qkv_offset.argtypes = [i64, i32, i32, i32, i32, i32, i32, i32]
-    l.xnrs_seq_encoder_fwd_train_rows.restype = i32
-    l.xnrs_seq_encoder_fwd_train_rows.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                                  C.POINTER(HeadParams), p, p, p, p, sz, C.POINTER(RowLists), p]
-    l.xnrs_seq_encoder_bwd_rows.restype = i32
-    l.xnrs_seq_encoder_bwd_rows.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), i32, C.POINTER(AdditiveParams),
-                                            C.POINTER(HeadParams), p, sz, p, p, C.POINTER(MhaGrads), C.POINTER(AdditiveGrads),
-                                            C.POINTER(HeadGrads), C.POINTER(RowLists), p, sz, p]
-    l.xnrs_linear_bwd_workspace_bytes.restype = sz
-    l.xnrs_linear_bwd_workspace_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_linear_bwd.restype = i32
-    l.xnrs_linear_bwd.argtypes = [p, p, i32, p, p, p, p, p, i64, i32, i32, p, sz, p]
-    l.xnrs_embedding_linear_bwd_workspace_bytes.restype = sz
-    l.xnrs_embedding_linear_bwd_workspace_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_embedding_linear_bwd.restype = i32
-    l.xnrs_embedding_linear_bwd.argtypes = [p, p, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
-    l.xnrs_dot_scoring_bwd.restype = i32
-    l.xnrs_dot_scoring_bwd.argtypes = [p, p, p, p, p, i64, i32, i32, p]
-    l.xnrs_dot_scoring_norm_bwd.restype = i32
-    l.xnrs_dot_scoring_norm_bwd.argtypes = [p, p, p, p, p, i64, i32, i32, p]
-    l.xnrs_assemble_train_batch.restype = i32
-    l.xnrs_assemble_train_batch.argtypes = [p, i64, p, p, p, p, p, p, i32, i32, i32, C.c_uint64, p, p, p]
-    l.xnrs_assemble_eval_batch.restype = i32
-    l.xnrs_assemble_eval_batch.argtypes = [p, i64, p, p, p, p, p, p, i32, i32, p, p, p, p, p, p]
-    l.xnrs_gather_rows.restype = i32
-    l.xnrs_gather_rows.argtypes = [p, p, p, i64, i64, p]
-    l.xnrs_score_csr.restype = i32
-    l.xnrs_score_csr.argtypes = [p, p, p, p, p, i64, i32, i32, p]
-    l.xnrs_rank_metrics.restype = i32
-    l.xnrs_rank_metrics.argtypes = [p, p, p, p, i64, p]
-    l.xnrs_infonce_saved_bytes.restype = sz
-    l.xnrs_infonce_saved_bytes.argtypes = [i64, i32]
-    l.xnrs_infonce_fwd.restype = i32
-    l.xnrs_infonce_fwd.argtypes = [p, p, i64, i32, f, p, p, sz, p]
-    l.xnrs_infonce_bwd.restype = i32
-    l.xnrs_infonce_bwd.argtypes = [p, i64, i32, f, p, sz, p, p, p]
-    l.xnrs_set_gemm_mode.restype = i32
-    l.xnrs_set_gemm_mode.argtypes = [i32]
-    l.xnrs_get_gemm_mode.restype = i32
-    l.xnrs_get_gemm_mode.argtypes = []
-    l.xnrs_reload_knobs.restype = i32
-    l.xnrs_reload_knobs.argtypes = []
-    l.xnrs_profile_enable.restype = i32
-    l.xnrs_profile_enable.argtypes = [C.c_uint32]
-    l.xnrs_profile_read.restype = i32
-    l.xnrs_profile_read.argtypes = [p, p, p]
-    l.xnrs_train_fold_enabled.restype = i32
-    l.xnrs_train_fold_enabled.argtypes = []
-    l.xnrs_text_encoder_compact_workspace_bytes.restype = sz
-    l.xnrs_text_encoder_compact_workspace_bytes.argtypes = [i64, i32, i32, i32, i32, i32, i32, i64]
-    l.xnrs_text_encoder_fwd_compact.restype = i32
-    l.xnrs_text_encoder_fwd_compact.argtypes = [p, p, p, i64, i32, i32, C.POINTER(MhaParams), C.POINTER(AdditiveParams),
-                                                C.POINTER(HeadParams), p, p, i64, p, sz, p]
-    l.xnrs_fold_weights_workspace_bytes.restype = sz
-    l.xnrs_fold_weights_workspace_bytes.argtypes = [i32, i32]
-    l.xnrs_fold_weights.restype = i32
-    l.xnrs_fold_weights.argtypes = [C.POINTER(MhaParams), C.POINTER(AdditiveParams), i32, p, p, p, sz, p]
-    l.xnrs_build_id.restype = C.c_char_p
-    l.xnrs_build_id.argtypes = []
-    l.xnrs_row_lists_workspace_bytes.restype = sz
-    l.xnrs_row_lists_workspace_bytes.argtypes = [i64]
-    l.xnrs_build_row_lists.restype = i32
-    l.xnrs_build_row_lists.argtypes = [p, p, i64, i32, p, p, p, p, p, p, sz, p]
-    l.xnrs_fold_head_weights_workspace_bytes.restype = sz
-    l.xnrs_fold_head_weights_workspace_bytes.argtypes = [i32, i32]
-    l.xnrs_fold_head_weights.restype = i32
-    l.xnrs_fold_head_weights.argtypes = [C.POINTER(MhaParams), C.POINTER(HeadParams), i32, p, p, p, sz, p]
-    l.xnrs_set_status_word.restype = i32
-    l.xnrs_set_status_word.argtypes = [p]
-    l.xnrs_status_string.restype = C.c_char_p
-    l.xnrs_status_string.argtypes = [i32]
-    l.xnrs_bilinear_scoring_saved_bytes.restype = sz
-    l.xnrs_bilinear_scoring_saved_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_bilinear_scoring_fwd.restype = i32
-    l.xnrs_bilinear_scoring_fwd.argtypes = [p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
-    l.xnrs_bilinear_scoring_bwd_workspace_bytes.restype = sz
-    l.xnrs_bilinear_scoring_bwd_workspace_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_bilinear_scoring_bwd.restype = i32
-    l.xnrs_bilinear_scoring_bwd.argtypes = [p, p, p, p, sz, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
-    l.xnrs_mlp_scoring_saved_bytes.restype = sz
-    l.xnrs_mlp_scoring_saved_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_mlp_scoring_fwd.restype = i32
-    l.xnrs_mlp_scoring_fwd.argtypes = [p, p, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
-    l.xnrs_mlp_scoring_bwd_workspace_bytes.restype = sz
-    l.xnrs_mlp_scoring_bwd_workspace_bytes.argtypes = [i64, i32, i32]
-    l.xnrs_mlp_scoring_bwd.restype = i32
-    l.xnrs_mlp_scoring_bwd.argtypes = [p, p, p, p, p, sz, p, p, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
-    l.xnrs_mlp_scoring_news_proj.restype = i32
-    l.xnrs_mlp_scoring_news_proj.argtypes = [p, i64, i32, p, i32, p, p]
-    l.xnrs_score_csr_scorer_workspace_bytes.restype = sz
-    l.xnrs_score_csr_scorer_workspace_bytes.argtypes = [i64, i32]
-    l.xnrs_score_csr_bilinear.restype = i32
-    l.xnrs_score_csr_bilinear.argtypes = [p, p, p, p, i64, p, p, p, i64, i32, i32, p, sz, p]
-    l.xnrs_score_csr_mlp.restype = i32
-    l.xnrs_score_csr_mlp.argtypes = [p, p, p, p, i64, p, p, p, p, p, i64, i32, i32, i32, p, sz, p]
-    l.xnrs_l2_normalize_rows.restype = i32
-    l.xnrs_l2_normalize_rows.argtypes = [p, p, i64, i32, p]
-    if l.xnrs_abi_version() != 6:
-        raise XnrsHipError("libxnrs_hip.so ABI version mismatch; rebuild it")
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        getattr(l, name).restype, getattr(l, name).argtypes = restype, argtypes
+    if l.xnrs_abi_version() != ABI_VERSION:
+        raise XnrsHipError(f"libxnrs_hip.so has ABI version {l.xnrs_abi_version()}, include/xnrs_hip.h {ABI_VERSION}; rebuild it")
     _lib = l
     return l
 
 
 # ---- sticky device status word (include/xnrs_hip.h): what the sync-free entry points could not raise
-STATUS_NONBINARY_MASK, STATUS_ROW_RANGE = 1, 2
 _status = {}
 
 
@@ -324,13 +179,10 @@ def check(rc: int, what: str):
     if rc == 0:
         return
     msg = lib().xnrs_error_string(rc).decode()
-    if rc == -2:
+    if rc == _CONSTANTS["EHEADS"]:
         # same exception type as the reference's failing .view() (layers.py:111,133)
         raise RuntimeError(f"{what}: {msg}")
     raise XnrsHipError(f"{what}: {msg} (code {rc})")
-
-
-GEMM_F32, GEMM_BF16X3, GEMM_BF16X2 = 0, 1, 2
 
 
 def set_gemm_mode(mode: int) -> int:
@@ -474,7 +326,6 @@ def invalidate_fold_cache():
 
 
 def folded_fc1(att, pool):
-    import weakref
     src = (att.out.weight, att.out.bias, pool.fc1.weight, pool.fc1.bias)
     ver = tuple(None if t is None else (t._version, t.data_ptr(), str(t.device), t.dtype) for t in src)
     key = (id(att), id(pool))
@@ -491,7 +342,7 @@ def folded_fc1(att, pool):
     l = lib()
     nws = l.xnrs_fold_weights_workspace_bytes(D, A)
     ws = workspace(dev, nws)
-    check(l.xnrs_fold_weights(C.byref(ap), C.byref(pp), D, ptr(w1f), ptr(b1f), ptr(ws), nws, stream_ptr(dev)), "xnrs_fold_weights")
+    check(l.xnrs_fold_weights(ref(ap), ref(pp), D, ptr(w1f), ptr(b1f), ptr(ws), nws, stream_ptr(dev)), "xnrs_fold_weights")
     if len(_fold_cache) > 64:  # modules come and go (tests): keep the table small
         _fold_cache.clear()
     _fold_cache[key] = (tuple(None if t is None else weakref.ref(t) for t in src), ver, w1f, b1f)
@@ -522,7 +373,6 @@ FOLD_HEAD = os.environ.get("XNRS_FOLD_HEAD", "1") != "0" and os.environ.get("XNR
 
 def folded_head(att, head):
     """(W0 . Wo [E, D], W0 . bo [E] or None) of an (attention stage, head) pair, cached like folded_fc1."""
-    import weakref
     src = (att.out.weight, att.out.bias, head[0].weight)
     ver = tuple(None if t is None else (t._version, t.data_ptr(), str(t.device), t.dtype) for t in src)
     key = (id(att), id(head), "head")
@@ -541,7 +391,7 @@ def folded_head(att, head):
     l = lib()
     nws = l.xnrs_fold_head_weights_workspace_bytes(D, E)
     ws = workspace(dev, nws)
-    check(l.xnrs_fold_head_weights(C.byref(ap), C.byref(hp), D, ptr(w0f), ptr(b0v), ptr(ws), nws, stream_ptr(dev)),
+    check(l.xnrs_fold_head_weights(ref(ap), ref(hp), D, ptr(w0f), ptr(b0v), ptr(ws), nws, stream_ptr(dev)),
           "xnrs_fold_head_weights")
     if FOLD_CACHE:
         if len(_fold_cache) > 64:

@@ -6,7 +6,6 @@ singleton dim exactly as the reference passes them.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Optional
 
@@ -56,7 +55,7 @@ def mha_forward(x: torch.Tensor, m: Optional[torch.Tensor], att, dropout_p: floa
     l = hip.lib()
     nbytes = l.xnrs_mha_workspace_bytes(B, S, D)
     ws = hip.workspace(x.device, nbytes)
-    hip.check(l.xnrs_mha_fwd(hip.ptr(x), hip.ptr(m2), C.byref(p), hip.ptr(y), B, S, D, hip.ptr(ws), nbytes,
+    hip.check(l.xnrs_mha_fwd(hip.ptr(x), hip.ptr(m2), hip.ref(p), hip.ptr(y), B, S, D, hip.ptr(ws), nbytes,
                              hip.stream_ptr(x.device)), "xnrs_mha_fwd")
     return y
 
@@ -74,7 +73,7 @@ def additive_forward(x: torch.Tensor, m: Optional[torch.Tensor], pool, return_we
     l = hip.lib()
     nbytes = l.xnrs_additive_workspace_bytes(B, N, D, p.hidden)
     ws = hip.workspace(x.device, nbytes)
-    hip.check(l.xnrs_additive_attention_fwd(hip.ptr(x), hip.ptr(m2), C.byref(p), hip.ptr(y), hip.ptr(a), B, N, D,
+    hip.check(l.xnrs_additive_attention_fwd(hip.ptr(x), hip.ptr(m2), hip.ref(p), hip.ptr(y), hip.ptr(a), B, N, D,
                                             hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
               "xnrs_additive_attention_fwd")
     return (y, a) if return_weights else y
@@ -105,16 +104,30 @@ def collapse_mask(m: torch.Tensor):
     return hm
 
 
-def _pool_args(pooler, att=None):
-    """att: the attention stage in front of the pooler in an INFERENCE call (the cached folded fc1 rides along)."""
+def _encoder_params(att, pooler, head, dropout_p: float = 0.0, seed: int = 0, additive_only: Optional[str] = None):
+    """-> (pool_kind, MhaParams|None, AdditiveParams|None, HeadParams|None, keepalive list) of one encoder call.
+    Without dropout the cached folds of an inference call ride along: fc1 folded behind the attention stage, and -- behind
+    attention + additive pooling -- the out-projection folded into the head's first layer.  additive_only: the encoder
+    that needs the additive pooler, named in the error."""
     from .models.components import layers
+    fold = att if dropout_p == 0.0 else None
     if isinstance(pooler, layers.AdditiveAttention):
-        p, keep = hip.additive_params(pooler, att)
-        return hip.POOL_ADDITIVE, p, keep
-    if isinstance(pooler, layers.MaskedMean):
-        return hip.POOL_MEAN, None, []
-    raise hip.XnrsHipError(f"pooler {type(pooler).__name__} has no HIP implementation "
-                           "(supported: AdditiveAttention, MaskedMean)")
+        pool_kind, (pp, keep) = hip.POOL_ADDITIVE, hip.additive_params(pooler, fold)
+    elif isinstance(pooler, layers.MaskedMean):
+        pool_kind, pp, keep = hip.POOL_MEAN, None, []
+    else:
+        raise hip.XnrsHipError(f"pooler {type(pooler).__name__} has no HIP implementation "
+                               "(supported: AdditiveAttention, MaskedMean)")
+    if additive_only and pool_kind != hip.POOL_ADDITIVE:
+        raise hip.XnrsHipError(f"the {additive_only} encoder needs the additive pooler")
+    ap = hp = None
+    if att is not None:
+        ap, k2 = hip.mha_params(att, dropout_p, seed)
+        keep += k2
+    if head is not None:
+        hp, k3 = hip.head_params(head, fold if pool_kind == hip.POOL_ADDITIVE else None)
+        keep += k3
+    return pool_kind, ap, pp, hp, keep
 
 
 def text_encoder_forward(x: torch.Tensor, m: torch.Tensor, att, pooler, head, ids: Optional[torch.Tensor] = None,
@@ -133,14 +146,7 @@ def text_encoder_forward(x: torch.Tensor, m: torch.Tensor, att, pooler, head, id
         n = ids.numel()
     else:
         n = n_tab
-    pool_kind, pp, keep = _pool_args(pooler, att if dropout_p == 0.0 else None)
-    ap = hp = None
-    if att is not None:
-        ap, k2 = hip.mha_params(att, dropout_p, seed)
-        keep += k2
-    if head is not None:  # (behind attention + additive pooling the out-projection folds into the head's first layer)
-        hp, k3 = hip.head_params(head, att if (pool_kind == hip.POOL_ADDITIVE and dropout_p == 0.0) else None)
-        keep += k3
+    pool_kind, ap, pp, hp, keep = _encoder_params(att, pooler, head, dropout_p, seed)
     A = pp.hidden if pp is not None else 0
     E = hp.out_features if hp is not None else D
     y = torch.empty((n, E), dtype=torch.float32, device=x.device)
@@ -149,10 +155,8 @@ def text_encoder_forward(x: torch.Tensor, m: torch.Tensor, att, pooler, head, id
     nbytes = l.xnrs_text_encoder_workspace_bytes(n, S, D, A, E, int(att is not None), pool_kind, int(head is not None),
                                                  chunk)
     ws = hip.workspace(x.device, nbytes)
-    hip.check(l.xnrs_text_encoder_fwd(hip.ptr(x), hip.ptr(m2), hip.ptr(ids), n, S, D,
-                                      None if ap is None else C.byref(ap), pool_kind,
-                                      None if pp is None else C.byref(pp), None if hp is None else C.byref(hp),
-                                      hip.ptr(y), hip.ptr(hm), chunk, hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
+    hip.check(l.xnrs_text_encoder_fwd(hip.ptr(x), hip.ptr(m2), hip.ptr(ids), n, S, D, hip.ref(ap), pool_kind, hip.ref(pp),
+                                      hip.ref(hp), hip.ptr(y), hip.ptr(hm), chunk, hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
               "xnrs_text_encoder_fwd")
     return y, hm
 
@@ -176,17 +180,8 @@ def text_encoder_forward_unpadded(x: torch.Tensor, m: torch.Tensor, att, pooler,
         live = m2.ne(0)
         base = None
     n = live.shape[0]
-    pool_kind, pp, keep = _pool_args(pooler, att)
-    if pool_kind != hip.POOL_ADDITIVE:
-        raise hip.XnrsHipError("the unpadded encoder needs the additive pooler")
+    pool_kind, ap, pp, hp, keep = _encoder_params(att, pooler, head, additive_only="unpadded")
     bad = ((m2 != 0) & (m2 != 1)).any()
-    ap = hp = None
-    if att is not None:
-        ap, k2 = hip.mha_params(att, 0.0, 0)
-        keep += k2
-    if head is not None:
-        hp, k3 = hip.head_params(head, att)
-        keep += k3
     A, E = pp.hidden, (hp.out_features if hp is not None else D)
     y = torch.empty((n, E), dtype=torch.float32, device=x.device)
     hm = torch.empty((n,), dtype=torch.float32, device=x.device)
@@ -213,8 +208,7 @@ def text_encoder_forward_unpadded(x: torch.Tensor, m: torch.Tensor, att, pooler,
         nbytes = l.xnrs_text_encoder_unpadded_workspace_bytes(nc, nv, S, D, A, E, int(att is not None), int(head is not None))
         ws = hip.workspace(x.device, nbytes)
         hip.check(l.xnrs_text_encoder_fwd_unpadded(hip.ptr(xp), hip.ptr(idp), nc, S, D, hip.ptr(rows), hip.ptr(roff), nv,
-                                                   None if ap is None else C.byref(ap), C.byref(pp),
-                                                   None if hp is None else C.byref(hp), hip.ptr(y[c0:c1]), hip.ptr(hm[c0:c1]),
+                                                   hip.ref(ap), hip.ref(pp), hip.ref(hp), hip.ptr(y[c0:c1]), hip.ptr(hm[c0:c1]),
                                                    hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
                   "xnrs_text_encoder_fwd_unpadded")
     return y, hm
@@ -235,16 +229,7 @@ def text_encoder_forward_compact(x: torch.Tensor, m: torch.Tensor, att, pooler, 
         n = ids.numel()
     else:
         n = n_tab
-    pool_kind, pp, keep = _pool_args(pooler, att)
-    if pool_kind != hip.POOL_ADDITIVE:
-        raise hip.XnrsHipError("the compact encoder needs the additive pooler")
-    ap = hp = None
-    if att is not None:
-        ap, k2 = hip.mha_params(att, 0.0, 0)
-        keep += k2
-    if head is not None:
-        hp, k3 = hip.head_params(head, att)
-        keep += k3
+    pool_kind, ap, pp, hp, keep = _encoder_params(att, pooler, head, additive_only="compact")
     A, E = pp.hidden, (hp.out_features if hp is not None else D)
     y = torch.empty((n, E), dtype=torch.float32, device=x.device)
     hm = torch.empty((n,), dtype=torch.float32, device=x.device)
@@ -261,8 +246,8 @@ def text_encoder_forward_compact(x: torch.Tensor, m: torch.Tensor, att, pooler, 
             nbytes = l.xnrs_text_encoder_compact_workspace_bytes(n, S, D, A, E, int(att is not None), int(head is not None), per_pass)
         chunk = per_pass
     ws = hip.workspace(x.device, nbytes)
-    hip.check(l.xnrs_text_encoder_fwd_compact(hip.ptr(x), hip.ptr(m2), hip.ptr(ids), n, S, D, None if ap is None else C.byref(ap),
-                                              C.byref(pp), None if hp is None else C.byref(hp), hip.ptr(y), hip.ptr(hm), chunk,
+    hip.check(l.xnrs_text_encoder_fwd_compact(hip.ptr(x), hip.ptr(m2), hip.ptr(ids), n, S, D, hip.ref(ap),
+                                              hip.ref(pp), hip.ref(hp), hip.ptr(y), hip.ptr(hm), chunk,
                                               hip.ptr(ws), nbytes, hip.stream_ptr(x.device)), "xnrs_text_encoder_fwd_compact")
     return y, hm
 
@@ -287,22 +272,14 @@ def user_encoder_forward(x: torch.Tensor, m: torch.Tensor, att, pooler, head, re
     x = hip.dev_f32(x, "user encoder input")
     B, H, E = x.shape
     m2 = _mask2d(m, B, H, "user encoder mask")
-    pool_kind, pp, keep = _pool_args(pooler, att if dropout_p == 0.0 else None)
-    ap = hp = None
-    if att is not None:
-        ap, k2 = hip.mha_params(att, dropout_p, seed)
-        keep += k2
-    if head is not None:  # (behind attention + additive pooling the out-projection folds into the head's first layer)
-        hp, k3 = hip.head_params(head, att if (pool_kind == hip.POOL_ADDITIVE and dropout_p == 0.0) else None)
-        keep += k3
+    pool_kind, ap, pp, hp, keep = _encoder_params(att, pooler, head, dropout_p, seed)
     A = pp.hidden if pp is not None else 0
     y = torch.empty((B, 1, E), dtype=torch.float32, device=x.device)
     a = torch.empty((B, H, 1), dtype=torch.float32, device=x.device) if return_weights else None
     l = hip.lib()
     nbytes = l.xnrs_user_encoder_workspace_bytes(B, H, E, A, int(att is not None), pool_kind, int(head is not None))
     ws = hip.workspace(x.device, nbytes)
-    hip.check(l.xnrs_user_encoder_fwd(hip.ptr(x), hip.ptr(m2), B, H, E, None if ap is None else C.byref(ap), pool_kind,
-                                      None if pp is None else C.byref(pp), None if hp is None else C.byref(hp),
+    hip.check(l.xnrs_user_encoder_fwd(hip.ptr(x), hip.ptr(m2), B, H, E, hip.ref(ap), pool_kind, hip.ref(pp), hip.ref(hp),
                                       hip.ptr(y), hip.ptr(a), hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
               "xnrs_user_encoder_fwd")
     return (y, a) if return_weights else y
