@@ -435,9 +435,12 @@ int32_t xnrs_train_fold_enabled(void);
  * are then the only signal); the caller zeroes it.  xnrs_status_string explains a value.
  *   XNRS_STATUS_NONBINARY_MASK  xnrs_text_encoder_fwd_compact met a mask value other than 0 / 1
  *   XNRS_STATUS_ROW_RANGE       (set by the Python host layer, NewsStore.gather) a table row id outside the table; the
- *                               id was clamped so that no kernel read out of bounds */
+ *                               id was clamped so that no kernel read out of bounds
+ *   XNRS_STATUS_QUERY_RANGE     xnrs_personalized_fwd* met a q_idx outside [0, n_q) (that sequence's outputs are NaN), or
+ *                               (set by the Python host layer, NPA.queries) a user id outside the user table (clamped) */
 #define XNRS_STATUS_NONBINARY_MASK 1
 #define XNRS_STATUS_ROW_RANGE 2
+#define XNRS_STATUS_QUERY_RANGE 4
 int32_t xnrs_set_status_word(int32_t *device_word);
 const char *xnrs_status_string(int32_t word);
 
@@ -516,6 +519,56 @@ int32_t xnrs_score_csr_mlp(const float *P, const int32_t *cand_rows, const int32
                            int64_t n_cand, int32_t E, int32_t H, int32_t relu, void *ws, size_t ws_bytes, void *stream);
 /* y[r,:] = x[r,:] / ||x[r,:]|| (no epsilon, scoring.py:20-22); y may equal x */
 int32_t xnrs_l2_normalize_rows(const float *x, float *y, int64_t rows, int32_t E, void *stream);
+
+/* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
+ *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
+ * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head
+ * y = W2 act(W0 p + b0) + b2.  The query is per sequence: sequence s scores with row q_idx[s] of q, the user's projected
+ * embedding q_fc(user_embedder(uid)) -- q_idx = s / n_per_user replaces repeat_interleave (npa.py:67,80), q_idx = the
+ * impression of a CSR candidate list serves evaluation.  x:(n_seq,L,D), m:(n_seq,L) fp32 or NULL; with ids, x and m are the
+ * table ([n_table,L,D], [n_table,L]) and sequence s is its row ids[s].  y:(n_seq,E) (E = D without a head), a_out:(n_seq,L)
+ * and hm:(n_seq) = clamp(sum m, 0, 1) nullable.  L <= 4096.
+ *   fwd        ws: xnrs_personalized_saved_bytes of scratch
+ *   fwd_train  the same arithmetic; `saved` (xnrs_personalized_saved_bytes) keeps tanh(x_fc x), a, p and the head's hidden
+ *              layer for the backward
+ *   bwd        dy:(n_seq,E) -> dwx / dbx (x_fc), dq:(n_q, hidden) = d loss / d q per QUERY ROW (the sequences sharing a row
+ *              are summed in sequence order), the head's gradients, and dx:(n_seq,L,D) = a_i dp + (dpre . Wx)_i (the user
+ *              tower's input; not with ids).  Every output nullable, written (not accumulated), no float atomics. */
+typedef struct {
+  const float *wx, *bx;   /* x_fc: Linear(D, hidden) weight [hidden][D], bias [hidden] (nullable) */
+  const float *q;         /* projected queries, row r at q + r * q_ld */
+  const int32_t *q_idx;   /* [n_seq] int32 device array: the query row of every sequence */
+  int32_t hidden;
+  int32_t q_ld;           /* row stride of q in floats (0 = hidden): two projections side by side in one GEMM output */
+  int32_t n_q;            /* rows of q.  A sequence whose q_idx is outside [0, n_q) reads no query: its outputs are NaN, it
+                           * passes no gradient, and XNRS_STATUS_QUERY_RANGE is set in the status word */
+} xnrs_personalized_params;
+
+size_t xnrs_personalized_saved_bytes(int64_t n_seq, int32_t L, int32_t D, int32_t A, int32_t E, int32_t has_head);
+int32_t xnrs_personalized_fwd(const float *x, const float *m, const int32_t *ids, int64_t n_seq, int32_t L, int32_t D,
+                              const xnrs_personalized_params *p, const xnrs_head_params *head, float *y, float *a_out,
+                              float *hm, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_personalized_fwd_train(const float *x, const float *m, const int32_t *ids, int64_t n_seq, int32_t L, int32_t D,
+                                    const xnrs_personalized_params *p, const xnrs_head_params *head, float *y, float *a_out,
+                                    float *hm, void *saved, size_t saved_bytes, void *stream);
+size_t xnrs_personalized_bwd_workspace_bytes(int64_t n_seq, int32_t L, int32_t D, int32_t A, int32_t E, int32_t has_head);
+int32_t xnrs_personalized_bwd(const float *x, const int32_t *ids, int64_t n_seq, int32_t L, int32_t D,
+                              const xnrs_personalized_params *p, const xnrs_head_params *head, const void *saved,
+                              size_t saved_bytes, const float *dy, float *dx, float *dwx, float *dbx, float *dq, int64_t n_q,
+                              const xnrs_head_grads *g_head, void *ws, size_t ws_bytes, void *stream);
+
+/* nn.Embedding backward at table scale (npa.py:12-15: 703 790 rows, NO padding row): d_table:(n_rows,K) = zeros except
+ * row ids[m] += d_rows[m] -- one 16-byte-store zero fill, then one workgroup per id; the workgroup of an id's first
+ * occurrence sums all its occurrences in batch order (no atomics).  Cost: the ids, not the table.  Ids outside
+ * [0, n_rows) are skipped. */
+int32_t xnrs_embedding_grad_sparse(const float *d_rows, const int32_t *ids, int64_t M, int32_t K, float *d_table,
+                                   int32_t n_rows, void *stream);
+/* xnrs_embedding_linear_bwd with that table gradient (fc(embedder(ids)) with a large table: NPA's stacked q_fc
+ * projections).  Every output nullable. */
+size_t xnrs_embedding_linear_bwd_sparse_workspace_bytes(int64_t M, int32_t N, int32_t K);
+int32_t xnrs_embedding_linear_bwd_sparse(const float *table, const int32_t *ids, const float *w, const float *dy,
+                                         float *d_table, float *dw, float *db, int64_t M, int32_t N, int32_t K, int32_t n_rows,
+                                         void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,8 +13,8 @@ _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 __version__ = "0.1.0"
 
 
-def install(force: bool = False) -> bool:
+def install(force: bool = False, hip_models=()) -> bool:
     """Make the reference's own `from xnrs.models import make_model` (train.py:12) resolve to the HIP-backed modules
-    without touching a reference file -- see xnrs_amd/mirrors.py."""
+    without touching a reference file -- see xnrs_amd/mirrors.py.  hip_models=("NPA",) opts NPA in as well."""
     from .mirrors import install as _install
-    return _install(force)
+    return _install(force, hip_models=hip_models)

@@ -7,6 +7,7 @@ through HIP kernels; torch only routes gradients between the Functions.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import List, Optional
 
@@ -811,3 +812,115 @@ class _MlpScoring(torch.autograd.Function):
 
 def mlp_scoring(u, c, w1, b1, w2, b2):
     return _MlpScoring.apply(u, c, w1, b1, w2, b2)
+
+
+# ---- layers.PersonalizedAttention (layers.py:72-102) [+ NPA's news head, npa.py:22-26]: include/xnrs_hip.h
+#      xnrs_personalized_*.  One node per encoder call; the query rows q are an input like any other (their gradient is
+#      summed per query row on the device), q_idx / ids / m are not differentiable.
+def personalized_params(x_fc, q, q_idx, keep):
+    """xnrs_personalized_params of x_fc + the query rows q:(n_q, A) (row stride q.stride(0), unit column stride).  A q_idx
+    outside [0, n_q) reads no query: that sequence's outputs are NaN and hip.STATUS_QUERY_RANGE is set (hip.check_status)."""
+    wx = hip.dev_f32(x_fc.weight, "x_fc weight")
+    bx = None if x_fc.bias is None else hip.dev_f32(x_fc.bias, "x_fc bias")
+    if not q.is_cuda or not q_idx.is_cuda:
+        raise hip.XnrsHipError("personalized attention: the query rows and their indices must live on the HIP device")
+    if q.dtype != torch.float32 or q.dim() != 2 or q.stride(1) != 1:
+        q = hip.dev_f32(q, "query rows").reshape(q.shape[0], -1)
+    keep += [wx, bx, q, q_idx]
+    return hip.STRUCTS["xnrs_personalized_params"](wx.data_ptr(), _addr(bx), q.data_ptr(), q_idx.data_ptr(), wx.shape[0],
+                                                   q.stride(0), q.shape[0])
+
+
+def personalized_head(head, keep):
+    if head is None:
+        return None
+    ts = [hip.dev_f32(head[0].weight, "head weight"), None if head[0].bias is None else hip.dev_f32(head[0].bias, "head bias"),
+          hip.dev_f32(head[2].weight, "head weight"), None if head[2].bias is None else hip.dev_f32(head[2].bias, "head bias")]
+    keep += ts
+    return hip.HeadParams(*[_addr(t) for t in ts], head[0].weight.shape[0], hip.head_activation(head[1]))
+
+
+class _Personalized(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mods, x, m, ids, q, q_idx, wx, bx, w0, b0, w2, b2):
+        from . import ops
+        x_fc, head = mods
+        with torch.no_grad():
+            y, hm, saved = ops.personalized_forward(x, m, ids, q, q_idx, x_fc, head, keep=True)
+        ctx.save_for_backward(x, ids, q, q_idx, saved)
+        n_seq = ids.numel() if ids is not None else x.shape[0]
+        ctx.mods, ctx.n_q, ctx.dims = mods, q.shape[0], (n_seq, x.shape[-2], x.shape[-1], wx.shape[0], y.shape[1])
+        ctx.has = [True, m is not None, ids is not None, True, True, True, bx is not None, w0 is not None,
+                   b0 is not None, w2 is not None, b2 is not None]
+        ctx.mark_non_differentiable(hm)
+        return y, hm
+
+    @staticmethod
+    def backward(ctx, dy, _dhm):
+        x, ids, q, q_idx, saved = ctx.saved_tensors
+        x_fc, head = ctx.mods
+        n_seq, L, D, A, E = ctx.dims
+        wanted = _wanted_inputs(ctx, [False] + ctx.has, 1)
+        need = [n and w for n, w in zip(ctx.needs_input_grad[1:], wanted)]  # x m ids q q_idx wx bx w0 b0 w2 b2
+        dev = x.device
+        dy = hip.dev_f32(dy, "dy")
+        x = hip.dev_f32(x, "personalized attention input")  # (what the forward read: no copy for a contiguous input)
+        ids = None if ids is None else ids.to(torch.int32).contiguous()
+        keep = []
+        pp = personalized_params(x_fc, q, q_idx.contiguous(), keep)
+        hp = personalized_head(head, keep)
+        dx = torch.empty_like(x) if need[0] and ids is None else None
+        dq = torch.empty((ctx.n_q, A), dtype=torch.float32, device=dev) if need[3] else None
+        dwx = torch.empty_like(x_fc.weight) if need[5] else None
+        dbx = torch.empty_like(x_fc.bias) if need[6] else None
+        hw = [head[0].weight, head[0].bias, head[2].weight, head[2].bias] if head is not None else [None] * 4
+        g = [torch.empty_like(t) if (t is not None and need[7 + i]) else None for i, t in enumerate(hw)]
+        gh = hip.HeadGrads(*[_addr(t) for t in g]) if head is not None else None
+        l = hip.lib()
+        nws = l.xnrs_personalized_bwd_workspace_bytes(n_seq, L, D, A, E, int(head is not None))
+        ws = hip.workspace(dev, nws)
+        hip.check(l.xnrs_personalized_bwd(hip.ptr(x), hip.ptr(ids), n_seq, L, D, ctypes.byref(pp), hip.ref(hp), hip.ptr(saved),
+                                          saved.numel(), hip.ptr(dy), hip.ptr(dx), hip.ptr(dwx), hip.ptr(dbx), hip.ptr(dq),
+                                          ctx.n_q, hip.ref(gh), hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_personalized_bwd")
+        return (None, dx, None, None, dq, None, dwx, dbx, *g)
+
+
+def personalized(x, m, ids, q, q_idx, x_fc, head):
+    """Differentiable xnrs_personalized_fwd_train / _bwd: -> (y:(n_seq, E), hm:(n_seq))."""
+    hw = [None] * 4 if head is None else [head[0].weight, head[0].bias, head[2].weight, head[2].bias]
+    return _Personalized.apply((x_fc, head), x, m, ids, q, q_idx, x_fc.weight, x_fc.bias, *hw)
+
+
+class _EmbeddingLinearTable(torch.autograd.Function):
+    """fc(embedder(ids)) over a LARGE table (NPA's user table): the forward is _EmbeddingLinear's; the table gradient costs
+    what the ids cost (xnrs_embedding_linear_bwd_sparse: one zero fill, then one workgroup per id)."""
+
+    @staticmethod
+    def forward(ctx, ids, table, w, b):
+        out = _EmbeddingLinear.forward(ctx, ids, table, w, b)
+        ctx.has = [True, True, True, b is not None]
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, tab, w = ctx.saved_tensors
+        dy = hip.dev_f32(dy, "dy")
+        M, K, N = idx.numel(), tab.shape[1], w.shape[0]
+        wanted = _wanted_inputs(ctx, ctx.has, 0)
+        need = [n and k for n, k in zip(ctx.needs_input_grad, wanted)]
+        d_tab = torch.empty_like(tab) if need[1] else None
+        dw = torch.empty_like(w) if need[2] else None
+        db = torch.empty(N, dtype=torch.float32, device=tab.device) if (ctx.has_bias and need[3]) else None
+        l = hip.lib()
+        nws = l.xnrs_embedding_linear_bwd_sparse_workspace_bytes(M, N, K)
+        ws = hip.workspace(tab.device, nws)
+        hip.check(l.xnrs_embedding_linear_bwd_sparse(hip.ptr(tab), hip.ptr(idx), hip.ptr(w), hip.ptr(dy), hip.ptr(d_tab),
+                                                     hip.ptr(dw), hip.ptr(db), M, N, K, tab.shape[0], hip.ptr(ws), nws,
+                                                     hip.stream_ptr(tab.device)), "xnrs_embedding_linear_bwd_sparse")
+        return None, d_tab, dw, db
+
+
+def embedding_linear_table(idx, table, w, b):
+    if not idx.is_cuda:
+        raise hip.XnrsHipError("user indices must live on the HIP device")
+    return _EmbeddingLinearTable.apply(idx, table, w, b)

@@ -749,6 +749,10 @@ int32_t xnrs_set_status_word(int32_t* device_word) {
 }
 
 const char* xnrs_status_string(int32_t word) {
+  if (word == XNRS_STATUS_QUERY_RANGE)
+    return "a query row index or user id outside its table (personalized attention: NaN outputs / clamped user ids)";
+  if (word & XNRS_STATUS_QUERY_RANGE)
+    return "several status bits: a query row index or user id out of range, and a bad mask value or table row id";
   switch (word & 3) {
     case 0: return "ok";
     case XNRS_STATUS_NONBINARY_MASK: return "a mask value other than 0 / 1 reached the device-compacted encoder (its outputs are NaN)";

@@ -290,7 +290,10 @@ class Behaviors:
         hist = _csr([store.rows(s["history"]) for s in sessions])
         pos = _csr([store.rows(s["positives"]) for s in sessions])
         neg = _csr([store.rows(s["negatives"]) for s in sessions])
-        return cls(hist, pos, neg, [str(s.get("main_theme", "")) for s in sessions])
+        b = cls(hist, pos, neg, [str(s.get("main_theme", "")) for s in sessions])
+        if sessions and all("user_index" in s for s in sessions):  # dataset.py:139-144,157 (NPA's user table)
+            b.user_index = torch.tensor([int(s["user_index"]) for s in sessions], dtype=torch.int64)
+        return b
 
     def __len__(self):
         return self.hist_off.numel() - 1
@@ -299,6 +302,8 @@ class Behaviors:
         b = Behaviors.__new__(Behaviors)
         for k in ("hist_off", "hist_val", "pos_off", "pos_val", "neg_off", "neg_val", "theme_labels"):
             setattr(b, k, getattr(self, k).to(device))
+        if hasattr(self, "user_index"):
+            b.user_index = self.user_index.to(device)
         b.themes = self.themes
         return b
 

@@ -93,6 +93,37 @@ def encode_news_table_sharded(model, store: NewsStore, rank: int, world: int):
     return both[:, :E].contiguous(), both[:, E:].contiguous()
 
 
+def _evaluate_per_batch(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: int, distributed) -> Dict[str, float]:
+    """evaluate() for a model whose news vectors depend on the user (NPA: its title pooler's query is the user's embedding),
+    so no table of news vectors exists: every impression batch encodes its own history and CSR candidates through the
+    model's hook score_impressions(store, hist_rows, cand_rows, cand_sess, uid), then rank_metrics.  Under a process group
+    every rank scores a contiguous block of the sessions (distributed.shard_range) and one fp64 all-reduce adds the sums.
+    Runs under evaluate()'s torch.no_grad()."""
+    uidx = getattr(behaviors, "user_index", None)
+    if uidx is None:
+        raise ValueError(f"evaluate(): {type(model).__name__} needs the user index of every session (sessions without "
+                         "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    rank, world, on = _dist_rank_world(distributed)
+    n = len(behaviors)
+    s_lo, s_hi = 0, n
+    if on:
+        from .distributed import shard_range
+        s_lo, s_hi = shard_range(n, rank, world)
+    batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
+    dev = behaviors.hist_off.device
+    uidx = uidx.to(dev)
+    sums = torch.zeros(len(METRIC_NAMES), dtype=torch.float64, device=dev)
+    for lo in range(s_lo, s_hi, batch):
+        sess = torch.arange(lo, min(lo + batch, s_hi), device=dev)
+        hist, off, rows, csess, targets = batcher.eval_batch(sess)
+        r = model.score_impressions(store, hist, rows, csess, uidx[sess], relu=True)
+        sums += rank_metrics(r, targets, off).double().sum(0)
+    mean = sharded_mean(sums, n, on)
+    out = {k: float(v) for k, v in zip(METRIC_NAMES, mean.tolist())}
+    hip.check_status(dev)
+    return out
+
+
 @torch.no_grad()
 def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: int = 4096, distributed=None) -> Dict[str, float]:
     """Mean of the per-impression metrics over all sessions (training.py:245-303 aggregates the same way).
@@ -111,6 +142,8 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
     if prepare is None or score is None:
         raise NotImplementedError(f"evaluate(): the scorer {type(scorer).__name__} has no CSR scoring path (prepare_csr / "
                                   "score_csr); scoring it with a plain dot product would report another model's metrics")
+    if getattr(model, "user_dependent_news", False):
+        return _evaluate_per_batch(model, store, behaviors, l_hist, batch, distributed)
     rank, world, on = _dist_rank_world(distributed)
     if on:
         from .distributed import shard_range

@@ -89,11 +89,24 @@ class _Mirror(types.ModuleType):
         raise AttributeError(f"module {self.__name__!r} (xnrs_amd mirror) has no attribute {item!r}")
 
 
-def install(force: bool = False) -> bool:
+#: models that run on the reference's stock-torch classes by default but have a HIP implementation to opt into
+_OPT_IN = ("NPA",)
+
+
+def install(force: bool = False, hip_models=()) -> bool:
     """Register the mirrors.  Must run before `xnrs.models` is imported (raises otherwise unless it already IS the mirror);
-    idempotent.  Returns True when the reference package was found on sys.path (False: mirrors only)."""
-    if _state["installed"] and not force:
+    idempotent.  Returns True when the reference package was found on sys.path (False: mirrors only).
+    hip_models: names of _OPT_IN to route to xnrs_amd too -- ("NPA",): `from xnrs.models.full_models import NPA` and the
+    mirrored make_model build xnrs_amd.models.NPA instead of the reference's file (the default keeps the reference's)."""
+    hip_models = tuple(hip_models)
+    bad = [k for k in hip_models if k not in _OPT_IN]
+    if bad:
+        raise ValueError(f"install(hip_models=...): no HIP implementation to opt into for {bad} (available: {_OPT_IN})")
+    if _state["installed"] and not force and set(hip_models) <= set(_state.get("hip_models", ())):
         return bool(_state["ref"])
+    # (an opt-in asked for after a plain install() re-registers the mirrors with it, as force=True would: names already
+    # imported from the old mirrors keep what they were bound to)
+    hip_models = tuple(sorted(set(hip_models) | (set() if force else set(_state.get("hip_models", ())))))
     present = sys.modules.get("xnrs.models")
     if present is not None and not getattr(present, "_xnrs_amd_mirror", False):
         raise RuntimeError("xnrs_amd.install() must run before the reference's xnrs.models is imported "
@@ -138,6 +151,10 @@ def install(force: bool = False) -> bool:
                      LSTURNewsEncoder=assemblies.LSTURNewsEncoder)
     # out-of-scope models stay the reference's classes, from the reference's files: name -> (file, attribute)
     ref_models = {"CAUM": "caum", "LSTUR": "lstur", "NPA": "npa", "SmallNAML": "naml"}
+    if "NPA" in hip_models:
+        from .models import npa
+        ours_full["NPA"] = npa.NPA
+        del ref_models["NPA"]
     full = _Mirror("xnrs.models.full_models", ours_full, None, "xnrs.models.full_models", path=[fdir] if fdir else [])
 
     def full_getattr(item):
@@ -150,7 +167,10 @@ def install(force: bool = False) -> bool:
     def make_model(cfg):
         """xnrs/models/make_model.py:15-56 on the HIP path (dot, bilin and fc scorers); a model or scorer outside the path
         (NPA, CAUM, LSTUR, smallNAML, CAUMScoring) is built by the REFERENCE's own make_model on stock torch, exactly as
-        before the install."""
+        before the install.  A model opted in with install(hip_models=...) is built here."""
+        if cfg.model == "NPA" and "NPA" in hip_models:
+            from .models import npa
+            return npa.make_npa(cfg)
         try:
             return assemblies.make_model(cfg)
         except NotImplementedError:
@@ -177,7 +197,7 @@ def install(force: bool = False) -> bool:
     for k, v in comp_sub.items():
         sys.modules["xnrs.models.components." + k] = v
     sys.modules["xnrs.models.full_models"] = full
-    _state.update(installed=True, ref=root)
+    _state.update(installed=True, ref=root, hip_models=hip_models)
     del M
     return bool(root)
 
@@ -188,4 +208,4 @@ def uninstall() -> None:
         if k in _MIRRORED or k.endswith("._reference") and k.startswith("xnrs.models"):
             if getattr(sys.modules[k], "_xnrs_amd_mirror", False) or k.endswith("._reference"):
                 sys.modules.pop(k, None)
-    _state.update(installed=False, ref=None)
+    _state.update(installed=False, ref=None, hip_models=())

@@ -3,3 +3,4 @@ from .assemblies import (NAML, NRMS, NRMS_LF, BaseRec, LSTURNewsEncoder, MeanRec
                          make_model)
 from .blocks import ParentRec, TextEncoder, UserEncoder  # noqa: F401
 from .components import layers, scoring  # noqa: F401
+from .npa import NPA, PersonalizedAttention  # noqa: F401  (not in components.*: install() mirrors those)

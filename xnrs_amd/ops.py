@@ -6,6 +6,7 @@ singleton dim exactly as the reference passes them.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import Optional
 
@@ -573,6 +574,69 @@ def user_encoder(x, m, enc, return_weights=False):
         from . import autograd
         return autograd.user_encoder(x, m, enc, return_weights, p, seed)
     return user_encoder_forward(x, m, att, pooler, head, return_weights, dropout_p=p, seed=seed)
+
+
+def personalized_forward(x, m, ids, q, q_idx, x_fc, head, keep: bool = False):
+    """layers.PersonalizedAttention (layers.py:72-102) [+ head], include/xnrs_hip.h xnrs_personalized_fwd:
+    x:(n_seq,L,D) (or the table with ids:(n_seq,) int32), m:(n_seq,L) or None, q:(n_q,A) query rows (unit column stride),
+    q_idx:(n_seq,) int32 -> (y:(n_seq,E), hm:(n_seq,)[, saved blob when keep])."""
+    from . import autograd as AG
+    x = hip.dev_f32(x, "personalized attention input")
+    L, D = x.shape[-2], x.shape[-1]
+    if ids is not None:
+        ids = ids.to(torch.int32).contiguous()
+        if not ids.is_cuda:
+            raise hip.XnrsHipError("news ids must live on the HIP device")
+    n_seq = ids.numel() if ids is not None else x.numel() // (L * D)
+    m = None if m is None else hip.dev_f32(m, "personalized attention mask")
+    if m is not None and m.numel() != (x.numel() // D if ids is not None else n_seq * L):
+        raise ValueError(f"mask of {m.numel()} values for {n_seq} sequences of {L}")
+    if q_idx.numel() != n_seq or q_idx.dtype != torch.int32:
+        raise ValueError("q_idx: one int32 query row per sequence")
+    keep_alive = []
+    pp = AG.personalized_params(x_fc, q, q_idx.contiguous(), keep_alive)
+    hp = AG.personalized_head(head, keep_alive)
+    E = hp.out_features if hp is not None else D
+    l = hip.lib()
+    nbytes = l.xnrs_personalized_saved_bytes(n_seq, L, D, pp.hidden, E, int(hp is not None))
+    buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device) if keep else hip.workspace(x.device, nbytes)
+    y = torch.empty((n_seq, E), dtype=torch.float32, device=x.device)
+    hm = torch.empty((n_seq,), dtype=torch.float32, device=x.device)
+    fn = l.xnrs_personalized_fwd_train if keep else l.xnrs_personalized_fwd
+    hip.check(fn(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n_seq, L, D, C.byref(pp), hip.ref(hp), hip.ptr(y), None, hip.ptr(hm),
+                 hip.ptr(buf), nbytes, hip.stream_ptr(x.device)), "xnrs_personalized_fwd")
+    return (y, hm, buf) if keep else (y, hm)
+
+
+def personalized(x, m, ids, q, q_idx, x_fc, head=None):
+    """-> (y, hm); through autograd when the input, the queries or the weights need a gradient."""
+    if _needs_grad(x, q, x_fc, head):
+        from . import autograd
+        return autograd.personalized(x, m, ids, q, q_idx, x_fc, head)
+    return personalized_forward(x, m, ids, q, q_idx, x_fc, head)
+
+
+def embedding_linear_table(idx: torch.Tensor, table: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]):
+    """table[idx] . w^T + b as ONE GEMM whose rows are gathered from a large embedding table; its gradient is the
+    table-scale one (xnrs_embedding_linear_bwd_sparse).  idx:(M,) -> (M, N)."""
+    if _needs_grad(table, w, b):
+        from . import autograd
+        return autograd.embedding_linear_table(idx, table, w, b)
+    if not idx.is_cuda:
+        raise hip.XnrsHipError("user indices must live on the HIP device")
+    return linear_gather_rows(table, idx, w, b)
+
+
+def linear_gather_rows(table, idx, w, b):
+    tab = hip.dev_f32(table, "embedding table")
+    wd = hip.dev_f32(w, "fc weight")
+    bd = None if b is None else hip.dev_f32(b, "fc bias")
+    ids = idx.to(torch.int32).contiguous()
+    M, K, N = ids.numel(), tab.shape[1], wd.shape[0]
+    y = torch.empty(tuple(idx.shape) + (N,), dtype=torch.float32, device=tab.device)
+    hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(ids), 1, hip.ptr(wd), hip.ptr(bd), hip.ptr(y), M, N, K,
+                                        hip.ACT_NONE, hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
+    return y
 
 
 def embedding_linear(idx: torch.Tensor, embedder, fc):
