@@ -112,7 +112,7 @@ def test_abi_version_and_error_strings():
 
 
 def test_binary_was_built_from_the_sources_in_this_tree():
-    """xnrs_build_id() = hash of csrc/*.hip + kernels.h + include/xnrs_hip.h at build time (csrc/Makefile); it must equal
+    """xnrs_build_id() = hash of csrc/*.hip + csrc/*.h + include/xnrs_hip.h at build time (csrc/Makefile); it must equal
     the hash of those files NOW -- a measured binary that is not the tree's fails here, without a rebuild."""
     assert hip.build_id() == hip.tree_build_id(), "libxnrs_hip.so is stale: run __graft_entry__.build()"
     assert len(hip.build_id()) == 16

@@ -592,7 +592,7 @@ def test_attention_core_pair_kernel_branches(S, h, dk):
 
 @pytest.mark.parametrize("live,bias", [(True, True), (False, True), (True, False)])
 def test_folded_out_projection_gradients(live, bias):
-    """Training with the out-projection folded behind the pooling (api.hip "fold": the forward pools the O rows, the
+    """Training with the out-projection folded behind the pooling (encoder_fwd.hip "fold": the forward pools the O rows, the
     backward builds dO = a_i g + dpre W', dW1 = dW' Wo^T + db' (x) bo, dWo = dp^T po + W1^T dW', dbo = sum s dp + W1^T db')
     against the per-token order (XNRS_FOLD_TRAIN=0) and oracle autograd: every parameter gradient and the input
     gradient, with and without biases, over live rows and dense, masks with holes, an all-masked and a fully live news."""

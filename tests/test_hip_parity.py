@@ -405,7 +405,7 @@ def test_naml_with_padding_free_encoders_matches_golden():
                                                    (33, 128, 8, 256, True, True), (7, 20, 5, 16, True, False),
                                                    (64, 32, 2, 100, False, True)])
 def test_folded_out_projection_matches_per_token_out_projection(S, D, h, A, bias, with_ids):
-    """Inference folds the attention out-projection behind the pooling (api.hip "fold": fc1 on the O rows with W1.Wo, one
+    """Inference folds the attention out-projection behind the pooling (encoder_fwd.hip "fold": fc1 on the O rows with W1.Wo, one
     Wo product per news after the weighted sum, bias times the sum of the weights) -- exact algebra for every input, a
     different rounding order.  Against the per-token out-projection (XNRS_FOLD_OUT=0, the reference's order) and the
     oracle: news vectors, news mask, with and without biases, the id-gather path, an all-masked and a fully live news,

@@ -310,7 +310,7 @@ def test_shared_projection_is_bitwise_neutral_with_attention_dropout_on(monkeypa
 
 @pytest.mark.parametrize("model_name", ["NRMS", "standard"])
 def test_side_lane_of_the_backward_is_bitwise_neutral(model_name, monkeypatch):
-    """The backward's weight-gradient launches on the library's side stream (api.hip SideLane: forked from and joined back
+    """The backward's weight-gradient launches on the library's side stream (encoder_bwd.hip SideLane: forked from and joined back
     into the caller's stream inside the call) against the same step on one stream: the same launches, so loss and every
     gradient bit for bit -- also when the caller's stream is not the default one, and with nothing but the call's own join
     between the backward and the gradients' first reader (the clone right behind it)."""

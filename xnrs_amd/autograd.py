@@ -481,8 +481,8 @@ def _host_lists(cfg, m, ids, dev):
 
 
 def _device_lists_ok(cfg, x, params) -> bool:
-    """Do the kernels that read their row count on the device serve this call?  (The conditions api.hip checks again:
-    fp32 GEMM mode, D and A multiples of 4, 16-byte aligned input and weights.)"""
+    """Do the kernels that read their row count on the device serve this call?  (The conditions device_counts_ok in
+    encoder_fwd.hip checks again: fp32 GEMM mode, D and A multiples of 4, 16-byte aligned input and weights.)"""
     if hip.get_gemm_mode() != 0 or cfg.D % 4 != 0 or cfg.A % 4 != 0 or cfg.n_seq * cfg.L >= 2 ** 31:
         return False
     if x.data_ptr() % 16 != 0:

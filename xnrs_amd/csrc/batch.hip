@@ -15,7 +15,7 @@
 //                    of the explainer, explain.py:160-166); the encoders themselves gather inside their first load.
 #include <atomic>
 
-#include "kernels.h"
+#include "host.h"
 
 namespace xnrs {
 
@@ -610,3 +610,74 @@ hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_
 }
 
 }  // namespace xnrs
+
+// ---------------------------------------------------------------- C entry points (include/xnrs_hip.h)
+using namespace xnrs;
+
+extern "C" {
+
+size_t xnrs_row_lists_workspace_bytes(int64_t n_seq) { return n_seq > 0 ? align_up((size_t)n_seq * sizeof(int32_t)) : 0; }
+
+int32_t xnrs_build_row_lists(const float* m, const int32_t* ids, int64_t n_seq, int32_t L, int32_t* live_rows,
+                             int32_t* live_src_rows, int32_t* kv_rows, int32_t* kv_src_rows, int64_t* counts, void* ws,
+                             size_t ws_bytes, void* stream) {
+  if (n_seq < 0 || L <= 0 || !m || !live_rows || !kv_rows || !counts) return XNRS_EINVAL;
+  if (ids && (!live_src_rows || !kv_src_rows)) return XNRS_EINVAL;  // a gathered table needs the tokens' table rows
+  if (n_seq * (int64_t)L > 0x7fffffffLL) return XNRS_EUNSUPPORTED;   // int32 row indices
+  if (n_seq == 0) return hip_rc(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
+  if (!ws || ws_bytes < xnrs_row_lists_workspace_bytes(n_seq)) return XNRS_EWORKSPACE;
+  return hip_rc(launch_build_row_lists(m, ids, n_seq, L, live_rows, ids ? live_src_rows : nullptr, kv_rows,
+                                       ids ? kv_src_rows : nullptr, counts, static_cast<int32_t*>(ws), (hipStream_t)stream));
+}
+
+int32_t xnrs_assemble_train_batch(const int64_t* sess, int64_t B, const int64_t* hist_off, const int32_t* hist_val,
+                                  const int64_t* pos_off, const int32_t* pos_val, const int64_t* neg_off,
+                                  const int32_t* neg_val, int32_t l_hist, int32_t n_neg, int32_t pad_row, uint64_t seed,
+                                  int32_t* hist_rows, int32_t* cand_rows, void* stream) {
+  if (B == 0) return XNRS_OK;
+  if (!sess || !hist_off || !pos_off || !neg_off || !hist_rows || !cand_rows || B < 0 || l_hist <= 0 || n_neg < 0)
+    return XNRS_EINVAL;
+  BatchArgs a{};
+  a.sess = sess; a.hist_off = hist_off; a.hist_val = hist_val; a.pos_off = pos_off; a.pos_val = pos_val;
+  a.neg_off = neg_off; a.neg_val = neg_val; a.B = B; a.l_hist = l_hist; a.n_neg = n_neg; a.pad_row = pad_row;
+  a.seed = seed; a.hist_out = hist_rows; a.cand_out = cand_rows;
+  return hip_rc(launch_assemble_train(a, (hipStream_t)stream));
+}
+
+int32_t xnrs_assemble_eval_batch(const int64_t* sess, int64_t B, const int64_t* hist_off, const int32_t* hist_val,
+                                 const int64_t* pos_off, const int32_t* pos_val, const int64_t* neg_off,
+                                 const int32_t* neg_val, int32_t l_hist, int32_t pad_row, const int64_t* cand_off,
+                                 int32_t* hist_rows, int32_t* cand_rows, int32_t* cand_sess, float* targets, void* stream) {
+  if (B == 0) return XNRS_OK;
+  if (!sess || !hist_off || !pos_off || !neg_off || !cand_off || !hist_rows || !cand_rows || !cand_sess || !targets ||
+      B < 0 || l_hist <= 0)
+    return XNRS_EINVAL;
+  BatchArgs a{};
+  a.sess = sess; a.hist_off = hist_off; a.hist_val = hist_val; a.pos_off = pos_off; a.pos_val = pos_val;
+  a.neg_off = neg_off; a.neg_val = neg_val; a.B = B; a.l_hist = l_hist; a.pad_row = pad_row;
+  a.hist_out = hist_rows; a.cand_out = cand_rows; a.cand_off_out = cand_off; a.cand_sess_out = cand_sess;
+  a.targets_out = targets;
+  return hip_rc(launch_assemble_eval(a, (hipStream_t)stream));
+}
+
+int32_t xnrs_gather_rows(const float* table, const int32_t* ids, float* out, int64_t n, int64_t row_floats, void* stream) {
+  if (n == 0) return XNRS_OK;
+  if (!table || !ids || !out || n < 0 || row_floats <= 0) return XNRS_EINVAL;
+  return hip_rc(launch_gather_rows(table, ids, out, n, row_floats, (hipStream_t)stream));
+}
+
+int32_t xnrs_score_csr(const float* vecs, const int32_t* cand_rows, const int32_t* cand_sess, const float* u, float* r,
+                       int64_t n_cand, int32_t E, int32_t relu, void* stream) {
+  if (n_cand == 0) return XNRS_OK;
+  if (!vecs || !cand_rows || !cand_sess || !u || !r || n_cand < 0 || E <= 0) return XNRS_EINVAL;
+  return hip_rc(launch_score_csr(vecs, cand_rows, cand_sess, u, r, n_cand, E, relu, (hipStream_t)stream));
+}
+
+int32_t xnrs_rank_metrics(const float* scores, const float* targets, const int64_t* cand_off, float* out, int64_t B,
+                          void* stream) {
+  if (B == 0) return XNRS_OK;
+  if (!scores || !targets || !cand_off || !out || B < 0) return XNRS_EINVAL;
+  return hip_rc(launch_rank_metrics(scores, targets, cand_off, out, B, (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -1,0 +1,914 @@
+// Forward orchestration of the sequence encoders: the padded pipeline (seq_encode), the host-compacted and the
+// device-compacted padding-free pipelines, the folded out-projection they share, and their extern "C" entry points.
+// No device allocation and no sync: everything is enqueued on the caller's stream into the caller's workspace
+// (hipGraph-capturable).
+//
+// Sequence-encoder pipeline (TextEncoder news_encoding.py:34-60 / UserEncoder user_encoding.py:50-81),
+// per chunk of sequences:
+//   [att]   QKV = x.[Wq|Wk|Wv]^T + b   (one 3-segment MFMA GEMM, optional id-gather on the rows)
+//           O   = softmax(rowmask(QK^T/sqrt(dk))) V          (mha_core, per sequence/head/q-tile)
+//           Y   = O.Wo^T + bo                                  (MFMA GEMM)
+//   [pool]  T   = tanh(Y.W1^T + b1)                            (MFMA GEMM, tanh epilogue)
+//           p   = sum_i a_i Y_i,  a = exp(T.w2+b2)*m / (sum+1e-8)   (additive_pool)  | masked mean
+//   [head]  y   = W4 relu(W3 p + b3) + b4                      (two MFMA GEMMs over all sequences)
+// Short sequences (L <= 32, D <= 320: BASELINE configs[1]) take [att] + [pool] as ONE launch (news_fused.hip).
+//
+// The three pipelines must stay bit for bit equal (tested).  Every stage they share is therefore described ONCE, by the
+// builders below (fc1_pair, qkv_projection, mha_core_args, fc1_product, additive_pool_args, pooled_tail); a pipeline sets
+// only what differs: where its rows come from, where the row count lives, its output block.
+#include "host.h"
+
+using namespace xnrs;
+
+namespace xnrs {
+
+// workspace carve for one chunk
+Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additive, bool head, bool pooled, int64_t chunk,
+               bool train, int n_heads) {
+  Plan p{};
+  if (train) chunk = n_seq > 0 ? n_seq : 1;  // the saved activations of the whole batch live in one carve
+  if (chunk <= 0) chunk = 65536 / L;  // <= 64k token rows per pass: 512 full 128-row GEMM tiles (whole rounds of workgroups)
+  if (chunk > n_seq) chunk = n_seq;
+  if (chunk < 1) chunk = 1;
+  p.chunk = chunk;
+  const size_t rows = (size_t)chunk * L;
+  Carver c;
+  p.off_qkv = c.take_if(att, rows * 3 * (size_t)D * F32);
+  p.off_o = c.take_if(att, rows * (size_t)D * F32);
+  p.off_y = c.take_if(att && pooled, rows * (size_t)D * F32);  // att output when a pooler follows
+  p.off_t = c.take_if(pooled && additive, rows * (size_t)A * F32);
+  // pooled vectors / head hidden of ALL sequences: the head runs once after the chunk loop (two GEMMs over
+  // n_seq rows instead of 2 x n_chunks launches of ~20 workgroups each)
+  p.off_p = c.take_if(pooled && head, (size_t)n_seq * D * F32);
+  p.off_h = c.take_if(pooled && head, (size_t)n_seq * E * F32);
+  p.off_stats = c.take_if(train && att, (size_t)chunk * n_heads * L * 2 * F32);
+  p.off_a = c.take_if(train && additive, rows * F32);
+  // always reserved (15 MB at D = 768), so the plan does not depend on the GEMM mode of the moment
+  size_t pl = 0;
+  if (att) pl += 4 * align_up(split_planes_bytes(D, D));
+  if (pooled && additive) pl += align_up(split_planes_bytes(A, D));
+  p.off_planes = c.take(pl);
+  // fused short-sequence path (news_fused.hip): reserved whenever the shape is eligible, whatever the knobs say
+  // (a size query does not know the head count: it reserves the bound over all of them)
+  NewsFusedPlan nf{};
+  size_t nfb = 0;
+  if (att && additive && !train) {
+    if (n_heads <= 0) nfb = news_fused_img_bound_bytes(L, D, A);
+    else if (news_fused_plan(L, D, n_heads, A, &nf)) nfb = nf.img_bytes;
+  }
+  p.off_nf = c.take_if(nfb != 0, nfb);
+  p.off_nfo = c.take_if(nfb != 0, news_fused_scratch_bytes(L, D));  // its O rows while the out-projection is folded away
+  // folded out-projection ("fold" below): reserved whenever the shape is eligible, whatever the knob says
+  // (training keeps W', b', the pooled O rows and the weight sums for the backward)
+  p.fold = carve_fold(c, att && additive, n_seq, D, A);
+  p.total = c.total();
+  return p;
+}
+
+bool device_counts_ok(const float* x, int D, int A, const xnrs_mha_params* att, const xnrs_additive_params* pool) {
+  auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (!knobs().gemm_buf || gemm_mode() != 0 || D % 4 != 0 || D < 4 || (A > 0 && A % 4 != 0)) return false;
+  if (!al16(x) || (pool && !al16(pool->w1))) return false;
+  if (att && !(al16(att->wq) && al16(att->wk) && al16(att->wv) && al16(att->wo))) return false;
+  return (int64_t)D * D * 4 <= (1ll << 30) && (int64_t)A * D * 4 <= (1ll << 30);
+}
+
+}  // namespace xnrs
+
+namespace {
+
+// ---- "fold": the out-projection behind the pooling (inference).
+// The pooler never needs the attention OUTPUT rows Y_i = Wo O_i + bo one by one (layers.py:154 -> layers.py:60-65):
+//   fc1(Y_i)           = W1 (Wo O_i + bo) + b1 = (W1 Wo) O_i + (W1 bo + b1)            -> scores straight from the O rows
+//   sum_i a_i Y_i      = Wo (sum_i a_i O_i) + bo (sum_i a_i)                             -> ONE out-projection per sequence
+// so the rows x D x D out-projection GEMM (12.4 of 57 ms of the benchmark step) becomes an n_seq x D x D one, plus an
+// A x D x D product for the folded weight per call (0.3 GFLOP; the ABI keeps no state between calls).  Exact algebra for
+// every input -- only the rounding order differs from the reference's (observed <= 2e-6 on the scores, bar 1e-4); the
+// training forward keeps Y (the backward needs it).  XNRS_FOLD_OUT=0 keeps the per-token out-projection.
+// The folded weight is rebuilt per call (the ABI keeps no state): a split-K product over 8 slices and a wave-per-row bias
+// kernel, ~20 us per call at D = 768 -- three short launches.  One impression (1 250 + 250 token rows, three encoder calls)
+// pays ~0.05 ms for that (a single unsliced product cost twice as much); from a few thousand token rows on the fold wins,
+// +25 % at the benchmark batch.  The choice deliberately never depends on the batch size (only the short-title dispatch
+// below does: fused kernel or pipeline by news count) -- a news item's vector must not change in the last bit with the batch
+// it is encoded in (chunking, id gather, skip_empty and the padding-free path are all tested bitwise against the plain
+// path).  Knob (fold_wanted): 0 never, anything else always.
+
+// C[M][D] = X[M][D] . Wo[D][D]: a weight folded behind the out-projection (W1 -> W1.Wo, the head's W0 -> W0.Wo)
+hipError_t fold_product(const float* X, int M, const float* wo, int D, float* C, float* slabs, hipStream_t stream) {
+  GemmArgs g = gemm_kmajor_b(X, D, wo, D, C, D, M, D, D);
+  if (D >= 64 * FOLD_SPLITS) {  // enough contraction to slice: 8 x the workgroups, fixed-order reduce (bitwise reproducible)
+    g.slabs = slabs;
+    g.nsplit = FOLD_SPLITS;
+  }
+  return launch_gemm_f32(g, stream);
+}
+
+// wf = W1 . Wo, bf = W1 . bo + b1.  Returns the fc1 bias to use (nullptr if there is none).
+const float* fold_out_projection(const xnrs_mha_params* att, const xnrs_additive_params* pool, int D, int A, float* wf,
+                                 float* bf, float* slabs, hipStream_t stream, hipError_t* err) {
+  *err = fold_product(pool->w1, A, att->wo, D, wf, slabs, stream);
+  if (*err != hipSuccess || !att->bo) return pool->b1;
+  *err = launch_fold_bias(pool->w1, att->bo, pool->b1, bf, A, D, stream);  // bf = W1 . bo + b1
+  return bf;
+}
+
+// The pooler's first layer as a call runs it: the module's own pair, or -- fold -- the caller's copy of the folded pair
+// (xnrs_fold_weights: nothing to rebuild; training: the backward call is then given the same pair, the saved blob's copy
+// stays unwritten), or the folded pair rebuilt into the workspace.
+struct Fc1 {
+  const float* w;
+  const float* b;
+};
+int32_t fc1_pair(bool fold, const xnrs_mha_params* att, const xnrs_additive_params* pool, int D, void* ws, const FoldRegions& fr,
+                 hipStream_t stream, Fc1* fc1) {
+  *fc1 = Fc1{pool ? pool->w1 : nullptr, pool ? pool->b1 : nullptr};
+  if (!fold) return XNRS_OK;
+  if (pool->w1_folded) {
+    if (att->bo && !pool->b1_folded) return XNRS_EINVAL;
+    *fc1 = Fc1{pool->w1_folded, att->bo ? pool->b1_folded : pool->b1};
+    return XNRS_OK;
+  }
+  hipError_t fe = hipSuccess;
+  fc1->w = at(ws, fr.fw);
+  fc1->b = fold_out_projection(att, pool, D, pool->hidden, at(ws, fr.fw), at(ws, fr.fb), at(ws, fr.fsl), stream, &fe);
+  return hip_rc(fe);
+}
+
+// the fused row dots ride on the raw-buffer-load forward kernel: 16-byte aligned operands
+bool fc1_rowdot_ok(const float* x, bool att, const xnrs_additive_params* pool, int D) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // (rows of any count / any gather: beyond the 1-GB descriptor window or with row ids the launcher takes the
+  // pointer-gather variant of the same kernel)
+  return knobs().fc1_rowdot && knobs().gemm_buf && gemm_mode() == 0 && pool && pool->w2 && D % 4 == 0 && D >= 4 &&
+         al16(pool->w1) && (att || al16(x)) && (int64_t)pool->hidden * D * 4 <= (1ll << 30);
+}
+inline int n_epart(int A) { return (A + 31) / 32; }  // partial fc2 dots per row: one per 32 hidden columns
+
+// ---- the stages every pipeline shares
+// the padding-free pipelines' attention runs on the LDS-staged kernel with compact queries
+int32_t compact_attention_rc(const xnrs_mha_params* att, int S, int D) {
+  if (att->n_heads <= 0 || D % att->n_heads != 0) return XNRS_EHEADS;
+  if (S > 64 || D / att->n_heads > 64 || (D / att->n_heads) % 4 != 0 || D % 4 != 0) return XNRS_EUNSUPPORTED;
+  return XNRS_OK;
+}
+
+// [Q|]K|V = x . [Wq|]Wk|Wv^T + b as ONE multi-segment product into the row-major image C of pitch ldc (first = 0: Q|K|V,
+// 1: K|V only).  planes (nullable): the pre-split weights {q, k, v} of the bf16-split modes.
+GemmArgs qkv_projection(const float* x, RowIds rows, const xnrs_mha_params* att, int first, float* C, int64_t ldc, int64_t M,
+                        int D, const unsigned short* const* planes = nullptr) {
+  const float* W[3] = {att->wq, att->wk, att->wv};
+  const float* b[3] = {att->bq, att->bk, att->bv};
+  GemmArgs g = gemm_base(x, D, nullptr, D, C, ldc, M, D, D);
+  g.gather_ids = rows.ids;
+  g.gather_S = rows.S;
+  for (int s = first; s < 3; ++s) {
+    g.W[s - first] = W[s];
+    g.bias[s - first] = b[s];
+    g.Wp[s - first] = planes ? planes[s] : nullptr;
+  }
+  g.ldp = split_plane_ld(D);
+  g.nseg = 3 - first;
+  return g;
+}
+
+// Attention over the K | V columns of a row-major image (k = its K columns, pitch ld; V follows D columns on), one S-row
+// block per sequence.  The caller sets the query source (q; compact queries: q_off / ldq / kv_block), the mask, the
+// dropout seeds, stats and skip_dead.
+// Q/K/V stay a row-major image.  A head-major image (every (sequence, head) block one contiguous S x d_k run) was
+// measured: attention -4 %, but the projection's scattered 64-B stores cost it +2 % -- a net loss at the shipped shape, so
+// it was dropped.
+MhaCoreArgs mha_core_args(const float* k, int64_t ld, const xnrs_mha_params* att, float* out, int64_t n_seq, int S, int D) {
+  MhaCoreArgs ma{};
+  ma.k = k;
+  ma.v = k + D;
+  ma.ld = ld;
+  ma.seq_stride = (int64_t)S * ld;
+  ma.head_stride = D / att->n_heads;
+  ma.out = out;
+  ma.ldo = D;
+  ma.n_seq = n_seq;
+  ma.S = S;
+  ma.n_heads = att->n_heads;
+  ma.d_k = D / att->n_heads;
+  ma.scaled = att->scaled;
+  return ma;
+}
+
+// T = tanh(rows . W1^T + b1) over M rows; rowdot: the fc2 dot per 32 hidden columns straight from the epilogue instead
+// (GemmArgs::rowdot_out; tanh(fc1 x) is never stored, the T region then holds n_epart(A) partial dots per row)
+GemmArgs fc1_product(const float* seq, RowIds rows, Fc1 fc1, float* t, int64_t M, int D, int A, bool rowdot,
+                     const xnrs_additive_params* pool, const unsigned short* planes = nullptr) {
+  GemmArgs g = gemm_linear(seq, rows, D, fc1.w, fc1.b, t, A, M, A, D, XNRS_ACT_TANH, planes);
+  if (rowdot) {
+    g.rowdot_w = pool->w2;
+    g.rowdot_out = t;
+    g.ldrd = n_epart(A);
+  }
+  return g;
+}
+
+// the additive pooler over what fc1_product left in t; the caller sets the row layout (mask / gathers, or row_off /
+// row_ids / poison for compact rows) and the outputs
+AdditivePoolArgs additive_pool_args(const float* t, bool rowdot, const xnrs_additive_params* pool, const float* x, int64_t n_seq,
+                                    int N, int D, int A) {
+  AdditivePoolArgs pa{};
+  pa.t = rowdot ? nullptr : t;
+  pa.epart = rowdot ? t : nullptr;
+  pa.n_epart = n_epart(A);
+  pa.w2 = pool->w2;
+  pa.b2 = pool->b2;
+  pa.x = x;
+  pa.ldx = D;
+  pa.n_seq = n_seq;
+  pa.N = N;
+  pa.D = D;
+  pa.A = A;
+  return pa;
+}
+
+// dst[n] = Wo po[n] + bo s[n]: the out-projection behind the pooling.  fp32 GEMM mode: the bias term rides in the GEMM's
+// epilogue (fmaf(s, bo, acc): the same bits as the separate pass, one launch less); split modes keep the separate pass.
+hipError_t pooled_out_projection(const float* po, const float* s, const xnrs_mha_params* att, float* dst, int64_t n, int D,
+                                 const unsigned short* planes, hipStream_t stream) {
+  GemmArgs g = gemm_linear(po, {}, D, att->wo, nullptr, dst, D, n, D, D, XNRS_ACT_NONE, planes);
+  const bool in_epilogue = att->bo && gemm_mode() == 0;
+  if (in_epilogue) {
+    g.rowscale = s;
+    g.rowscale_vec = att->bo;
+  }
+  hipError_t e = launch_gemm_f32(g, stream);
+  if (e != hipSuccess || !att->bo || in_epilogue) return e;
+  return launch_add_rowscaled_bias(dst, D, s, att->bo, n, D, stream);
+}
+
+// The tail of a pooled encoder call: [out-projection behind the pooling] -> [head].
+//   fold && head && head->w0_folded (inference, fp32 GEMM mode): the out-projection is folded INTO the head's first layer,
+//     W0 (Wo po + bo s) + b0 = (W0 Wo) po + (W0 bo) s + b0 -- the caller's cached pair (xnrs_fold_head_weights) -- and the
+//     n x D x D product disappears (0.31 of the 44.4 ms benchmark step, 13 of the 299 us of configs[1]); the rank-1 term
+//     rides in the GEMM's epilogue like bo s did.  Exact algebra, another rounding order (~1e-6).
+//   otherwise: pooled = Wo po + bo s, then the head's two layers as written (news_encoding.py:27-31).
+int32_t pooled_tail(bool fold, const float* pob, const float* asum, const xnrs_mha_params* att, const xnrs_head_params* head,
+                    float* pb, float* hb, float* y, int64_t n, int D, int E, const unsigned short* wo_planes, bool train,
+                    hipStream_t stream) {
+  const bool fold_head = fold && head && !train && head->w0_folded && gemm_mode() == 0 && (!att->bo || head->b0_rowvec);
+  if (fold && !fold_head) {
+    ProfScope ps(2, 2.0 * n * (double)D * D, stream);
+    XNRS_TRY(pooled_out_projection(pob, asum, att, head ? pb : y, n, D, wo_planes, stream));
+  }
+  if (head) {
+    ProfScope ps(5, 2.0 * n * ((double)D * E + (double)E * E), stream);
+    GemmArgs g1 = gemm_linear(fold_head ? pob : pb, {}, D, fold_head ? head->w0_folded : head->w0, head->b0, hb, E, n, E, D,
+                              head->activation);
+    if (fold_head && att->bo) {
+      g1.rowscale = asum;
+      g1.rowscale_vec = head->b0_rowvec;
+    }
+    XNRS_TRY(launch_gemm_f32(g1, stream));
+    XNRS_TRY(launch_gemm_f32(gemm_linear(hb, {}, E, head->w2, head->b2, y, E, n, E, E), stream));
+  }
+  return XNRS_OK;
+}
+
+}  // namespace
+
+int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
+  const float *x = r.x, *m = r.m;
+  const int32_t* ids = r.ids;
+  const int64_t n_seq = r.n_seq;
+  const int L = r.L, D = r.D, pool_kind = r.pool_kind;
+  const xnrs_mha_params* att = r.att;
+  const xnrs_additive_params* pool = r.pool;
+  const xnrs_head_params* head = r.head;
+  const bool pooled = r.pooled, train = r.train;
+  float *y = r.y, *a_out = r.a_out, *hm = r.hm;
+  const xnrs_row_lists no_lists{};
+  const xnrs_row_lists* rl = r.rl ? r.rl : &no_lists;
+  const int32_t *live_rows = rl->live_rows, *live_src_rows = rl->live_src_rows, *kv_rows = rl->kv_rows,
+                *kv_src_rows = rl->kv_src_rows;
+  const float* qkv_shared = rl->qkv_shared;
+  // counts on the device (xnrs_row_lists::counts_dev): the list lengths below are then CAPACITIES (every row), the
+  // products over a list read their row count on the device (GemmArgs::m_dev)
+  const int64_t* cnt = rl->counts_dev;
+  const int64_t n_live = cnt ? n_seq * L : rl->n_live, n_kv = cnt ? n_seq * L : rl->n_kv;
+  if (n_seq == 0) return XNRS_OK;
+  if (n_seq < 0 || L <= 0 || D <= 0 || !x || !y) return XNRS_EINVAL;
+  if (att) {
+    if (att->n_heads <= 0 || !att->wq || !att->wk || !att->wv || !att->wo) return XNRS_EINVAL;
+    if (D % att->n_heads != 0) return XNRS_EHEADS;
+    if (L > 128) return XNRS_EUNSUPPORTED;
+  }
+  const bool additive = pooled && pool_kind == XNRS_POOL_ADDITIVE;
+  if (pooled) {
+    if (pool_kind != XNRS_POOL_ADDITIVE && pool_kind != XNRS_POOL_MEAN) return XNRS_EINVAL;
+    if (additive && (!pool || !pool->w1 || !pool->w2 || pool->hidden <= 0)) return XNRS_EINVAL;
+    if (pool_kind == XNRS_POOL_MEAN && !m) return XNRS_EINVAL;
+    if (L > 512) return XNRS_EUNSUPPORTED;
+    if (head && (!head->w0 || !head->w2 || head->out_features <= 0 || head->activation < 0 || head->activation > 2))
+      return XNRS_EINVAL;
+  }
+  if (ids && !m && pooled && pool_kind == XNRS_POOL_MEAN) return XNRS_EINVAL;
+  const int A = additive ? pool->hidden : 0;
+  const int E = (pooled && head) ? head->out_features : D;
+  const Plan p = make_plan(n_seq, L, D, A, E, att != nullptr, additive, pooled && head, pooled, r.chunk, train,
+                           att ? att->n_heads : 0);
+  if (p.total > r.ws_bytes || (p.total > 0 && !r.ws)) return XNRS_EWORKSPACE;
+  void* w = r.ws;
+  float* stats = (train && att) ? at(w, p.off_stats) : nullptr;
+  float* a_save = (train && additive) ? at(w, p.off_a) : nullptr;
+  // (training) the Q|K|V image of another forward over the same input and weights: read it, project nothing (xnrs_row_lists)
+  const bool qkv_given = train && att && qkv_shared;
+  float* qkv = qkv_given ? const_cast<float*>(qkv_shared) : at(w, p.off_qkv);
+  float *o = at(w, p.off_o), *yb = at(w, p.off_y), *t = at(w, p.off_t), *pb = at(w, p.off_p), *hb = at(w, p.off_h);
+
+  // Training forward over the UNMASKED token rows (optional, exact): a masked token row has pooling weight exp(e) * 0, so
+  // its query projection, its out-projection row and its fc1 row never reach the output or any gradient (K and V stay
+  // dense: padded tokens are keys, layers.py:142-144).  Those three products run over the live rows in place (A rows
+  // gathered, C rows scattered through the same list); the dead rows of Q, Y and T are ZEROED first, which keeps every
+  // later consumer -- attention core, pooling, and the backward kernels that read the saved activations -- finite and
+  // exactly as if the rows had been computed and then multiplied by the zero weight.
+  // An attention-FREE additive tower (StandardRec, NAML's views) takes the same list for its one row-parallel product:
+  // fc1 runs over the live token rows of x, T of the masked rows is zero.
+  const bool live = train && additive && m && live_rows && (cnt || (n_live >= 0 && n_live < n_seq * L)) &&
+                    !(ids && !live_src_rows);
+  if (cnt && live && !device_counts_ok(x, D, A, att, pool)) return XNRS_EUNSUPPORTED;
+  const int32_t* lvx = live ? (ids ? live_src_rows : live_rows) : nullptr;  // rows of x (table rows with ids)
+  // ... and K|V over the token rows of the NON-EMPTY news only (kv_rows, optional, exact): the keys and values of a news
+  // are read by that news' own queries alone, and an all-masked news has no live query, so its K and V rows (zeroed
+  // here: its attention rows then come out as finite zeros) reach neither the output nor a gradient.
+  const bool kvl = live && kv_rows && (cnt || (n_kv >= 0 && n_kv < n_seq * L)) && !(ids && !kv_src_rows);
+  const int32_t* kvx = kvl ? (ids ? kv_src_rows : kv_rows) : nullptr;
+
+  // Short sequences go through the fused kernel (below); everything else folds the out-projection behind the pooling.
+  // The predicate covers EVERY precondition of the launch (shape, 16-byte aligned operands, 160 KB of dynamic LDS on the
+  // current device: news_fused_ready), so a batch the kernel cannot take runs on the pipeline instead of failing.
+  NewsFusedArgs f{};
+  bool fused = att && additive && !train && !a_out && att->dropout_p == 0.f && gemm_mode() == 0 &&
+               knobs().news_fused && news_fused_plan(L, D, att->n_heads, A, nullptr) &&
+               (D / att->n_heads) * att->n_heads == D &&
+               (knobs().news_fused == 2 || (L >= 26 && n_seq >= 192));
+  if (fused) {
+    f.x = x; f.ids = ids; f.mask = m;
+    f.wq = att->wq; f.bq = att->bq; f.wk = att->wk; f.bk = att->bk; f.wv = att->wv; f.bv = att->bv;
+    f.wo = att->wo; f.bo = att->bo;
+    f.w1 = pool->w1; f.b1 = pool->b1; f.w2 = pool->w2; f.b2 = pool->b2;
+    f.img = at(w, p.off_nf);
+    f.p = head ? pb : y;
+    f.ldp = D;
+    f.hm = m ? hm : nullptr;
+    f.n_seq = n_seq;
+    f.S = L; f.D = D; f.n_heads = att->n_heads; f.d_k = D / att->n_heads; f.A = A; f.scaled = att->scaled;
+    f.npw = knobs().news_fused_npw ? knobs().news_fused_npw : (n_seq < 512 ? 1 : 2);
+    if (fold_wanted(knobs().fold_out)) {  // the kernel pools the attention rows; Wo is applied once per news below
+      f.fold = 1;
+      f.o_scratch = at(w, p.off_nfo);
+      f.asum = at(w, p.fold.as);
+      f.p = at(w, p.fold.po);
+    }
+    fused = p.off_nf != 0 && news_fused_ready(f);
+  }
+  const bool fold = att && additive && fold_wanted(train ? knobs().fold_train : knobs().fold_out);
+  float *pob = at(w, p.fold.po), *asum = at(w, p.fold.as);
+  // inference, fp32 GEMM mode, 16-byte-aligned shapes the buffer-load kernel serves, no gathered rows: the pooler's fc2
+  // dot is taken in the fc1 epilogue (fc1_product)
+  // (every input path -- dense rows, id gather, padding-free -- takes it, so they stay bitwise equal)
+  const bool rowdot = additive && !train && !fused && fc1_rowdot_ok(x, att != nullptr, pool, D);
+  Fc1 fc1{};
+  XNRS_TRY_RC(fc1_pair(fold, att, additive ? pool : nullptr, D, w, p.fold, stream, &fc1));
+  if (fold && fused) {  // the fused kernel's fc1 image is built from the folded pair
+    f.w1 = fc1.w;
+    f.b1 = fc1.b;
+  }
+
+  // Additive-only towers (no self-attention: StandardRec / BaseRec / NAML / LSTUR news encoders) from a batch that fills
+  // the chip: fc1 + tanh + fc2 + exp + mask + normalise + weighted sum as ONE persistent launch (additive_fused.hip).  Its
+  // result equals the GEMM + pooling pipeline's bit for bit (same MFMA fragments and k order, same reduction orders), so
+  // the choice may depend on the batch size without a news vector ever changing: from two 256-row tiles per CU on the
+  // fused launch wins (tools/bench_af.py, settled clocks: 2 560 news x 50 x 768 -- two tiles per CU -- 0.447 vs 0.469 ms for
+  // the pipeline; 12 800 news -- ten per CU -- 2.13 vs 2.33 ms, i.e. 0.98 of the plain fc1 GEMM of the same shape with the
+  // pooling included); below that the pipeline's smaller tiles fill the chip better.
+  bool afused = !att && additive && !train && !a_out && gemm_mode() == 0 && knobs().additive_fused &&
+                additive_fused_plan(L, D, A, nullptr, nullptr) && rowdot &&
+                (knobs().additive_fused == 2 || additive_fused_tiles(n_seq, L) >= 512);
+  if (afused) {
+    AdditiveFusedArgs af{};
+    af.x = x; af.ids = ids; af.mask = m;
+    af.w1 = pool->w1; af.b1 = pool->b1; af.w2 = pool->w2; af.b2 = pool->b2;
+    af.y = head ? pb : y;
+    af.ldy = D;
+    af.hm = m ? hm : nullptr;
+    af.n_seq = n_seq;
+    af.S = L; af.D = D; af.A = A;
+    afused = additive_fused_ready(af);
+    if (afused) {
+      const double fl = (double)n_seq * (2.0 * L * D * A + 2.0 * L * (A + D));
+      ProfScope ps(3, fl, stream);
+      XNRS_TRY(launch_additive_fused(af, stream));
+    }
+  }
+
+  // bf16-split GEMM modes: split the weights ONCE per call (the chunk loop below reuses them ~20 times per step)
+  const unsigned short* pqkv[3] = {nullptr, nullptr, nullptr};
+  const unsigned short *po = nullptr, *p1 = nullptr;
+  if (gemm_mode() != 0) {
+    char* pw = at<char>(w, p.off_planes);
+    auto prep = [&](const float* W, int N, int K) -> const unsigned short* {
+      unsigned short* dst = reinterpret_cast<unsigned short*>(pw);
+      pw += align_up(split_planes_bytes(N, K));
+      return launch_split_weights(W, N, K, dst, stream) == hipSuccess ? dst : nullptr;
+    };
+    if (att) {
+      pqkv[0] = prep(att->wq, D, D);
+      pqkv[1] = prep(att->wk, D, D);
+      pqkv[2] = prep(att->wv, D, D);
+      po = prep(att->wo, D, D);
+    }
+    if (pooled && additive) p1 = prep(fc1.w, A, D);
+  }
+
+  // Short sequences: attention + additive pooling of ALL sequences in one launch (news_fused.hip); only the pooled
+  // vectors leave the CU.  Inference only (nothing is saved for a backward), fp32 arithmetic only.
+  // Dispatch (measured, tools/bench_news_fused.py at D = 320; profiles/r02_news_fused_dispatch_sweep.txt): a workgroup owns
+  // news padded to 32 token rows each, so the kernel wins from ~26 tokens (<= 19 % padding) upwards and once there are
+  // enough news to fill the CUs -- with 1 news per workgroup (two workgroups per CU) from ~200, with 2 news per workgroup
+  // (every weight fragment feeds 4 row tiles) from 512: 256 x 30 tokens 116 vs 149 us for the pipeline, 512 x 30: 177 vs
+  // 217 us, 1024 x 30: 325 vs 329 us.  From ~1500 news on the pipeline is ahead again since it folds the out-projection
+  // behind the pooling (fold_out_projection above; the fused kernel computes it per token): 2048 x 30: 623 vs 592 us,
+  // 28 160 x 30: 8.2 vs 7.1 ms; 64 x 30: 111 vs 104 us, 1024 x 20: 318 vs 255 us.  XNRS_NEWS_FUSED=2 forces the kernel
+  // for every eligible shape (tests), 0 turns it off.
+  if (fused) {
+    const double fl = (double)n_seq * ((f.fold ? 6.0 : 8.0) * L * D * D + 4.0 * L * L * D + 2.0 * L * D * A + 2.0 * L * (A + D));
+    ProfScope ps(6, fl, stream);
+    XNRS_TRY(launch_news_fused(f, stream));
+  }
+  for (int64_t c0 = 0; !fused && !afused && c0 < n_seq; c0 += p.chunk) {
+    const int64_t nc = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
+    const int64_t rows = nc * L;
+    // this chunk's view of the inputs
+    const int32_t* cids = ids ? ids + c0 : nullptr;
+    const float* cx = ids ? x : x + c0 * (int64_t)L * D;      // table stays whole when gathering
+    const float* cm = m ? (ids ? m : m + c0 * (int64_t)L) : nullptr;
+
+    const float* seq = cx;            // what the pooler sees
+    const int32_t* seq_ids = cids;    // gather for the pooler's value rows
+    if (att) {
+      const int64_t ld3 = 3 * (int64_t)D;
+      if (qkv_given) {
+        // nothing to project
+      } else if (live) {  // K|V of every row (kvl: of the rows of the non-empty news), Q of the live rows only (dead rows = 0)
+        const double nl = (double)prof_count(0, cnt, 0, n_live, stream), nkv = (double)prof_count(0, cnt, 1, n_kv, stream);
+        ProfScope ps(0, 2.0 * (kvl ? nkv : rows) * 2.0 * D * D + 2.0 * nl * (double)D * D, stream);
+        GemmArgs g = qkv_projection(cx, {cids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
+        if (kvl) {
+          XNRS_TRY(launch_zero_dead_qkv(qkv, cm, cids, nc, L, D, stream));
+          g.gather_ids = kvx;
+          g.gather_S = 1;
+          g.c_scatter = 1;
+          g.c_scatter_ids = kv_rows;
+          g.M = n_kv;
+          g.m_dev = cnt ? cnt + 1 : nullptr;
+          g.m_fill_hint = 0.6f;
+          if (n_kv > 0) XNRS_TRY(launch_gemm_f32(g, stream));
+        } else {
+          XNRS_TRY(launch_gemm_f32(g, stream));
+          XNRS_TRY(launch_zero_cols(qkv, ld3, D, rows, stream));
+        }
+        if (n_live > 0) {
+          GemmArgs q = gemm_linear(cx, {lvx, 1}, D, att->wq, att->bq, qkv, ld3, n_live, D, D, XNRS_ACT_NONE, pqkv[0]);
+          q.c_scatter = 1;
+          q.c_scatter_ids = live_rows;
+          q.m_dev = cnt;
+          q.m_fill_hint = 0.4f;
+          XNRS_TRY(launch_gemm_f32(q, stream));
+        }
+      } else {
+        ProfScope ps(0, 2.0 * rows * 3.0 * D * D, stream);
+        XNRS_TRY(launch_gemm_f32(qkv_projection(cx, {cids, L}, att, 0, qkv, ld3, rows, D, pqkv), stream));
+      }
+
+      MhaCoreArgs ma = mha_core_args(qkv + D, ld3, att, o, nc, L, D);
+      ma.q = qkv;
+      ma.mask = cm;
+      ma.mask_gather_ids = cids;
+      ma.dropout_p = att->dropout_p;
+      ma.seed = att->seed + (uint64_t)c0 * 0x9E3779B97F4A7C15ull;
+      ma.seed_dev = att->seed_dev;
+      ma.stats = stats;
+      // an all-masked sequence: zeros instead of attention over keys nobody weights (kernels.h).  Training over row lists,
+      // and (round 4) every POOLED call with a mask: both poolers multiply a masked row by exactly 0 (layers.py:33,62-65), so
+      // the pooled vector is bit for bit the same whether such a row holds the uniform average of V or zeros -- the empty
+      // history slots of the benchmark batch (49.5 % of its news) cost the attention core nothing.  MultiHeadAttention
+      // alone (pooled == false) returns its masked rows to the caller and computes them.
+      ma.skip_dead = (live || (pooled && cm && knobs().mha_skip_masked)) ? 1 : 0;
+      {
+        ProfScope ps(1, 4.0 * rows * (double)L * D, stream);
+        XNRS_TRY(launch_mha_core(ma, stream));
+      }
+
+      float* dst = pooled ? yb : y + c0 * (int64_t)L * D;
+      if (fold) {
+        dst = o;  // the pooler works on the O rows (fold_out_projection); masked rows of O are finite and carry weight 0
+      } else if (live) {
+        ProfScope ps(2, 2.0 * (double)prof_count(2, cnt, 0, n_live, stream) * (double)D * D, stream);
+        XNRS_TRY(hipMemsetAsync(dst, 0, (size_t)rows * D * sizeof(float), stream));
+        if (n_live > 0) {
+          GemmArgs og = gemm_linear(o, {live_rows, 1}, D, att->wo, att->bo, dst, D, n_live, D, D, XNRS_ACT_NONE, po);
+          og.c_scatter = 1;
+          og.m_dev = cnt;
+          og.m_fill_hint = 0.4f;
+          XNRS_TRY(launch_gemm_f32(og, stream));
+        }
+      } else {
+        ProfScope ps(2, 2.0 * rows * (double)D * D, stream);
+        XNRS_TRY(launch_gemm_f32(gemm_linear(o, {}, D, att->wo, att->bo, dst, D, rows, D, D, XNRS_ACT_NONE, po), stream));
+      }
+      seq = dst;
+      seq_ids = nullptr;
+    }
+    if (!pooled) continue;
+
+    float* pooled_dst = (head ? pb : y) + c0 * (int64_t)D;
+    float* hm_dst = hm ? hm + c0 : nullptr;
+    if (additive) {
+      if (live) {  // with attention seq is the dense attention output; without, the rows of x (table rows with ids: lvx)
+        ProfScope ps(3, 2.0 * (double)prof_count(3, cnt, 0, n_live, stream) * (double)D * A, stream);
+        XNRS_TRY(hipMemsetAsync(t, 0, (size_t)rows * A * sizeof(float), stream));
+        if (n_live > 0) {
+          GemmArgs fg = fc1_product(seq, {att ? live_rows : lvx, 1}, fc1, t, n_live, D, A, false, pool, p1);
+          fg.c_scatter = 1;
+          fg.c_scatter_ids = live_rows;
+          fg.m_dev = cnt;
+          fg.m_fill_hint = 0.4f;
+          XNRS_TRY(launch_gemm_f32(fg, stream));
+        }
+      } else {
+        ProfScope ps(3, 2.0 * rows * (double)D * A, stream);
+        XNRS_TRY(launch_gemm_f32(fc1_product(seq, {seq_ids, L}, fc1, t, rows, D, A, rowdot, pool, p1), stream));
+      }
+      AdditivePoolArgs pa = additive_pool_args(t, rowdot, pool, seq, nc, L, D, A);
+      pa.mask = cm;
+      pa.mask_gather_ids = cids;
+      pa.x_gather_ids = seq_ids;
+      pa.y = fold ? pob + c0 * (int64_t)D : pooled_dst;
+      pa.asum_out = fold ? asum + c0 : nullptr;
+      pa.a_out = a_save ? a_save : (a_out ? a_out + c0 * (int64_t)L : nullptr);
+      pa.hm_out = cm ? hm_dst : nullptr;
+      {
+        ProfScope ps(4, 2.0 * rows * (double)(A + D), stream);
+        XNRS_TRY(launch_additive_pool(pa, stream));
+      }
+      if (a_save && a_out)
+        XNRS_TRY(hipMemcpyAsync(a_out, a_save, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    } else {
+      MeanPoolArgs mp{};
+      mp.x = seq;
+      mp.ldx = D;
+      mp.mask = cm;
+      mp.mask_gather_ids = cids;
+      mp.x_gather_ids = seq_ids;
+      mp.y = pooled_dst;
+      mp.hm_out = hm_dst;
+      mp.n_seq = nc;
+      mp.N = L;
+      mp.D = D;
+      {
+        ProfScope ps(4, 2.0 * rows * (double)D, stream);
+        XNRS_TRY(launch_mean_pool(mp, stream));
+      }
+    }
+  }
+  // pooled = Wo (sum_i a_i O_i) + bo (sum_i a_i): one out-projection per sequence (or folded into the head), then the head
+  return pooled_tail(fold, pob, asum, att, pooled ? head : nullptr, pb, hb, y, n_seq, D, E, po, train, stream);
+}
+
+namespace {
+
+// ---- unpadded news encoder (inference): workspace carve
+struct UnpadPlan {
+  size_t off_kv, off_q, off_o, off_y, off_t, off_p, off_h;
+  FoldRegions fold;
+  size_t total;
+};
+UnpadPlan make_unpad_plan(int64_t n_news, int64_t n_valid, int S, int D, int A, int E, bool att, bool head) {
+  UnpadPlan p{};
+  Carver c;
+  const size_t nv = (size_t)(n_valid > 0 ? n_valid : 1);
+  p.off_kv = c.take_if(att, (size_t)n_news * S * 2 * D * F32);
+  p.off_q = c.take_if(att, nv * D * F32);
+  p.off_o = c.take_if(att, nv * D * F32);
+  p.off_y = c.take_if(att, nv * D * F32);
+  p.off_t = c.take(nv * A * F32);
+  p.off_p = c.take_if(head, (size_t)n_news * D * F32);
+  p.off_h = c.take_if(head, (size_t)n_news * E * F32);
+  p.fold = carve_fold(c, att, n_news, D, A);
+  p.total = c.total();
+  return p;
+}
+
+// ---- the padding-free encoder with the row lists built ON THE DEVICE (no host sync: hipGraph-capturable)
+struct CompactPlan {
+  int64_t chunk;
+  size_t off_kv, off_q, off_o, off_t, off_roff, off_live, off_kvs, off_kvb, off_cnt, off_p, off_h;
+  FoldRegions fold;
+  size_t total;
+};
+CompactPlan make_compact_plan(int64_t n_news, int S, int D, int A, int E, bool att, bool head, int64_t chunk) {
+  CompactPlan p{};
+  // default pass: ~262 k token rows (3.2 GB of worst-case scratch at D = 768 -- sized for 288 GB of HBM).  Four times the
+  // padded path's pass: the row counts are only known on the device, so every pass pays the latency of its five launches
+  // even when most of its rows are dead (tools/bench_compact_chunk.py: 95 % empty news 6.1 -> 3.6 ms per 25 600 news,
+  // 50 %: 20.4 -> 18.5 ms; beyond ~10 k news per pass the one-workgroup-per-pass compaction kernel becomes the cost)
+  if (chunk <= 0) chunk = 262144 / S;
+  if (chunk > n_news) chunk = n_news;
+  if (chunk < 1) chunk = 1;
+  p.chunk = chunk;
+  Carver c;
+  const size_t rows = (size_t)chunk * S;  // worst case of a pass: every token live
+  p.off_kv = c.take_if(att, rows * 2 * D * F32);
+  p.off_q = c.take_if(att, rows * D * F32);
+  p.off_o = c.take_if(att, rows * D * F32);
+  p.off_t = c.take(rows * (size_t)n_epart(A) * F32);
+  const size_t passes = (size_t)((n_news + chunk - 1) / chunk);
+  p.off_roff = c.take(passes * ((size_t)chunk + 1) * 8);  // the row lists of EVERY pass (one compaction launch per call)
+  p.off_live = c.take(passes * rows * 4);
+  p.off_kvs = c.take(passes * rows * 4);
+  p.off_kvb = c.take(passes * (size_t)chunk * 4);
+  p.off_cnt = c.take(passes * 3 * 8);  // {live rows, K|V rows, bad-mask flag} per pass
+  p.off_p = c.take_if(head, (size_t)n_news * D * F32);
+  p.off_h = c.take_if(head, (size_t)n_news * E * F32);
+  p.fold = carve_fold(c, att, n_news, D, A);
+  p.total = c.total();
+  return p;
+}
+
+SeqEncode padded_call(const float* x, const float* m, int64_t n_seq, int L, int D, float* y, void* ws, size_t ws_bytes) {
+  SeqEncode r{};
+  r.x = x; r.m = m; r.n_seq = n_seq; r.L = L; r.D = D; r.y = y; r.ws = ws; r.ws_bytes = ws_bytes;
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t xnrs_linear_fwd(const float* x, const int32_t* gather_ids, int32_t gather_S, const float* w, const float* bias,
+                        float* y, int64_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+  if (!x || !w || !y || M < 0 || N <= 0 || K <= 0 || act < 0 || act > 2) return XNRS_EINVAL;
+  if (gather_ids && gather_S <= 0) return XNRS_EINVAL;
+  return hip_rc(launch_gemm_f32(gemm_linear(x, {gather_ids, gather_S}, K, w, bias, y, N, M, N, K, act), (hipStream_t)stream));
+}
+
+size_t xnrs_mha_workspace_bytes(int64_t B, int32_t S, int32_t D) {
+  return make_plan(B, S, D, 0, D, true, false, false, false, 0).total;
+}
+
+int32_t xnrs_mha_fwd(const float* x, const float* m, const xnrs_mha_params* p, float* y, int64_t B, int32_t S, int32_t D,
+                     void* ws, size_t ws_bytes, void* stream) {
+  if (!p) return XNRS_EINVAL;
+  SeqEncode r = padded_call(x, m, B, S, D, y, ws, ws_bytes);
+  r.att = p;
+  return seq_encode(r, (hipStream_t)stream);
+}
+
+size_t xnrs_additive_workspace_bytes(int64_t B, int32_t N, int32_t D, int32_t A) {
+  return make_plan(B, N, D, A, D, false, true, false, true, 0).total;
+}
+
+int32_t xnrs_additive_attention_fwd(const float* x, const float* m, const xnrs_additive_params* p, float* y, float* a_out,
+                                    int64_t B, int32_t N, int32_t D, void* ws, size_t ws_bytes, void* stream) {
+  if (!p) return XNRS_EINVAL;
+  SeqEncode r = padded_call(x, m, B, N, D, y, ws, ws_bytes);
+  r.pooled = true; r.pool_kind = XNRS_POOL_ADDITIVE; r.pool = p; r.a_out = a_out;
+  return seq_encode(r, (hipStream_t)stream);
+}
+
+int32_t xnrs_masked_mean_fwd(const float* x, const float* m, float* y, int64_t B, int32_t N, int32_t D, void* stream) {
+  SeqEncode r = padded_call(x, m, B, N, D, y, nullptr, 0);
+  r.pooled = true; r.pool_kind = XNRS_POOL_MEAN;
+  return seq_encode(r, (hipStream_t)stream);
+}
+
+size_t xnrs_text_encoder_workspace_bytes(int64_t n_news, int32_t S, int32_t D, int32_t A, int32_t E, int32_t has_att,
+                                         int32_t pool_kind, int32_t has_head, int64_t chunk) {
+  return make_plan(n_news, S, D, A, E, has_att != 0, pool_kind == XNRS_POOL_ADDITIVE, has_head != 0, true, chunk).total;
+}
+
+int32_t xnrs_text_encoder_fwd(const float* x, const float* m, const int32_t* ids, int64_t n_news, int32_t S, int32_t D,
+                              const xnrs_mha_params* att, int32_t pool_kind, const xnrs_additive_params* pool,
+                              const xnrs_head_params* head, float* y, float* hm, int64_t chunk, void* ws, size_t ws_bytes,
+                              void* stream) {
+  if (n_news == 0) return XNRS_OK;
+  if (!m) return XNRS_EINVAL;  // TextEncoder always receives a token mask (news_encoding.py:41-50)
+  SeqEncode r = padded_call(x, m, n_news, S, D, y, ws, ws_bytes);
+  r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
+  return seq_encode(r, (hipStream_t)stream);
+}
+
+size_t xnrs_user_encoder_workspace_bytes(int64_t B, int32_t H, int32_t E, int32_t A, int32_t has_att, int32_t pool_kind,
+                                         int32_t has_head) {
+  return make_plan(B, H, E, A, E, has_att != 0, pool_kind == XNRS_POOL_ADDITIVE, has_head != 0, true, 0).total;
+}
+
+int32_t xnrs_user_encoder_fwd(const float* x, const float* m, int64_t B, int32_t H, int32_t E, const xnrs_mha_params* att,
+                              int32_t pool_kind, const xnrs_additive_params* pool, const xnrs_head_params* head, float* y,
+                              float* a_out, void* ws, size_t ws_bytes, void* stream) {
+  SeqEncode r = padded_call(x, m, B, H, E, y, ws, ws_bytes);
+  r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.a_out = a_out;
+  return seq_encode(r, (hipStream_t)stream);
+}
+
+size_t xnrs_text_encoder_unpadded_workspace_bytes(int64_t n_news, int64_t n_valid, int32_t S, int32_t D, int32_t A,
+                                                  int32_t E, int32_t has_att, int32_t has_head) {
+  return make_unpad_plan(n_news, n_valid, S, D, A, E, has_att != 0, has_head != 0).total;
+}
+
+int32_t xnrs_text_encoder_fwd_unpadded(const float* x, const int32_t* ids, int64_t n_news, int32_t S, int32_t D,
+                                       const int32_t* rows, const int64_t* row_off, int64_t n_valid,
+                                       const xnrs_mha_params* att, const xnrs_additive_params* pool,
+                                       const xnrs_head_params* head, float* y, float* hm, void* ws, size_t ws_bytes,
+                                       void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n_news == 0) return XNRS_OK;
+  if (!x || !row_off || !pool || !y || n_news < 0 || n_valid < 0 || S <= 0 || D <= 0 || (n_valid > 0 && !rows))
+    return XNRS_EINVAL;
+  if (S > 512) return XNRS_EUNSUPPORTED;
+  const int A = pool->hidden, E = head ? head->out_features : D;
+  if (att) XNRS_TRY_RC(compact_attention_rc(att, S, D));
+  const UnpadPlan p = make_unpad_plan(n_news, n_valid, S, D, A, E, att != nullptr, head != nullptr);
+  if (p.total > 0 && (!ws || ws_bytes < p.total)) return XNRS_EWORKSPACE;
+  float *kv = at(ws, p.off_kv), *qc = at(ws, p.off_q), *oc = at(ws, p.off_o), *yc = at(ws, p.off_y), *tc = at(ws, p.off_t);
+  float *pb = at(ws, p.off_p), *hb = at(ws, p.off_h), *pob = at(ws, p.fold.po), *asum = at(ws, p.fold.as);
+  const int64_t rows_all = n_news * (int64_t)S;
+
+  const float* vals = x;          // what the pooler weights: compact y rows, or x rows through `rows`
+  const int32_t* val_ids = rows;
+  const bool fold = att && fold_wanted(knobs().fold_out);
+  Fc1 fc1{};
+  XNRS_TRY_RC(fc1_pair(fold, att, pool, D, ws, p.fold, stream, &fc1));
+  if (att) {
+    {  // K and V of EVERY token row: padded tokens stay keys (QUERY-row mask, layers.py:142-144)
+      ProfScope ps(0, 2.0 * rows_all * 2.0 * D * D + 2.0 * n_valid * (double)D * D, stream);
+      XNRS_TRY(launch_gemm_f32(qkv_projection(x, {ids, S}, att, 1, kv, 2 * (int64_t)D, rows_all, D), stream));
+      // Q of the live rows only (row gather through `rows`)
+      if (n_valid > 0) XNRS_TRY(launch_gemm_f32(gemm_linear(x, {rows, 1}, D, att->wq, att->bq, qc, D, n_valid, D, D), stream));
+    }
+    if (n_valid > 0) {
+      MhaCoreArgs ma = mha_core_args(kv, 2 * (int64_t)D, att, oc, n_news, S, D);
+      ma.q = qc;
+      ma.q_off = row_off;
+      ma.ldq = D;
+      {
+        ProfScope ps(1, 4.0 * n_valid * (double)S * D, stream);
+        XNRS_TRY(launch_mha_core(ma, stream));
+      }
+      if (!fold) {
+        ProfScope ps(2, 2.0 * n_valid * (double)D * D, stream);
+        XNRS_TRY(launch_gemm_f32(gemm_linear(oc, {}, D, att->wo, att->bo, yc, D, n_valid, D, D), stream));
+      }
+    }
+    vals = fold ? oc : yc;
+    val_ids = nullptr;
+  }
+  const bool rowdot = fc1_rowdot_ok(x, att != nullptr, pool, D);
+  if (n_valid > 0) {
+    ProfScope ps(3, 2.0 * n_valid * (double)D * A, stream);
+    XNRS_TRY(launch_gemm_f32(fc1_product(vals, {val_ids, 1}, fc1, tc, n_valid, D, A, rowdot, pool), stream));
+  }
+  AdditivePoolArgs pa = additive_pool_args(tc, rowdot, pool, vals, n_news, S, D, A);
+  pa.row_off = row_off;
+  pa.row_ids = val_ids;
+  pa.y = fold ? pob : (head ? pb : y);
+  pa.asum_out = fold ? asum : nullptr;
+  pa.hm_out = hm;
+  {
+    ProfScope ps(4, 2.0 * n_valid * (double)(A + D), stream);
+    XNRS_TRY(launch_additive_pool(pa, stream));
+  }
+  return pooled_tail(fold, pob, asum, att, head, pb, hb, y, n_news, D, E, nullptr, false, stream);
+}
+
+size_t xnrs_text_encoder_compact_workspace_bytes(int64_t n_news, int32_t S, int32_t D, int32_t A, int32_t E, int32_t has_att,
+                                                 int32_t has_head, int64_t chunk) {
+  return make_compact_plan(n_news, S, D, A, E, has_att != 0, has_head != 0, chunk).total;
+}
+
+int32_t xnrs_text_encoder_fwd_compact(const float* x, const float* m, const int32_t* ids, int64_t n_news, int32_t S, int32_t D,
+                                      const xnrs_mha_params* att, const xnrs_additive_params* pool, const xnrs_head_params* head,
+                                      float* y, float* hm, int64_t chunk, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n_news == 0) return XNRS_OK;
+  if (!x || !m || !pool || !pool->w1 || !pool->w2 || !y || n_news < 0 || S <= 0 || D <= 0 || pool->hidden <= 0) return XNRS_EINVAL;
+  if (S > 512) return XNRS_EUNSUPPORTED;
+  const int A = pool->hidden, E = head ? head->out_features : D;
+  if (att) {
+    XNRS_TRY_RC(compact_attention_rc(att, S, D));
+    if (att->dropout_p != 0.f) return XNRS_EUNSUPPORTED;  // inference only
+  }
+  // the device row counts ride on the fp32 forward kernel with the fc2 dot in its epilogue (what the padded and the
+  // host-compacted paths run too: the three stay bitwise equal)
+  if (gemm_mode() != 0 || !fc1_rowdot_ok(x, att != nullptr, pool, D)) return XNRS_EUNSUPPORTED;
+  const CompactPlan p = make_compact_plan(n_news, S, D, A, E, att != nullptr, head != nullptr, chunk);
+  if (!ws || ws_bytes < p.total) return XNRS_EWORKSPACE;
+  float *kv = at(ws, p.off_kv), *qc = at(ws, p.off_q), *oc = at(ws, p.off_o), *tc = at(ws, p.off_t);
+  int64_t *roff0 = at<int64_t>(ws, p.off_roff), *cnt0 = at<int64_t>(ws, p.off_cnt);
+  int32_t *live0 = at<int32_t>(ws, p.off_live), *kvs0 = at<int32_t>(ws, p.off_kvs), *kvb0 = at<int32_t>(ws, p.off_kvb);
+  float *pb = at(ws, p.off_p), *hb = at(ws, p.off_h), *pob = at(ws, p.fold.po), *asum = at(ws, p.fold.as);
+  const bool fold = att && fold_wanted(knobs().fold_out);
+  Fc1 fc1{};
+  XNRS_TRY_RC(fc1_pair(fold, att, pool, D, ws, p.fold, stream, &fc1));
+  if (att && !fold) return XNRS_EUNSUPPORTED;  // (the per-token out-projection order: use the host-compacted entry point)
+  XNRS_TRY(launch_compact_rows(m, ids, n_news, p.chunk, S, roff0, live0, kvs0, kvb0, cnt0, stream));
+  for (int64_t c0 = 0; c0 < n_news; c0 += p.chunk) {
+    const int64_t nc = (n_news - c0 < p.chunk) ? (n_news - c0) : p.chunk;
+    const int64_t rows = nc * S;  // worst case
+    const int64_t pass = c0 / p.chunk;
+    const int64_t* cnt = cnt0 + 3 * pass;
+    const int64_t* roff = roff0 + pass * (p.chunk + 1);
+    const int32_t* live = live0 + pass * p.chunk * S;
+    const int32_t* kvs = kvs0 + pass * p.chunk * S;
+    const int32_t* kvb = kvb0 + pass * p.chunk;
+    const float* vals = x;           // what the pooler weights: compact O rows, or x rows through `live`
+    const int32_t* val_ids = live;
+    if (att) {
+      {  // K and V of every token of the news that have a live token: rows gathered through the device list, written as
+         // consecutive S-row blocks (the attention kernel finds a news' block through kv_block: no row scatter)
+        GemmArgs g = qkv_projection(x, {kvs, 1}, att, 1, kv, 2 * (int64_t)D, rows, D);
+        g.m_dev = cnt + 1;
+        ProfScope ps(0, 2.0 * rows * 3.0 * D * D, stream);  // (worst case: the row counts live on the device)
+        XNRS_TRY(launch_gemm_f32(g, stream));
+        GemmArgs q = gemm_linear(x, {live, 1}, D, att->wq, att->bq, qc, D, rows, D, D);
+        q.m_dev = cnt;
+        XNRS_TRY(launch_gemm_f32(q, stream));
+      }
+      MhaCoreArgs ma = mha_core_args(kv, 2 * (int64_t)D, att, oc, nc, S, D);
+      ma.q = qc;
+      ma.q_off = roff;
+      ma.ldq = D;
+      ma.kv_block = kvb;
+      {
+        ProfScope ps(1, 4.0 * rows * (double)S * D, stream);
+        XNRS_TRY(launch_mha_core(ma, stream));
+      }
+      vals = oc;
+      val_ids = nullptr;
+    }
+    {
+      ProfScope ps(3, 2.0 * rows * (double)D * A, stream);
+      GemmArgs fg = fc1_product(vals, {val_ids, 1}, fc1, tc, rows, D, A, true, pool);
+      fg.m_dev = cnt;
+      XNRS_TRY(launch_gemm_f32(fg, stream));
+    }
+    AdditivePoolArgs pa = additive_pool_args(tc, true, pool, vals, nc, S, D, A);
+    pa.row_off = roff;
+    pa.row_ids = val_ids;
+    pa.poison = cnt + 2;  // a mask value other than 0 / 1: NaN out, not a silently different result
+    pa.y = (fold ? pob : (head ? pb : y)) + c0 * (int64_t)D;
+    pa.asum_out = fold ? asum + c0 : nullptr;
+    pa.hm_out = hm ? hm + c0 : nullptr;
+    {
+      ProfScope ps(4, 2.0 * rows * (double)(A + D), stream);
+      XNRS_TRY(launch_additive_pool(pa, stream));
+    }
+  }
+  XNRS_TRY_RC(pooled_tail(fold, pob, asum, att, head, pb, hb, y, n_news, D, E, nullptr, false, stream));
+  // a mask value other than 0 / 1 in any pass: NaN over the whole result (a ReLU head would swallow a NaN fed in earlier)
+  const int n_pass = (int)((n_news + p.chunk - 1) / p.chunk);
+  XNRS_TRY(launch_poison(y, n_news * (int64_t)E, cnt0 + 2, n_pass, 3, stream));
+  if (hm) XNRS_TRY(launch_poison(hm, n_news, cnt0 + 2, n_pass, 3, stream));
+  return XNRS_OK;
+}
+
+size_t xnrs_fold_weights_workspace_bytes(int32_t D, int32_t A) {
+  return D > 0 && A > 0 ? align_up((size_t)FOLD_SPLITS * A * D * sizeof(float)) : 0;
+}
+
+int32_t xnrs_fold_weights(const xnrs_mha_params* att, const xnrs_additive_params* pool, int32_t D, float* w1f, float* b1f,
+                          void* ws, size_t ws_bytes, void* stream) {
+  if (!att || !pool || !att->wo || !pool->w1 || pool->hidden <= 0 || D <= 0 || !w1f || !b1f) return XNRS_EINVAL;
+  if (ws_bytes < xnrs_fold_weights_workspace_bytes(D, pool->hidden) || !ws) return XNRS_EWORKSPACE;
+  hipError_t fe = hipSuccess;
+  const float* b = fold_out_projection(att, pool, D, pool->hidden, w1f, b1f, static_cast<float*>(ws), (hipStream_t)stream, &fe);
+  XNRS_TRY(fe);
+  if (b != b1f) {  // no out-projection bias: b1 as it is (or zeros)
+    if (pool->b1) XNRS_TRY(hipMemcpyAsync(b1f, pool->b1, (size_t)pool->hidden * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else XNRS_TRY(hipMemsetAsync(b1f, 0, (size_t)pool->hidden * sizeof(float), (hipStream_t)stream));
+  }
+  return XNRS_OK;
+}
+
+size_t xnrs_fold_head_weights_workspace_bytes(int32_t D, int32_t E) {  // (unaligned, unlike xnrs_fold_weights_workspace_bytes)
+  return (D > 0 && E > 0) ? (size_t)FOLD_SPLITS * (size_t)E * (size_t)D * sizeof(float) : 0;
+}
+
+int32_t xnrs_fold_head_weights(const xnrs_mha_params* att, const xnrs_head_params* head, int32_t D, float* w0f, float* b0v,
+                               void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!att || !head || !att->wo || !head->w0 || !w0f || D <= 0 || head->out_features <= 0) return XNRS_EINVAL;
+  if (att->bo && !b0v) return XNRS_EINVAL;
+  const int E = head->out_features;
+  if (ws_bytes < xnrs_fold_head_weights_workspace_bytes(D, E) || !ws) return XNRS_EWORKSPACE;
+  XNRS_TRY(fold_product(head->w0, E, att->wo, D, w0f, static_cast<float*>(ws), stream));  // w0f = W0 . Wo
+  if (att->bo) XNRS_TRY(launch_fold_bias(head->w0, att->bo, nullptr, b0v, E, D, stream));  // b0v = W0 . bo
+  return XNRS_OK;
+}
+
+}  // extern "C"

@@ -707,7 +707,7 @@ hipError_t launch_zero_cols(float* p, int64_t ld, int width, int64_t rows, hipSt
   return hipGetLastError();
 }
 
-// The rows of a [n_seq*L, 3D] Q|K|V image that the live-row / kv-row projections (api.hip, xnrs_row_lists) leave unwritten,
+// The rows of a [n_seq*L, 3D] Q|K|V image that the live-row / kv-row projections (encoder_fwd.hip, xnrs_row_lists) leave unwritten,
 // zeroed by the mask itself (fp32 [.., L], optionally through news ids): the Q columns of every masked token row, and the
 // K|V columns of every row of an all-masked sequence.  One workgroup per sequence; writes 0.37 instead of 0.74 GB at the
 // grad step's 80 000 x 2304 image (zero_cols over the whole image: 0.14 ms per encode).

@@ -1,4 +1,4 @@
-// Internal launcher declarations shared by the .hip translation units of libxnrs_hip.so.
+// Internal launcher declarations shared by the .hip translation units of libxnrs_hip.so (host-side helpers: host.h).
 // gfx950 (MI355X / CDNA4) only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@ struct Knobs {
   long long split_min_tiles = 512;  // XNRS_GEMM_SPLIT_MIN_TILES: smallest launch the bf16-split kernel takes
   bool fc1_rowdot = true;       // XNRS_FC1_ROWDOT=0: inference materialises tanh(fc1 x) and the pooling kernel takes the fc2 dot
   int fold_train = 1;           // XNRS_FOLD_TRAIN=0: the training forward / backward keep the per-token out-projection
-  int fold_out = 1;             // XNRS_FOLD_OUT=0: inference keeps the per-token out-projection (api.hip "fold")
+  int fold_out = 1;             // XNRS_FOLD_OUT=0: inference keeps the per-token out-projection (encoder_fwd.hip "fold")
   int gemm_dw = 2;              // XNRS_GEMM_DW: weight gradients on gemm_dw.hip -- 0 none, 1 the live-row launches, 2 (default) those +
                                 // the dense ones that take its 256 x 256 tile, 3 every eligible launch (tests)
   int gemm_dw_tile = 256;       // XNRS_GEMM_DW_TILE=128: never the 256 x 256 tile of gemm_dw.hip
@@ -39,7 +39,7 @@ struct Knobs {
   int additive_fused = 1;       // XNRS_ADDITIVE_FUSED=0|2: never / whenever eligible use the one-launch additive encoder
                                 // (additive_fused.hip); 1 = from a batch that fills the chip (results are bitwise equal)
   int af_fbuf = 1;              // XNRS_AF_FBUF=1|2: MFMA fragment register sets of that kernel
-  bool bwd_side_stream = true;  // XNRS_BWD_SIDE_STREAM=0: the backward's weight-gradient products stay on the caller's stream (api.hip: SideLane)
+  bool bwd_side_stream = true;  // XNRS_BWD_SIDE_STREAM=0: the backward's weight-gradient products stay on the caller's stream (encoder_bwd.hip: SideLane)
   long long bwd_side_min_rows = 0;  // XNRS_BWD_SIDE_MIN_ROWS: ... for attention towers of at least this many token rows
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
@@ -192,7 +192,7 @@ struct MhaCoreArgs {
   const int32_t* kv_block;
   // 1 (optional, with mask; pair kernel only, ignored elsewhere): a sequence whose query rows are ALL masked is not
   // computed -- its output rows are written as zeros and its statistics as those of masked rows {-1e9, S}.  For callers
-  // whose consumers give masked rows a zero weight (the training forward over live rows, api.hip): such rows reach
+  // whose consumers give masked rows a zero weight (the training forward over live rows, encoder_fwd.hip): such rows reach
   // neither the output nor a gradient, and with K = V = 0 (xnrs_row_lists) zeros are what the kernel would compute.
   int32_t skip_dead;
 };
@@ -371,7 +371,7 @@ struct NewsFusedArgs {
   int32_t S, D, n_heads, d_k, A, scaled;
   int32_t npw;         // news per workgroup: 2 (default, 0 means 2) or 1
   int32_t tanh_act;    // filled in by the launcher: 2 = ocml tanhf, 3 = fast_tanh (knob)
-  // fold (api.hip "fold": the out-projection behind the pooling): w1 / b1 are then the FOLDED fc1 (W1.Wo, W1.bo + b1), the
+  // fold (encoder_fwd.hip "fold": the out-projection behind the pooling): w1 / b1 are then the FOLDED fc1 (W1.Wo, W1.bo + b1), the
   // kernel skips the out-projection, pools the attention rows O and emits p = sum_i a_i O_i and asum = sum_i a_i; the
   // caller applies Wo once per news.  o_scratch: news_fused_scratch_bytes() of L2-resident scratch (the O tiles of a
   // workgroup's news are parked there while the token rows still occupy LDS).
@@ -440,7 +440,7 @@ struct AdditivePoolArgs {
                            // could not check without a sync was violated: launch_compact_rows saw a non-0/1 mask)
 };
 hipError_t launch_additive_pool(const AdditivePoolArgs& a, hipStream_t stream);
-// p[n][d] += s[n] * b[d]   (the out-projection bias behind a pooled out-projection, api.hip "fold")
+// p[n][d] += s[n] * b[d]   (the out-projection bias behind a pooled out-projection, encoder_fwd.hip "fold")
 // bf[a] = W1[a,:] . bo + b1[a]  (b1 nullable): the fc1 bias behind a folded out-projection
 hipError_t launch_fold_bias(const float* w1, const float* bo, const float* b1, float* bf, int A, int D, hipStream_t stream);
 hipError_t launch_add_rowscaled_bias(float* p, int64_t ld, const float* s, const float* b, int64_t n, int D, hipStream_t stream);

@@ -2,7 +2,7 @@
 //   TextEncoder.forward   xnrs/models/components/news_encoding.py:48-54   (att -> pooler; the MLP head stays a GEMM pair)
 //   MultiHeadAttention    xnrs/models/components/layers.py:128-154        (Q/K/V projection, row-masked softmax, PV, out)
 //   AdditiveAttention     xnrs/models/components/layers.py:60-65          (fc1, tanh, fc2, exp, mask, normalise, sum)
-// BASELINE configs[1] (1024 news x 30 tokens, D = 300 / 320): the six-launch pipeline of api.hip runs at 0.50-0.54
+// BASELINE configs[1] (1024 news x 30 tokens, D = 300 / 320): the six-launch pipeline of encoder_fwd.hip runs at 0.50-0.54
 // of the fp32 matrix peak there because every stage is a few dozen microseconds of partially filled tiles.
 //
 // Decomposition.  A workgroup of 8 waves owns one CU and NPW = 2 news = 4 tiles of 16 token rows, and keeps them on

@@ -7,8 +7,7 @@
 //   query_reduce           : dq[r] = sum over the sequences s with q_idx[s] == r of dq_s, in sequence order
 //   embedding_grad_sparse  : nn.Embedding backward as a dense table, one workgroup per id (zero fill + the rows in the batch)
 // The C entry points at the bottom compose these with the library's own GEMM entry points.
-#include "kernels.h"
-#include "../../include/xnrs_hip.h"
+#include "host.h"
 
 namespace xnrs {
 
@@ -229,19 +228,20 @@ __global__ __launch_bounds__(64) void embedding_grad_sparse_kernel(const float* 
   }
 }
 
-inline size_t pa_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct PaLayout {  // saved blob of a (training) forward: T | a | p | h1
   size_t t, a, p, h1, total;
 };
 PaLayout pa_layout(int64_t n_seq, int32_t L, int32_t D, int32_t A, int32_t E, int32_t has_head) {
   PaLayout o;
   const int64_t rows = n_seq * L;
-  o.t = 0;
-  o.a = o.t + pa_align((size_t)rows * A * sizeof(float));
-  o.p = o.a + pa_align((size_t)rows * sizeof(float));
-  o.h1 = o.p + (has_head ? pa_align((size_t)n_seq * D * sizeof(float)) : 0);
-  o.total = o.h1 + (has_head ? pa_align((size_t)n_seq * E * sizeof(float)) : 0);
+  Carver c;
+  o.t = c.take((size_t)rows * A * F32);
+  o.a = c.take((size_t)rows * F32);
+  o.p = c.off;  // (without a head nothing is kept here: the pooled vectors are the output)
+  if (has_head) c.take((size_t)n_seq * D * F32);
+  o.h1 = c.off;
+  if (has_head) c.take((size_t)n_seq * E * F32);
+  o.total = c.total();
   return o;
 }
 
@@ -252,19 +252,23 @@ size_t pa_linear_ws(int64_t n_seq, int32_t L, int32_t D, int32_t A, int32_t E, b
     lin = lin > l2 ? lin : l2;
     lin = lin > l0 ? lin : l0;
   }
-  return pa_align(lin);
+  return align_up(lin);
 }
 
-#define PA_TRY(expr)                \
-  do {                              \
-    int32_t _rc = (expr);           \
-    if (_rc != XNRS_OK) return _rc; \
-  } while (0)
-#define PA_HIP(expr)                          \
-  do {                                        \
-    hipError_t _e = (expr);                   \
-    if (_e != hipSuccess) return (int32_t)_e; \
-  } while (0)
+struct PaBwdWs {  // backward workspace: linear-backward scratch (lin bytes) | dpre | dq per sequence | dh1 | dp  (the last two: head)
+  size_t lin, dpre, dq_seq, dh1, dpb, total;
+};
+PaBwdWs pa_bwd_ws(int64_t n_seq, int32_t L, int32_t D, int32_t A, int32_t E, bool has_head) {
+  PaBwdWs o;
+  o.lin = pa_linear_ws(n_seq, L, D, A, E, has_head);
+  Carver c{o.lin};
+  o.dpre = c.take((size_t)n_seq * L * A * F32);
+  o.dq_seq = c.take((size_t)n_seq * A * F32);
+  o.dh1 = c.take_if(has_head, (size_t)n_seq * E * F32);
+  o.dpb = c.take_if(has_head, (size_t)n_seq * D * F32);
+  o.total = c.total();
+  return o;
+}
 
 int32_t pa_check(const float* x, int64_t n_seq, int32_t L, int32_t D, const xnrs_personalized_params* p,
                  const xnrs_head_params* head) {
@@ -282,11 +286,8 @@ int32_t pa_forward(const float* x, const float* m, const int32_t* ids, int64_t n
                    char* buf, hipStream_t stream) {
   const int32_t A = p->hidden, E = head ? head->out_features : D;
   const PaLayout lo = pa_layout(n_seq, L, D, A, E, head != nullptr);
-  float* T = reinterpret_cast<float*>(buf + lo.t);
-  float* a = reinterpret_cast<float*>(buf + lo.a);
-  float* pooled = head ? reinterpret_cast<float*>(buf + lo.p) : y;
-  float* h1 = reinterpret_cast<float*>(buf + lo.h1);
-  PA_TRY(xnrs_linear_fwd(x, ids, L, p->wx, p->bx, T, n_seq * L, A, D, XNRS_ACT_TANH, stream));  // layers.py:88
+  float *T = at(buf, lo.t), *a = at(buf, lo.a), *pooled = head ? at(buf, lo.p) : y, *h1 = at(buf, lo.h1);
+  XNRS_TRY_RC(xnrs_linear_fwd(x, ids, L, p->wx, p->bx, T, n_seq * L, A, D, XNRS_ACT_TANH, stream));  // layers.py:88
   PersonalizedPoolArgs pa;
   pa.t = T;
   pa.q = p->q;
@@ -305,11 +306,11 @@ int32_t pa_forward(const float* x, const float* m, const int32_t* ids, int64_t n
   pa.D = D;
   pa.A = A;
   hipLaunchKernelGGL(personalized_pool_kernel, dim3((unsigned)n_seq), dim3(PA_THREADS), (size_t)L * sizeof(float), stream, pa);
-  PA_HIP(hipGetLastError());
-  if (a_out) PA_HIP(hipMemcpyAsync(a_out, a, (size_t)n_seq * L * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  XNRS_TRY(hipGetLastError());
+  if (a_out) XNRS_TRY(hipMemcpyAsync(a_out, a, (size_t)n_seq * L * sizeof(float), hipMemcpyDeviceToDevice, stream));
   if (head) {  // news_head (npa.py:22-26): Linear(D,E) - act - Linear(E,E)
-    PA_TRY(xnrs_linear_fwd(pooled, nullptr, 0, head->w0, head->b0, h1, n_seq, E, D, head->activation, stream));
-    PA_TRY(xnrs_linear_fwd(h1, nullptr, 0, head->w2, head->b2, y, n_seq, E, E, XNRS_ACT_NONE, stream));
+    XNRS_TRY_RC(xnrs_linear_fwd(pooled, nullptr, 0, head->w0, head->b0, h1, n_seq, E, D, head->activation, stream));
+    XNRS_TRY_RC(xnrs_linear_fwd(h1, nullptr, 0, head->w2, head->b2, y, n_seq, E, E, XNRS_ACT_NONE, stream));
   }
   return XNRS_OK;
 }
@@ -328,7 +329,7 @@ size_t xnrs_personalized_saved_bytes(int64_t n_seq, int32_t L, int32_t D, int32_
 int32_t xnrs_personalized_fwd(const float* x, const float* m, const int32_t* ids, int64_t n_seq, int32_t L, int32_t D,
                               const xnrs_personalized_params* p, const xnrs_head_params* head, float* y, float* a_out,
                               float* hm, void* ws, size_t ws_bytes, void* stream) {
-  PA_TRY(pa_check(x, n_seq, L, D, p, head));
+  XNRS_TRY_RC(pa_check(x, n_seq, L, D, p, head));
   if (!y) return XNRS_EINVAL;
   if (n_seq == 0) return XNRS_OK;
   const int32_t E = head ? head->out_features : D;
@@ -343,10 +344,7 @@ int32_t xnrs_personalized_fwd_train(const float* x, const float* m, const int32_
 }
 
 size_t xnrs_personalized_bwd_workspace_bytes(int64_t n_seq, int32_t L, int32_t D, int32_t A, int32_t E, int32_t has_head) {
-  const int64_t rows = n_seq * L;
-  return pa_linear_ws(n_seq, L, D, A, E, has_head != 0) + pa_align((size_t)rows * A * sizeof(float)) +
-         pa_align((size_t)n_seq * A * sizeof(float)) +
-         (has_head ? pa_align((size_t)n_seq * E * sizeof(float)) + pa_align((size_t)n_seq * D * sizeof(float)) : 0);
+  return pa_bwd_ws(n_seq, L, D, A, E, has_head != 0).total;
 }
 
 int32_t xnrs_personalized_bwd(const float* x, const int32_t* ids, int64_t n_seq, int32_t L, int32_t D,
@@ -354,7 +352,7 @@ int32_t xnrs_personalized_bwd(const float* x, const int32_t* ids, int64_t n_seq,
                               size_t saved_bytes, const float* dy, float* dx, float* dwx, float* dbx, float* dq, int64_t n_q,
                               const xnrs_head_grads* g_head, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  PA_TRY(pa_check(x, n_seq, L, D, p, head));
+  XNRS_TRY_RC(pa_check(x, n_seq, L, D, p, head));
   if (!saved || !dy || n_q < 0 || n_q >= ((int64_t)1 << 31)) return XNRS_EINVAL;
   if (ids && dx) return XNRS_EINVAL;  // a gathered table gets no gradient
   const int32_t A = p->hidden, E = head ? head->out_features : D;
@@ -364,40 +362,34 @@ int32_t xnrs_personalized_bwd(const float* x, const int32_t* ids, int64_t n_seq,
   const xnrs_head_grads none = {nullptr, nullptr, nullptr, nullptr};
   const xnrs_head_grads& g = (head && g_head) ? *g_head : none;
   if (n_seq == 0) {  // nothing pooled: zero weight / query gradients
-    if (dwx) PA_HIP(hipMemsetAsync(dwx, 0, (size_t)A * D * sizeof(float), stream));
-    if (dbx) PA_HIP(hipMemsetAsync(dbx, 0, (size_t)A * sizeof(float), stream));
-    if (dq && n_q) PA_HIP(hipMemsetAsync(dq, 0, (size_t)n_q * A * sizeof(float), stream));
-    if (g.w0) PA_HIP(hipMemsetAsync(g.w0, 0, (size_t)E * D * sizeof(float), stream));
-    if (g.b0) PA_HIP(hipMemsetAsync(g.b0, 0, (size_t)E * sizeof(float), stream));
-    if (g.w2) PA_HIP(hipMemsetAsync(g.w2, 0, (size_t)E * E * sizeof(float), stream));
-    if (g.b2) PA_HIP(hipMemsetAsync(g.b2, 0, (size_t)E * sizeof(float), stream));
+    if (dwx) XNRS_TRY(hipMemsetAsync(dwx, 0, (size_t)A * D * sizeof(float), stream));
+    if (dbx) XNRS_TRY(hipMemsetAsync(dbx, 0, (size_t)A * sizeof(float), stream));
+    if (dq && n_q) XNRS_TRY(hipMemsetAsync(dq, 0, (size_t)n_q * A * sizeof(float), stream));
+    if (g.w0) XNRS_TRY(hipMemsetAsync(g.w0, 0, (size_t)E * D * sizeof(float), stream));
+    if (g.b0) XNRS_TRY(hipMemsetAsync(g.b0, 0, (size_t)E * sizeof(float), stream));
+    if (g.w2) XNRS_TRY(hipMemsetAsync(g.w2, 0, (size_t)E * E * sizeof(float), stream));
+    if (g.b2) XNRS_TRY(hipMemsetAsync(g.b2, 0, (size_t)E * sizeof(float), stream));
     return XNRS_OK;
   }
-  if (!ws || ws_bytes < xnrs_personalized_bwd_workspace_bytes(n_seq, L, D, A, E, head != nullptr)) return XNRS_EWORKSPACE;
-  const char* sv = static_cast<const char*>(saved);
-  const float* T = reinterpret_cast<const float*>(sv + lo.t);
-  const float* a = reinterpret_cast<const float*>(sv + lo.a);
-  const float* pooled = reinterpret_cast<const float*>(sv + lo.p);
-  const float* h1 = reinterpret_cast<const float*>(sv + lo.h1);
-  const size_t lin = pa_linear_ws(n_seq, L, D, A, E, head != nullptr);
-  char* w = static_cast<char*>(ws);
-  float* dpre = reinterpret_cast<float*>(w + lin);
-  float* dq_seq = reinterpret_cast<float*>(reinterpret_cast<char*>(dpre) + pa_align((size_t)rows * A * sizeof(float)));
-  float* dh1 = reinterpret_cast<float*>(reinterpret_cast<char*>(dq_seq) + pa_align((size_t)n_seq * A * sizeof(float)));
-  float* dpb = reinterpret_cast<float*>(reinterpret_cast<char*>(dh1) + pa_align((size_t)n_seq * E * sizeof(float)));
+  if (!ws || ws_bytes < pa_bwd_ws(n_seq, L, D, A, E, head != nullptr).total) return XNRS_EWORKSPACE;
+  const float *T = at(saved, lo.t), *a = at(saved, lo.a), *pooled = at(saved, lo.p), *h1 = at(saved, lo.h1);
+  const PaBwdWs wl = pa_bwd_ws(n_seq, L, D, A, E, head != nullptr);
+  const size_t lin = wl.lin;
+  void* w = ws;
+  float *dpre = at(ws, wl.dpre), *dq_seq = at(ws, wl.dq_seq), *dh1 = at(ws, wl.dh1), *dpb = at(ws, wl.dpb);
   const bool pool_grads = dx || dwx || dbx || dq;
   const float* dp = dy;
   if (head) {
     const bool below = pool_grads || g.w0 || g.b0;  // does anything need the gradient below the second head layer?
-    PA_TRY(xnrs_linear_bwd(h1, nullptr, 0, head->w2, dy, below ? dh1 : nullptr, g.w2, g.b2, n_seq, E, E, w, lin, stream));
+    XNRS_TRY_RC(xnrs_linear_bwd(h1, nullptr, 0, head->w2, dy, below ? dh1 : nullptr, g.w2, g.b2, n_seq, E, E, w, lin, stream));
     if (!below) return XNRS_OK;
     if (head->activation != XNRS_ACT_NONE) {
       const int64_t n = n_seq * E;
       hipLaunchKernelGGL(personalized_act_bwd_kernel, dim3((unsigned)((n + PA_THREADS - 1) / PA_THREADS)), dim3(PA_THREADS), 0,
                          stream, dh1, h1, n, head->activation);
-      PA_HIP(hipGetLastError());
+      XNRS_TRY(hipGetLastError());
     }
-    PA_TRY(xnrs_linear_bwd(pooled, nullptr, 0, head->w0, dh1, pool_grads ? dpb : nullptr, g.w0, g.b0, n_seq, E, D, w, lin, stream));
+    XNRS_TRY_RC(xnrs_linear_bwd(pooled, nullptr, 0, head->w0, dh1, pool_grads ? dpb : nullptr, g.w0, g.b0, n_seq, E, D, w, lin, stream));
     dp = dpb;
   }
   if (!pool_grads) return XNRS_OK;
@@ -418,17 +410,17 @@ int32_t xnrs_personalized_bwd(const float* x, const int32_t* ids, int64_t n_seq,
   pb.D = D;
   pb.A = A;
   hipLaunchKernelGGL(personalized_pool_bwd_kernel, dim3((unsigned)n_seq), dim3(PA_THREADS), (size_t)2 * L * sizeof(float), stream, pb);
-  PA_HIP(hipGetLastError());
+  XNRS_TRY(hipGetLastError());
   if (dx || dwx || dbx)  // x_fc (layers.py:88): dWx = dpre^T x, dbx = colsum dpre, dx = dpre Wx
-    PA_TRY(xnrs_linear_bwd(x, ids, L, p->wx, dpre, dx, dwx, dbx, rows, A, D, w, lin, stream));
+    XNRS_TRY_RC(xnrs_linear_bwd(x, ids, L, p->wx, dpre, dx, dwx, dbx, rows, A, D, w, lin, stream));
   if (dx) {
     hipLaunchKernelGGL(personalized_dx_add_kernel, dim3((unsigned)rows), dim3(PA_THREADS), 0, stream, a, dp, dx, rows, L, D);
-    PA_HIP(hipGetLastError());
+    XNRS_TRY(hipGetLastError());
   }
   if (dq && n_q > 0) {
     hipLaunchKernelGGL(personalized_query_reduce_kernel, dim3((unsigned)n_q), dim3(128), 0, stream, dq_seq, p->q_idx, n_seq, A, dq,
                        (int64_t)A);
-    PA_HIP(hipGetLastError());
+    XNRS_TRY(hipGetLastError());
   }
   return XNRS_OK;
 }
@@ -440,20 +432,20 @@ int32_t xnrs_embedding_grad_sparse(const float* d_rows, const int32_t* ids, int6
   if (M >= ((int64_t)1 << 31)) return XNRS_EUNSUPPORTED;
   const int64_t n = (int64_t)n_rows * K;
   if ((reinterpret_cast<uintptr_t>(d_table) & 15) != 0) {
-    PA_HIP(hipMemsetAsync(d_table, 0, (size_t)n * sizeof(float), stream));
+    XNRS_TRY(hipMemsetAsync(d_table, 0, (size_t)n * sizeof(float), stream));
   } else {
     const int64_t blocks = (n + 4 * PA_THREADS - 1) / (4 * PA_THREADS);
     hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)blocks), dim3(PA_THREADS), 0, stream, d_table, n);
-    PA_HIP(hipGetLastError());
+    XNRS_TRY(hipGetLastError());
   }
   if (M == 0) return XNRS_OK;
   hipLaunchKernelGGL(embedding_grad_sparse_kernel, dim3((unsigned)M), dim3(64), 0, stream, d_rows, ids, M, K, d_table, n_rows);
-  PA_HIP(hipGetLastError());
+  XNRS_TRY(hipGetLastError());
   return XNRS_OK;
 }
 
 size_t xnrs_embedding_linear_bwd_sparse_workspace_bytes(int64_t M, int32_t N, int32_t K) {
-  return pa_align(xnrs_linear_bwd_workspace_bytes(M, N, K)) + pa_align((size_t)M * K * sizeof(float));
+  return align_up(xnrs_linear_bwd_workspace_bytes(M, N, K)) + align_up((size_t)M * K * F32);  // linear backward | the dense rows dy . W
 }
 
 int32_t xnrs_embedding_linear_bwd_sparse(const float* table, const int32_t* ids, const float* w, const float* dy, float* d_table,
@@ -461,18 +453,18 @@ int32_t xnrs_embedding_linear_bwd_sparse(const float* table, const int32_t* ids,
                                          size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!table || !ids || !w || !dy || M < 0 || N <= 0 || K <= 0 || n_rows <= 0) return XNRS_EINVAL;
-  const size_t s1 = pa_align(xnrs_linear_bwd_workspace_bytes(M, N, K));
+  const size_t s1 = align_up(xnrs_linear_bwd_workspace_bytes(M, N, K));
   if (M == 0) {
-    if (dw) PA_HIP(hipMemsetAsync(dw, 0, (size_t)N * K * sizeof(float), stream));
-    if (db) PA_HIP(hipMemsetAsync(db, 0, (size_t)N * sizeof(float), stream));
+    if (dw) XNRS_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * sizeof(float), stream));
+    if (db) XNRS_TRY(hipMemsetAsync(db, 0, (size_t)N * sizeof(float), stream));
     return d_table ? xnrs_embedding_grad_sparse(nullptr, nullptr, 0, K, d_table, n_rows, stream_) : XNRS_OK;
   }
-  if (!ws || s1 + pa_align((size_t)M * K * sizeof(float)) > ws_bytes) return XNRS_EWORKSPACE;
-  if (dw || db) PA_TRY(xnrs_linear_bwd(table, ids, 1, w, dy, nullptr, dw, db, M, N, K, ws, s1, stream_));
+  if (!ws || xnrs_embedding_linear_bwd_sparse_workspace_bytes(M, N, K) > ws_bytes) return XNRS_EWORKSPACE;
+  if (dw || db) XNRS_TRY_RC(xnrs_linear_bwd(table, ids, 1, w, dy, nullptr, dw, db, M, N, K, ws, s1, stream_));
   if (d_table) {
-    float* d_rows = reinterpret_cast<float*>(static_cast<char*>(ws) + s1);
-    PA_TRY(xnrs_linear_bwd(table, nullptr, 0, w, dy, d_rows, nullptr, nullptr, M, N, K, ws, s1, stream_));  // d_rows = dy W
-    PA_TRY(xnrs_embedding_grad_sparse(d_rows, ids, M, K, d_table, n_rows, stream_));
+    float* d_rows = at(ws, s1);
+    XNRS_TRY_RC(xnrs_linear_bwd(table, nullptr, 0, w, dy, d_rows, nullptr, nullptr, M, N, K, ws, s1, stream_));  // d_rows = dy W
+    XNRS_TRY_RC(xnrs_embedding_grad_sparse(d_rows, ids, M, K, d_table, n_rows, stream_));
   }
   return XNRS_OK;
 }

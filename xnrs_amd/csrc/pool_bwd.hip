@@ -4,7 +4,7 @@
 //   mean_pool_bwd     : autograd of layers.MaskedMean.forward (layers.py:35-36)
 //   colsum            : out[n] = sum_m w[m] * X[m][n]  (bias grads: w == NULL; fc2.weight grad: X = tanh(fc1 x), w = de)
 //   dot_scoring_bwd   : autograd of DotScoring.forward (scoring.py:20-23), plain and L2-normalised
-#include "kernels.h"
+#include "host.h"
 
 namespace xnrs {
 
@@ -425,3 +425,23 @@ hipError_t launch_embedding_grad(const float* d_rows, const int32_t* ids, int64_
 }
 
 }  // namespace xnrs
+
+// ---------------------------------------------------------------- C entry points (include/xnrs_hip.h)
+using namespace xnrs;
+
+extern "C" {
+
+int32_t xnrs_dot_scoring_bwd(const float* u, const float* c, const float* dr, float* du, float* dc, int64_t B, int32_t C,
+                             int32_t E, void* stream) {
+  if (!u || !c || !dr || B < 0 || C <= 0 || E <= 0) return XNRS_EINVAL;
+  return hip_rc(launch_dot_scoring_bwd(u, c, dr, du, dc, B, C, E, (hipStream_t)stream));
+}
+
+int32_t xnrs_dot_scoring_norm_bwd(const float* u, const float* c, const float* dr, float* du, float* dc, int64_t B, int32_t C,
+                                  int32_t E, void* stream) {
+  if (!u || !c || !dr || B < 0 || C <= 0 || E <= 0) return XNRS_EINVAL;
+  if (E > 1024) return XNRS_EUNSUPPORTED;
+  return hip_rc(launch_dot_scoring_norm_bwd(u, c, dr, du, dc, B, C, E, (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@
 //   collapse_mask : xnrs.utils.collaps_mask                           (xnrs/utils.py:74-75)
 //   dot_scoring   : scoring.DotScoring.forward                        (xnrs/models/components/scoring.py:12-23)
 // One workgroup (256 threads) per sequence for the poolers: N <= a few hundred rows of D floats.
-#include "kernels.h"
+#include "host.h"
 
 namespace xnrs {
 
@@ -268,3 +268,21 @@ hipError_t launch_dot_scoring(const float* u, const float* c, float* r, int64_t 
 }
 
 }  // namespace xnrs
+
+// ---------------------------------------------------------------- C entry points (include/xnrs_hip.h)
+using namespace xnrs;
+
+extern "C" {
+
+int32_t xnrs_collapse_mask(const float* m, float* hm, int64_t n_rows, int32_t S, void* stream) {
+  if (!m || !hm || n_rows < 0 || S <= 0) return XNRS_EINVAL;
+  return hip_rc(launch_collapse_mask(m, nullptr, hm, n_rows, S, (hipStream_t)stream));
+}
+
+int32_t xnrs_dot_scoring_fwd(const float* u, const float* c, float* r, int64_t B, int32_t C, int32_t E, int32_t normalize,
+                             void* stream) {
+  if (!u || !c || !r || B < 0 || C <= 0 || E <= 0) return XNRS_EINVAL;
+  return hip_rc(launch_dot_scoring(u, c, r, B, C, E, normalize, (hipStream_t)stream));
+}
+
+}  // extern "C"

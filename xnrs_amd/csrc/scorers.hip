@@ -1,11 +1,11 @@
 // The bilinear and MLP scorers of the reference (xnrs/models/components/scoring.py:41-102) around the existing GEMMs:
 // the dense projections (v = U.W, q = U.W1u^T + b1, p = C.W1c^T and the weight-gradient products) run on
-// launch_gemm_f32 (api.hip); these kernels are the per-pair parts no GEMM does, and the fixed-order reductions.
+// launch_gemm_f32 (the C entry points at the bottom); these kernels are the per-pair parts no GEMM does, and the fixed-order reductions.
 //   bilinear : s[b,n] = v_b . c^_bn + bias                    v_b = W[0]^T u^_b, u^ / c^ optionally L2-normalised
 //   MLP      : s[b,n] = w2 . tanh(q_b + p_bn) + b2            q_b = W1u u_b + b1, p_bn = W1c c_bn
 // fp32 throughout, no atomics: every sum runs in an order fixed by the launch shape alone, which does not depend on
 // the data (the same bits on every run, in a hipGraph replay too).
-#include "kernels.h"
+#include "host.h"
 
 namespace xnrs {
 
@@ -293,3 +293,211 @@ hipError_t launch_colsum_segments(const ColSumSeg* segs, int n_segs, hipStream_t
 }
 
 }  // namespace xnrs
+
+// =================================================================================================
+// C entry points of the bilinear / MLP scorers (scoring.py:41-102): the dense projections on the fp32 GEMM, the per-pair
+// parts on the kernels above
+// =================================================================================================
+using namespace xnrs;
+
+namespace {
+
+// C[M, N] = A[M, K] . op(W) (+ bias): W row-major [N][K] at pitch ldw (w_kn = 0: nn.Linear layout) or [K][N] at pitch ldw
+// (w_kn = 1); one launch, no split-K
+hipError_t sc_gemm(const float* A, int64_t lda, const float* W, int64_t ldw, int w_kn, const float* bias, float* C, int64_t ldc,
+                   int64_t M, int N, int64_t K, hipStream_t stream) {
+  GemmArgs g = w_kn ? gemm_kmajor_b(A, lda, W, ldw, C, ldc, M, N, K) : gemm_linear(A, {}, lda, W, bias, C, ldc, M, N, K);
+  g.bias[0] = bias;
+  g.ldw = ldw;
+  return launch_gemm_f32(g, stream);
+}
+
+// dW[M, N] (pitch ldc) = dY[R, M]^T . X[R, N] over R rows (dY pitch lddy, X pitch ldx); one launch, no split-K
+hipError_t sc_gemm_dw(const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW, int64_t ldc, int M, int N, int64_t R,
+                      hipStream_t stream) {
+  if (R <= 0) return hipMemset2DAsync(dW, (size_t)ldc * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)M, stream);
+  return launch_gemm_f32(gemm_kmajor_ab(dY, lddy, X, ldx, dW, ldc, M, N, R), stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t xnrs_bilinear_scoring_saved_bytes(int64_t B, int32_t E, int32_t normalize) {  // v [B, E] | u^ [B, E] (normalize)
+  if (B < 0 || E <= 0) return 0;
+  return carve_total({(size_t)B * E * F32, normalize ? (size_t)B * E * F32 : 0});
+}
+
+int32_t xnrs_bilinear_scoring_fwd(const float* u, const float* c, const float* w, const float* bias, float* s, int64_t B, int32_t N,
+                                  int32_t E, int32_t normalize, void* saved, size_t saved_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B < 0 || N < 0 || E <= 0) return XNRS_EINVAL;
+  if (B == 0 || N == 0) return XNRS_OK;
+  if (!u || !c || !w || !s) return XNRS_EINVAL;
+  if (!saved || saved_bytes < xnrs_bilinear_scoring_saved_bytes(B, E, normalize)) return XNRS_EWORKSPACE;
+  Carver sv;
+  float* v = at(saved, sv.take((size_t)B * E * F32));
+  const float* uh = u;
+  if (normalize) {  // u^ = u / ||u|| kept beside v for the backward (dW = U^^T G)
+    float* un = at(saved, sv.take((size_t)B * E * F32));
+    XNRS_TRY(launch_l2_normalize_rows(u, un, B, E, stream));
+    uh = un;
+  }
+  XNRS_TRY(sc_gemm(uh, E, w, E, 1, nullptr, v, E, B, E, E, stream));  // v_b = W[0]^T u^_b
+  XNRS_TRY(launch_bilinear_pair_fwd(v, c, bias, s, B, N, E, normalize, stream));
+  return XNRS_OK;
+}
+
+size_t xnrs_bilinear_scoring_bwd_workspace_bytes(int64_t B, int32_t E, int32_t normalize) {  // G [B, E] | du^ [B, E] (normalize)
+  return xnrs_bilinear_scoring_saved_bytes(B, E, normalize);
+}
+
+int32_t xnrs_bilinear_scoring_bwd(const float* u, const float* c, const float* w, const void* saved, size_t saved_bytes,
+                                  const float* ds, float* du, float* dc, float* dw, float* dbias, int64_t B, int32_t N, int32_t E,
+                                  int32_t normalize, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B < 0 || N < 0 || E <= 0) return XNRS_EINVAL;
+  if ((B == 0 || N == 0) && !dw && !dbias) return XNRS_OK;
+  if (!w || (B * N > 0 && (!u || !c || !ds))) return XNRS_EINVAL;  // (an empty tensor may have no storage)
+  if (B > 0x7fffffffLL || B * N >= (1ll << 31)) return XNRS_EUNSUPPORTED;  // one workgroup per impression; 32-bit contraction
+  if (!saved || saved_bytes < xnrs_bilinear_scoring_saved_bytes(B, E, normalize)) return XNRS_EWORKSPACE;
+  const size_t second = align_up((size_t)B * E * F32);  // the second region of the saved blob and of the workspace
+  const float* v = static_cast<const float*>(saved);
+  const float* uh = normalize ? at(saved, second) : u;
+  const bool pairs = B > 0 && N > 0;
+  if (du || dc || dw) {
+    if (pairs && (!ws || ws_bytes < xnrs_bilinear_scoring_bwd_workspace_bytes(B, E, normalize))) return XNRS_EWORKSPACE;
+    float* G = static_cast<float*>(ws);
+    if (pairs) XNRS_TRY(launch_bilinear_pair_bwd(v, c, ds, dc, G, B, N, E, normalize, stream));
+    if (dw) XNRS_TRY(sc_gemm_dw(uh, E, G, E, dw, E, E, E, pairs ? B : 0, stream));  // dW[0] = U^^T G
+    if (du && B > 0) {
+      if (N == 0) XNRS_TRY(hipMemsetAsync(du, 0, (size_t)B * E * sizeof(float), stream));
+      else if (!normalize) XNRS_TRY(sc_gemm(G, E, w, E, 0, nullptr, du, E, B, E, E, stream));  // du_b = W[0] G_b
+      else {
+        float* duh = at(ws, second);
+        XNRS_TRY(sc_gemm(G, E, w, E, 0, nullptr, duh, E, B, E, E, stream));
+        XNRS_TRY(launch_l2_normalize_bwd(u, uh, duh, du, B, E, stream));
+      }
+    }
+  }
+  if (dbias) {
+    ColSumSeg seg{ds, 1, B * N, 1, dbias};
+    XNRS_TRY(launch_colsum_segments(&seg, 1, stream));
+  }
+  return XNRS_OK;
+}
+
+size_t xnrs_mlp_scoring_saved_bytes(int64_t B, int32_t N, int32_t H) {
+  if (B < 0 || N < 0 || H <= 0) return 0;
+  return carve_total({(size_t)B * H * F32, (size_t)B * N * H * F32});  // q [B, H] | p [B*N, H]
+}
+
+int32_t xnrs_mlp_scoring_news_proj(const float* c, int64_t rows, int32_t E, const float* w1, int32_t H, float* p, void* stream) {
+  if (rows < 0 || E <= 0 || H <= 0) return XNRS_EINVAL;
+  if (rows == 0) return XNRS_OK;
+  if (!c || !w1 || !p) return XNRS_EINVAL;
+  return hip_rc(sc_gemm(c, E, w1 + E, 2 * (int64_t)E, 0, nullptr, p, H, rows, H, E, (hipStream_t)stream));  // p = C W1c^T
+}
+
+int32_t xnrs_mlp_scoring_fwd(const float* u, const float* c, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* s, int64_t B, int32_t N, int32_t E, int32_t H, void* saved, size_t saved_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B < 0 || N < 0 || E <= 0 || H <= 0) return XNRS_EINVAL;
+  if (B == 0 || N == 0) return XNRS_OK;
+  if (!u || !c || !w1 || !w2 || !s) return XNRS_EINVAL;
+  if (!saved || saved_bytes < xnrs_mlp_scoring_saved_bytes(B, N, H)) return XNRS_EWORKSPACE;
+  Carver sv;
+  float *q = at(saved, sv.take((size_t)B * H * F32)), *p = at(saved, sv.take((size_t)B * N * H * F32));
+  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, B, H, E, stream));      // q_b = W1u u_b + b1, once per impression
+  XNRS_TRY(sc_gemm(c, E, w1 + E, 2 * (int64_t)E, 0, nullptr, p, H, B * N, H, E, stream));  // p_bn = W1c c_bn
+  XNRS_TRY(launch_mlp_pair_fwd(q, p, w2, b2, s, B, N, H, stream));
+  return XNRS_OK;
+}
+
+size_t xnrs_mlp_scoring_bwd_workspace_bytes(int64_t B, int32_t N, int32_t H) {
+  if (B < 0 || N < 0 || H <= 0) return 0;
+  // delta [B*N, H] | Delta [B, H] | per-impression dw2 partials [B, H]
+  return carve_total({(size_t)B * N * H * F32, (size_t)B * H * F32, (size_t)B * H * F32});
+}
+
+int32_t xnrs_mlp_scoring_bwd(const float* u, const float* c, const float* w1, const float* w2, const void* saved, size_t saved_bytes,
+                             const float* ds, float* du, float* dc, float* dw1, float* db1, float* dw2, float* db2, int64_t B,
+                             int32_t N, int32_t E, int32_t H, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B < 0 || N < 0 || E <= 0 || H <= 0) return XNRS_EINVAL;
+  const int64_t BN = B * N;
+  if (!w1 || !w2 || (BN > 0 && (!u || !c || !ds))) return XNRS_EINVAL;  // (an empty tensor may have no storage)
+  if (!saved || saved_bytes < xnrs_mlp_scoring_saved_bytes(B, N, H)) return XNRS_EWORKSPACE;
+  if (B > 0x7fffffffLL || BN >= (1ll << 31)) return XNRS_EUNSUPPORTED;  // one workgroup per impression; 32-bit contraction
+  Carver sv, wl;
+  const float *q = at(saved, sv.take((size_t)B * H * F32)), *p = at(saved, sv.take((size_t)BN * H * F32));
+  float* delta = at(ws, wl.take((size_t)BN * H * F32));
+  float *Delta = at(ws, wl.take((size_t)B * H * F32)), *dw2p = at(ws, wl.take((size_t)B * H * F32));
+  const bool need_delta = dc || dw1;
+  const bool need_Delta = du || dw1 || db1;
+  if (BN == 0) {  // no pair: every gradient is zero
+    if (du && B > 0) XNRS_TRY(hipMemsetAsync(du, 0, (size_t)B * E * sizeof(float), stream));
+    if (dw1) XNRS_TRY(hipMemsetAsync(dw1, 0, (size_t)H * 2 * E * sizeof(float), stream));
+    if (db1) XNRS_TRY(hipMemsetAsync(db1, 0, (size_t)H * sizeof(float), stream));
+    if (dw2) XNRS_TRY(hipMemsetAsync(dw2, 0, (size_t)H * sizeof(float), stream));
+    if (db2) XNRS_TRY(hipMemsetAsync(db2, 0, sizeof(float), stream));
+    return XNRS_OK;
+  }
+  if (!ws || ws_bytes < xnrs_mlp_scoring_bwd_workspace_bytes(B, N, H)) return XNRS_EWORKSPACE;
+  if (need_delta || need_Delta || dw2)
+    XNRS_TRY(launch_mlp_pair_bwd(q, p, w2, ds, need_delta ? delta : nullptr, need_Delta ? Delta : nullptr, dw2 ? dw2p : nullptr, B,
+                                 N, H, stream));
+  if (dw1) {  // fc1.weight.grad = [dW1u | dW1c]: the two column halves of one (H, 2E) buffer
+    XNRS_TRY(sc_gemm_dw(Delta, H, u, E, dw1, 2 * (int64_t)E, H, E, B, stream));       // dW1u = sum_b Delta_b (x) u_b
+    XNRS_TRY(sc_gemm_dw(delta, H, c, E, dw1 + E, 2 * (int64_t)E, H, E, BN, stream));  // dW1c = sum_bn delta_bn (x) c_bn
+  }
+  {  // dw2 = sum_b (sum_n g t), db1 = sum_b Delta_b, db2 = sum g: one fixed-order launch
+    ColSumSeg segs[3] = {{dw2p, H, B, H, dw2}, {Delta, H, B, H, db1}, {ds, 1, BN, 1, db2}};
+    XNRS_TRY(launch_colsum_segments(segs, 3, stream));
+  }
+  if (du) XNRS_TRY(sc_gemm(Delta, H, w1, 2 * (int64_t)E, 1, nullptr, du, E, B, E, H, stream));       // du_b = W1u^T Delta_b
+  if (dc) XNRS_TRY(sc_gemm(delta, H, w1 + E, 2 * (int64_t)E, 1, nullptr, dc, E, BN, E, H, stream));  // dc_bn = W1c^T delta_bn
+  return XNRS_OK;
+}
+
+size_t xnrs_score_csr_scorer_workspace_bytes(int64_t n_sess, int32_t width) {
+  if (n_sess < 0 || width <= 0) return 0;
+  return align_up((size_t)n_sess * width * sizeof(float));
+}
+
+int32_t xnrs_score_csr_bilinear(const float* vecs, const int32_t* cand_rows, const int32_t* cand_sess, const float* u, int64_t n_sess,
+                                const float* w, const float* bias, float* r, int64_t n_cand, int32_t E, int32_t relu, void* ws,
+                                size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n_cand < 0 || n_sess < 0 || E <= 0) return XNRS_EINVAL;
+  if (n_cand == 0) return XNRS_OK;
+  if (!vecs || !cand_rows || !cand_sess || !u || !w || !r) return XNRS_EINVAL;
+  if (!ws || ws_bytes < xnrs_score_csr_scorer_workspace_bytes(n_sess, E)) return XNRS_EWORKSPACE;
+  float* v = static_cast<float*>(ws);
+  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, n_sess, E, E, stream));  // v_b = W[0]^T u_b, once per impression
+  XNRS_TRY(launch_score_csr_bilinear(vecs, cand_rows, cand_sess, v, bias, r, n_cand, E, relu, stream));
+  return XNRS_OK;
+}
+
+int32_t xnrs_score_csr_mlp(const float* P, const int32_t* cand_rows, const int32_t* cand_sess, const float* u, int64_t n_sess,
+                           const float* w1, const float* b1, const float* w2, const float* b2, float* r, int64_t n_cand, int32_t E,
+                           int32_t H, int32_t relu, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n_cand < 0 || n_sess < 0 || E <= 0 || H <= 0) return XNRS_EINVAL;
+  if (n_cand == 0) return XNRS_OK;
+  if (!P || !cand_rows || !cand_sess || !u || !w1 || !w2 || !r) return XNRS_EINVAL;
+  if (!ws || ws_bytes < xnrs_score_csr_scorer_workspace_bytes(n_sess, H)) return XNRS_EWORKSPACE;
+  float* q = static_cast<float*>(ws);
+  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, n_sess, H, E, stream));  // q_b = W1u u_b + b1
+  XNRS_TRY(launch_score_csr_mlp(P, cand_rows, cand_sess, q, w2, b2, r, n_cand, H, relu, stream));
+  return XNRS_OK;
+}
+
+int32_t xnrs_l2_normalize_rows(const float* x, float* y, int64_t rows, int32_t E, void* stream) {
+  if (rows < 0 || E <= 0) return XNRS_EINVAL;
+  if (rows == 0) return XNRS_OK;
+  if (!x || !y) return XNRS_EINVAL;
+  return hip_rc(launch_l2_normalize_rows(x, y, rows, E, (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -167,7 +167,8 @@ def tree_build_id() -> str:
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")), key=os.path.basename)
-    files += [os.path.join(csrc, "kernels.h"), os.path.join(os.path.dirname(_HERE), "include", "xnrs_hip.h")]
+    files += sorted(glob.glob(os.path.join(csrc, "*.h")), key=os.path.basename)
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "xnrs_hip.h"))
     h = hashlib.sha256()
     for f in files:
         with open(f, "rb") as fh:
