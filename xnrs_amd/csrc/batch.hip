@@ -609,6 +609,73 @@ hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_
   return hipGetLastError();
 }
 
+// ---- live row tiles of the DENSE encoder passes (GemmArgs::live_tiles).
+// The rows stay where they are; what is listed is, for every pass of `chunk` sequences, the BM-row tiles of its
+// [cn * L]-row image in which at least one row belongs to a sequence with any mask value != 0 (mask [.., L] fp32,
+// optionally gathered by id), in ascending order, and their number.  A sequence whose mask is all zero has a result that
+// needs none of its rows (encoder_fwd.hip), so a tile that holds only such rows is not computed.  ONE launch for the whole
+// call, one 1024-thread workgroup per pass, like the row compaction above:
+//   alive [n_seq] bytes     scratch: 1 = the sequence has an unmasked token (a thread per sequence walks its mask row)
+//   n_tiles [pass]          number of live tiles of the pass (device scalar the GEMMs read)
+//   tiles [pass * cap ..]   their indices; cap = tiles of a full pass
+__global__ __launch_bounds__(1024) void live_tiles_kernel(const float* __restrict__ mask, const int32_t* __restrict__ ids,
+                                                           int64_t n_seq, int64_t chunk, int L, int BM, int64_t cap,
+                                                           uint8_t* __restrict__ alive_all, int64_t* __restrict__ n_tiles,
+                                                           int32_t* __restrict__ tiles_all) {
+  __shared__ int s_wsum[16];
+  __shared__ int s_carry;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t seq0 = (int64_t)blockIdx.x * chunk;
+  const int64_t cn = n_seq - seq0 < chunk ? n_seq - seq0 : chunk;
+  uint8_t* alive = alive_all + seq0;
+  int32_t* tiles = tiles_all + (int64_t)blockIdx.x * cap;
+  for (int64_t j = tid; j < cn; j += 1024) {
+    const float* mp = mask + (ids ? (int64_t)ids[seq0 + j] : seq0 + j) * L;
+    int any = 0;
+#pragma unroll 4
+    for (int s = 0; s < L; ++s) any |= mp[s] != 0.f ? 1 : 0;
+    alive[j] = (uint8_t)any;
+  }
+  if (tid == 0) s_carry = 0;
+  __syncthreads();  // (the flags were written by this workgroup: visible to it behind the barrier)
+  const int64_t rows = cn * L;
+  const int64_t nt = (rows + BM - 1) / BM;
+  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (int64_t base = 0; base < nt; base += 1024) {
+    const int64_t t = base + tid;
+    bool live = false;
+    if (t < nt) {
+      const int64_t r0 = t * BM, r1 = (r0 + BM < rows ? r0 + BM : rows) - 1;
+      for (int64_t n = r0 / L; n <= r1 / L; ++n) live = live || alive[n] != 0;
+    }
+    const uint64_t b = __ballot(live);
+    if (lane == 0) s_wsum[wave] = __popcll(b);
+    __syncthreads();
+    int before = s_carry;
+    for (int w = 0; w < wave; ++w) before += s_wsum[w];
+    if (live) tiles[before + __popcll(b & below)] = (int32_t)t;
+    __syncthreads();
+    if (tid == 0) {
+      int tot = s_carry;
+      for (int w = 0; w < 16; ++w) tot += s_wsum[w];
+      s_carry = tot;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) n_tiles[blockIdx.x] = s_carry;
+}
+
+hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM, uint8_t* alive,
+                             int64_t* n_tiles, int32_t* tiles, hipStream_t stream) {
+  if (n_seq <= 0 || chunk <= 0 || L <= 0 || BM <= 0) return hipSuccess;
+  const int64_t passes = (n_seq + chunk - 1) / chunk;
+  const int64_t cap = live_tiles_cap(chunk, L, BM);
+  if (passes > 0x7fffffffLL || cap > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_tiles_kernel, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_seq, chunk, L, BM, cap, alive,
+                     n_tiles, tiles);
+  return hipGetLastError();
+}
+
 }  // namespace xnrs
 
 // ---------------------------------------------------------------- C entry points (include/xnrs_hip.h)

@@ -16,6 +16,8 @@
 // The three pipelines must stay bit for bit equal (tested).  Every stage they share is therefore described ONCE, by the
 // builders below (fc1_pair, qkv_projection, mha_core_args, fc1_product, additive_pool_args, pooled_tail); a pipeline sets
 // only what differs: where its rows come from, where the row count lives, its output block.
+#include <vector>
+
 #include "host.h"
 
 using namespace xnrs;
@@ -58,6 +60,13 @@ Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additiv
   }
   p.off_nf = c.take_if(nfb != 0, nfb);
   p.off_nfo = c.take_if(nfb != 0, news_fused_scratch_bytes(L, D));  // its O rows while the out-projection is folded away
+  // live row tiles of the dense passes (launch_live_tiles; a few KB): reserved for every pooled inference plan with an
+  // attention tower, whatever the knobs and the batch size say
+  const bool lt = att && pooled && !train;
+  const size_t passes = (size_t)(((n_seq > 0 ? n_seq : 1) + chunk - 1) / chunk);
+  p.off_lt_alive = c.take_if(lt, (size_t)(n_seq > 0 ? n_seq : 1));
+  p.off_lt_n = c.take_if(lt, passes * sizeof(int64_t));
+  p.off_lt_tiles = c.take_if(lt, passes * (size_t)live_tiles_cap(chunk, L, LIVE_TILE_BM) * sizeof(int32_t));
   // folded out-projection ("fold" below): reserved whenever the shape is eligible, whatever the knob says
   // (training keeps W', b', the pooled O rows and the weight sums for the backward)
   p.fold = carve_fold(c, att && additive, n_seq, D, A);
@@ -440,9 +449,54 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
     ProfScope ps(6, fl, stream);
     XNRS_TRY(launch_news_fused(f, stream));
   }
+  // Live row tiles (inference, the news encoder's pooled calls with a mask; XNRS_GEMM_LIVE_TILES=0: off).  An all-masked
+  // sequence -- an empty history slot, 49.5 % of the benchmark's -- has a result that needs none of its rows: every query
+  // row is masked, the pooler multiplies every row by 0, the pooled vector is 0.  Its rows are contiguous, so whole
+  // 128-row GEMM tiles hold nothing else: the two row-parallel products of a pass walk the tiles that hold a row of a live
+  // sequence (GemmArgs::live_tiles; the list of every pass is built by ONE launch per call, rows stay where they are).
+  //   Q|K|V: only while the attention kernel of this shape leaves a dead sequence before reading its rows
+  //          (mha_core_skips_dead: the skipped rows of the image are never written);
+  //   fc1:   with the fc2 dot in its epilogue; the pooler then leaves a dead sequence before reading its scores.
+  // By size: the list costs one short launch per call (a workgroup per pass; measured 33 us at 20 passes), which must not
+  // show where a call is latency-bound (one impression: 2 750 token rows) -- from live_tiles_min_rows token rows per call
+  // on (default 16 384 = 128 tiles: the list then pays for itself from ~9 dead tiles, 3.6 us each at D = 768 for the two
+  // products).
+  // The choice never depends on the data (hipGraph) and changes no bit: a live sequence's rows are computed as before.
+  const bool lt = r.live_tiles && knobs().gemm_live_tiles && !train && pooled && m && att && !fused && !afused &&
+                  n_seq * (int64_t)L >= knobs().gemm_live_tiles_min_rows &&
+                  device_counts_ok(x, D, A, att, additive ? pool : nullptr);
+  bool lt_qkv = false;
+  if (lt && knobs().mha_skip_masked) {
+    MhaCoreArgs probe = mha_core_args(qkv + D, 3 * (int64_t)D, att, o, p.chunk, L, D);
+    probe.q = qkv;
+    probe.mask = m;
+    probe.skip_dead = 1;
+    lt_qkv = mha_core_skips_dead(probe);
+  }
+  const bool lt_fc1 = lt && additive && rowdot;
+  const int64_t lt_cap = live_tiles_cap(p.chunk, L, LIVE_TILE_BM);
+  const int64_t* lt_n = at<int64_t>(w, p.off_lt_n);
+  const int32_t* lt_tiles = at<int32_t>(w, p.off_lt_tiles);
+  if (lt_qkv || lt_fc1)
+    XNRS_TRY(launch_live_tiles(m, ids, n_seq, p.chunk, L, LIVE_TILE_BM, at<uint8_t>(w, p.off_lt_alive), at<int64_t>(w, p.off_lt_n),
+                               at<int32_t>(w, p.off_lt_tiles), stream));
+  // launch timer on: the live-tile counts of every pass, read back ONCE per call (the timer is a measurement aid that
+  // synchronises anyway; nothing is read while it is off) -- stages 0 and 3 then report EXECUTED FLOPs
+  std::vector<int64_t> lt_host;
+  if ((lt_qkv && prof_on(0)) || (lt_fc1 && prof_on(3))) {
+    lt_host.resize((size_t)((n_seq + p.chunk - 1) / p.chunk));
+    if (hipStreamSynchronize(stream) != hipSuccess ||
+        hipMemcpy(lt_host.data(), lt_n, lt_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
+      lt_host.clear();
+  }
   for (int64_t c0 = 0; !fused && !afused && c0 < n_seq; c0 += p.chunk) {
     const int64_t nc = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
     const int64_t rows = nc * L;
+    // this pass's live row tiles, and the rows they hold for the launch timer (executed FLOPs: live tiles x tile height)
+    const int64_t* ltn = lt_n + c0 / p.chunk;
+    const int32_t* ltl = lt_tiles + (c0 / p.chunk) * lt_cap;
+    const double lt_rows = (double)LIVE_TILE_BM *
+                           (double)(lt_host.empty() ? (rows + LIVE_TILE_BM - 1) / LIVE_TILE_BM : lt_host[(size_t)(c0 / p.chunk)]);
     // this chunk's view of the inputs
     const int32_t* cids = ids ? ids + c0 : nullptr;
     const float* cx = ids ? x : x + c0 * (int64_t)L * D;      // table stays whole when gathering
@@ -481,8 +535,13 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
           XNRS_TRY(launch_gemm_f32(q, stream));
         }
       } else {
-        ProfScope ps(0, 2.0 * rows * 3.0 * D * D, stream);
-        XNRS_TRY(launch_gemm_f32(qkv_projection(cx, {cids, L}, att, 0, qkv, ld3, rows, D, pqkv), stream));
+        GemmArgs g = qkv_projection(cx, {cids, L}, att, 0, qkv, ld3, rows, D, pqkv);
+        if (lt_qkv) {  // the rows of the dead tiles stay unwritten: the attention kernel below never reads them
+          g.live_n = ltn;
+          g.live_tiles = ltl;
+        }
+        ProfScope ps(0, 2.0 * (lt_qkv ? lt_rows : (double)rows) * 3.0 * D * D, stream);
+        XNRS_TRY(launch_gemm_f32(g, stream));
       }
 
       MhaCoreArgs ma = mha_core_args(qkv + D, ld3, att, o, nc, L, D);
@@ -499,6 +558,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       // history slots of the benchmark batch (49.5 % of its news) cost the attention core nothing.  MultiHeadAttention
       // alone (pooled == false) returns its masked rows to the caller and computes them.
       ma.skip_dead = (live || (pooled && cm && knobs().mha_skip_masked)) ? 1 : 0;
+      if (lt_qkv && !mha_core_skips_dead(ma)) return XNRS_EUNSUPPORTED;  // (never: the two are decided by one rule)
       {
         ProfScope ps(1, 4.0 * rows * (double)L * D, stream);
         XNRS_TRY(launch_mha_core(ma, stream));
@@ -541,10 +601,16 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
           XNRS_TRY(launch_gemm_f32(fg, stream));
         }
       } else {
-        ProfScope ps(3, 2.0 * rows * (double)D * A, stream);
-        XNRS_TRY(launch_gemm_f32(fc1_product(seq, {seq_ids, L}, fc1, t, rows, D, A, rowdot, pool, p1), stream));
+        GemmArgs fg = fc1_product(seq, {seq_ids, L}, fc1, t, rows, D, A, rowdot, pool, p1);
+        if (lt_fc1) {  // the scores of the dead tiles stay unwritten: the pooler below leaves their sequences first
+          fg.live_n = ltn;
+          fg.live_tiles = ltl;
+        }
+        ProfScope ps(3, 2.0 * (lt_fc1 ? lt_rows : (double)rows) * (double)D * A, stream);
+        XNRS_TRY(launch_gemm_f32(fg, stream));
       }
       AdditivePoolArgs pa = additive_pool_args(t, rowdot, pool, seq, nc, L, D, A);
+      pa.skip_dead = lt_fc1 ? 1 : 0;
       pa.mask = cm;
       pa.mask_gather_ids = cids;
       pa.x_gather_ids = seq_ids;
@@ -700,6 +766,7 @@ int32_t xnrs_text_encoder_fwd(const float* x, const float* m, const int32_t* ids
   if (!m) return XNRS_EINVAL;  // TextEncoder always receives a token mask (news_encoding.py:41-50)
   SeqEncode r = padded_call(x, m, n_news, S, D, y, ws, ws_bytes);
   r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
+  r.live_tiles = true;  // empty history slots are news: whole row tiles of a pass may hold nothing else
   return seq_encode(r, (hipStream_t)stream);
 }
 

@@ -83,10 +83,15 @@ constexpr unsigned BUF_OOB = 0x40000000u;
 // MDEV (forward layout): the row count is a device scalar (GemmArgs::m_dev), read once into SGPRs -- its own
 // instantiations (a first version wrote it into the by-value argument block: that moved the whole 400-byte struct to
 // scratch in EVERY variant -- 59 spilled VGPRs in the main forward kernel, 140 -> 84 TFLOP/s).
+// LIVE (forward layout): the launch computes the row tiles of a device-built list only (GemmArgs::live_n / live_tiles: the
+// tiles of a dense encoder pass that hold a row of a sequence with an unmasked token) -- the same mechanism: the number of
+// listed tiles is read once into an SGPR, the tile walk runs over them, the workgroups past them leave at once, and the row
+// tile of a workgroup is looked up in the list (one scalar load).  Its own instantiations; the K loop is the dense one.
 template <int TM, int TN, bool A_COL, bool B_KN, bool VEC, int PIPE, int BK, bool BUF = false, int MINW = 2, bool GATH = false,
-          int KG = 2, bool RDOT = false, bool MDEV = false>
+          int KG = 2, bool RDOT = false, bool MDEV = false, bool LIVE = false>
 __global__ __launch_bounds__(256, MINW) void gemm_f32_kernel(const GemmArgs a, int m_tiles, int n_tiles_seg, int gn) {
   static_assert(!MDEV || (!A_COL && !B_KN), "device row counts: forward layout only");
+  static_assert(!LIVE || (BUF && !MDEV), "live row tiles: buffer-load forward kernels, host row count");
   static_assert(!BUF || (!A_COL && !B_KN && VEC), "buffer loads are implemented for the forward layout");
   static_assert(!RDOT || PIPE == 5, "the fused row dots ride on the interleaved pipeline (its MFMA call is the swapped one)");
   static_assert(!GATH || BUF, "the gathered-A variant keeps buffer loads for B");
@@ -123,6 +128,12 @@ __global__ __launch_bounds__(256, MINW) void gemm_f32_kernel(const GemmArgs a, i
     nwg = m_tiles * n_tiles_seg * a.nseg;
     if ((int)blockIdx.x >= nwg) return;  // workgroup-uniform, before any barrier
   }
+  if constexpr (LIVE) {  // the same over the LISTED row tiles (m_tiles was the grid's worst case: every tile of the pass)
+    const int nl = __builtin_amdgcn_readfirstlane((int)load_dev_scalar(a.live_n));
+    m_tiles = nl < m_tiles ? (nl > 0 ? nl : 0) : m_tiles;
+    nwg = m_tiles * n_tiles_seg * a.nseg;
+    if ((int)blockIdx.x >= nwg) return;  // workgroup-uniform, before any barrier
+  }
   // ---- XCD-aware tile order (bijective for any grid size); blockIdx.y = k slice
   const int bid = blockIdx.x;
   const int xcd = bid & 7;
@@ -139,7 +150,8 @@ __global__ __launch_bounds__(256, MINW) void gemm_f32_kernel(const GemmArgs a, i
   const int nt = grp * gn + (rem - mt * gw);
   const int seg = nt / n_tiles_seg;
   const int nts = nt - seg * n_tiles_seg;
-  const int64_t m0 = (int64_t)mt * BM;
+  int64_t m0 = (int64_t)mt * BM;
+  if constexpr (LIVE) m0 = (int64_t)__builtin_amdgcn_readfirstlane(a.live_tiles[mt]) * BM;  // mt-th live tile of the pass
   const int n0 = nts * BN;  // column inside the segment
 
   // contraction indices are 32-bit in the kernel (the launcher refuses K >= 2^31): the k-tail tests and tile offsets of
@@ -800,7 +812,23 @@ static hipError_t launch_cfg(const GemmArgs& a, bool vec, int nsplit, hipStream_
 #define XNRS_LAUNCH_GATH(MINWV)                                                                                       \
   hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, A_COL, B_KN, true, 5, 16, true, MINWV, true>), g, dim3(256), 0, stream, a, \
                      (int)m_tiles, n_tiles_seg, gn)
+  if constexpr (TM == 2 && TN == 2 && !A_COL && !B_KN) {
+    if (a.live_tiles) {  // live row tiles of a dense encoder pass: its own instantiations of the main tile
+      if (!vec || !(buf || gath) || a.m_dev || !a.live_n || nsplit != 1 || a.c_scatter) return hipErrorInvalidValue;
+#define XNRS_LAUNCH_LIVE(GATHV, RDOTV)                                                                                            \
+  hipLaunchKernelGGL((gemm_f32_kernel<2, 2, false, false, true, 5, 16, true, 4, GATHV, 2, RDOTV, false, true>), g, dim3(256), 0, \
+                     stream, a, (int)m_tiles, n_tiles_seg, gn)
+      if (a.rowdot_out) {
+        if (buf) XNRS_LAUNCH_LIVE(false, true);
+        else XNRS_LAUNCH_LIVE(true, true);
+      } else if (buf) XNRS_LAUNCH_LIVE(false, false);
+      else XNRS_LAUNCH_LIVE(true, false);
+#undef XNRS_LAUNCH_LIVE
+      return hipGetLastError();
+    }
+  }
   if constexpr (!A_COL && !B_KN) {
+    if (a.live_tiles && !(TM == 2 && TN == 2)) return hipErrorInvalidValue;  // (the launcher forces the main tile)
     if (a.m_dev) {  // device row count (the device-compacted padding-free encoder): its own instantiations
       if (!vec || !(buf || gath)) return hipErrorInvalidValue;
       if (a.rowdot_out) {
@@ -893,6 +921,7 @@ static hipError_t launch_layout(const GemmArgs& a, bool vec, int nsplit, hipStre
     }
   }
   if (knobs().gemm_tile >= 0 && knobs().gemm_tile <= 3) best = knobs().gemm_tile;  // development knob
+  if (a.live_tiles) best = 0;  // the list is in tiles of LIVE_TILE_BM = 128 rows (every tile shape gives the same bits)
   switch (best) {
     case 0: return launch_cfg<2, 2, A_COL, B_KN>(a, vec, nsplit, stream);
     case 1: return launch_cfg<2, 1, A_COL, B_KN>(a, vec, nsplit, stream);
@@ -952,6 +981,8 @@ static Knobs read_knobs() {
   k.additive_fused = (int)num("XNRS_ADDITIVE_FUSED", 1);
   k.af_fbuf = num("XNRS_AF_FBUF", 1) == 2 ? 2 : 1;
   k.mha_skip_masked = num("XNRS_MHA_SKIP_MASKED", 1) != 0;
+  k.gemm_live_tiles = num("XNRS_GEMM_LIVE_TILES", 1) != 0;
+  k.gemm_live_tiles_min_rows = num("XNRS_GEMM_LIVE_TILES_MIN_ROWS", 16384);
   k.bwd_side_stream = num("XNRS_BWD_SIDE_STREAM", 1) != 0;
   k.bwd_side_min_rows = num("XNRS_BWD_SIDE_MIN_ROWS", 0);
   const long long m = num("XNRS_GEMM_MODE", 0);
@@ -1013,6 +1044,7 @@ hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t stream, int* nsplit
   // smaller tiles is faster (measured: 4099 x 260 x 300 -> 38 TF fp32 vs 22 TF split)
   const int64_t min_tiles = knobs().split_min_tiles;  // tests force the split kernel onto tiny shapes with 0
   if (a.m_dev && (a.a_col || a.b_kn || nsplit != 1 || mode != 0)) return hipErrorInvalidValue;  // device row count: fp32 forward only
+  if (a.live_tiles && (a.a_col || a.b_kn || nsplit != 1 || mode != 0 || a.m_dev)) return hipErrorInvalidValue;  // live row tiles: fp32 forward only
   if (a.rowscale && (a.a_col || a.b_kn || a.nseg != 1 || nsplit != 1 || !a.rowscale_vec || a.c_scatter || a.rowdot_out))
     return hipErrorInvalidValue;  // rank-1 epilogue term: plain forward launches only
   if (mode && !a.rowdot_out && !a.rowscale && !a.a_col && !a.b_kn && vec && nsplit == 1 &&

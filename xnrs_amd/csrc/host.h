@@ -153,6 +153,7 @@ struct Plan {
   size_t off_stats, off_a;  // training only: softmax row statistics, pooling weights
   size_t off_planes;        // bf16-split GEMM modes: pre-split weight planes (wq, wk, wv, wo, w1)
   size_t off_nf, off_nfo;   // fused short-sequence encoder: fragment-ordered weight images, O-row scratch (fold)
+  size_t off_lt_alive, off_lt_n, off_lt_tiles;  // live row tiles of the dense passes (launch_live_tiles)
   FoldRegions fold;
   size_t total;
 };
@@ -179,6 +180,7 @@ struct SeqEncode {
   size_t ws_bytes;
   bool train;                // keep the activations the backward reads (ws = the saved blob)
   const xnrs_row_lists* rl;  // nullable (training): live-row / K|V-row lists
+  bool live_tiles;           // inference: the row-parallel products may skip row tiles that hold only all-masked sequences
 };
 int32_t seq_encode(const SeqEncode& r, hipStream_t stream);
 

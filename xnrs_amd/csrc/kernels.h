@@ -41,6 +41,9 @@ struct Knobs {
   int af_fbuf = 1;              // XNRS_AF_FBUF=1|2: MFMA fragment register sets of that kernel
   bool bwd_side_stream = true;  // XNRS_BWD_SIDE_STREAM=0: the backward's weight-gradient products stay on the caller's stream (encoder_bwd.hip: SideLane)
   long long bwd_side_min_rows = 0;  // XNRS_BWD_SIDE_MIN_ROWS: ... for attention towers of at least this many token rows
+  bool gemm_live_tiles = true;  // XNRS_GEMM_LIVE_TILES=0: the dense encoder passes project and score every row tile, also those that
+                                // hold only all-masked sequences (encoder_fwd.hip "live row tiles"; bitwise the same results)
+  long long gemm_live_tiles_min_rows = 16384;  // XNRS_GEMM_LIVE_TILES_MIN_ROWS: token rows per encoder call from which the list is built
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
 };
@@ -129,6 +132,11 @@ struct GemmArgs {
   // forward layout with m_dev (optional): the expected fraction of the capacity M that exists (0 = unknown = all), for the
   // tile choice only -- a launch sized for 80 000 rows of which ~25 % are live fills the chip better with smaller tiles
   float m_fill_hint;
+  // forward layout, 128 x 128 tile, no m_dev (nullable pair): the launch computes only the row tiles live_tiles[0 .. *live_n)
+  // (ascending tile indices of height LIVE_TILE_BM, built on the device: launch_live_tiles); the C rows / row dots of the
+  // other tiles are NOT written.  The grid is sized for every tile: the launch sequence does not depend on the data.
+  const int64_t* live_n;
+  const int32_t* live_tiles;
   // split-K (deterministic slabs + ordered reduce); set by the caller via slabs/nsplit
   float* slabs;        // nullable workspace of nsplit * M * ldc floats
   int32_t nsplit;
@@ -197,6 +205,8 @@ struct MhaCoreArgs {
   int32_t skip_dead;
 };
 hipError_t launch_mha_core(const MhaCoreArgs& a, hipStream_t stream);
+// would this launch go to the kernel that honours skip_dead, i.e. reads NO q / k / v row of an all-masked sequence?
+bool mha_core_skips_dead(const MhaCoreArgs& a);
 
 // backward of the attention core: recomputes P from Q, K and the saved row statistics
 struct MhaBwdArgs {
@@ -436,6 +446,8 @@ struct AdditivePoolArgs {
   // (x_gather_ids unused); every compact row is unmasked, `mask` is ignored and hm_out = (count > 0).
   const int64_t* row_off;
   const int32_t* row_ids;  // nullable, with row_off: value row of compact row j is x[row_ids[j]] (t stays compact)
+  int32_t skip_dead;       // 1 (with mask): an all-masked sequence is left before any score is read -- zeros to y / a_out /
+                           // asum_out / hm_out, what the kernel computes for it anyway (its scores may be unwritten)
   const int64_t* poison;   // nullable device flag: non-zero -> every output of the launch is NaN (a precondition the host
                            // could not check without a sync was violated: launch_compact_rows saw a non-0/1 mask)
 };
@@ -541,6 +553,12 @@ hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_
 // rows in the gathered table; counts[0] = live rows, counts[1] = kv rows; cnt_scratch: int32 [n_seq]
 hipError_t launch_build_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int L, int32_t* live, int32_t* live_src,
                                   int32_t* kv, int32_t* kv_src, int64_t* counts, int32_t* cnt_scratch, hipStream_t stream);
+// the live row tiles of every dense encoder pass of `chunk` sequences, built on the device in one launch (batch.hip): pass p
+// writes n_tiles[p] and its ascending tile list at tiles[p * live_tiles_cap(chunk, L, BM) ..]; alive: n_seq bytes of scratch
+constexpr int LIVE_TILE_BM = 128;  // the forward GEMM's main tile height (GemmArgs::live_tiles launches take that tile)
+inline int64_t live_tiles_cap(int64_t chunk, int L, int BM) { return (chunk * L + BM - 1) / BM; }
+hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM, uint8_t* alive,
+                             int64_t* n_tiles, int32_t* tiles, hipStream_t stream);
 hipError_t launch_assemble_train(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_assemble_eval(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_score_csr(const float* vecs, const int32_t* rows, const int32_t* sess, const float* u, float* r, int64_t n,

@@ -823,24 +823,46 @@ static hipError_t launch_kt(const MhaCoreArgs& a, bool vec, hipStream_t stream) 
   return hipGetLastError();
 }
 
+// the launcher's kernel choice (one definition: launch_mha_core and mha_core_skips_dead must agree)
+struct MhaPick {
+  bool vec, fast, use_lds, pair;  // pair: mha_core_pair_kernel<KTM, tail> serves the launch
+  int KT, KTM;
+  bool tail;
+};
+static MhaPick mha_pick(const MhaCoreArgs& a) {
+  MhaPick p{};
+  p.vec = (a.d_k % 4 == 0) && (a.ld % 4 == 0) && (a.ldo % 4 == 0) &&
+          ((reinterpret_cast<uintptr_t>(a.q) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.k) & 15) == 0) &&
+          ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
+  p.KT = (a.S + 15) / 16;
+  // knobs().mha_headwave / mha_lds: development knobs for A/B runs
+  p.fast = p.vec && a.S <= 64 && a.d_k <= 64 && ((int64_t)a.S * a.ld < (1ll << 31)) && knobs().mha_headwave;
+  // three or four query tiles: LDS-staged kernel (one wave per tile, K/V shared through LDS; 0.99 vs 1.06 ms
+  // at S=50); one or two tiles: head-per-wave kernel (0.17 vs 0.21 ms at S=30).  XNRS_MHA_LDS=0|1 forces one.
+  p.use_lds = a.q_off ? true : (knobs().mha_lds >= 0 ? knobs().mha_lds != 0 : (p.KT >= 3));
+  // full key tiles through the MFMAs, a remainder of 1..4 keys through the VALU
+  const int rem = a.S & 15;
+  p.tail = a.S > 16 && rem >= 1 && rem <= 4;
+  p.KTM = p.tail ? a.S >> 4 : p.KT;
+  p.pair = p.fast && p.use_lds && knobs().mha_pair && (int64_t)a.n_seq * a.S < (1ll << 31) &&
+           (p.tail ? (p.KTM == 2 || p.KTM == 3) : (p.KTM == 3 || p.KTM == 4));
+  return p;
+}
+
+bool mha_core_skips_dead(const MhaCoreArgs& a) {
+  return a.skip_dead && a.mask && !a.q_off && a.S <= 128 && mha_pick(a).pair;
+}
+
 hipError_t launch_mha_core(const MhaCoreArgs& a, hipStream_t stream) {
   if (a.n_seq <= 0 || a.S <= 0) return hipSuccess;
   if (a.S > 128) return hipErrorInvalidValue;
-  const bool vec = (a.d_k % 4 == 0) && (a.ld % 4 == 0) && (a.ldo % 4 == 0) &&
-                   ((reinterpret_cast<uintptr_t>(a.q) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.k) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
-  const int KT = (a.S + 15) / 16;
-  // knobs().mha_headwave / mha_lds: development knobs for A/B runs
-  const bool fast = vec && a.S <= 64 && a.d_k <= 64 && ((int64_t)a.S * a.ld < (1ll << 31)) && knobs().mha_headwave;
-  // three or four query tiles: LDS-staged kernel (one wave per tile, K/V shared through LDS; 0.99 vs 1.06 ms
-  // at S=50); one or two tiles: head-per-wave kernel (0.17 vs 0.21 ms at S=30).  XNRS_MHA_LDS=0|1 forces one.
-  const bool use_lds = a.q_off ? true : (knobs().mha_lds >= 0 ? knobs().mha_lds != 0 : (KT >= 3));
+  const MhaPick pk = mha_pick(a);
+  const bool vec = pk.vec, fast = pk.fast, use_lds = pk.use_lds;
+  const int KT = pk.KT;
   if (a.q_off && (!fast || a.stats || a.dropout_p > 0.f || a.ldq % 4 != 0)) return hipErrorInvalidValue;
-  if (fast && use_lds && knobs().mha_pair && (int64_t)a.n_seq * a.S < (1ll << 31)) {
-    // full key tiles through the MFMAs, a remainder of 1..4 keys through the VALU
-    const int rem = a.S & 15;
-    const bool tail = a.S > 16 && rem >= 1 && rem <= 4;
-    const int KTM = tail ? a.S >> 4 : KT;
+  if (pk.pair) {
+    const bool tail = pk.tail;
+    const int KTM = pk.KTM;
     if (tail && KTM == 2) return launch_pair<2, true>(a, stream);
     if (tail && KTM == 3) return launch_pair<3, true>(a, stream);
     if (!tail && KTM == 3) return launch_pair<3, false>(a, stream);

@@ -34,6 +34,24 @@ __global__ __launch_bounds__(256) void additive_pool_kernel(AdditivePoolArgs a) 
   const int N = csr ? (int)(a.row_off[seq + 1] - r0) : a.N;
   const float* mask = csr ? nullptr : a.mask;
 
+  // (skip_dead) an all-masked sequence leaves before any score is read: the fc1 launch over the live row tiles
+  // (GemmArgs::live_tiles) never wrote the scores of its rows.  What it writes is what the code below produces for it --
+  // every weight exp(e) * 0 = 0, the sum 0, 0 / 1e-8 = 0 -- unless exp overflows on a masked row (inf * 0: DESIGN.md section 2).
+  if (a.skip_dead && mask) {
+    int any = 0;
+    for (int i = tid; i < N; i += 256) any |= mask[src * N + i] != 0.f ? 1 : 0;
+    if (!__syncthreads_or(any)) {  // (uniform)
+      for (int d = tid; d < D; d += 256) a.y[seq * D + d] = 0.f;
+      if (a.a_out)
+        for (int i = tid; i < N; i += 256) a.a_out[r0 + i] = 0.f;
+      if (tid == 0) {
+        if (a.asum_out) a.asum_out[seq] = 0.f;
+        if (a.hm_out) a.hm_out[seq] = 0.f;
+      }
+      return;
+    }
+  }
+
   // 1. scores: one wave per row, lanes stride over the hidden dimension -- or, with the fc2 dot already taken per block
   //    of 32 hidden columns in the fc1 GEMM's epilogue (epart), one thread per row adding the blocks in column order
   const float b2 = a.b2 ? a.b2[0] : 0.f;
