@@ -468,7 +468,7 @@ int32_t xnrs_get_gemm_mode(void);
 /* ---- development knobs (no reference counterpart) ---------------------------------------------
  * Kernel-selection switches for A/B measurements and tests (XNRS_GEMM_PIPE, _BK, _BUF, _GROUP, _TILE,
  * XNRS_GEMM_SPLIT_MIN_TILES, XNRS_GEMM_DW, XNRS_MHA_LDS, XNRS_MHA_HEADWAVE, XNRS_MHA_PAIR, XNRS_MHA_BWD_FUSED,
- * XNRS_NEWS_FUSED, XNRS_NEWS_FUSED_NPW, XNRS_FOLD_OUT, XNRS_FOLD_TRAIN, XNRS_FC1_ROWDOT, XNRS_MHA_SKIP_MASKED, XNRS_BWD_SIDE_STREAM, XNRS_BWD_SIDE_MIN_ROWS).  The library reads
+ * XNRS_NEWS_FUSED, XNRS_NEWS_FUSED_NPW, XNRS_FOLD_OUT, XNRS_FOLD_TRAIN, XNRS_FC1_ROWDOT, XNRS_MHA_SKIP_MASKED, XNRS_BWD_SIDE_STREAM, XNRS_BWD_SIDE_MIN_ROWS; DESIGN.md section 6 -- and XNRS_GRU_LAYOUT).  The library reads
  * them from the environment ONCE when it is loaded -- no launch calls getenv -- and again only when this function is
  * called.  None changes a result beyond summation / association order (XNRS_FOLD_*: whether the attention
  * out-projection is applied per token row, as the reference writes it, or once per sequence behind the additive
@@ -569,6 +569,42 @@ size_t xnrs_embedding_linear_bwd_sparse_workspace_bytes(int64_t M, int32_t N, in
 int32_t xnrs_embedding_linear_bwd_sparse(const float *table, const int32_t *ids, const float *w, const float *dy,
                                          float *d_table, float *dw, float *db, int64_t M, int32_t N, int32_t K, int32_t n_rows,
                                          void *ws, size_t ws_bytes, void *stream);
+
+/* ---- nn.GRU, one layer, batch_first (LSTUR's short-term user tower, lstur.py:113-154) --------------------------------------
+ * x:(B,T,E) the first T history vectors of every user, m: fp32 0/1 history mask, row b at m + b * ldm (ldm >= T; NULL: every
+ * row is full), h0:(B,Hd) or NULL (zeros) -> y:(B,Hd), the hidden state after step len_b - 1 with len_b = sum_t m[b][t].  The
+ * GRU reads the FIRST len_b slots of a row wherever the mask's ones are (pack_padded_sequence, lstur.py:141-145); len_b is
+ * computed on the device (no host read).  A row with len_b == 0 returns its initial state (the reference raises there).
+ * Weights in nn.GRU's layout: w_ih [3Hd][E], w_hh [3Hd][Hd], b_ih / b_hh [3Hd] (nullable), gate order r, z, n:
+ *   r = s(W_ir x + b_ir + W_hr h + b_hr)   z = s(W_iz x + b_iz + W_hz h + b_hz)   n = tanh(W_in x + b_in + r (W_hn h + b_hn))
+ *   h' = (1 - z) n + z h
+ * The input projection of all B*T rows is one dense GEMM; the recurrence runs one launch per step (or one launch in all:
+ * knob XNRS_GRU_LAYOUT=1); no atomics, no grid-wide barrier, no host synchronisation: hipGraph-capturable, bit-identical
+ * run to run.
+ *   fwd        ws: xnrs_gru_workspace_bytes of scratch
+ *   fwd_train  the same arithmetic; `saved` (xnrs_gru_saved_bytes) keeps the gates r | z | n, W_hn h + b_hn and the state
+ *              before every step
+ *   bwd        dy:(B,Hd) -> dx:(B,T,E), dh0:(B,Hd) and the four parameter gradients, every output nullable, written (not
+ *              accumulated).  BPTT over the steps in reverse (dh_{t-1} = dGh_t . W_hh + z dh_t), then ONE product each over
+ *              the stacked B*T rows: dW_hh = dGh^T . H_prev, dW_ih = dGi^T . X, dX = dGi . W_ih; bias gradients = column sums.
+ *              ws: xnrs_gru_bwd_workspace_bytes. */
+typedef struct {
+  const float *w_ih, *w_hh, *b_ih, *b_hh;
+  int32_t hidden; /* Hd */
+} xnrs_gru_params;
+typedef struct {
+  float *w_ih, *w_hh, *b_ih, *b_hh;
+} xnrs_gru_grads;
+size_t xnrs_gru_workspace_bytes(int64_t B, int32_t T, int32_t E, int32_t Hd);
+size_t xnrs_gru_saved_bytes(int64_t B, int32_t T, int32_t E, int32_t Hd);
+int32_t xnrs_gru_fwd(const float *x, const float *m, int32_t ldm, const float *h0, const xnrs_gru_params *p, float *y,
+                     int64_t B, int32_t T, int32_t E, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_gru_fwd_train(const float *x, const float *m, int32_t ldm, const float *h0, const xnrs_gru_params *p, float *y,
+                           int64_t B, int32_t T, int32_t E, void *saved, size_t saved_bytes, void *stream);
+size_t xnrs_gru_bwd_workspace_bytes(int64_t B, int32_t T, int32_t E, int32_t Hd);
+int32_t xnrs_gru_bwd(const float *x, const xnrs_gru_params *p, const void *saved, size_t saved_bytes, const float *dy,
+                     float *dx, float *dh0, const xnrs_gru_grads *g, int64_t B, int32_t T, int32_t E, void *ws,
+                     size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -924,3 +924,73 @@ def embedding_linear_table(idx, table, w, b):
     if not idx.is_cuda:
         raise hip.XnrsHipError("user indices must live on the HIP device")
     return _EmbeddingLinearTable.apply(idx, table, w, b)
+
+
+# ---- nn.GRU, one layer (LSTUR's short-term tower, lstur.py:113-154): include/xnrs_hip.h xnrs_gru_*.  One node per call; the
+#      mask is not differentiable, the initial state is an input like any other (LSTUR 'ini': the long-term vector).
+class _Gru(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, m, h0, w_ih, w_hh, b_ih, b_hh):
+        from . import ops
+        with torch.no_grad():
+            y, xc, saved = ops.gru_forward(x, m, h0, (w_ih, w_hh, b_ih, b_hh), keep=True)
+        # the weights go through save_for_backward: an in-place update between forward and backward raises in autograd
+        ctx.save_for_backward(xc, saved, w_ih, w_hh, b_ih, b_hh)
+        ctx.has = [True, m is not None, h0 is not None, True, True, b_ih is not None, b_hh is not None]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import ops
+        x, saved, *weights = ctx.saved_tensors
+        B, T, E = x.shape
+        Hd = weights[1].shape[1]
+        wanted = _wanted_inputs(ctx, ctx.has, 0)
+        need = [n and w for n, w in zip(ctx.needs_input_grad, wanted)]  # x m h0 w_ih w_hh b_ih b_hh
+        dev = x.device
+        dy = hip.dev_f32(dy, "dy")
+        keep = []
+        p = ops.gru_params(weights, keep)
+        dx = torch.empty_like(x) if need[0] else None
+        dh0 = torch.empty((B, Hd), dtype=torch.float32, device=dev) if (ctx.has[2] and need[2]) else None
+        g = [torch.empty_like(t) if (t is not None and need[3 + i]) else None for i, t in enumerate(weights)]
+        gg = hip.STRUCTS["xnrs_gru_grads"](*[_addr(t) for t in g])
+        l = hip.lib()
+        nws = l.xnrs_gru_bwd_workspace_bytes(B, T, E, Hd)
+        ws = hip.workspace(dev, nws)
+        hip.check(l.xnrs_gru_bwd(hip.ptr(x), ctypes.byref(p), hip.ptr(saved), saved.numel(), hip.ptr(dy), hip.ptr(dx), hip.ptr(dh0),
+                                 ctypes.byref(gg), B, T, E, hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_gru_bwd")
+        return (dx, None, dh0, *g)
+
+
+def gru(x, m, h0, weights):
+    return _Gru.apply(x, m, h0, *weights)
+
+
+class _EmbeddingRows(torch.autograd.Function):
+    """table[ids] of a large table; backward = xnrs_embedding_grad_sparse (one zero fill + one workgroup per id, no atomics),
+    with the padding row's ids dropped (nn.Embedding(padding_idx=...): that row never receives a gradient)."""
+
+    @staticmethod
+    def forward(ctx, ids, table, padding_idx):
+        from . import ops
+        ids = ids.reshape(-1).to(torch.int32).contiguous()
+        gids = ids if padding_idx is None else torch.where(ids == padding_idx, torch.full_like(ids, -1), ids)
+        ctx.save_for_backward(gids)
+        ctx.shape = tuple(table.shape)
+        with torch.no_grad():
+            return ops.embedding_rows_forward(ids, table)
+
+    @staticmethod
+    def backward(ctx, dy):
+        gids, = ctx.saved_tensors
+        dy = hip.dev_f32(dy, "dy")
+        n_rows, K = ctx.shape
+        d_tab = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
+        hip.check(hip.lib().xnrs_embedding_grad_sparse(hip.ptr(dy), hip.ptr(gids), gids.numel(), K, hip.ptr(d_tab), n_rows,
+                                                       hip.stream_ptr(dy.device)), "xnrs_embedding_grad_sparse")
+        return None, d_tab, None
+
+
+def embedding_rows(idx, table, padding_idx):
+    return _EmbeddingRows.apply(idx, table, padding_idx)

@@ -46,6 +46,8 @@ struct Knobs {
   long long gemm_live_tiles_min_rows = 16384;  // XNRS_GEMM_LIVE_TILES_MIN_ROWS: token rows per encoder call from which the list is built
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
+  int gru_layout = 0;           // XNRS_GRU_LAYOUT=1: the GRU recurrence as ONE launch of workgroups that own 32 batch rows for all
+                                // steps (gru.hip) instead of one 2-D launch per step (0, default; the two are compared in DESIGN.md section 10b)
 };
 const Knobs& knobs();
 void reload_knobs();
@@ -599,5 +601,38 @@ hipError_t launch_infonce_fwd(const float* x, const int64_t* lab, int64_t B, int
                               hipStream_t stream);
 hipError_t launch_infonce_bwd(const int64_t* lab, int64_t B, int E, float temperature, const float* ws, const float* gout,
                               float* dx, hipStream_t stream);
+
+// ---------------------------------------------------------------- GRU recurrence (gru.hip; lstur.py:113-154, nn.GRU one layer)
+// Forward over the steps t < T of every batch row: Gh = h_{t-1} . W_hh^T + b_hh, r = s(Gi_r + Gh_r), z = s(Gi_z + Gh_z),
+// n = tanh(Gi_n + r Gh_n), h_t = (1 - z) n + z h_{t-1}; a row with t >= len[row] carries h_{t-1} through.
+struct GruFwdArgs {
+  float* g;          // [B*T, 3Hd], row b*T + t: the input projection Gi on entry; training overwrites it with r | z | n
+  const float* whh;  // [3Hd][Hd]
+  const float* bhh;  // [3Hd] nullable
+  const float* h0;   // [B, Hd] nullable (zero initial state)
+  const int32_t* len;  // [B] steps each row takes (<= T)
+  float* y;          // [B, Hd] final state
+  float* hs;         // training: [B*T, Hd], row b*T + t = the state BEFORE step t; inference: two [B, Hd] buffers
+  float* q;          // training: [B*T, Hd] Gh_n + b_hn; null at inference
+  int32_t B, T, Hd;
+  int32_t vec;       // 16-byte loads along k are legal (Hd % 4 == 0, aligned operands)
+};
+hipError_t launch_gru_lengths(const float* m, int64_t ldm, int32_t* len, int64_t B, int T, hipStream_t stream);
+hipError_t launch_gru_fwd(const GruFwdArgs& a, hipStream_t stream);
+// Backward through the steps in reverse.  Per step dGi_t = [dr', dz', dn'], dGh_t = [dr', dz', dn' r] (pre-activation
+// gradients) and dh_{t-1} = dGh_t . W_hh + z dh_t; the weight and input products over the stacked rows are the caller's.
+struct GruBwdArgs {
+  const float* g;      // saved r | z | n
+  const float* q;      // saved Gh_n + b_hn
+  const float* hs;     // saved states before each step
+  const float* whh_t;  // [Hd][3Hd]: W_hh transposed (k-contiguous for dGh . W_hh)
+  const float* dy;     // [B, Hd] gradient of the final state
+  float* dh;           // [B, Hd] running state gradient; ends as the gradient of h0
+  float* dgi;          // [B*T, 3Hd]
+  float* dgh;          // [B*T, 3Hd]
+  int32_t B, T, Hd;
+  int32_t vec;
+};
+hipError_t launch_gru_bwd(const GruBwdArgs& a, hipStream_t stream);
 
 }  // namespace xnrs

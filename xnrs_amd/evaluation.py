@@ -155,6 +155,13 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
     table = prepare(vecs)  # once per epoch: the scorer's news-side work (identity for the plain dot product)
     batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
     dev = vecs.device
+    uidx = None
+    if getattr(model, "uses_user_index", False):  # (LSTUR: the user tower reads a row of its long-term table per session)
+        uidx = getattr(behaviors, "user_index", None)
+        if uidx is None:
+            raise ValueError(f"evaluate(): {type(model).__name__} needs the user index of every session (sessions without "
+                             "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+        uidx = uidx.to(dev)
     sums = torch.zeros(len(METRIC_NAMES), dtype=torch.float64, device=dev)
     n = len(behaviors)
     for lo in range(s_lo, s_hi, batch):
@@ -162,7 +169,7 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
         hist, off, rows, csess, targets = batcher.eval_batch(sess)
         h = vecs[hist.long()]            # (B, l_hist, E) row gather of pre-encoded vectors (data movement only)
         m = hm[hist.long()]
-        u = model.encode_user(h, m)
+        u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
         r = score(table, rows, csess, u, relu=True)
         sums += rank_metrics(r, targets, off).double().sum(0)
     mean = sharded_mean(sums, n, on)

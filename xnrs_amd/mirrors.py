@@ -90,14 +90,15 @@ class _Mirror(types.ModuleType):
 
 
 #: models that run on the reference's stock-torch classes by default but have a HIP implementation to opt into
-_OPT_IN = ("NPA",)
+_OPT_IN = ("NPA", "LSTUR")
 
 
 def install(force: bool = False, hip_models=()) -> bool:
     """Register the mirrors.  Must run before `xnrs.models` is imported (raises otherwise unless it already IS the mirror);
     idempotent.  Returns True when the reference package was found on sys.path (False: mirrors only).
     hip_models: names of _OPT_IN to route to xnrs_amd too -- ("NPA",): `from xnrs.models.full_models import NPA` and the
-    mirrored make_model build xnrs_amd.models.NPA instead of the reference's file (the default keeps the reference's)."""
+    mirrored make_model build xnrs_amd.models.NPA instead of the reference's file (the default keeps the reference's);
+    ("LSTUR",) does the same for xnrs_amd.models.LSTUR."""
     hip_models = tuple(hip_models)
     bad = [k for k in hip_models if k not in _OPT_IN]
     if bad:
@@ -155,6 +156,10 @@ def install(force: bool = False, hip_models=()) -> bool:
         from .models import npa
         ours_full["NPA"] = npa.NPA
         del ref_models["NPA"]
+    if "LSTUR" in hip_models:
+        from .models import lstur
+        ours_full.update(LSTUR=lstur.LSTUR, LSTURUserEncoder=lstur.LSTURUserEncoder)
+        del ref_models["LSTUR"]
     full = _Mirror("xnrs.models.full_models", ours_full, None, "xnrs.models.full_models", path=[fdir] if fdir else [])
 
     def full_getattr(item):
@@ -171,6 +176,9 @@ def install(force: bool = False, hip_models=()) -> bool:
         if cfg.model == "NPA" and "NPA" in hip_models:
             from .models import npa
             return npa.make_npa(cfg)
+        if cfg.model == "LSTUR" and "LSTUR" in hip_models:
+            from .models import lstur
+            return lstur.make_lstur(cfg)
         try:
             return assemblies.make_model(cfg)
         except NotImplementedError:

@@ -4,3 +4,4 @@ from .assemblies import (NAML, NRMS, NRMS_LF, BaseRec, LSTURNewsEncoder, MeanRec
 from .blocks import ParentRec, TextEncoder, UserEncoder  # noqa: F401
 from .components import layers, scoring  # noqa: F401
 from .npa import NPA, PersonalizedAttention  # noqa: F401  (not in components.*: install() mirrors those)
+from .lstur import LSTUR, LSTURUserEncoder  # noqa: F401  (opt-in like NPA: install(hip_models=("LSTUR",)))

@@ -656,3 +656,82 @@ def embedding_linear(idx: torch.Tensor, embedder, fc):
     hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(ids), 1, hip.ptr(w), hip.ptr(b), hip.ptr(y), M, N, K,
                                         hip.ACT_NONE, hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
     return y
+
+
+# ---- nn.GRU, one layer (LSTUR's short-term user tower, lstur.py:113-154): include/xnrs_hip.h xnrs_gru_*
+def gru_weights(gru):
+    """(w_ih, w_hh, b_ih, b_hh) of a one-layer, unidirectional, batch_first nn.GRU (torch's own layout, gate order r, z, n)."""
+    if gru.num_layers != 1 or gru.bidirectional or not gru.batch_first or getattr(gru, "proj_size", 0):
+        raise hip.XnrsHipError("the HIP GRU is the one-layer, unidirectional, batch_first nn.GRU of LSTUR")
+    return (gru.weight_ih_l0, gru.weight_hh_l0) + tuple(getattr(gru, k) if gru.bias else None for k in ("bias_ih_l0", "bias_hh_l0"))
+
+
+def gru_params(weights, keep):
+    """xnrs_gru_params of (w_ih:(3Hd,E), w_hh:(3Hd,Hd), b_ih, b_hh:(3Hd,) or None)."""
+    ts = [hip.dev_f32(weights[0], "gru weight_ih"), hip.dev_f32(weights[1], "gru weight_hh")]
+    ts += [None if t is None else hip.dev_f32(t, "gru bias") for t in weights[2:]]
+    keep += ts
+    return hip.STRUCTS["xnrs_gru_params"](*[None if t is None else t.data_ptr() for t in ts], ts[1].shape[1])
+
+
+def gru_forward(x, m, h0, weights, keep: bool = False):
+    """x:(B,T,E), m:(B,N>=T[,1]) history mask or None, h0:(B,Hd) or None, weights as gru_weights gives them -> final hidden
+    state (B,Hd): the state after the first sum(m[b, :T]) slots of row b (a row of length 0 keeps its initial state).
+    keep: -> (y, x, saved blob)."""
+    x = hip.dev_f32(x, "gru input")
+    if x.dim() != 3:
+        raise RuntimeError(f"gru: expected (B, T, E), got {tuple(x.shape)}")
+    B, T, E = x.shape
+    Hd = weights[1].shape[1]
+    if tuple(weights[0].shape) != (3 * Hd, E) or tuple(weights[1].shape) != (3 * Hd, Hd):
+        raise RuntimeError(f"gru: input width {E} does not match weights {tuple(weights[0].shape)} / {tuple(weights[1].shape)}")
+    ldm = 0
+    if m is not None:
+        m = hip.dev_f32(m, "gru mask").reshape(B, -1)
+        ldm = m.shape[1]
+        if ldm < T:
+            raise RuntimeError(f"gru: mask of {ldm} slots for {T} steps")
+    if h0 is not None:
+        h0 = hip.dev_f32(h0, "gru initial state")
+        if tuple(h0.shape) != (B, Hd):
+            raise RuntimeError(f"gru: initial state {tuple(h0.shape)}, expected ({B}, {Hd})")
+    keep_alive = []
+    p = gru_params(weights, keep_alive)
+    y = torch.empty((B, Hd), dtype=torch.float32, device=x.device)
+    l = hip.lib()
+    nbytes = l.xnrs_gru_saved_bytes(B, T, E, Hd) if keep else l.xnrs_gru_workspace_bytes(B, T, E, Hd)
+    buf = _saved(x.device, nbytes, keep)
+    fn = l.xnrs_gru_fwd_train if keep else l.xnrs_gru_fwd
+    hip.check(fn(hip.ptr(x), hip.ptr(m), ldm, hip.ptr(h0), C.byref(p), hip.ptr(y), B, T, E, hip.ptr(buf), nbytes,
+                 hip.stream_ptr(x.device)), "xnrs_gru_fwd")
+    return (y, x, buf) if keep else y
+
+
+def gru(x, m, h0, gru_mod):
+    """Final hidden state of nn.GRU over the masked prefix of every row; through autograd when anything needs a gradient."""
+    weights = gru_weights(gru_mod)
+    if _needs_grad(x, h0, *weights):
+        from . import autograd
+        return autograd.gru(x, m, h0, weights)
+    return gru_forward(x, m, h0, weights)
+
+
+def embedding_rows(idx: torch.Tensor, table: torch.Tensor, padding_idx: Optional[int] = None):
+    """table[idx] for a LARGE table (LSTUR's long-term user table, lstur.py:94-98,134); its gradient costs what the ids cost
+    (xnrs_embedding_grad_sparse) and row `padding_idx` receives none.  idx:(M,) int32 -> (M, K)."""
+    if not idx.is_cuda:
+        raise hip.XnrsHipError("user indices must live on the HIP device")
+    if _needs_grad(table):
+        from . import autograd
+        return autograd.embedding_rows(idx, table, padding_idx)
+    return embedding_rows_forward(idx, table)
+
+
+def embedding_rows_forward(idx, table):
+    tab = hip.dev_f32(table, "embedding table")
+    ids = idx.reshape(-1).to(torch.int32).contiguous()
+    K = tab.shape[1]
+    y = torch.empty((ids.numel(), K), dtype=torch.float32, device=tab.device)
+    hip.check(hip.lib().xnrs_gather_rows(hip.ptr(tab), hip.ptr(ids), hip.ptr(y), ids.numel(), K, hip.stream_ptr(tab.device)),
+              "xnrs_gather_rows")
+    return y
