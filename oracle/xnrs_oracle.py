@@ -23,6 +23,7 @@ from __future__ import annotations
 import math
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 Tensor = torch.Tensor
@@ -74,8 +75,53 @@ def additive_attention(x: Tensor, m: Optional[Tensor], sd: State, return_weights
     return out
 
 
-def multi_head_attention(x: Tensor, m: Optional[Tensor], sd: State, n_heads: int, scaled: bool = True) -> Tensor:
-    """xnrs/models/components/layers.py:120-156 (eval mode: the Dropout(0.1) at :148 is identity).
+def attention_drop_uniform(seed: int, n_seq: int, n_heads: int, S: int) -> np.ndarray:
+    """The uniform draw of every attention probability (sequence, head, query, key) of one HIP launch: float32
+    [n_seq, n_heads, S, S], bit for bit the value of ``drop_uniform`` in xnrs_amd/csrc/kernels.h, restated in numpy integer
+    arithmetic (uint64 / uint32 arrays wrap like the device's unsigned types).
+
+    One splitmix64 of (seed, sequence * heads + head); per probability the murmur3 fmix32 finaliser of its low word xor
+    (query * S + key) * 0x9E3779B9, xor its high word; u = (x >> 8) * 2^-24 (exact in fp32).  ``seed`` is taken mod 2^64:
+    the host draws an int64 (ops._att_dropout) and the kernel argument is unsigned.
+    """
+    seed = int(seed) % (1 << 64)
+    pair = np.arange(n_seq * n_heads, dtype=np.uint64) + np.uint64(1)
+    z = np.full_like(pair, seed) + np.uint64(0x9E3779B97F4A7C15) * pair
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    lo = (z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    hi = (z >> np.uint64(32)).astype(np.uint32)
+    idx = np.arange(S * S, dtype=np.uint32) * np.uint32(0x9E3779B9)  # query * S + key, row-major
+    x = lo[:, None] ^ idx[None, :]
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x85EBCA6B)
+    x ^= x >> np.uint32(13)
+    x *= np.uint32(0xC2B2AE35)
+    x ^= x >> np.uint32(16)
+    x ^= hi[:, None]
+    u = (x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return u.reshape(n_seq, n_heads, S, S)
+
+
+def attention_keep_mask(seed: int, n_seq: int, n_heads: int, S: int, p: float) -> np.ndarray:
+    """bool [n_seq, n_heads, S, S]: the probabilities the kernels keep, ``u < 1.f - p`` in fp32 as they compare it."""
+    return attention_drop_uniform(seed, n_seq, n_heads, S) < (np.float32(1) - np.float32(p))
+
+
+def _drop_probabilities(att: Tensor, drop) -> Tensor:
+    """nn.Dropout(p) on the attention probabilities (layers.py:148) under a GIVEN keep mask: where(keep, P / (1 - p), 0),
+    the survivors' scale being the fp32 ``1.f - p`` the kernels divide by."""
+    keep_mask, p = drop
+    keep_mask = torch.as_tensor(keep_mask, dtype=torch.bool).reshape(att.shape)
+    keep = float(np.float32(1) - np.float32(p))
+    return torch.where(keep_mask, att / keep, torch.zeros_like(att))
+
+
+def multi_head_attention(x: Tensor, m: Optional[Tensor], sd: State, n_heads: int, scaled: bool = True, drop=None) -> Tensor:
+    """xnrs/models/components/layers.py:120-156 (eval mode: the Dropout(0.1) at :148 is identity; train mode with
+    ``drop=(keep_mask, p)``, keep_mask bool [B, n_heads, S, S] as attention_keep_mask gives it: the probabilities after
+    the softmax -- the uniform rows of masked queries included, :142-148 -- become where(keep, P / keep, 0)).
 
     NOTE the reference's mask is a *query-row* mask: rows with m==0 are filled with -1e9 for ALL
     keys (layers.py:142-144), so such a row's softmax is uniform 1/S and valid rows still attend
@@ -98,6 +144,8 @@ def multi_head_attention(x: Tensor, m: Optional[Tensor], sd: State, n_heads: int
     if m is not None:
         att = att.masked_fill(m.unsqueeze(1) == 0, -1e9)
     att = torch.softmax(att, dim=-1)
+    if drop is not None:
+        att = _drop_probabilities(att, drop)
     out = torch.matmul(att, v)
     out = out.transpose(1, 2).contiguous().view(B, S, D)
     return linear(out, sd["out.weight"], sd["out.bias"])
@@ -119,8 +167,9 @@ def _pool(x: Tensor, m: Tensor, sd: State, return_weights: bool = False):
     return masked_mean(x, m)
 
 
-def text_encoder(x: Tensor, m: Tensor, sd: State, n_heads: Optional[int] = None) -> Tuple[Tensor, Tensor]:
-    """xnrs/models/components/news_encoding.py:34-60 (eval mode, dropout identity).
+def text_encoder(x: Tensor, m: Tensor, sd: State, n_heads: Optional[int] = None, drop=None) -> Tuple[Tensor, Tensor]:
+    """xnrs/models/components/news_encoding.py:34-60 (eval mode, dropout identity; ``drop=(keep_mask [B*N, h, S, S], p)``:
+    the attention-probability dropout of train mode under that mask, see multi_head_attention).
 
     x:(B,N,S,D) m:(B,N,S,1) -> (y:(B,N,E), hm:(B,N,1)).  att is applied iff the state_dict has
     ``att.*`` keys; the head iff it has ``head.*`` keys.
@@ -130,7 +179,7 @@ def text_encoder(x: Tensor, m: Tensor, sd: State, n_heads: Optional[int] = None)
     m2 = m.reshape(b * n, s, 1)
     if any(k.startswith("att.") for k in sd):
         assert n_heads is not None
-        x = multi_head_attention(x, m2, _sub(sd, "att"), n_heads)
+        x = multi_head_attention(x, m2, _sub(sd, "att"), n_heads, drop=drop)
     x = _pool(x, m2, sd)
     if any(k.startswith("head.") for k in sd):
         x = _mlp_head(x, _sub(sd, "head"))
@@ -140,11 +189,12 @@ def text_encoder(x: Tensor, m: Tensor, sd: State, n_heads: Optional[int] = None)
     return x, hm
 
 
-def user_encoder(x: Tensor, m: Tensor, sd: State, n_heads: Optional[int] = None, return_weights: bool = False):
-    """xnrs/models/components/user_encoding.py:50-81 (eval mode).  x:(B,N,E) m:(B,N,1) -> (B,1,E)."""
+def user_encoder(x: Tensor, m: Tensor, sd: State, n_heads: Optional[int] = None, return_weights: bool = False, drop=None):
+    """xnrs/models/components/user_encoding.py:50-81 (eval mode; ``drop=(keep_mask [B, h, N, N], p)``: attention dropout
+    of train mode under that mask).  x:(B,N,E) m:(B,N,1) -> (B,1,E)."""
     if any(k.startswith("att.") for k in sd):
         assert n_heads is not None
-        x = multi_head_attention(x, m, _sub(sd, "att"), n_heads)
+        x = multi_head_attention(x, m, _sub(sd, "att"), n_heads, drop=drop)
     if return_weights:
         x, a = _pool(x, m, sd, return_weights=True)
     else:

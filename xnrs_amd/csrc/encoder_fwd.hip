@@ -549,7 +549,9 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       ma.mask = cm;
       ma.mask_gather_ids = cids;
       ma.dropout_p = att->dropout_p;
-      ma.seed = att->seed + (uint64_t)c0 * 0x9E3779B97F4A7C15ull;
+      // the kernels count (sequence, head) pairs from the launch's first sequence (kernels.h drop_uniform): a pass that starts
+      // at sequence c0 continues the counter at pair c0 * heads, so sequence c0 + i draws what it draws in an unchunked call.
+      ma.seed = att->seed + (uint64_t)c0 * (uint64_t)att->n_heads * 0x9E3779B97F4A7C15ull;
       ma.seed_dev = att->seed_dev;
       ma.stats = stats;
       // an all-masked sequence: zeros instead of attention over keys nobody weights (kernels.h).  Training over row lists,

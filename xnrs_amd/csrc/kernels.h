@@ -338,8 +338,10 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 }
 
 // Counter-based RNG for attention dropout (training mode only) -> uniform [0,1) per probability.  Parity with torch's CPU
-// Philox stream is impossible (SURVEY.md section 7 "hard parts"); only the distribution matters (tests: expectation,
-// determinism per seed, forward / backward mask consistency).
+// Philox stream is impossible (SURVEY.md section 7 "hard parts"), but this stream is a pure function of (seed, sequence,
+// head, query, key): the test suite restates it bit for bit in plain integer arithmetic, and
+// tests/test_hip_attention_dropout.py compares every kernel that calls drop_uniform with an fp64 reference under that exact
+// mask.  Whoever changes the arithmetic below changes the restatement with it.
 // the dropout seed of a launch: the host value plus, when given, a device word (wave-uniform scalar load)
 template <class Args>
 __device__ __forceinline__ uint64_t drop_seed(const Args& a) {
