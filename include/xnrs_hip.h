@@ -606,6 +606,65 @@ int32_t xnrs_gru_bwd(const float *x, const xnrs_gru_params *p, const void *saved
                      float *dx, float *dh0, const xnrs_gru_grads *g, int64_t B, int32_t T, int32_t E, void *ws,
                      size_t ws_bytes, void *stream);
 
+/* ---- CAUM's candidate-aware user tower (xnrs/models/full_models/caum.py:31-111) -------------------------------------------
+ * Additive to ABI 6.  P = B * C (user, candidate) pairs, row (b, i, j) = pair p = b * C + i, history slot j.
+ *
+ * Long attention: unmasked softmax(Q K^T / sqrt(d_k)) V per head over a packed Q|K|V image at ANY length (caum.py:92 runs
+ * nn.MultiheadAttention without batch_first on a (P, H, E) view: the attended axis is P, hundreds to thousands long).
+ *   qkv : element (l, nb, col) at qkv[l * seq_stride + nb * batch_stride + col], l < L, nb < Nb; q | k | v at columns
+ *         0 | E | 2E, head h at columns [h d_k, (h + 1) d_k) of each (nn.MultiheadAttention's in_proj layout); a contiguous
+ *         seq-first (L, Nb, 3E) image has seq_stride = Nb * 3E, batch_stride = 3E
+ *   o   : (l, nb, col) at o[l * o_seq_stride + nb * o_batch_stride + col], heads concatenated (the out_proj input)
+ * Any L >= 1, Nb >= 1, d_k = E / n_heads from 1 to 128 (XNRS_EHEADS when E % n_heads != 0, XNRS_EUNSUPPORTED above 128).
+ * Online softmax over 32-key tiles: the L x L scores never reach memory.
+ *   fwd_train  also keeps the log-sum-exp of every score row in `saved` (xnrs_attn_long_saved_bytes)
+ *   bwd        d_o (addressed like o) -> dqkv (addressed like qkv, every element written); the probabilities are recomputed
+ *              from `saved`.  ws: xnrs_attn_long_workspace_bytes.  No float atomics: bit-identical run to run. */
+size_t xnrs_attn_long_saved_bytes(int64_t L, int64_t Nb, int32_t E, int32_t n_heads);
+size_t xnrs_attn_long_workspace_bytes(int64_t L, int64_t Nb, int32_t E, int32_t n_heads);
+int32_t xnrs_attn_long_fwd(const float *qkv, int64_t seq_stride, int64_t batch_stride, float *o, int64_t o_seq_stride,
+                           int64_t o_batch_stride, int64_t L, int64_t Nb, int32_t E, int32_t n_heads, void *stream);
+int32_t xnrs_attn_long_fwd_train(const float *qkv, int64_t seq_stride, int64_t batch_stride, float *o, int64_t o_seq_stride,
+                                 int64_t o_batch_stride, int64_t L, int64_t Nb, int32_t E, int32_t n_heads, void *saved,
+                                 size_t saved_bytes, void *stream);
+int32_t xnrs_attn_long_bwd(const float *qkv, int64_t seq_stride, int64_t batch_stride, const float *o, const float *d_o,
+                           int64_t o_seq_stride, int64_t o_batch_stride, const void *saved, size_t saved_bytes, float *dqkv,
+                           int64_t L, int64_t Nb, int32_t E, int32_t n_heads, void *ws, size_t ws_bytes, void *stream);
+
+/* Pair broadcast / combine (caum.py:70-89 without its (B, C, H, 4E) and (B, C, H, 2E) concatenations).  With
+ * linear1.weight = [Wl | Wm | Wr | Wc] and linear2.weight = [W2c | W2h]:
+ *   hp:(B*H, 4E) = h' . [Wl; Wm; Wr; W2h]^T      cp: row p at cp + p * ld_cp, columns 0:E = Wc c' + b1, E:2E = W2c c' + b2
+ *   h_cnn[b,i,j] = hp[b, (j-1) mod H, 0:E] + hp[b, j, E:2E] + hp[b, (j+1) mod H, 2E:3E] + cp[b,i, 0:E]        (B*C*H, E)
+ *   z[b,i,j]     = hp[b, j, 3E:4E] + cp[b,i, E:2E]                                                            (B*C*H, E)
+ * bwd: d_hp = sums over the candidates with the shifts inverted, d_cp (row pitch ld_dcp, columns 0:2E) = sums over the
+ * slots; each nullable, fixed order, no atomics.  H = 1: left, middle and right are the same slot. */
+int32_t xnrs_caum_pair_fwd(const float *hp, const float *cp, int64_t ld_cp, float *h_cnn, float *z, int64_t B, int32_t C,
+                           int32_t H, int32_t E, void *stream);
+int32_t xnrs_caum_pair_bwd(const float *d_hcnn, const float *d_z, float *d_hp, float *d_cp, int64_t ld_dcp, int64_t B,
+                           int32_t C, int32_t H, int32_t E, void *stream);
+
+/* t[p*H + j, :] = tanh(pre[p*H + j, :] + cb[p, :]) -- the candidate half of dense_att.linear (layers.py:163,170 under
+ * caum.py:100-101) added per row; cb: row p at cb + p * ld_cb.  bwd: dpre = dt (1 - t^2), dcb:(P, E) = sum_j dpre (nullable). */
+int32_t xnrs_caum_bias_tanh_fwd(const float *pre, const float *cb, int64_t ld_cb, float *t, int64_t P, int32_t H, int32_t E,
+                                void *stream);
+int32_t xnrs_caum_bias_tanh_bwd(const float *t, const float *dt, float *dpre, float *dcb, int64_t P, int32_t H, int32_t E,
+                                void *stream);
+/* dpre[i] = dy[i] f'(y[i]) for an activation fused into xnrs_linear_fwd (y = act(pre)): tanh 1 - y^2, relu (y > 0), none 1 */
+int32_t xnrs_act_bwd(const float *y, const float *dy, float *dpre, int64_t n, int32_t act, void *stream);
+
+/* Candidate pooling (caum.py:101-109): s_j = w3 . t2[p, j] + b3, a = softmax_j(s) over the H slots of pair p (NO mask),
+ * u[p] = sum_j a_j h_all[p, j].  t2:(P*H, A) the activated second layer of dense_att, w3:(A), b3:(1) nullable,
+ * h_all:(P*H, E) -> u:(P, E), a_out:(P, H) nullable (the backward needs it).  H <= 8192.
+ * bwd: du:(P, E) -> d_t2, d_w3:(A), d_b3:(1), d_hall, each nullable; d_b3 is the sum of the score gradients, which cancels
+ * analytically (a bias in front of a softmax): what is written is its summation noise, as in the reference.
+ * ws: xnrs_caum_pool_bwd_workspace_bytes. */
+int32_t xnrs_caum_pool_fwd(const float *t2, const float *w3, const float *b3, const float *h_all, float *u, float *a_out,
+                           int64_t P, int32_t H, int32_t A, int32_t E, void *stream);
+size_t xnrs_caum_pool_bwd_workspace_bytes(int64_t P, int32_t H, int32_t A);
+int32_t xnrs_caum_pool_bwd(const float *t2, const float *w3, const float *h_all, const float *a, const float *du, float *d_t2,
+                           float *d_w3, float *d_b3, float *d_hall, int64_t P, int32_t H, int32_t A, int32_t E, void *ws,
+                           size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

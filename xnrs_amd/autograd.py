@@ -994,3 +994,198 @@ class _EmbeddingRows(torch.autograd.Function):
 
 def embedding_rows(idx, table, padding_idx):
     return _EmbeddingRows.apply(idx, table, padding_idx)
+
+
+# ---- CAUM's candidate-aware user tower (caum.py:31-111): include/xnrs_hip.h xnrs_attn_long_* / xnrs_caum_* / xnrs_act_bwd.
+#      One node per stage; torch only routes gradients between them (weight slices and concatenations are data movement).
+def _f32_out(shape, dev):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+class _LinearAct(torch.autograd.Function):
+    """y = act(x w^T + b) with the activation in the GEMM epilogue; backward = xnrs_act_bwd, then xnrs_linear_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act):
+        from . import ops
+        with torch.no_grad():
+            y = ops.linear(x, w, b, act)
+        ctx.save_for_backward(hip.dev_f32(x, "x"), hip.dev_f32(w, "w"), y)
+        ctx.has_bias, ctx.act = b is not None, int(act)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        dy = hip.dev_f32(dy, "dy")
+        dev = x.device
+        l = hip.lib()
+        K, N = w.shape[1], w.shape[0]
+        M = x.numel() // K
+        dpre = torch.empty_like(dy)
+        hip.check(l.xnrs_act_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dpre), dy.numel(), ctx.act, hip.stream_ptr(dev)), "xnrs_act_bwd")
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        db = _f32_out((N,), dev) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        nws = l.xnrs_linear_bwd_workspace_bytes(M, N, K)
+        ws = hip.workspace(dev, nws)
+        hip.check(l.xnrs_linear_bwd(hip.ptr(x), None, 0, hip.ptr(w), hip.ptr(dpre), hip.ptr(dx), hip.ptr(dw), hip.ptr(db), M, N, K,
+                                    hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_linear_bwd")
+        return dx, dw, db, None
+
+
+def linear_act(x, w, b, act):
+    return _LinearAct.apply(x, w, b, act)
+
+
+class _EmbeddingLinearAct(torch.autograd.Function):
+    """act(fc(embedder(ids))) as one row-gathered GEMM (CategoryEncoder, news_encoding.py:63-91)."""
+
+    @staticmethod
+    def forward(ctx, ids, table, w, b, act):
+        from . import ops
+        with torch.no_grad():
+            y, idx, tab, wd = ops.embedding_linear_act_forward(ids, table, w, b, act)
+        ctx.save_for_backward(idx, tab, wd, y)
+        ctx.has_bias, ctx.act = b is not None, int(act)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, tab, w, y = ctx.saved_tensors
+        dy = hip.dev_f32(dy, "dy")
+        dev = tab.device
+        M, K, N = idx.numel(), tab.shape[1], w.shape[0]
+        l = hip.lib()
+        dpre = torch.empty_like(dy)
+        hip.check(l.xnrs_act_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dpre), dy.numel(), ctx.act, hip.stream_ptr(dev)), "xnrs_act_bwd")
+        need = ctx.needs_input_grad
+        d_tab = torch.empty_like(tab) if need[1] else None
+        dw = torch.empty_like(w) if need[2] else None
+        db = _f32_out((N,), dev) if (ctx.has_bias and need[3]) else None
+        nws = l.xnrs_embedding_linear_bwd_workspace_bytes(M, N, K)
+        ws = hip.workspace(dev, nws)
+        hip.check(l.xnrs_embedding_linear_bwd(hip.ptr(tab), hip.ptr(idx), hip.ptr(w), hip.ptr(dpre), hip.ptr(d_tab), hip.ptr(dw),
+                                              hip.ptr(db), M, N, K, tab.shape[0], hip.ptr(ws), nws, hip.stream_ptr(dev)),
+                  "xnrs_embedding_linear_bwd")
+        return None, d_tab, dw, db, None
+
+
+def embedding_linear_act(idx, table, w, b, act):
+    return _EmbeddingLinearAct.apply(idx, table, w, b, act)
+
+
+class _AttnLong(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, n_heads):
+        from . import ops
+        with torch.no_grad():
+            o, qkv_c, saved = ops.attn_long_forward(qkv, n_heads, keep=True)
+        ctx.save_for_backward(qkv_c, o, saved)
+        ctx.n_heads = int(n_heads)
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o):
+        qkv, o, saved = ctx.saved_tensors
+        d_o = hip.dev_f32(d_o, "d_o")
+        L, Nb, E3 = qkv.shape
+        E = E3 // 3
+        dqkv = torch.empty_like(qkv)
+        l = hip.lib()
+        nws = l.xnrs_attn_long_workspace_bytes(L, Nb, E, ctx.n_heads)
+        ws = hip.workspace(qkv.device, nws)
+        hip.check(l.xnrs_attn_long_bwd(hip.ptr(qkv), Nb * E3, E3, hip.ptr(o), hip.ptr(d_o), Nb * E, E, hip.ptr(saved), saved.numel(),
+                                       hip.ptr(dqkv), L, Nb, E, ctx.n_heads, hip.ptr(ws), nws, hip.stream_ptr(qkv.device)),
+                  "xnrs_attn_long_bwd")
+        return dqkv, None
+
+
+def attn_long(qkv, n_heads):
+    return _AttnLong.apply(qkv, n_heads)
+
+
+class _CaumPair(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hp, cp, B, C, H):
+        from . import ops
+        ctx.dims = (int(B), int(C), int(H), hp.shape[-1] // 4)
+        with torch.no_grad():
+            return ops.caum_pair_forward(hp, cp, B, C, H)
+
+    @staticmethod
+    def backward(ctx, d_hcnn, d_z):
+        B, C, H, E = ctx.dims
+        dev = d_hcnn.device
+        d_hcnn, d_z = hip.dev_f32(d_hcnn, "d h_cnn"), hip.dev_f32(d_z, "d z")
+        d_hp = _f32_out((B * H, 4 * E), dev) if ctx.needs_input_grad[0] else None
+        d_cp = _f32_out((B * C, 2 * E), dev) if ctx.needs_input_grad[1] else None
+        hip.check(hip.lib().xnrs_caum_pair_bwd(hip.ptr(d_hcnn), hip.ptr(d_z), hip.ptr(d_hp), hip.ptr(d_cp), 2 * E, B, C, H, E,
+                                               hip.stream_ptr(dev)), "xnrs_caum_pair_bwd")
+        return d_hp, d_cp, None, None, None
+
+
+def caum_pair(hp, cp, B, C, H):
+    return _CaumPair.apply(hp, cp, B, C, H)
+
+
+class _CaumBiasTanh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pre, cb, H):
+        from . import ops
+        with torch.no_grad():
+            t = ops.caum_bias_tanh_forward(pre, cb, H)
+        ctx.save_for_backward(t)
+        ctx.H = int(H)
+        return t
+
+    @staticmethod
+    def backward(ctx, dt):
+        t, = ctx.saved_tensors
+        dt = hip.dev_f32(dt, "dt")
+        E = t.shape[-1]
+        P = t.numel() // (E * ctx.H)
+        dpre = torch.empty_like(t)
+        dcb = _f32_out((P, E), t.device) if ctx.needs_input_grad[1] else None
+        hip.check(hip.lib().xnrs_caum_bias_tanh_bwd(hip.ptr(t), hip.ptr(dt), hip.ptr(dpre), hip.ptr(dcb), P, ctx.H, E,
+                                                    hip.stream_ptr(t.device)), "xnrs_caum_bias_tanh_bwd")
+        return dpre, dcb, None
+
+
+def caum_bias_tanh(pre, cb, H):
+    return _CaumBiasTanh.apply(pre, cb, H)
+
+
+class _CaumPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t2, w3, b3, h_all, H):
+        from . import ops
+        with torch.no_grad():
+            u, a, ts = ops.caum_pool_forward(t2, w3, b3, h_all, H, keep=True)
+        ctx.save_for_backward(*ts, a)
+        ctx.H, ctx.has_bias = int(H), b3 is not None
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        t2, w3, h_all, a = ctx.saved_tensors
+        du = hip.dev_f32(du, "du")
+        dev = t2.device
+        H, A, E = ctx.H, t2.shape[-1], h_all.shape[-1]
+        P = a.numel() // H
+        need = ctx.needs_input_grad
+        d_t2 = torch.empty_like(t2) if need[0] else None
+        d_w3 = torch.empty_like(w3) if need[1] else None
+        d_b3 = _f32_out((1,), dev) if (ctx.has_bias and need[2]) else None
+        d_hall = torch.empty_like(h_all) if need[3] else None
+        l = hip.lib()
+        nws = l.xnrs_caum_pool_bwd_workspace_bytes(P, H, A)
+        ws = hip.workspace(dev, nws)
+        hip.check(l.xnrs_caum_pool_bwd(hip.ptr(t2), hip.ptr(w3), hip.ptr(h_all), hip.ptr(a), hip.ptr(du), hip.ptr(d_t2), hip.ptr(d_w3),
+                                       hip.ptr(d_b3), hip.ptr(d_hall), P, H, A, E, hip.ptr(ws), nws, hip.stream_ptr(dev)),
+                  "xnrs_caum_pool_bwd")
+        return d_t2, d_w3, d_b3, d_hall, None
+
+
+def caum_pool(t2, w3, b3, h_all, H):
+    return _CaumPool.apply(t2, w3, b3, h_all, H)

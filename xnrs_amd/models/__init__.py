@@ -5,3 +5,5 @@ from .blocks import ParentRec, TextEncoder, UserEncoder  # noqa: F401
 from .components import layers, scoring  # noqa: F401
 from .npa import NPA, PersonalizedAttention  # noqa: F401  (not in components.*: install() mirrors those)
 from .lstur import LSTUR, LSTURUserEncoder  # noqa: F401  (opt-in like NPA: install(hip_models=("LSTUR",)))
+from .caum import (CAUM, CAUMNewsEncoder, CAUMScoring, CAUMUserEncoder, CategoryEncoder,  # noqa: F401  (not routed by
+                   DenseAttention)                                                         # install(): INTEGRATION.md)

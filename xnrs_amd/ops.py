@@ -735,3 +735,170 @@ def embedding_rows_forward(idx, table):
     hip.check(hip.lib().xnrs_gather_rows(hip.ptr(tab), hip.ptr(ids), hip.ptr(y), ids.numel(), K, hip.stream_ptr(tab.device)),
               "xnrs_gather_rows")
     return y
+
+
+# ---- CAUM's candidate-aware user tower (caum.py:31-111): include/xnrs_hip.h xnrs_attn_long_* / xnrs_caum_* / xnrs_act_bwd
+def linear_act(x, weight, bias, act: int):
+    """act(x w^T + b) with the activation fused into the GEMM epilogue; through autograd when anything needs a gradient."""
+    if _needs_grad(x, weight, bias):
+        from . import autograd
+        return autograd.linear_act(x, weight, bias, act)
+    return linear(x, weight, bias, act)
+
+
+def embedding_linear_act_forward(idx, table, w, b, act: int):
+    tab = hip.dev_f32(table, "embedding table")
+    wd = hip.dev_f32(w, "fc weight")
+    bd = None if b is None else hip.dev_f32(b, "fc bias")
+    if not idx.is_cuda:
+        raise hip.XnrsHipError("category indices must live on the HIP device")
+    ids = idx.to(torch.int32).contiguous()
+    M, K, N = ids.numel(), tab.shape[1], wd.shape[0]
+    y = torch.empty(tuple(idx.shape) + (N,), dtype=torch.float32, device=tab.device)
+    hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(ids), 1, hip.ptr(wd), hip.ptr(bd), hip.ptr(y), M, N, K, act,
+                                        hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
+    return y, ids, tab, wd
+
+
+def embedding_linear_act(idx: torch.Tensor, embedder, fc, act: int):
+    """act(fc(embedder(idx))) (CategoryEncoder, news_encoding.py:63-91) as ONE GEMM whose rows are gathered from the table."""
+    if _needs_grad(embedder, fc):
+        from . import autograd
+        if not idx.is_cuda:
+            raise hip.XnrsHipError("category indices must live on the HIP device")
+        return autograd.embedding_linear_act(idx, embedder.weight, fc.weight, fc.bias, act)
+    return embedding_linear_act_forward(idx, embedder.weight, fc.weight, fc.bias, act)[0]
+
+
+def attn_long_forward(qkv: torch.Tensor, n_heads: int, keep: bool = False):
+    """qkv:(L, Nb, 3E) seq-first packed q | k | v (nn.MultiheadAttention's in_proj layout) -> o:(L, Nb, E), the heads'
+    softmax(q k^T / sqrt(d_k)) v concatenated; no mask, any L.  keep: -> (o, qkv, saved log-sum-exp blob)."""
+    qkv = hip.dev_f32(qkv, "attention q|k|v")
+    if qkv.dim() != 3 or qkv.shape[-1] % 3:
+        raise RuntimeError(f"attn_long: expected (L, Nb, 3E), got {tuple(qkv.shape)}")
+    L, Nb, E3 = qkv.shape
+    E = E3 // 3
+    o = torch.empty((L, Nb, E), dtype=torch.float32, device=qkv.device)
+    l = hip.lib()
+    st = hip.stream_ptr(qkv.device)
+    if keep:
+        nbytes = l.xnrs_attn_long_saved_bytes(L, Nb, E, n_heads)
+        saved = _saved(qkv.device, nbytes, True)
+        hip.check(l.xnrs_attn_long_fwd_train(hip.ptr(qkv), Nb * E3, E3, hip.ptr(o), Nb * E, E, L, Nb, E, n_heads, hip.ptr(saved),
+                                             nbytes, st), "xnrs_attn_long_fwd_train")
+        return o, qkv, saved
+    hip.check(l.xnrs_attn_long_fwd(hip.ptr(qkv), Nb * E3, E3, hip.ptr(o), Nb * E, E, L, Nb, E, n_heads, st), "xnrs_attn_long_fwd")
+    return o
+
+
+def attn_long(qkv: torch.Tensor, n_heads: int):
+    """Unmasked multi-head attention over a packed seq-first (L, Nb, 3E) image at any length; autograd when qkv needs it."""
+    if _needs_grad(qkv):
+        from . import autograd
+        return autograd.attn_long(qkv, n_heads)
+    return attn_long_forward(qkv, n_heads)
+
+
+def caum_pair_forward(hp, cp, B: int, C: int, H: int):
+    """hp:(B*H, 4E), cp:(B*C, 2E) -> (h_cnn, z), each (B*C*H, E)  (include/xnrs_hip.h: xnrs_caum_pair_fwd)."""
+    hp, cp = hip.dev_f32(hp, "history projections"), hip.dev_f32(cp, "candidate projections")
+    E = hp.shape[-1] // 4
+    if tuple(hp.shape) != (B * H, 4 * E) or tuple(cp.shape) != (B * C, 2 * E):
+        raise RuntimeError(f"caum_pair: hp {tuple(hp.shape)} / cp {tuple(cp.shape)} for B={B}, C={C}, H={H}")
+    h_cnn = torch.empty((B * C * H, E), dtype=torch.float32, device=hp.device)
+    z = torch.empty_like(h_cnn)
+    hip.check(hip.lib().xnrs_caum_pair_fwd(hip.ptr(hp), hip.ptr(cp), 2 * E, hip.ptr(h_cnn), hip.ptr(z), B, C, H, E,
+                                           hip.stream_ptr(hp.device)), "xnrs_caum_pair_fwd")
+    return h_cnn, z
+
+
+def caum_pair(hp, cp, B: int, C: int, H: int):
+    if _needs_grad(hp, cp):
+        from . import autograd
+        return autograd.caum_pair(hp, cp, B, C, H)
+    return caum_pair_forward(hp, cp, B, C, H)
+
+
+def caum_bias_tanh_forward(pre, cb, H: int):
+    pre, cb = hip.dev_f32(pre, "dense attention pre-activation"), hip.dev_f32(cb, "candidate term")
+    E = pre.shape[-1]
+    P = cb.shape[0]
+    if tuple(pre.shape) != (P * H, E) or tuple(cb.shape) != (P, E):
+        raise RuntimeError(f"caum_bias_tanh: pre {tuple(pre.shape)} / cb {tuple(cb.shape)} for H={H}")
+    t = torch.empty_like(pre)
+    hip.check(hip.lib().xnrs_caum_bias_tanh_fwd(hip.ptr(pre), hip.ptr(cb), E, hip.ptr(t), P, H, E, hip.stream_ptr(pre.device)),
+              "xnrs_caum_bias_tanh_fwd")
+    return t
+
+
+def caum_bias_tanh(pre, cb, H: int):
+    """tanh(pre[p*H + j] + cb[p]): pre:(P*H, E), cb:(P, E)."""
+    if _needs_grad(pre, cb):
+        from . import autograd
+        return autograd.caum_bias_tanh(pre, cb, H)
+    return caum_bias_tanh_forward(pre, cb, H)
+
+
+def caum_pool_forward(t2, w3, b3, h_all, H: int, keep: bool = False):
+    t2, w3, h_all = hip.dev_f32(t2, "dense attention hidden"), hip.dev_f32(w3, "dense attention linear3 weight"), hip.dev_f32(h_all, "h_all")
+    b3 = None if b3 is None else hip.dev_f32(b3, "dense attention linear3 bias")
+    A, E = t2.shape[-1], h_all.shape[-1]
+    R = t2.numel() // A
+    if R % H or h_all.numel() != R * E or w3.numel() != A:
+        raise RuntimeError(f"caum_pool: t2 {tuple(t2.shape)}, h_all {tuple(h_all.shape)}, w3 {tuple(w3.shape)} for H={H}")
+    P = R // H
+    u = torch.empty((P, E), dtype=torch.float32, device=t2.device)
+    a = torch.empty((P, H), dtype=torch.float32, device=t2.device) if keep else None
+    hip.check(hip.lib().xnrs_caum_pool_fwd(hip.ptr(t2), hip.ptr(w3), hip.ptr(b3), hip.ptr(h_all), hip.ptr(u), hip.ptr(a), P, H, A, E,
+                                           hip.stream_ptr(t2.device)), "xnrs_caum_pool_fwd")
+    return (u, a, (t2, w3, h_all)) if keep else u
+
+
+def caum_pool(t2, w3, b3, h_all, H: int):
+    """softmax over the H slots of w3 . t2 + b3, weighted sum of h_all: t2:(P*H, A), h_all:(P*H, E) -> (P, E)."""
+    if _needs_grad(t2, w3, b3, h_all):
+        from . import autograd
+        return autograd.caum_pool(t2, w3, b3, h_all, H)
+    return caum_pool_forward(t2, w3, b3, h_all, H)
+
+
+def caum_user(h, c, enc):
+    """CAUMUserEncoder.forward (caum.py:56-111) on h:(B,H,E) history and c:(B,C,E) candidate vectors -> u:(B,C,E).  `enc`
+    holds the reference's modules (dropout1-3, linear1-3, dense_att, multihead_attention); none of the Linear /
+    MultiheadAttention modules is called.  The dropouts are torch's, on the device."""
+    h, c = hip.dev_f32(h, "history vectors"), hip.dev_f32(c, "candidate vectors")
+    B, H, E = h.shape
+    C = c.shape[1]
+    if c.shape[0] != B or c.shape[2] != E:
+        raise RuntimeError(f"caum_user: history {tuple(h.shape)} against candidates {tuple(c.shape)}")
+    mha, da = enc.multihead_attention, enc.dense_att
+    if mha.in_proj_weight is None or mha.bias_k is not None or mha.add_zero_attn or mha.batch_first or mha.dropout != 0.0:
+        raise hip.XnrsHipError("the HIP CAUM tower is nn.MultiheadAttention(E, n_heads) as caum.py:52-54 builds it")
+    cd, hd = enc.dropout1(c), enc.dropout2(h)
+    w1, w2 = enc.linear1.weight, enc.linear2.weight
+    # weight blocks side by side (slices and concatenations: data movement, differentiable by torch's own bookkeeping)
+    w_h = torch.cat([w1[:, :E], w1[:, E:2 * E], w1[:, 2 * E:3 * E], w2[:, E:]], dim=0)     # [Wl; Wm; Wr; W2h]
+    w_c = torch.cat([w1[:, 3 * E:], w2[:, :E], da.linear.weight[:, E:]], dim=0)           # [Wc; W2c; Wdc]
+    b_c = torch.cat([enc.linear1.bias, enc.linear2.bias, da.linear.bias], dim=0)
+    hp = linear(hd.reshape(B * H, E), w_h, None)                                          # (B*H, 4E)
+    cp = linear(cd.reshape(B * C, E), w_c, b_c)                                           # (B*C, 3E)
+    h_cnn, z = caum_pair(hp, cp[:, :2 * E], B, C, H)
+    # nn.MultiheadAttention without batch_first on the (P, H, E) view: the attended axis is P = B*C, the slot is the batch
+    qkv = linear(z, mha.in_proj_weight, mha.in_proj_bias)
+    o = attn_long(qkv.reshape(B * C, H, 3 * E), mha.num_heads)
+    h_att = linear(o.reshape(B * C * H, E), mha.out_proj.weight, mha.out_proj.bias)
+    h_all = linear(enc.dropout3(torch.cat([h_cnn, h_att], dim=1)), enc.linear3.weight, enc.linear3.bias)
+    pre = linear(h_all, da.linear.weight[:, :E], None)
+    t1 = caum_bias_tanh(pre, cp[:, 2 * E:], H)
+    t2 = linear_act(t1, da.linear2.weight, da.linear2.bias, hip.ACT_TANH)
+    u = caum_pool(t2, da.linear3.weight, da.linear3.bias, h_all, H)
+    return u.reshape(B, C, E)
+
+
+def diag_scoring(u, c, normalize: bool = False):
+    """CAUMScoring.forward (scoring.py:26-38): r[b, i] = u[b, i] . c[b, i], the diagonal of DotScoring's (C, C) product --
+    dot_scoring over (B*C, 1) pairs.  u, c:(B,C,E) -> (B,C,1)."""
+    B, C, E = c.shape
+    if tuple(u.shape) != (B, C, E):
+        raise RuntimeError(f"CAUMScoring: user vectors {tuple(u.shape)} against candidates {tuple(c.shape)}")
+    return dot_scoring(u.reshape(B * C, 1, E), c.reshape(B * C, 1, E), normalize).reshape(B, C, 1)
