@@ -351,10 +351,30 @@ __global__ __launch_bounds__(1024) void compact_rows_kernel(const float* __restr
 // news' offset + the popcount of the bits below it).  378 -> 249 us per call of 25 600 news x 50 in five passes (it sits on
 // the critical path of the device-compacted encoder; one workgroup per pass is what bounds it now: the passes' rounds of
 // 1 024 news run one after the other).
+//
+// DENSE: the same sweep for the DENSE encoder passes (encoder_fwd.hip "live rows"): rows stay where they are, so what a pass
+// needs is the ascending list of its unmasked token rows in the pass's own row space (dl.live_loc: where Q and the scores are
+// written, and where the O rows are read), the same tokens' rows in the gathered table when there are ids (live_all, else not
+// written), their number (counts[0]), and the live 128-row tile list of launch_live_tiles (list_live_tiles below) -- ONE list
+// launch per encoder call.  row_off / kv_src / kv_block are not written; a mask value other than 0 / 1 is legal there (a
+// row is live iff mask != 0, the dense path's own rule), so counts[2] is not written either.
+struct DenseLists {
+  int32_t* live_loc;  // [passes * chunk * S]
+  uint8_t* alive;     // [n_news] scratch
+  int64_t* n_tiles;   // [passes]
+  int32_t* tiles;     // [passes * cap]
+  int64_t cap;
+  int BM;
+};
+__device__ void list_live_tiles(const uint8_t* __restrict__ alive, int64_t cn, int L, int BM, int32_t* __restrict__ tiles,
+                                int64_t* __restrict__ n_out, int* s_wsum, int* s_carry);
+
+template <bool DENSE>
 __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __restrict__ mask, const int32_t* __restrict__ ids,
                                                                int64_t n_news, int64_t chunk, int S, int64_t* __restrict__ row_off_all,
                                                                int32_t* __restrict__ live_all, int32_t* __restrict__ kvs_all,
-                                                               int32_t* __restrict__ kvb_all, int64_t* __restrict__ counts_all) {
+                                                               int32_t* __restrict__ kvb_all, int64_t* __restrict__ counts_all,
+                                                               DenseLists dl) {
   __shared__ unsigned long long s_bits[1024];
   __shared__ int64_t s_row[1024];
   __shared__ int s_ex[2][1024];
@@ -363,14 +383,16 @@ __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __res
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t news0 = (int64_t)blockIdx.x * chunk;
   const int cn = (int)(n_news - news0 < chunk ? n_news - news0 : chunk);
-  int64_t* row_off = row_off_all + (int64_t)blockIdx.x * (chunk + 1);
-  int32_t* live_src = live_all + (int64_t)blockIdx.x * chunk * S;
-  int32_t* kv_src = kvs_all + (int64_t)blockIdx.x * chunk * S;
-  int32_t* kv_block = kvb_all + (int64_t)blockIdx.x * chunk;
+  int64_t* row_off = DENSE ? nullptr : row_off_all + (int64_t)blockIdx.x * (chunk + 1);
+  int32_t* live_src = live_all ? live_all + (int64_t)blockIdx.x * chunk * S : nullptr;
+  int32_t* kv_src = DENSE ? nullptr : kvs_all + (int64_t)blockIdx.x * chunk * S;
+  int32_t* kv_block = DENSE ? nullptr : kvb_all + (int64_t)blockIdx.x * chunk;
   int64_t* counts = counts_all + 3 * (int64_t)blockIdx.x;
+  int32_t* live_loc = DENSE ? dl.live_loc + (int64_t)blockIdx.x * chunk * S : nullptr;
+  uint8_t* alive = DENSE ? dl.alive + news0 : nullptr;
   int bad = 0;
   if (tid < 2) s_carry[tid] = 0;
-  if (tid == 0) row_off[0] = 0;
+  if (!DENSE && tid == 0) row_off[0] = 0;
   for (int base = 0; base < cn; base += 1024) {
     const int nn = cn - base < 1024 ? cn - base : 1024;
     s_bits[tid] = 0ull;
@@ -415,8 +437,12 @@ __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __res
       s_ex[which][tid] = before + incl[which] - v[which];
     }
     if (tid < nn) {
-      row_off[base + tid + 1] = s_ex[0][tid] + cnt;
-      kv_block[base + tid] = s_ex[1][tid] / S;  // (an empty news: the block the next non-empty one gets -- never read)
+      if constexpr (DENSE) {
+        alive[base + tid] = bits != 0ull ? 1 : 0;
+      } else {
+        row_off[base + tid + 1] = s_ex[0][tid] + cnt;
+        kv_block[base + tid] = s_ex[1][tid] / S;  // (an empty news: the block the next non-empty one gets -- never read)
+      }
     }
     __syncthreads();
     if (tid == 1023) {
@@ -429,10 +455,28 @@ __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __res
       const unsigned long long b = s_bits[jj];
       if (b == 0ull) continue;
       const int32_t src = (int32_t)(s_row[jj] * S + sl);
-      kv_src[s_ex[1][jj] + sl] = src;
-      if ((b >> sl) & 1ull) live_src[s_ex[0][jj] + __popcll(b & ((1ull << sl) - 1ull))] = src;
+      if constexpr (DENSE) {
+        if ((b >> sl) & 1ull) {
+          const int at = s_ex[0][jj] + __popcll(b & ((1ull << sl) - 1ull));
+          live_loc[at] = (int32_t)((base + jj) * S + sl);
+          if (live_src) live_src[at] = src;
+        }
+      } else {
+        kv_src[s_ex[1][jj] + sl] = src;
+        if ((b >> sl) & 1ull) live_src[s_ex[0][jj] + __popcll(b & ((1ull << sl) - 1ull))] = src;
+      }
     }
     __syncthreads();
+  }
+  if constexpr (DENSE) {  // (the loop's last barrier has passed: s_carry is final, the alive flags of this pass are visible)
+    if (tid == 0) {
+      counts[0] = s_carry[0];
+      counts[1] = s_carry[1];
+      s_carry[0] = 0;
+    }
+    __syncthreads();
+    list_live_tiles(alive, cn, S, dl.BM, dl.tiles + (int64_t)blockIdx.x * dl.cap, dl.n_tiles + blockIdx.x, s_wsum[0], &s_carry[0]);
+    return;
   }
   bad = __syncthreads_or(bad);
   if (tid == 0) {
@@ -601,8 +645,8 @@ hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_
   const int64_t passes = (n_news + chunk - 1) / chunk;
   if (passes > 0x7fffffffLL) return hipErrorInvalidValue;
   if (S <= 64)
-    hipLaunchKernelGGL(compact_rows64_kernel, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_news, chunk, S, row_off,
-                       live_src, kv_src, kv_block, counts);
+    hipLaunchKernelGGL(compact_rows64_kernel<false>, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_news, chunk, S,
+                       row_off, live_src, kv_src, kv_block, counts, DenseLists{});
   else
     hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_news, chunk, S, row_off,
                        live_src, kv_src, kv_block, counts);
@@ -624,7 +668,7 @@ __global__ __launch_bounds__(1024) void live_tiles_kernel(const float* __restric
                                                            int32_t* __restrict__ tiles_all) {
   __shared__ int s_wsum[16];
   __shared__ int s_carry;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int64_t seq0 = (int64_t)blockIdx.x * chunk;
   const int64_t cn = n_seq - seq0 < chunk ? n_seq - seq0 : chunk;
   uint8_t* alive = alive_all + seq0;
@@ -638,6 +682,14 @@ __global__ __launch_bounds__(1024) void live_tiles_kernel(const float* __restric
   }
   if (tid == 0) s_carry = 0;
   __syncthreads();  // (the flags were written by this workgroup: visible to it behind the barrier)
+  list_live_tiles(alive, cn, L, BM, tiles, n_tiles + blockIdx.x, s_wsum, &s_carry);
+}
+
+// the tile scan of a pass (one 1024-thread workgroup; *s_carry == 0 and the alive flags visible on entry, s_wsum: 16 ints):
+// tiles[0 .. *n_out) = the BM-row tiles of the [cn * L]-row image that hold a row of an alive sequence, ascending
+__device__ void list_live_tiles(const uint8_t* __restrict__ alive, int64_t cn, int L, int BM, int32_t* __restrict__ tiles,
+                                int64_t* __restrict__ n_out, int* s_wsum, int* s_carry) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t rows = cn * L;
   const int64_t nt = (rows + BM - 1) / BM;
   const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -651,18 +703,18 @@ __global__ __launch_bounds__(1024) void live_tiles_kernel(const float* __restric
     const uint64_t b = __ballot(live);
     if (lane == 0) s_wsum[wave] = __popcll(b);
     __syncthreads();
-    int before = s_carry;
+    int before = *s_carry;
     for (int w = 0; w < wave; ++w) before += s_wsum[w];
     if (live) tiles[before + __popcll(b & below)] = (int32_t)t;
     __syncthreads();
     if (tid == 0) {
-      int tot = s_carry;
+      int tot = *s_carry;
       for (int w = 0; w < 16; ++w) tot += s_wsum[w];
-      s_carry = tot;
+      *s_carry = tot;
     }
     __syncthreads();
   }
-  if (tid == 0) n_tiles[blockIdx.x] = s_carry;
+  if (tid == 0) *n_out = *s_carry;
 }
 
 hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM, uint8_t* alive,
@@ -673,6 +725,19 @@ hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_se
   if (passes > 0x7fffffffLL || cap > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(live_tiles_kernel, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_seq, chunk, L, BM, cap, alive,
                      n_tiles, tiles);
+  return hipGetLastError();
+}
+
+// the lists of the dense passes' live rows AND live row tiles in one launch (S <= 64; kernels.h)
+hipError_t launch_dense_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM,
+                                  int32_t* live_loc, int32_t* live_src, int64_t* counts, uint8_t* alive, int64_t* n_tiles,
+                                  int32_t* tiles, hipStream_t stream) {
+  if (n_seq <= 0 || chunk <= 0 || L <= 0 || BM <= 0) return hipSuccess;
+  const int64_t passes = (n_seq + chunk - 1) / chunk;
+  const int64_t cap = live_tiles_cap(chunk, L, BM);
+  if (L > 64 || passes > 0x7fffffffLL || cap > 0x7fffffffLL || chunk * L > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(compact_rows64_kernel<true>, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_seq, chunk, L,
+                     nullptr, ids ? live_src : nullptr, nullptr, nullptr, counts, DenseLists{live_loc, alive, n_tiles, tiles, cap, BM});
   return hipGetLastError();
 }
 

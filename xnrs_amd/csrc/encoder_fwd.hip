@@ -67,6 +67,12 @@ Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additiv
   p.off_lt_alive = c.take_if(lt, (size_t)(n_seq > 0 ? n_seq : 1));
   p.off_lt_n = c.take_if(lt, passes * sizeof(int64_t));
   p.off_lt_tiles = c.take_if(lt, passes * (size_t)live_tiles_cap(chunk, L, LIVE_TILE_BM) * sizeof(int32_t));
+  // ... and their live rows (launch_dense_row_lists: 8 bytes per token row of the call, 11 MB at the benchmark's history call),
+  // in the pass's row space and in the gathered table's; {live rows, -, -} per pass
+  const bool lr = lt && L <= 64;
+  p.off_lr_loc = c.take_if(lr, passes * rows * sizeof(int32_t));
+  p.off_lr_src = c.take_if(lr, passes * rows * sizeof(int32_t));
+  p.off_lr_cnt = c.take_if(lr, passes * 3 * sizeof(int64_t));
   // folded out-projection ("fold" below): reserved whenever the shape is eligible, whatever the knob says
   // (training keeps W', b', the pooled O rows and the weight sums for the backward)
   p.fold = carve_fold(c, att && additive, n_seq, D, A);
@@ -477,17 +483,43 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   const int64_t lt_cap = live_tiles_cap(p.chunk, L, LIVE_TILE_BM);
   const int64_t* lt_n = at<int64_t>(w, p.off_lt_n);
   const int32_t* lt_tiles = at<int32_t>(w, p.off_lt_tiles);
-  if (lt_qkv || lt_fc1)
+  // Live rows (the second half of the same saving; XNRS_GEMM_LIVE_ROWS=0: off).  A masked token row of a LIVE sequence stays
+  // a key and a value (the mask is a query-row mask, layers.py:142-144), but its Q row feeds only its own attention row and
+  // its fc1 row only its own score -- and both poolers multiply that row by exactly 0.  So wherever a product walks the
+  // live row tiles, its query / score half walks the ascending list of the pass's unmasked token rows instead (mask != 0:
+  // the dense path's own rule, any mask value keeps its meaning), rows gathered and results scattered IN PLACE:
+  //   Q|K|V: K|V over the live row tiles as before (N = 2D), Q over the live rows (N = D) into the same image; the Q rows
+  //          of masked tokens stay UNWRITTEN -- the attention kernel does not read a masked query's row (mha_core.hip);
+  //   fc1:   the fc2 dots of the live rows, scattered to their own rows of the score image; the pooler does not read a
+  //          masked token's score (AdditivePoolArgs::skip_masked), so its summation order -- and every bit -- is unchanged.
+  // The lists of every pass come from the ONE list launch of the call (launch_dense_row_lists writes the tile lists too);
+  // the grids are sized for every row, the counts stay on the device (GemmArgs::m_dev): nothing depends on the data.
+  const bool lr = lt && knobs().gemm_live_rows && p.off_lr_cnt != 0 && L <= 64 && n_seq * (int64_t)L <= 0x7fffffffLL &&
+                  n_seq * (int64_t)L >= knobs().gemm_live_rows_min_rows;
+  const bool lr_qkv = lr && lt_qkv, lr_fc1 = lr && lt_fc1;
+  const int32_t *lr_loc = at<int32_t>(w, p.off_lr_loc), *lr_src = at<int32_t>(w, p.off_lr_src);
+  const int64_t* lr_cnt = at<int64_t>(w, p.off_lr_cnt);
+  constexpr float LR_FILL = 0.3f;  // tile choice only: the share of a pass's rows expected on the list (ragged titles x empty slots)
+  if (lr_qkv || lr_fc1)
+    XNRS_TRY(launch_dense_row_lists(m, ids, n_seq, p.chunk, L, LIVE_TILE_BM, at<int32_t>(w, p.off_lr_loc), at<int32_t>(w, p.off_lr_src),
+                                    at<int64_t>(w, p.off_lr_cnt), at<uint8_t>(w, p.off_lt_alive), at<int64_t>(w, p.off_lt_n),
+                                    at<int32_t>(w, p.off_lt_tiles), stream));
+  else if (lt_qkv || lt_fc1)
     XNRS_TRY(launch_live_tiles(m, ids, n_seq, p.chunk, L, LIVE_TILE_BM, at<uint8_t>(w, p.off_lt_alive), at<int64_t>(w, p.off_lt_n),
                                at<int32_t>(w, p.off_lt_tiles), stream));
-  // launch timer on: the live-tile counts of every pass, read back ONCE per call (the timer is a measurement aid that
-  // synchronises anyway; nothing is read while it is off) -- stages 0 and 3 then report EXECUTED FLOPs
-  std::vector<int64_t> lt_host;
+  // launch timer on: the live-tile (and live-row) counts of every pass, read back ONCE per call (the timer is a measurement
+  // aid that synchronises anyway; nothing is read while it is off) -- stages 0 and 3 then report EXECUTED FLOPs
+  std::vector<int64_t> lt_host, lr_host;
   if ((lt_qkv && prof_on(0)) || (lt_fc1 && prof_on(3))) {
     lt_host.resize((size_t)((n_seq + p.chunk - 1) / p.chunk));
     if (hipStreamSynchronize(stream) != hipSuccess ||
         hipMemcpy(lt_host.data(), lt_n, lt_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
       lt_host.clear();
+    if (lr_qkv || lr_fc1) {
+      lr_host.resize(3 * lt_host.size());
+      if (lt_host.empty() || hipMemcpy(lr_host.data(), lr_cnt, lr_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        lr_host.clear();
+    }
   }
   for (int64_t c0 = 0; !fused && !afused && c0 < n_seq; c0 += p.chunk) {
     const int64_t nc = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
@@ -497,6 +529,11 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
     const int32_t* ltl = lt_tiles + (c0 / p.chunk) * lt_cap;
     const double lt_rows = (double)LIVE_TILE_BM *
                            (double)(lt_host.empty() ? (rows + LIVE_TILE_BM - 1) / LIVE_TILE_BM : lt_host[(size_t)(c0 / p.chunk)]);
+    // this pass's live rows: the list in its own row space, in x's (the table's with ids), the count, and -- timer -- its value
+    const int32_t* lrl = lr_loc + (c0 / p.chunk) * p.chunk * L;
+    const int32_t* lrs = lr_src + (c0 / p.chunk) * p.chunk * L;
+    const int64_t* lrn = lr_cnt + 3 * (c0 / p.chunk);
+    const double lr_rows = lr_host.empty() ? (double)rows : (double)lr_host[(size_t)(3 * (c0 / p.chunk))];
     // this chunk's view of the inputs
     const int32_t* cids = ids ? ids + c0 : nullptr;
     const float* cx = ids ? x : x + c0 * (int64_t)L * D;      // table stays whole when gathering
@@ -534,6 +571,18 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
           q.m_fill_hint = 0.4f;
           XNRS_TRY(launch_gemm_f32(q, stream));
         }
+      } else if (lr_qkv) {  // K|V of the live row tiles, Q of the live rows: a masked token's Q row stays unwritten, nobody reads it
+        ProfScope ps(0, 2.0 * lt_rows * 2.0 * D * D + 2.0 * lr_rows * (double)D * D, stream);
+        GemmArgs g = qkv_projection(cx, {cids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
+        g.live_n = ltn;
+        g.live_tiles = ltl;
+        XNRS_TRY(launch_gemm_f32(g, stream));
+        GemmArgs q = gemm_linear(cx, {ids ? lrs : lrl, 1}, D, att->wq, att->bq, qkv, ld3, rows, D, D);
+        q.c_scatter = 1;
+        q.c_scatter_ids = lrl;
+        q.m_dev = lrn;
+        q.m_fill_hint = LR_FILL;
+        XNRS_TRY(launch_gemm_f32(q, stream));
       } else {
         GemmArgs g = qkv_projection(cx, {cids, L}, att, 0, qkv, ld3, rows, D, pqkv);
         if (lt_qkv) {  // the rows of the dead tiles stay unwritten: the attention kernel below never reads them
@@ -602,6 +651,14 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
           fg.m_fill_hint = 0.4f;
           XNRS_TRY(launch_gemm_f32(fg, stream));
         }
+      } else if (lr_fc1) {  // the scores of the live rows, in place; the pooler below reads no other
+        GemmArgs fg = fc1_product(seq, {seq_ids ? lrs : lrl, 1}, fc1, t, rows, D, A, true, pool, p1);
+        fg.c_scatter = 1;
+        fg.c_scatter_ids = lrl;
+        fg.m_dev = lrn;
+        fg.m_fill_hint = LR_FILL;
+        ProfScope ps(3, 2.0 * lr_rows * (double)D * A, stream);
+        XNRS_TRY(launch_gemm_f32(fg, stream));
       } else {
         GemmArgs fg = fc1_product(seq, {seq_ids, L}, fc1, t, rows, D, A, rowdot, pool, p1);
         if (lt_fc1) {  // the scores of the dead tiles stay unwritten: the pooler below leaves their sequences first
@@ -613,6 +670,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       }
       AdditivePoolArgs pa = additive_pool_args(t, rowdot, pool, seq, nc, L, D, A);
       pa.skip_dead = lt_fc1 ? 1 : 0;
+      pa.skip_masked = lr_fc1 ? 1 : 0;
       pa.mask = cm;
       pa.mask_gather_ids = cids;
       pa.x_gather_ids = seq_ids;

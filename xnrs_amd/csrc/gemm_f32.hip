@@ -596,8 +596,13 @@ __global__ __launch_bounds__(256, MINW) void gemm_f32_kernel(const GemmArgs a, i
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const float sc = rowdot_block_t_lds<decltype(FAST)::value>(acc[i][j], s_bw + cb, half);
-          const int64_t row = m0 + wm * 32 * TM + 32 * i + (lane & 31);
-          if (lane < 32 && row < Mrun && n0 + cb < a.Nseg) a.rowdot_out[row * a.ldrd + ((n0 + cb) >> 5)] = sc;
+          int64_t row = m0 + wm * 32 * TM + 32 * i + (lane & 31);
+          if (lane < 32 && row < Mrun && n0 + cb < a.Nseg) {
+            if constexpr (GATH && MDEV) {  // scores scattered in place: the row the list names (one row per id; launcher)
+              if (a.c_scatter) row = (a.c_scatter_ids ? a.c_scatter_ids : a.gather_ids)[row];
+            }
+            a.rowdot_out[row * a.ldrd + ((n0 + cb) >> 5)] = sc;
+          }
         }
       }
     };
@@ -983,6 +988,8 @@ static Knobs read_knobs() {
   k.mha_skip_masked = num("XNRS_MHA_SKIP_MASKED", 1) != 0;
   k.gemm_live_tiles = num("XNRS_GEMM_LIVE_TILES", 1) != 0;
   k.gemm_live_tiles_min_rows = num("XNRS_GEMM_LIVE_TILES_MIN_ROWS", 16384);
+  k.gemm_live_rows = num("XNRS_GEMM_LIVE_ROWS", 1) != 0;
+  k.gemm_live_rows_min_rows = num("XNRS_GEMM_LIVE_ROWS_MIN_ROWS", 16384);
   k.bwd_side_stream = num("XNRS_BWD_SIDE_STREAM", 1) != 0;
   k.bwd_side_min_rows = num("XNRS_BWD_SIDE_MIN_ROWS", 0);
   k.gru_layout = num("XNRS_GRU_LAYOUT", 0) == 1 ? 1 : 0;
@@ -1036,9 +1043,11 @@ hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t stream, int* nsplit
     if (al16(a.colsum_out)) a.colsum = a.colsum_out;
     else cs_copy = true;
   }
-  if (a.rowdot_out && (a.a_col || a.b_kn || a.nseg != 1 || nsplit != 1 || !a.rowdot_w || a.c_scatter || a.accumulate || a.aux_mode ||
+  if (a.rowdot_out && (a.a_col || a.b_kn || a.nseg != 1 || nsplit != 1 || !a.rowdot_w || a.accumulate || a.aux_mode ||
                        (a.act != 2 && a.act != ACT_TANH_FAST)))
     return hipErrorInvalidValue;  // fused row dots: plain forward launches with a tanh epilogue only (the pooler's fc1)
+  // ... scattered in place only from a one-row-per-id list with a device count (the GATH + MDEV instantiation)
+  if (a.rowdot_out && a.c_scatter && !(a.gather_ids && a.gather_S == 1 && a.m_dev)) return hipErrorInvalidValue;
   hipError_t e;
   const int mode = gemm_mode();
   // the split kernel has one tile shape (128x128): below one full round of workgroups the fp32 kernel with its

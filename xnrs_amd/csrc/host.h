@@ -154,6 +154,7 @@ struct Plan {
   size_t off_planes;        // bf16-split GEMM modes: pre-split weight planes (wq, wk, wv, wo, w1)
   size_t off_nf, off_nfo;   // fused short-sequence encoder: fragment-ordered weight images, O-row scratch (fold)
   size_t off_lt_alive, off_lt_n, off_lt_tiles;  // live row tiles of the dense passes (launch_live_tiles)
+  size_t off_lr_loc, off_lr_src, off_lr_cnt;    // live rows of the dense passes (launch_dense_row_lists); 0 = not reserved (L > 64)
   FoldRegions fold;
   size_t total;
 };

@@ -44,6 +44,11 @@ struct Knobs {
   bool gemm_live_tiles = true;  // XNRS_GEMM_LIVE_TILES=0: the dense encoder passes project and score every row tile, also those that
                                 // hold only all-masked sequences (encoder_fwd.hip "live row tiles"; bitwise the same results)
   long long gemm_live_tiles_min_rows = 16384;  // XNRS_GEMM_LIVE_TILES_MIN_ROWS: token rows per encoder call from which the list is built
+  bool gemm_live_rows = true;   // XNRS_GEMM_LIVE_ROWS=0: the calls that walk the live row tiles project Q and take fc1 for every row of
+                                // those tiles, also the masked token rows of live sequences (encoder_fwd.hip "live rows"; bitwise the
+                                // same results)
+  long long gemm_live_rows_min_rows = 16384;  // XNRS_GEMM_LIVE_ROWS_MIN_ROWS: token rows per encoder call from which the row lists
+                                              // are built (on top of XNRS_GEMM_LIVE_TILES_MIN_ROWS)
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
   int gru_layout = 0;           // XNRS_GRU_LAYOUT=1: the GRU recurrence as ONE launch of workgroups that own 32 batch rows for all
@@ -106,6 +111,7 @@ struct GemmArgs {
   // activated row with rowdot_w over each block of 32 columns: rowdot_out[row * ldrd + col / 32] (the additive pooler's
   // fc2 score straight from the fc1 epilogue: tanh(fc1 x) never exists in memory).  The 32-column blocks and the
   // butterfly order inside them do not depend on the tile shape, so every launch shape gives the same bits.
+  // With c_scatter (gathered rows + m_dev only): the dots of logical row m go to the row c_scatter names, in place.
   const float* rowdot_w;
   float* rowdot_out;
   int64_t ldrd;
@@ -452,6 +458,8 @@ struct AdditivePoolArgs {
   const int32_t* row_ids;  // nullable, with row_off: value row of compact row j is x[row_ids[j]] (t stays compact)
   int32_t skip_dead;       // 1 (with mask): an all-masked sequence is left before any score is read -- zeros to y / a_out /
                            // asum_out / hm_out, what the kernel computes for it anyway (its scores may be unwritten)
+  int32_t skip_masked;     // 1 (with mask): the score of a token with mask == 0 is not read (it may be unwritten: the fc1 launch
+                           // over the live rows, encoder_fwd.hip); its weight is the exp(e) * 0 = 0 of every finite score
   const int64_t* poison;   // nullable device flag: non-zero -> every output of the launch is NaN (a precondition the host
                            // could not check without a sync was violated: launch_compact_rows saw a non-0/1 mask)
 };
@@ -563,6 +571,12 @@ constexpr int LIVE_TILE_BM = 128;  // the forward GEMM's main tile height (GemmA
 inline int64_t live_tiles_cap(int64_t chunk, int L, int BM) { return (chunk * L + BM - 1) / BM; }
 hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM, uint8_t* alive,
                              int64_t* n_tiles, int32_t* tiles, hipStream_t stream);
+// launch_live_tiles AND the live rows of every dense pass in ONE launch (L <= 64; batch.hip compact_rows64_kernel<true>): pass p
+// writes counts[3 * p] = its unmasked token rows (mask != 0) and their ascending list at [p * chunk * L ..] -- live_loc in the
+// pass's own row space (news j of the pass, token s: j * L + s), live_src (written only with ids) as rows of the gathered table
+hipError_t launch_dense_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM,
+                                  int32_t* live_loc, int32_t* live_src, int64_t* counts, uint8_t* alive, int64_t* n_tiles,
+                                  int32_t* tiles, hipStream_t stream);
 hipError_t launch_assemble_train(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_assemble_eval(const BatchArgs& a, hipStream_t stream);
 hipError_t launch_score_csr(const float* vecs, const int32_t* rows, const int32_t* sess, const float* u, float* r, int64_t n,

@@ -567,7 +567,9 @@ __global__ __launch_bounds__(256, (KTM * NFB <= 9 ? 8 : 5)) void mha_core_pair_k
 #pragma unroll
   for (int fb = 0; fb < NFB; ++fb) {
     const int f0 = fb * 16 + 4 * g;
-    qf[fb] = (qvalid && !tile_dead && f0 < dk) ? *reinterpret_cast<const f32x4*>(qrow + f0) : f32x4{0.f, 0.f, 0.f, 0.f};
+    // (a masked query's row is not read: its scores are REPLACED by -1e9 below whatever they are, and the dense passes over
+    // the live rows -- encoder_fwd.hip -- never wrote it)
+    qf[fb] = (qvalid && !tile_dead && mq != 0.f && f0 < dk) ? *reinterpret_cast<const f32x4*>(qrow + f0) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
   // ---- staging.  K: thread = (chunk ch of the row, key slot ks), keys ks, ks + KP, ...; one ds_write_b128 per chunk.

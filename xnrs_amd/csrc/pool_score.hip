@@ -57,6 +57,13 @@ __global__ __launch_bounds__(256) void additive_pool_kernel(AdditivePoolArgs a) 
   const float b2 = a.b2 ? a.b2[0] : 0.f;
   if (a.epart) {
     for (int i = tid; i < N; i += 256) {
+      if (a.skip_masked && mask) {  // a masked token's score may be unwritten: its weight without reading it (e * 0, sign kept)
+        const float mi = mask[src * N + i];
+        if (mi == 0.f) {
+          s_w[i] = mi;
+          continue;
+        }
+      }
       const float* ep = a.epart + (r0 + i) * (int64_t)a.n_epart;
       float acc = 0.f;
       for (int s = 0; s < a.n_epart; ++s) acc += ep[s];
