@@ -365,6 +365,24 @@ int32_t xnrs_dot_scoring_norm_bwd(const float *u, const float *c, const float *d
 int32_t xnrs_gather_rows(const float *table, const int32_t *ids, float *out, int64_t n, int64_t row_floats,
                          void *stream);
 
+/* ---- input dropout of the towers (news_encoding.py:51, user_encoding.py:69: nn.Dropout(p) on the token rows / the
+ * history vectors), optionally fused with the row gather above ----
+ * out[i, j] = keep(i, j) ? x[src(i), j] * (1/(1-p)) : 0      i < n, j < row_floats
+ * src(i) = ids ? ids[i] : i      (ids: the contract of xnrs_gather_rows; NULL = dense, and then out may alias x)
+ * The backward of a dense call is the same call on dy with the same (p, seed, seed_dev).
+ *
+ * The draw is the attention dropout's counter-based generator (xnrs_mha_params::seed) with one "head": the 64-bit state of
+ * row i is one splitmix64 of (seed + (seed_dev ? *seed_dev : 0), i) -- i is the row's position IN THIS CALL, never the
+ * table row, so two occurrences of one news get two masks as nn.Dropout gives them -- and element j's uniform u is the
+ * 32-bit finaliser of that state and j.  keep = u < 1.f - p in fp32; a kept element is ONE fp32 multiply by 1.f / (1.f - p);
+ * a dropped element is the literal 0.f, not x * 0: an inf or NaN in a dropped slot gives 0 where torch gives NaN.
+ * p <= 0: plain copy / gather, no draw.  p == 1: zeros.  p NaN or outside [0, 1], row_floats >= 2^32 (j is a
+ * 32-bit index), NULL x or out, n < 0, row_floats <= 0: XNRS_EINVAL.  n == 0: XNRS_OK.
+ * One launch, no allocation, no host sync, capturable.  16-byte streaming accesses when row_floats % 4 == 0 and both
+ * pointers are 16-byte aligned, scalar accesses otherwise. */
+int32_t xnrs_dropout_rows(const float *x, const int32_t *ids, float *out, int64_t n, int64_t row_floats, float p,
+                          uint64_t seed, const uint64_t *seed_dev, void *stream);
+
 /* ---- device-side batch assembly and evaluation -----------------------
  * Click histories / positives / negatives live on the device as CSR arrays of ROWS into the resident news
  * table ([n_rows,S,D] + mask; `pad_row` = the empty slot: all-zero tokens and mask, dataset.py:82-85).

@@ -631,6 +631,28 @@ def user_encoder(x, m, enc, return_weights, dropout_p, seed):
     return (y, a.unsqueeze(-1)) if return_weights else y
 
 
+class _InputDropout(torch.autograd.Function):
+    """nn.Dropout on a tower's input (ops.input_dropout): the mask is a pure function of (seed, row, column), so the backward
+    recomputes it on dy -- the same launch -- and nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, word):
+        from . import ops
+        ctx.p, ctx.seed, ctx.word = p, seed, word  # (the word as of the forward, like _Cfg.seed_word)
+        x = hip.dev_f32(x, "input_dropout input")
+        return ops.dropout_rows(x, None, torch.empty_like(x), p, seed, word)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import ops
+        dy = hip.dev_f32(dy, "grad output")
+        return ops.dropout_rows(dy, None, torch.empty_like(dy), ctx.p, ctx.seed, ctx.word), None, None, None
+
+
+def input_dropout(x, p, seed, word):
+    return _InputDropout.apply(x, p, seed, word)
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):

@@ -13,6 +13,8 @@
 //                    device copy: out[i] = table[ids[i]] for whole news blocks (S*D floats, 150 KB at the shipped
 //                    shape) -- the materialised batch for consumers that need dense token tensors (input gradients
 //                    of the explainer, explain.py:160-166); the encoders themselves gather inside their first load.
+//   dropout_rows   : the towers' input dropout (news_encoding.py:51, user_encoding.py:69) on dense rows, or fused with
+//                    gather_rows for the id path: the dropped batch is materialised in the launch that gathers it.
 #include <atomic>
 
 #include "host.h"
@@ -195,8 +197,11 @@ hipError_t launch_rank_metrics(const float* score, const float* target, const in
 }
 
 // ---------------------------------------------------------------- gather_rows (HBM-bound block copy)
-// one workgroup per (output row, 16-KB piece): 4 independent 16-byte loads per thread in flight, streaming
-// (nontemporal) on both sides -- every byte is touched once
+// one workgroup per (output row, 16-KB piece): 4 independent 16-byte loads per thread, streaming (nontemporal) on both
+// sides -- every byte is touched once.  Each load sits behind its own bounds branch, and the compiler waits for it inside
+// that branch, so a wave has ONE of the four in flight at a time and the other waves of the CU cover the latency: a
+// branch-free path for full pieces (all four in flight) was measured on dropout_rows_kernel below, which has this loop
+// shape, and moved nothing
 template <bool VEC>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ ids,
                                                            float* __restrict__ out, int64_t row_floats, int pieces) {
@@ -232,6 +237,63 @@ hipError_t launch_gather_rows(const float* table, const int32_t* ids, float* out
   const dim3 grid((unsigned)(n * pieces));
   if (vec) hipLaunchKernelGGL((gather_rows_kernel<true>), grid, dim3(256), 0, stream, table, ids, out, row_floats, (int)pieces);
   else hipLaunchKernelGGL((gather_rows_kernel<false>), grid, dim3(256), 0, stream, table, ids, out, row_floats, (int)pieces);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- dropout_rows (gather_rows + the towers' input dropout)
+// The shape of gather_rows_kernel: one workgroup per (output row, 16-KB piece), 16-byte streaming accesses.  Element j of
+// output row i draws drop_uniform(row i of the CALL, j): the 64-bit part of the draw depends on (seed, i) alone -- uniform
+// over the workgroup, computed once -- and each element pays the 32-bit finaliser.  x and out are not __restrict__: a dense
+// call may run in place (every thread loads its elements before it stores them, and no other thread touches them).
+__device__ __forceinline__ float drop_element(const DropRowsArgs& a, int64_t row, uint32_t j, float v, float keep, float scale) {
+  return drop_uniform(a, row, j) < keep ? v * scale : 0.f;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void dropout_rows_kernel(const float* x, const int32_t* __restrict__ ids, float* out,
+                                                            int64_t row_floats, int pieces, float p, DropRowsArgs a0) {
+  // the device word is read ONCE, before any store (out is not __restrict__: a later read would have to be repeated)
+  const DropRowsArgs a{drop_seed(a0), nullptr, 1};
+  const int64_t row = blockIdx.x / pieces;
+  const int piece = (int)(blockIdx.x - row * pieces);
+  const int64_t src = (ids ? (int64_t)ids[row] : row) * row_floats, dst = row * row_floats;
+  const float keep = 1.f - p, scale = 1.f / (1.f - p);
+  if (VEC) {
+    const int64_t n4 = row_floats >> 2;
+    const f32x4* s4 = reinterpret_cast<const f32x4*>(x + src);
+    f32x4* d4 = reinterpret_cast<f32x4*>(out + dst);
+    const int64_t base = (int64_t)piece * 1024 + threadIdx.x;
+    f32x4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (base + 256 * u < n4) v[u] = __builtin_nontemporal_load(s4 + base + 256 * u);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (base + 256 * u < n4) {
+        const uint32_t j = (uint32_t)(base + 256 * u) * 4u;  // < row_floats < 2^32
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[u][c] = drop_element(a, row, j + c, v[u][c], keep, scale);
+        __builtin_nontemporal_store(v[u], d4 + base + 256 * u);
+      }
+  } else {
+    const int64_t base = (int64_t)piece * 4096 + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (base + 256 * u < row_floats)
+        out[dst + base + 256 * u] = drop_element(a, row, (uint32_t)(base + 256 * u), x[src + base + 256 * u], keep, scale);
+  }
+}
+
+// 0 < p < 1
+hipError_t launch_dropout_rows(const float* x, const int32_t* ids, float* out, int64_t n, int64_t row_floats, float p,
+                               uint64_t seed, const uint64_t* seed_dev, hipStream_t stream) {
+  if (n <= 0 || row_floats <= 0) return hipSuccess;
+  const bool vec = row_floats % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const int64_t pieces = (row_floats + 4095) / 4096;  // 16 KB per workgroup
+  if (n * pieces > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(n * pieces));
+  const DropRowsArgs a{seed, seed_dev, 1};
+  if (vec) hipLaunchKernelGGL((dropout_rows_kernel<true>), grid, dim3(256), 0, stream, x, ids, out, row_floats, (int)pieces, p, a);
+  else hipLaunchKernelGGL((dropout_rows_kernel<false>), grid, dim3(256), 0, stream, x, ids, out, row_floats, (int)pieces, p, a);
   return hipGetLastError();
 }
 
@@ -796,6 +858,21 @@ int32_t xnrs_gather_rows(const float* table, const int32_t* ids, float* out, int
   if (n == 0) return XNRS_OK;
   if (!table || !ids || !out || n < 0 || row_floats <= 0) return XNRS_EINVAL;
   return hip_rc(launch_gather_rows(table, ids, out, n, row_floats, (hipStream_t)stream));
+}
+
+int32_t xnrs_dropout_rows(const float* x, const int32_t* ids, float* out, int64_t n, int64_t row_floats, float p, uint64_t seed,
+                          const uint64_t* seed_dev, void* stream) {
+  if (!(p >= 0.f && p <= 1.f)) return XNRS_EINVAL;  // (NaN fails both comparisons)
+  if (n == 0) return XNRS_OK;
+  if (!x || !out || n < 0 || row_floats <= 0 || row_floats >= (1LL << 32)) return XNRS_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = (size_t)n * (size_t)row_floats * F32;
+  if (p >= 1.f) return hip_rc(hipMemsetAsync(out, 0, bytes, st));
+  if (p <= 0.f) {  // no draw: the plain gather, or a copy (nothing at all in place)
+    if (ids) return hip_rc(launch_gather_rows(x, ids, out, n, row_floats, st));
+    return out == x ? XNRS_OK : hip_rc(hipMemcpyAsync(out, x, bytes, hipMemcpyDeviceToDevice, st));
+  }
+  return hip_rc(launch_dropout_rows(x, ids, out, n, row_floats, p, seed, seed_dev, st));
 }
 
 int32_t xnrs_score_csr(const float* vecs, const int32_t* cand_rows, const int32_t* cand_sess, const float* u, float* r,

@@ -374,6 +374,16 @@ __device__ __forceinline__ float drop_uniform(const Args& a, int64_t seq, int hd
   x ^= (uint32_t)(z >> 32);
   return (float)(x >> 8) * (1.0f / 16777216.0f);
 }
+// The input dropout of a tower (batch.hip: dropout_rows_kernel) draws from the same stream with ONE "head": the pair is
+// row i of the call, and element j < 2^32 of the row stands where the attention kernels pass query * S + key.
+struct DropRowsArgs {
+  uint64_t seed;
+  const uint64_t* seed_dev;
+  int n_heads;  // 1
+};
+__device__ __forceinline__ float drop_uniform(const DropRowsArgs& a, int64_t row, uint32_t j) {
+  return drop_uniform(a, row, 0, 0, 0, (int)j);
+}
 
 // ---------------------------------------------------------------- fused news encoder, S <= 32 tokens (news_fused.hip)
 // att -> additive pooler of TextEncoder.forward in ONE launch (news_encoding.py:48-54, layers.py:60-65,128-154)

@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import hip, ops
 from .blocks import AdditiveAttention, BilinScoring, DotScoring, FCScoring, MaskedMean, MultiHeadAttention, ParentRec, TextEncoder, UserEncoder
 
 CFG_BIAS = "cfg.bias"  # marker: the tower takes bias=cfg.bias (otherwise the constructor default True)
@@ -131,6 +131,9 @@ class NAML(nn.Module):
         b, n = ids.shape
         flat = ids.reshape(1, -1)
         inv = None
+        if dedup and any(e.training and e.dropout.p > 0 for e in (self.title_encoder, self.body_encoder)):
+            raise hip.XnrsHipError("NAML: dedup=True encodes each distinct row once, so every occurrence of a news would share "
+                                   "one input-dropout mask (p_dropout > 0, train mode); call it with dedup=False")
         if dedup:
             uniq, inv = torch.unique(flat.reshape(-1), return_inverse=True)  # index bookkeeping only
             flat = uniq.reshape(1, -1)

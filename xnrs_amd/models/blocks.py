@@ -73,13 +73,24 @@ class _Tower(nn.Module):
         dev = self.dummy_param.device
         return tuple(t.to(dev) for t in tensors)
 
+    # Opt-in: the input dropout of forward() as one HIP launch (ops.input_dropout: the counter-based draw of the attention
+    # dropout, seeded from torch's CPU generator, mask recomputed in the backward) instead of nn.Dropout.  Another random
+    # stream than torch's, the same distribution.  The id path (TextEncoder.forward_ids) always drops on the HIP path.
+    hip_dropout: bool = False
+
+    def _drop(self, x: torch.Tensor) -> torch.Tensor:
+        if self.hip_dropout:
+            return ops.input_dropout(x, self.dropout.p, self.training)
+        return self.dropout(x)
+
 
 class TextEncoder(_Tower):
     """Reference: xnrs/models/components/news_encoding.py:8-60.
     forward((x:(B,N,S,D), m:(B,N,S,1))) -> (y:(B,N,out_features), news mask:(B,N,1)).
 
     Extension: forward_ids(table_x, table_m, ids) encodes news gathered by row id from a device-resident
-    token table (the gather is fused into the first GEMM's load)."""
+    token table (the gather is fused into the first GEMM's load; in train mode with p_dropout > 0 the rows are gathered and
+    dropped out in one launch and the dense path runs on that copy)."""
 
     def __init__(self, pooler: nn.Module, p_dropout: float, out_features: int, in_features: Optional[int] = 768,
                  head: bool = True, activation: nn.Module = nn.ReLU(), att: Optional[nn.Module] = None, bias: bool = True):
@@ -116,7 +127,7 @@ class TextEncoder(_Tower):
     def forward(self, inpt: tuple):
         x, m = self._to_own_device(*inpt)
         b, n, s, d = x.shape
-        xf, mf = self.dropout(x.reshape(b * n, s, d)), m.reshape(b * n, s, 1)
+        xf, mf = self._drop(x.reshape(b * n, s, d)), m.reshape(b * n, s, 1)
         encode = self._encoder_fn()
         if encode is ops.text_encoder_unpadded and ops.COMPACT_ON_DEVICE and ops.compact_supported(s, d, self.att, self.pooler) \
                 and not (self.att is not None and self.att.training and self.att.dropout.p > 0):
@@ -142,13 +153,19 @@ class TextEncoder(_Tower):
     def forward_ids(self, table_x: torch.Tensor, table_m: torch.Tensor, ids: torch.Tensor, dedup: bool = False):
         """dedup=True encodes every distinct row once and scatters the vectors back (SURVEY.md section 8f rank 1:
         "unique-news dedup per step"); it changes the algorithmic work, so benchmarks report it separately."""
-        if self.training and self.dropout.p > 0:
-            # forward() applies the input dropout (news_encoding.py:51); a gathered table row cannot be dropped out
-            # in the GEMM load, so training through the id path with p_dropout > 0 would silently train another model
-            raise hip.XnrsHipError("TextEncoder.forward_ids: input dropout (p_dropout > 0) is not applied on the id-gather "
-                                   "path; train with p_dropout = 0 (every shipped config) or through forward() on "
-                                   "NewsStore.gather(ids)")
         b, n = ids.shape
+        if self.training and self.dropout.p > 0:
+            # forward() applies the input dropout (news_encoding.py:51) and a gathered table row cannot be dropped out in the
+            # GEMM load: the dropped rows are materialised by the launch that gathers them (xnrs_dropout_rows), and the dense
+            # training path runs on them -- what forward() runs behind self.dropout.  Every call gets its own copy, so nothing
+            # is shared between two encodes of the same ids (their masks differ).
+            if dedup:
+                raise hip.XnrsHipError("TextEncoder.forward_ids: dedup=True encodes each distinct row once, so every "
+                                       "occurrence of a news would share one input-dropout mask (p_dropout > 0, train mode); "
+                                       "call it with dedup=False")
+            xd, md = ops.id_path_dropout(table_x, table_m, ids, self.dropout.p)  # (its seed is drawn before the attention's)
+            y, hm = self._encoder_fn()(xd, md, self)
+            return y.reshape(b, n, self.out_dim), hm.reshape(b, n, 1)
         flat = ids.reshape(-1)
         encode = self._encoder_fn()
         if dedup:
@@ -175,7 +192,7 @@ class UserEncoder(_Tower):
 
     def forward(self, inpt: tuple, add_features: Optional[dict] = None, return_weights: bool = False):
         x, m = self._to_own_device(*inpt)
-        return ops.user_encoder(self.dropout(x), m, self, return_weights)
+        return ops.user_encoder(self._drop(x), m, self, return_weights)
 
 
 # Scorers.  Besides forward, each one answers the evaluation epoch's two questions (xnrs_amd.evaluation.evaluate): what to do

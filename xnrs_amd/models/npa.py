@@ -143,22 +143,25 @@ class NPA(nn.Module):
                              uid=batch['user_features']['other']['user_index'])
 
     # ---- device data path
-    def _id_path_tables(self, store):
-        """The token table and mask of the id path (refused with input dropout: a gathered row cannot be dropped out)."""
+    def _id_path_rows(self, store, ids):
+        """(x, m, ids) of an id-path encoder call: the token table, its mask and the rows -- or, with input dropout active
+        (train mode, p_dropout > 0), the dense dropped rows of `ids`, their mask rows and None: the personalized encoder
+        takes dense rows as it is, and a gathered row cannot be dropped out inside its load."""
+        tx, tm = store.text('title_emb')
         if self.training and self.dropout.p > 0:
-            raise hip.XnrsHipError("NPA.forward_store: input dropout (p_dropout > 0) cannot be applied on the id-gather path; "
-                                   "use forward() on the dense batch")
-        return store.text('title_emb')
+            xd, md = ops.id_path_dropout(tx, tm, ids, self.dropout.p)
+            return xd, md.reshape(ids.numel(), -1), None
+        return tx, tm, ids
 
     def forward_store(self, store, hist_ids: torch.Tensor, cand_ids: torch.Tensor, uid: torch.Tensor):
         """forward() with the news as rows of a NewsStore (hist_ids:(B,nh), cand_ids:(B,nc), uid:(B,) or (B,1)); history and
         candidates go through ONE encoder call."""
-        tx, tm = self._id_path_tables(store)
         Q = self.queries(uid)
         dev = self._device()
         (b, nh), nc = hist_ids.shape, cand_ids.shape[1]
         ids = torch.cat([hist_ids.reshape(-1), cand_ids.reshape(-1)]).to(torch.int32)
         q_idx = torch.cat([_index_rows(b, nh, dev), _index_rows(b, nc, dev)])
+        tx, tm, ids = self._id_path_rows(store, ids)
         y, hm = self.encode_news(tx, tm, ids, Q[:, :HIDDEN], q_idx)
         e = y.shape[1]
         u = self.encode_user(y[:b * nh].reshape(b, nh, e), hm[:b * nh].reshape(b, nh), Q[:, HIDDEN:])
@@ -169,13 +172,13 @@ class NPA(nn.Module):
         """Evaluation hook (xnrs_amd.evaluation.evaluate): a batch of impressions with CSR candidate lists.  The history is
         encoded with q_idx = s / l_hist, the candidates with q_idx = their impression; then the user tower and the model's
         scorer (prepare_csr on the batch's candidate vectors, score_csr).  -> r:(n_cand,)."""
-        tx, tm = self._id_path_tables(store)
         Q = self.queries(uid)
         dev = self._device()
         b, nh = hist_rows.shape
         n = cand_rows.numel()
         ids = torch.cat([hist_rows.reshape(-1), cand_rows.reshape(-1)]).to(torch.int32)
         q_idx = torch.cat([_index_rows(b, nh, dev), cand_sess.to(torch.int32)])
+        tx, tm, ids = self._id_path_rows(store, ids)
         y, hm = self.encode_news(tx, tm, ids, Q[:, :HIDDEN], q_idx)
         e = y.shape[1]
         u = self.encode_user(y[:b * nh].reshape(b, nh, e), hm[:b * nh].reshape(b, nh), Q[:, HIDDEN:])

@@ -491,8 +491,72 @@ def _att_dropout(att):
     The seed is drawn from torch's CPU generator so torch.manual_seed() controls it."""
     if att is None or not att.training or att.dropout.p <= 0.0:
         return 0.0, 0
-    seed = int(torch.empty((), dtype=torch.int64).random_().item())
-    return float(att.dropout.p), seed
+    return float(att.dropout.p), _draw_seed()
+
+
+def _draw_seed() -> int:
+    return int(torch.empty((), dtype=torch.int64).random_().item())
+
+
+def dropout_rows(x: torch.Tensor, ids: Optional[torch.Tensor], out: torch.Tensor, p: float, seed: int, word=None):
+    """ONE xnrs_dropout_rows launch (include/xnrs_hip.h): out[i] = dropped(x[ids[i]] or x[i]).  x, out: contiguous fp32 on the
+    device, rows = everything behind the first dim; word: the device seed word of the call (None: host seed alone)."""
+    if out.numel() == 0:  # (n, 0) as well as (0, ...): nothing to draw, as nn.Dropout returns an empty tensor
+        return out
+    n = out.shape[0] if out.dim() else 1
+    row_floats = out.numel() // n
+    hip.check(hip.lib().xnrs_dropout_rows(hip.ptr(x), hip.ptr(ids), hip.ptr(out), n, row_floats, float(p),
+                                          int(seed) % (1 << 64), hip.ptr(word), hip.stream_ptr(out.device)), "xnrs_dropout_rows")
+    return out
+
+
+def gather_dropout(table: torch.Tensor, ids: torch.Tensor, p: float, seed: int):
+    """nn.Dropout(p)(table[ids]) in one launch: table:(n_rows, ...), ids:(n,) -> dense dropped rows (n, ...).  Row i of the
+    result draws its mask from (seed, i) -- its position in the call, not its table row -- so two occurrences of one news
+    get two masks.  The device seed word (set_dropout_seed_word) is added to the seed."""
+    tab = hip.dev_f32(table, "gather_dropout table")
+    if not ids.is_cuda:
+        raise hip.XnrsHipError("ids must live on the HIP device")
+    ids = ids.reshape(-1).to(torch.int32).contiguous()
+    out = torch.empty((ids.numel(),) + tuple(tab.shape[1:]), dtype=torch.float32, device=tab.device)
+    return dropout_rows(tab, ids, out, p, seed, dropout_seed_word())
+
+
+def gather_rows(table: torch.Tensor, ids: torch.Tensor):
+    """table[ids] as one xnrs_gather_rows launch: table:(n_rows, ...), ids:(n,) -> (n, ...)."""
+    tab = hip.dev_f32(table, "gather_rows table")
+    if not ids.is_cuda:
+        raise hip.XnrsHipError("ids must live on the HIP device")
+    ids = ids.reshape(-1).to(torch.int32).contiguous()
+    out = torch.empty((ids.numel(),) + tuple(tab.shape[1:]), dtype=torch.float32, device=tab.device)
+    hip.check(hip.lib().xnrs_gather_rows(hip.ptr(tab), hip.ptr(ids), hip.ptr(out), ids.numel(), tab[0].numel(),
+                                         hip.stream_ptr(tab.device)), "xnrs_gather_rows")
+    return out
+
+
+def id_path_dropout(table_x: torch.Tensor, table_m: torch.Tensor, ids: torch.Tensor, p: float):
+    """The dense batch of an id-path training call with input dropout: (nn.Dropout(p)(table_x[ids]), table_m[ids]) in two
+    launches (the dropped rows are never materialised undropped).  Draws the input-dropout seed: call this BEFORE the
+    encoder draws its attention-dropout seed (the reference's order: news_encoding.py:51, then layers.py:148)."""
+    return gather_dropout(table_x, ids, p, _draw_seed()), gather_rows(table_m, ids)
+
+
+def input_dropout(x: torch.Tensor, p: float, training: bool, seed: Optional[int] = None):
+    """nn.Dropout(p) on a tower's input (news_encoding.py:51, user_encoding.py:69) as one HIP launch; rows = x's first
+    dim.  Differentiable: the backward is the same launch on dy, and nothing is saved but (p, seed).  training=False or
+    p == 0 returns x itself.  seed=None draws one int64 from torch's CPU generator (torch.manual_seed controls it), as the
+    attention dropout does; a caller that runs both draws this one FIRST (the reference's order: news_encoding.py:51, then
+    layers.py:148)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"input_dropout: expected a tensor, got {type(x)}")
+    if not training or p == 0:
+        return x
+    if not x.is_cuda:
+        raise hip.XnrsHipError(f"input_dropout: tensor is on {x.device}; xnrs_amd runs on a HIP device only")
+    if seed is None:
+        seed = _draw_seed()
+    from . import autograd
+    return autograd.input_dropout(x, float(p), int(seed), dropout_seed_word())
 
 
 def _check_att(att):
