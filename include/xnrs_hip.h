@@ -336,7 +336,9 @@ int32_t xnrs_seq_encoder_bwd_rows(const float *x, const float *m, const int32_t 
                                   void *stream);
 
 /* autograd of nn.Linear (xnrs_linear_fwd): dx = dy.W (nullable), dw = dy^T.x, db = colsum(dy) (nullable).
- * gather_ids as in the forward (then dx must be NULL). */
+ * gather_ids as in the forward (then dx must be NULL).
+ * M == 0, here and in the two xnrs_embedding_linear_bwd* below: every output that was asked for is written as zeros and
+ * nothing else is touched; x / ids / dy and the workspace may be NULL. */
 size_t xnrs_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K);
 int32_t xnrs_linear_bwd(const float *x, const int32_t *gather_ids, int32_t gather_S, const float *w, const float *dy,
                         float *dx, float *dw, float *db, int64_t M, int32_t N, int32_t K, void *ws, size_t ws_bytes,
@@ -344,7 +346,7 @@ int32_t xnrs_linear_bwd(const float *x, const int32_t *gather_ids, int32_t gathe
 
 /* autograd of fc(embedder(idx)) (naml.py:82-86; forward = xnrs_linear_fwd with gather_S = 1):
  * dw:(N,K) = dy^T . table[ids], db:(N) = colsum(dy), d_table:(n_rows,K) = scatter-add of dy.W by ids
- * (deterministic).  ws: xnrs_embedding_linear_bwd_workspace_bytes. */
+ * (deterministic).  Every output nullable.  ws: xnrs_embedding_linear_bwd_workspace_bytes. */
 size_t xnrs_embedding_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K);
 int32_t xnrs_embedding_linear_bwd(const float *table, const int32_t *ids, const float *w, const float *dy, float *d_table,
                                   float *dw, float *db, int64_t M, int32_t N, int32_t K, int32_t n_rows, void *ws,
@@ -582,7 +584,7 @@ int32_t xnrs_personalized_bwd(const float *x, const int32_t *ids, int64_t n_seq,
 int32_t xnrs_embedding_grad_sparse(const float *d_rows, const int32_t *ids, int64_t M, int32_t K, float *d_table,
                                    int32_t n_rows, void *stream);
 /* xnrs_embedding_linear_bwd with that table gradient (fc(embedder(ids)) with a large table: NPA's stacked q_fc
- * projections).  Every output nullable. */
+ * projections): the same arguments, workspace size and M == 0 rule; the two sum an id's occurrences in different orders. */
 size_t xnrs_embedding_linear_bwd_sparse_workspace_bytes(int64_t M, int32_t N, int32_t K);
 int32_t xnrs_embedding_linear_bwd_sparse(const float *table, const int32_t *ids, const float *w, const float *dy,
                                          float *d_table, float *dw, float *db, int64_t M, int32_t N, int32_t K, int32_t n_rows,

@@ -98,6 +98,10 @@ def _addr(t):
     return None if t is None else t.data_ptr()
 
 
+def _f32_out(shape, dev):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
 #: The reference's train step encodes the history twice (training.py:406 scores, :409 get_user_embeddings); with input
 #: dropout 0 (every shipped config) the two encodes differ only in their attention-dropout draws, so their Q|K|V images are
 #: the same numbers.  A training forward of an attention tower registers its saved blob and row lists here under the
@@ -654,74 +658,53 @@ def input_dropout(x, p, seed, word):
 
 
 class _Linear(torch.autograd.Function):
+    """y = act(rows . w^T + b) (ops.linear): the rows are x's, or -- with ids -- the rows ids gather from the table x.  Backward:
+    xnrs_act_bwd when there is an activation, then ONE of xnrs_linear_bwd / xnrs_embedding_linear_bwd (table_grad "dense") /
+    xnrs_embedding_linear_bwd_sparse ("sparse": a large table, the gradient costs what the ids cost)."""
+
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, ids, w, b, act, table_grad):
         from . import ops
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
+        x, w = hip.dev_f32(x, "linear input"), hip.dev_f32(w, "linear weight")
+        ids = None if ids is None else ids.to(torch.int32).contiguous()
         with torch.no_grad():
-            return ops.linear(x, w, b)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        x = hip.dev_f32(x, "x")
-        w = hip.dev_f32(w, "w")
-        dy = hip.dev_f32(dy, "dy")
-        K, N = w.shape[1], w.shape[0]
-        M = x.numel() // K
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
-        db = torch.empty(N, dtype=torch.float32, device=x.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        l = hip.lib()
-        nws = l.xnrs_linear_bwd_workspace_bytes(M, N, K)
-        ws = hip.workspace(x.device, nws)
-        hip.check(l.xnrs_linear_bwd(hip.ptr(x), None, 0, hip.ptr(w), hip.ptr(dy), hip.ptr(dx), hip.ptr(dw), hip.ptr(db), M, N,
-                                    K, hip.ptr(ws), nws, hip.stream_ptr(x.device)), "xnrs_linear_bwd")
-        return dx, dw, db
-
-
-def linear(x, w, b):
-    return _Linear.apply(x, w, b)
-
-
-class _EmbeddingLinear(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ids, table, w, b):
-        tab = hip.dev_f32(table, "embedding table")
-        wd = hip.dev_f32(w, "fc weight")
-        bd = None if b is None else hip.dev_f32(b, "fc bias")
-        idx = ids.to(torch.int32).contiguous()
-        M, K, N = idx.numel(), tab.shape[1], wd.shape[0]
-        y = torch.empty(tuple(ids.shape) + (N,), dtype=torch.float32, device=tab.device)
-        hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(idx), 1, hip.ptr(wd), hip.ptr(bd), hip.ptr(y), M, N, K,
-                                            hip.ACT_NONE, hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
-        ctx.save_for_backward(idx, tab, wd)
-        ctx.has_bias = b is not None
+            y = ops.linear(x, w, b, act, ids=ids)
+        ctx.save_for_backward(x, ids, w, y if act != hip.ACT_NONE else None)
+        ctx.has_bias, ctx.act, ctx.table_grad = b is not None, int(act), table_grad
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        idx, tab, w = ctx.saved_tensors
+        x, ids, w, y = ctx.saved_tensors
         dy = hip.dev_f32(dy, "dy")
-        M, K, N = idx.numel(), tab.shape[1], w.shape[0]
-        need = ctx.needs_input_grad
-        d_tab = torch.empty_like(tab) if need[1] else None
+        dev, l = x.device, hip.lib()
+        if y is not None:
+            dpre = torch.empty_like(dy)
+            hip.check(l.xnrs_act_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dpre), dy.numel(), ctx.act, hip.stream_ptr(dev)), "xnrs_act_bwd")
+            dy = dpre
+        K, N = w.shape[1], w.shape[0]
+        M = x.numel() // K if ids is None else ids.numel()
+        wanted = _wanted_inputs(ctx, [True, ids is not None, True, ctx.has_bias, False, False], 0)
+        need = [n and k for n, k in zip(ctx.needs_input_grad, wanted)]  # x ids w b act table_grad
+        dx = torch.empty_like(x) if need[0] else None
         dw = torch.empty_like(w) if need[2] else None
-        db = torch.empty(N, dtype=torch.float32, device=tab.device) if (ctx.has_bias and need[3]) else None
-        l = hip.lib()
-        nws = l.xnrs_embedding_linear_bwd_workspace_bytes(M, N, K)
-        ws = hip.workspace(tab.device, nws)
-        hip.check(l.xnrs_embedding_linear_bwd(hip.ptr(tab), hip.ptr(idx), hip.ptr(w), hip.ptr(dy), hip.ptr(d_tab), hip.ptr(dw),
-                                              hip.ptr(db), M, N, K, tab.shape[0], hip.ptr(ws), nws,
-                                              hip.stream_ptr(tab.device)), "xnrs_embedding_linear_bwd")
-        return None, d_tab, dw, db
+        db = _f32_out((N,), dev) if (ctx.has_bias and need[3]) else None
+        if ids is None:
+            nws = l.xnrs_linear_bwd_workspace_bytes(M, N, K)
+            ws = hip.workspace(dev, nws)
+            hip.check(l.xnrs_linear_bwd(hip.ptr(x), None, 0, hip.ptr(w), hip.ptr(dy), hip.ptr(dx), hip.ptr(dw), hip.ptr(db), M, N,
+                                        K, hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_linear_bwd")
+        else:
+            name = "xnrs_embedding_linear_bwd_sparse" if ctx.table_grad == "sparse" else "xnrs_embedding_linear_bwd"
+            nws = getattr(l, name + "_workspace_bytes")(M, N, K)
+            ws = hip.workspace(dev, nws)
+            hip.check(getattr(l, name)(hip.ptr(x), hip.ptr(ids), hip.ptr(w), hip.ptr(dy), hip.ptr(dx), hip.ptr(dw), hip.ptr(db), M, N,
+                                       K, x.shape[0], hip.ptr(ws), nws, hip.stream_ptr(dev)), name)
+        return dx, None, dw, db, None, None
 
 
-def embedding_linear(idx, embedder, fc):
-    if not idx.is_cuda:
-        raise hip.XnrsHipError("category indices must live on the HIP device")
-    return _EmbeddingLinear.apply(idx, embedder.weight, fc.weight, fc.bias)
+def linear(x, ids, w, b, act, table_grad):
+    return _Linear.apply(x, ids, w, b, act, table_grad)
 
 
 class _DotScoring(torch.autograd.Function):
@@ -913,41 +896,6 @@ def personalized(x, m, ids, q, q_idx, x_fc, head):
     return _Personalized.apply((x_fc, head), x, m, ids, q, q_idx, x_fc.weight, x_fc.bias, *hw)
 
 
-class _EmbeddingLinearTable(torch.autograd.Function):
-    """fc(embedder(ids)) over a LARGE table (NPA's user table): the forward is _EmbeddingLinear's; the table gradient costs
-    what the ids cost (xnrs_embedding_linear_bwd_sparse: one zero fill, then one workgroup per id)."""
-
-    @staticmethod
-    def forward(ctx, ids, table, w, b):
-        out = _EmbeddingLinear.forward(ctx, ids, table, w, b)
-        ctx.has = [True, True, True, b is not None]
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        idx, tab, w = ctx.saved_tensors
-        dy = hip.dev_f32(dy, "dy")
-        M, K, N = idx.numel(), tab.shape[1], w.shape[0]
-        wanted = _wanted_inputs(ctx, ctx.has, 0)
-        need = [n and k for n, k in zip(ctx.needs_input_grad, wanted)]
-        d_tab = torch.empty_like(tab) if need[1] else None
-        dw = torch.empty_like(w) if need[2] else None
-        db = torch.empty(N, dtype=torch.float32, device=tab.device) if (ctx.has_bias and need[3]) else None
-        l = hip.lib()
-        nws = l.xnrs_embedding_linear_bwd_sparse_workspace_bytes(M, N, K)
-        ws = hip.workspace(tab.device, nws)
-        hip.check(l.xnrs_embedding_linear_bwd_sparse(hip.ptr(tab), hip.ptr(idx), hip.ptr(w), hip.ptr(dy), hip.ptr(d_tab),
-                                                     hip.ptr(dw), hip.ptr(db), M, N, K, tab.shape[0], hip.ptr(ws), nws,
-                                                     hip.stream_ptr(tab.device)), "xnrs_embedding_linear_bwd_sparse")
-        return None, d_tab, dw, db
-
-
-def embedding_linear_table(idx, table, w, b):
-    if not idx.is_cuda:
-        raise hip.XnrsHipError("user indices must live on the HIP device")
-    return _EmbeddingLinearTable.apply(idx, table, w, b)
-
-
 # ---- nn.GRU, one layer (LSTUR's short-term tower, lstur.py:113-154): include/xnrs_hip.h xnrs_gru_*.  One node per call; the
 #      mask is not differentiable, the initial state is an input like any other (LSTUR 'ini': the long-term vector).
 class _Gru(torch.autograd.Function):
@@ -1020,83 +968,6 @@ def embedding_rows(idx, table, padding_idx):
 
 # ---- CAUM's candidate-aware user tower (caum.py:31-111): include/xnrs_hip.h xnrs_attn_long_* / xnrs_caum_* / xnrs_act_bwd.
 #      One node per stage; torch only routes gradients between them (weight slices and concatenations are data movement).
-def _f32_out(shape, dev):
-    return torch.empty(shape, dtype=torch.float32, device=dev)
-
-
-class _LinearAct(torch.autograd.Function):
-    """y = act(x w^T + b) with the activation in the GEMM epilogue; backward = xnrs_act_bwd, then xnrs_linear_bwd."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, act):
-        from . import ops
-        with torch.no_grad():
-            y = ops.linear(x, w, b, act)
-        ctx.save_for_backward(hip.dev_f32(x, "x"), hip.dev_f32(w, "w"), y)
-        ctx.has_bias, ctx.act = b is not None, int(act)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, y = ctx.saved_tensors
-        dy = hip.dev_f32(dy, "dy")
-        dev = x.device
-        l = hip.lib()
-        K, N = w.shape[1], w.shape[0]
-        M = x.numel() // K
-        dpre = torch.empty_like(dy)
-        hip.check(l.xnrs_act_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dpre), dy.numel(), ctx.act, hip.stream_ptr(dev)), "xnrs_act_bwd")
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
-        db = _f32_out((N,), dev) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        nws = l.xnrs_linear_bwd_workspace_bytes(M, N, K)
-        ws = hip.workspace(dev, nws)
-        hip.check(l.xnrs_linear_bwd(hip.ptr(x), None, 0, hip.ptr(w), hip.ptr(dpre), hip.ptr(dx), hip.ptr(dw), hip.ptr(db), M, N, K,
-                                    hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_linear_bwd")
-        return dx, dw, db, None
-
-
-def linear_act(x, w, b, act):
-    return _LinearAct.apply(x, w, b, act)
-
-
-class _EmbeddingLinearAct(torch.autograd.Function):
-    """act(fc(embedder(ids))) as one row-gathered GEMM (CategoryEncoder, news_encoding.py:63-91)."""
-
-    @staticmethod
-    def forward(ctx, ids, table, w, b, act):
-        from . import ops
-        with torch.no_grad():
-            y, idx, tab, wd = ops.embedding_linear_act_forward(ids, table, w, b, act)
-        ctx.save_for_backward(idx, tab, wd, y)
-        ctx.has_bias, ctx.act = b is not None, int(act)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        idx, tab, w, y = ctx.saved_tensors
-        dy = hip.dev_f32(dy, "dy")
-        dev = tab.device
-        M, K, N = idx.numel(), tab.shape[1], w.shape[0]
-        l = hip.lib()
-        dpre = torch.empty_like(dy)
-        hip.check(l.xnrs_act_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dpre), dy.numel(), ctx.act, hip.stream_ptr(dev)), "xnrs_act_bwd")
-        need = ctx.needs_input_grad
-        d_tab = torch.empty_like(tab) if need[1] else None
-        dw = torch.empty_like(w) if need[2] else None
-        db = _f32_out((N,), dev) if (ctx.has_bias and need[3]) else None
-        nws = l.xnrs_embedding_linear_bwd_workspace_bytes(M, N, K)
-        ws = hip.workspace(dev, nws)
-        hip.check(l.xnrs_embedding_linear_bwd(hip.ptr(tab), hip.ptr(idx), hip.ptr(w), hip.ptr(dpre), hip.ptr(d_tab), hip.ptr(dw),
-                                              hip.ptr(db), M, N, K, tab.shape[0], hip.ptr(ws), nws, hip.stream_ptr(dev)),
-                  "xnrs_embedding_linear_bwd")
-        return None, d_tab, dw, db, None
-
-
-def embedding_linear_act(idx, table, w, b, act):
-    return _EmbeddingLinearAct.apply(idx, table, w, b, act)
-
-
 class _AttnLong(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, n_heads):

@@ -579,6 +579,39 @@ int32_t xnrs_seq_encoder_bwd_rows(const float* x, const float* m, const int32_t*
   return XNRS_OK;
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- nn.Linear and fc(embedder(ids)) backward
+// The gradients of an empty batch (M == 0) are zeros: every output that was asked for is written, nothing else is touched.
+static int32_t zero_grads(float* dw, float* db, float* d_table, int N, int K, int n_rows, hipStream_t stream) {
+  if (dw) XNRS_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * F32, stream));
+  if (db) XNRS_TRY(hipMemsetAsync(db, 0, (size_t)N * F32, stream));
+  if (d_table) XNRS_TRY(hipMemsetAsync(d_table, 0, (size_t)n_rows * K * F32, stream));
+  return XNRS_OK;
+}
+
+// dw, db = xnrs_linear_bwd over the gathered rows; d_table = the rows dy . W scattered by ids, summed per table row by
+// launch_embedding_grad (one workgroup per TABLE row: small tables) or by xnrs_embedding_grad_sparse (one per ID: large ones)
+int32_t xnrs::embedding_linear_bwd(const float* table, const int32_t* ids, const float* w, const float* dy, float* d_table,
+                                   float* dw, float* db, int64_t M, int N, int K, int n_rows, void* ws, size_t ws_bytes,
+                                   hipStream_t stream, bool sparse_table) {
+  if (!table || !w || M < 0 || N <= 0 || K <= 0 || n_rows <= 0) return XNRS_EINVAL;
+  if (M == 0) return zero_grads(dw, db, d_table, N, K, n_rows, stream);
+  if (!ids || !dy) return XNRS_EINVAL;
+  const size_t s1 = xnrs_linear_bwd_workspace_bytes(M, N, K);
+  if (xnrs_embedding_linear_bwd_workspace_bytes(M, N, K) > ws_bytes || !ws) return XNRS_EWORKSPACE;
+  if (dw || db) XNRS_TRY_RC(xnrs_linear_bwd(table, ids, 1, w, dy, nullptr, dw, db, M, N, K, ws, s1, stream));
+  if (d_table) {
+    float* d_rows = at(ws, s1);
+    XNRS_TRY(gemm_dx(dy, N, w, d_rows, K, M, N, K, stream));
+    if (sparse_table) XNRS_TRY_RC(xnrs_embedding_grad_sparse(d_rows, ids, M, K, d_table, n_rows, stream));
+    else XNRS_TRY(launch_embedding_grad(d_rows, ids, M, K, d_table, n_rows, stream));
+  }
+  return XNRS_OK;
+}
+
+extern "C" {
+
 size_t xnrs_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K) {
   return carve_total({gemm_splitk_workspace_bytes(N, K, M), colsum_workspace_bytes(N)});  // split-K slabs | column-sum partials
 }
@@ -587,8 +620,9 @@ int32_t xnrs_linear_bwd(const float* x, const int32_t* gather_ids, int32_t gathe
                         float* dx, float* dw, float* db, int64_t M, int32_t N, int32_t K, void* ws, size_t ws_bytes,
                         void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (M == 0) return XNRS_OK;
-  if (!x || !w || !dy || M < 0 || N <= 0 || K <= 0) return XNRS_EINVAL;
+  if (M < 0 || N <= 0 || K <= 0) return XNRS_EINVAL;
+  if (M == 0) return zero_grads(dw, db, nullptr, N, K, 0, stream);  // (dx has no rows)
+  if (!x || !w || !dy) return XNRS_EINVAL;
   if (gather_ids && (dx || gather_S <= 0)) return XNRS_EINVAL;
   if (xnrs_linear_bwd_workspace_bytes(M, N, K) > ws_bytes || !ws) return XNRS_EWORKSPACE;
   Carver c;
@@ -605,19 +639,8 @@ size_t xnrs_embedding_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K
 
 int32_t xnrs_embedding_linear_bwd(const float* table, const int32_t* ids, const float* w, const float* dy, float* d_table,
                                   float* dw, float* db, int64_t M, int32_t N, int32_t K, int32_t n_rows, void* ws,
-                                  size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (M == 0) return XNRS_OK;
-  if (!table || !ids || !w || !dy || M < 0 || N <= 0 || K <= 0 || n_rows <= 0) return XNRS_EINVAL;
-  const size_t s1 = xnrs_linear_bwd_workspace_bytes(M, N, K);
-  if (xnrs_embedding_linear_bwd_workspace_bytes(M, N, K) > ws_bytes || !ws) return XNRS_EWORKSPACE;
-  XNRS_TRY_RC(xnrs_linear_bwd(table, ids, 1, w, dy, nullptr, dw, db, M, N, K, ws, s1, stream_));
-  if (d_table) {
-    float* d_rows = at(ws, s1);
-    XNRS_TRY(gemm_dx(dy, N, w, d_rows, K, M, N, K, stream));
-    XNRS_TRY(launch_embedding_grad(d_rows, ids, M, K, d_table, n_rows, stream));
-  }
-  return XNRS_OK;
+                                  size_t ws_bytes, void* stream) {
+  return embedding_linear_bwd(table, ids, w, dy, d_table, dw, db, M, N, K, n_rows, ws, ws_bytes, (hipStream_t)stream, false);
 }
 
 }  // extern "C"

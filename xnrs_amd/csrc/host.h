@@ -216,4 +216,11 @@ struct DxAct {
 hipError_t gemm_dx(const float* dY, int64_t lddy, const float* W, float* dX, int64_t lddx, int64_t M, int N, int K,
                    hipStream_t stream, float* wt_scratch = nullptr, int accumulate = 0, LiveRows live = {}, DxAct act = {});
 
+
+// autograd of fc(embedder(ids)): the one body of xnrs_embedding_linear_bwd (sparse_table == false) and
+// xnrs_embedding_linear_bwd_sparse (true), which differ in the kernel that scatters dy . W into the table gradient
+int32_t embedding_linear_bwd(const float* table, const int32_t* ids, const float* w, const float* dy, float* d_table, float* dw,
+                             float* db, int64_t M, int N, int K, int n_rows, void* ws, size_t ws_bytes, hipStream_t stream,
+                             bool sparse_table);
+
 }  // namespace xnrs

@@ -445,28 +445,13 @@ int32_t xnrs_embedding_grad_sparse(const float* d_rows, const int32_t* ids, int6
 }
 
 size_t xnrs_embedding_linear_bwd_sparse_workspace_bytes(int64_t M, int32_t N, int32_t K) {
-  return align_up(xnrs_linear_bwd_workspace_bytes(M, N, K)) + align_up((size_t)M * K * F32);  // linear backward | the dense rows dy . W
+  return xnrs_embedding_linear_bwd_workspace_bytes(M, N, K);
 }
 
 int32_t xnrs_embedding_linear_bwd_sparse(const float* table, const int32_t* ids, const float* w, const float* dy, float* d_table,
                                          float* dw, float* db, int64_t M, int32_t N, int32_t K, int32_t n_rows, void* ws,
-                                         size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!table || !ids || !w || !dy || M < 0 || N <= 0 || K <= 0 || n_rows <= 0) return XNRS_EINVAL;
-  const size_t s1 = align_up(xnrs_linear_bwd_workspace_bytes(M, N, K));
-  if (M == 0) {
-    if (dw) XNRS_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * sizeof(float), stream));
-    if (db) XNRS_TRY(hipMemsetAsync(db, 0, (size_t)N * sizeof(float), stream));
-    return d_table ? xnrs_embedding_grad_sparse(nullptr, nullptr, 0, K, d_table, n_rows, stream_) : XNRS_OK;
-  }
-  if (!ws || xnrs_embedding_linear_bwd_sparse_workspace_bytes(M, N, K) > ws_bytes) return XNRS_EWORKSPACE;
-  if (dw || db) XNRS_TRY_RC(xnrs_linear_bwd(table, ids, 1, w, dy, nullptr, dw, db, M, N, K, ws, s1, stream_));
-  if (d_table) {
-    float* d_rows = at(ws, s1);
-    XNRS_TRY_RC(xnrs_linear_bwd(table, nullptr, 0, w, dy, d_rows, nullptr, nullptr, M, N, K, ws, s1, stream_));  // d_rows = dy W
-    XNRS_TRY_RC(xnrs_embedding_grad_sparse(d_rows, ids, M, K, d_table, n_rows, stream_));
-  }
-  return XNRS_OK;
+                                         size_t ws_bytes, void* stream) {
+  return embedding_linear_bwd(table, ids, w, dy, d_table, dw, db, M, N, K, n_rows, ws, ws_bytes, (hipStream_t)stream, true);
 }
 
 }  // extern "C"

@@ -38,8 +38,8 @@ class DenseAttention(nn.Module):
         self.linear3 = nn.Linear(hidden_dim2, 1)
 
     def forward(self, x: torch.Tensor):
-        t = ops.linear_act(x, self.linear.weight, self.linear.bias, hip.ACT_TANH)
-        t = ops.linear_act(t, self.linear2.weight, self.linear2.bias, hip.ACT_TANH)
+        t = ops.linear(x, self.linear.weight, self.linear.bias, hip.ACT_TANH)
+        t = ops.linear(t, self.linear2.weight, self.linear2.bias, hip.ACT_TANH)
         return ops.linear(t, self.linear3.weight, self.linear3.bias)
 
 
@@ -64,7 +64,7 @@ class CategoryEncoder(nn.Module):
         if not hasattr(self, 'linear'):
             raise NotImplementedError("CategoryEncoder(head=False) has no HIP implementation (CAUM builds it with head=True)")
         act = hip.ACT_RELU if hasattr(self, 'activation') else hip.ACT_NONE
-        return ops.embedding_linear_act(x.to(dev), self.embedding, self.linear, act)
+        return ops.embedding_linear(x.to(dev), self.embedding, self.linear, act)
 
 
 class CAUMScoring(DotScoring):

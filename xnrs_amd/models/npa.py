@@ -33,16 +33,9 @@ class PersonalizedAttention(nn.Module):
 
     def forward(self, q: torch.Tensor, x: torch.Tensor, m: torch.Tensor = None):
         b, n, d = x.shape
-        qp = _linear(q.reshape(b, -1), self.q_fc)
+        qp = ops.linear(q.reshape(b, -1), self.q_fc.weight, self.q_fc.bias)
         y, _ = ops.personalized(x, None if m is None else m.reshape(b, n), None, qp, _index_rows(b, 1, x.device), self.x_fc)
         return y.reshape(b, 1, d)
-
-
-def _linear(x, fc):
-    if ops._needs_grad(x, fc):
-        from .. import autograd
-        return autograd.linear(x, fc.weight, fc.bias)
-    return ops.linear(x, fc.weight, fc.bias)
 
 
 _IDX: Dict[Tuple, torch.Tensor] = {}

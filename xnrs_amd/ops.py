@@ -24,23 +24,32 @@ def _mask2d(m: Optional[torch.Tensor], rows: int, cols: int, what: str) -> Optio
     return m.reshape(rows, cols)
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = hip.ACT_NONE):
-    """nn.Linear forward (+ fused activation) on the fp32 MFMA GEMM.  x:(..., K) -> (..., N)."""
-    if act == hip.ACT_NONE and torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (x, weight, bias)):
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = hip.ACT_NONE, *,
+           ids: Optional[torch.Tensor] = None, table_grad: str = "dense"):
+    """nn.Linear forward (+ activation fused into the epilogue) on the fp32 MFMA GEMM.  x:(..., K) -> (..., N); with `ids`, x is
+    a table (n_rows, K) whose rows the GEMM gathers by id: -> ids.shape + (N,).  Through autograd when anything needs a
+    gradient; table_grad picks the kernel that scatters the table's: "dense" (one workgroup per table row: category tables)
+    or "sparse" (one per id: tables far larger than the batch)."""
+    if table_grad not in ("dense", "sparse"):
+        raise ValueError(f"table_grad {table_grad!r}: 'dense' or 'sparse'")
+    if _needs_grad(x, weight, bias):
         from . import autograd
-        return autograd.linear(x, weight, bias)
+        return autograd.linear(x, ids, weight, bias, act, table_grad)
     x = hip.dev_f32(x, "linear input")
     w = hip.dev_f32(weight, "linear weight")
     b = None if bias is None else hip.dev_f32(bias, "linear bias")
     K = x.shape[-1]
     N = w.shape[0]
+    if ids is not None and not ids.is_cuda:
+        raise hip.XnrsHipError("row ids must live on the HIP device")
+    rows = None if ids is None else ids.to(torch.int32).contiguous()
+    M = x.numel() // K if ids is None else rows.numel()
     if w.shape[1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({x.numel() // K}x{K} and {w.shape[1]}x{N})")
-    M = x.numel() // K
-    y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(x), None, 0, hip.ptr(w), hip.ptr(b), hip.ptr(y), M, N, K, act,
-                                        hip.stream_ptr(x.device)), "xnrs_linear_fwd")
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {w.shape[1]}x{N})")
+    y = torch.empty(tuple(x.shape[:-1] if ids is None else ids.shape) + (N,), dtype=torch.float32, device=x.device)
+    if M:
+        hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(x), hip.ptr(rows), 0 if ids is None else 1, hip.ptr(w), hip.ptr(b), hip.ptr(y),
+                                            M, N, K, act, hip.stream_ptr(x.device)), "xnrs_linear_fwd")
     return y
 
 
@@ -681,45 +690,14 @@ def personalized(x, m, ids, q, q_idx, x_fc, head=None):
 
 
 def embedding_linear_table(idx: torch.Tensor, table: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]):
-    """table[idx] . w^T + b as ONE GEMM whose rows are gathered from a large embedding table; its gradient is the
-    table-scale one (xnrs_embedding_linear_bwd_sparse).  idx:(M,) -> (M, N)."""
-    if _needs_grad(table, w, b):
-        from . import autograd
-        return autograd.embedding_linear_table(idx, table, w, b)
-    if not idx.is_cuda:
-        raise hip.XnrsHipError("user indices must live on the HIP device")
-    return linear_gather_rows(table, idx, w, b)
+    """table[idx] . w^T + b over a LARGE table (NPA's user table): its gradient costs what the ids cost.  idx:(M,) -> (M, N)."""
+    return linear(table, w, b, ids=idx, table_grad="sparse")
 
 
-def linear_gather_rows(table, idx, w, b):
-    tab = hip.dev_f32(table, "embedding table")
-    wd = hip.dev_f32(w, "fc weight")
-    bd = None if b is None else hip.dev_f32(b, "fc bias")
-    ids = idx.to(torch.int32).contiguous()
-    M, K, N = ids.numel(), tab.shape[1], wd.shape[0]
-    y = torch.empty(tuple(idx.shape) + (N,), dtype=torch.float32, device=tab.device)
-    hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(ids), 1, hip.ptr(wd), hip.ptr(bd), hip.ptr(y), M, N, K,
-                                        hip.ACT_NONE, hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
-    return y
-
-
-def embedding_linear(idx: torch.Tensor, embedder, fc):
-    """fc(embedder(idx)) (naml.py:82-86) as ONE GEMM whose A rows are gathered from the embedding
-    table by index.  idx:(B,N) int -> (B,N,out_features)."""
-    if _needs_grad(embedder, fc):
-        from . import autograd
-        return autograd.embedding_linear(idx, embedder, fc)
-    tab = hip.dev_f32(embedder.weight, "embedding table")
-    w = hip.dev_f32(fc.weight, "fc weight")
-    b = None if fc.bias is None else hip.dev_f32(fc.bias, "fc bias")
-    if not idx.is_cuda:
-        raise hip.XnrsHipError("category indices must live on the HIP device")
-    ids = idx.to(torch.int32).contiguous()
-    M, K, N = ids.numel(), tab.shape[1], w.shape[0]
-    y = torch.empty(tuple(idx.shape) + (N,), dtype=torch.float32, device=tab.device)
-    hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(ids), 1, hip.ptr(w), hip.ptr(b), hip.ptr(y), M, N, K,
-                                        hip.ACT_NONE, hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
-    return y
+def embedding_linear(idx: torch.Tensor, embedder, fc, act: int = hip.ACT_NONE):
+    """act(fc(embedder(idx))) (naml.py:82-86; CategoryEncoder, news_encoding.py:63-91) as ONE GEMM whose A rows are gathered
+    from the embedding table by index.  idx:(B,N) int -> (B,N,out_features)."""
+    return linear(embedder.weight, fc.weight, fc.bias, act, ids=idx)
 
 
 # ---- nn.GRU, one layer (LSTUR's short-term user tower, lstur.py:113-154): include/xnrs_hip.h xnrs_gru_*
@@ -802,38 +780,6 @@ def embedding_rows_forward(idx, table):
 
 
 # ---- CAUM's candidate-aware user tower (caum.py:31-111): include/xnrs_hip.h xnrs_attn_long_* / xnrs_caum_* / xnrs_act_bwd
-def linear_act(x, weight, bias, act: int):
-    """act(x w^T + b) with the activation fused into the GEMM epilogue; through autograd when anything needs a gradient."""
-    if _needs_grad(x, weight, bias):
-        from . import autograd
-        return autograd.linear_act(x, weight, bias, act)
-    return linear(x, weight, bias, act)
-
-
-def embedding_linear_act_forward(idx, table, w, b, act: int):
-    tab = hip.dev_f32(table, "embedding table")
-    wd = hip.dev_f32(w, "fc weight")
-    bd = None if b is None else hip.dev_f32(b, "fc bias")
-    if not idx.is_cuda:
-        raise hip.XnrsHipError("category indices must live on the HIP device")
-    ids = idx.to(torch.int32).contiguous()
-    M, K, N = ids.numel(), tab.shape[1], wd.shape[0]
-    y = torch.empty(tuple(idx.shape) + (N,), dtype=torch.float32, device=tab.device)
-    hip.check(hip.lib().xnrs_linear_fwd(hip.ptr(tab), hip.ptr(ids), 1, hip.ptr(wd), hip.ptr(bd), hip.ptr(y), M, N, K, act,
-                                        hip.stream_ptr(tab.device)), "xnrs_linear_fwd(gather)")
-    return y, ids, tab, wd
-
-
-def embedding_linear_act(idx: torch.Tensor, embedder, fc, act: int):
-    """act(fc(embedder(idx))) (CategoryEncoder, news_encoding.py:63-91) as ONE GEMM whose rows are gathered from the table."""
-    if _needs_grad(embedder, fc):
-        from . import autograd
-        if not idx.is_cuda:
-            raise hip.XnrsHipError("category indices must live on the HIP device")
-        return autograd.embedding_linear_act(idx, embedder.weight, fc.weight, fc.bias, act)
-    return embedding_linear_act_forward(idx, embedder.weight, fc.weight, fc.bias, act)[0]
-
-
 def attn_long_forward(qkv: torch.Tensor, n_heads: int, keep: bool = False):
     """qkv:(L, Nb, 3E) seq-first packed q | k | v (nn.MultiheadAttention's in_proj layout) -> o:(L, Nb, E), the heads'
     softmax(q k^T / sqrt(d_k)) v concatenated; no mask, any L.  keep: -> (o, qkv, saved log-sum-exp blob)."""
@@ -954,7 +900,7 @@ def caum_user(h, c, enc):
     h_all = linear(enc.dropout3(torch.cat([h_cnn, h_att], dim=1)), enc.linear3.weight, enc.linear3.bias)
     pre = linear(h_all, da.linear.weight[:, :E], None)
     t1 = caum_bias_tanh(pre, cp[:, 2 * E:], H)
-    t2 = linear_act(t1, da.linear2.weight, da.linear2.bias, hip.ACT_TANH)
+    t2 = linear(t1, da.linear2.weight, da.linear2.bias, hip.ACT_TANH)
     u = caum_pool(t2, da.linear3.weight, da.linear3.bias, h_all, H)
     return u.reshape(B, C, E)
 
