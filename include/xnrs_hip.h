@@ -185,9 +185,9 @@ int32_t xnrs_text_encoder_fwd_unpadded(const float *x, const int32_t *ids, int64
  * and are not projected either); the GEMMs are launched over the worst-case row count and read the real one from
  * device memory (tiles past it return at once).  No host sync, no data-dependent launch: the whole call can be captured
  * in a hipGraph.  0/1 masks are a PRECONDITION here (not checked: that would be the host read this entry point exists to
- * avoid); inference, additive pooler, fp32 GEMM mode, S <= 64, head width <= 64 and a multiple of 4 with an attention
- * stage (XNRS_EUNSUPPORTED otherwise: use xnrs_text_encoder_fwd).  Results equal xnrs_text_encoder_fwd bit for bit for
- * prefix masks. */
+ * avoid); inference, additive pooler, fp32 GEMM mode, S <= 512 -- and with an attention stage S <= 64, head width <= 64 and
+ * a multiple of 4 (XNRS_EUNSUPPORTED otherwise: use xnrs_text_encoder_fwd).  Results equal xnrs_text_encoder_fwd bit for
+ * bit for prefix masks, at every S up to 512 (tests/test_hip_length_limits.py holds it beyond 64 tokens). */
 size_t xnrs_text_encoder_compact_workspace_bytes(int64_t n_news, int32_t S, int32_t D, int32_t A, int32_t E,
                                                  int32_t has_att, int32_t has_head, int64_t chunk);
 int32_t xnrs_text_encoder_fwd_compact(const float *x, const float *m, const int32_t *ids, int64_t n_news, int32_t S,
@@ -676,7 +676,8 @@ int32_t xnrs_act_bwd(const float *y, const float *dy, float *dpre, int64_t n, in
  * u[p] = sum_j a_j h_all[p, j].  t2:(P*H, A) the activated second layer of dense_att, w3:(A), b3:(1) nullable,
  * h_all:(P*H, E) -> u:(P, E), a_out:(P, H) nullable (the backward needs it).  H <= 8192.
  * bwd: du:(P, E) -> d_t2, d_w3:(A), d_b3:(1), d_hall, each nullable; d_b3 is the sum of the score gradients, which cancels
- * analytically (a bias in front of a softmax): what is written is its summation noise, as in the reference.
+ * analytically (a bias in front of a softmax): each pair's share is summed in double around the weighted mean of its
+ * score gradients, so what is written is the rounding of that mean, far below the reference's own summation noise.
  * ws: xnrs_caum_pool_bwd_workspace_bytes. */
 int32_t xnrs_caum_pool_fwd(const float *t2, const float *w3, const float *b3, const float *h_all, float *u, float *a_out,
                            int64_t P, int32_t H, int32_t A, int32_t E, void *stream);

@@ -182,3 +182,11 @@ def assert_sampled_grads_close(grads, g, tol, prefix="gs/dW/", maxprefix="gs/max
         assert e <= tol, f"{k}: {e:.3e} > {tol:.1e}"
         n += 1
     return n
+
+
+def fc2_bias_extra_bar(rows, gw, scale, gmax):
+    """What `pooler.fc2.bias` of an additive pooler is allowed on top of the usual 2e-4 of its scale, as derived in
+    test_random_bi_encoder_gradients_match_oracle (tests/test_hip_random_shapes.py): 4 sqrt(rows) 2^-23 max|d fc2.weight|
+    plus 1e-6 of the step's largest gradient, both relative to `scale`.  rows: token rows that went through the pooler;
+    gw: max|d fc2.weight| of the reference; gmax: the largest reference gradient of the step."""
+    return 4.0 * (rows ** 0.5) * 2.0 ** -23 * gw / scale + 1e-6 * gmax / scale

@@ -177,7 +177,7 @@ def test_random_bi_encoder_gradients_match_oracle(seed):
             if k.startswith("news_encoder."):
                 rows += c["B"] * c["C"] * S  # the candidates go through the same tower
             gw = osd[k[:-len("bias")] + "weight"].grad.abs().max().item()
-            bar += 4.0 * (rows ** 0.5) * 2.0 ** -23 * gw / scale + 1e-6 * gmax / scale
+            bar += H.fc2_bias_extra_bar(rows, gw, scale, gmax)
         assert e <= bar, f"{what}: {k}: {e:.3e} (bar {bar:.3e})"
         n += 1
     assert n >= 2

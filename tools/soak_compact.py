@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Soak: the device-compacted padding-free encoder (xnrs_text_encoder_fwd_compact) against the padded call over random
-shapes, news counts spanning several passes (small chunk), prefix masks (bitwise equal) and masks with holes (<= 2e-6:
-the pooling normaliser's summation order), +- attention tower, +- head, +- id table, the workspace and the allocator's free
-blocks NaN-filled first.   python tools/soak_compact.py [n] [seed0]"""
+shapes (titles of up to 64 tokens with an attention tower, up to 512 without), news counts spanning several passes (small
+chunk), prefix masks (bitwise equal) and masks with holes (<= 2e-6: the pooling normaliser's summation order), +- attention
+tower, +- head, +- id table, the workspace and the allocator's free blocks NaN-filled first.   python tools/soak_compact.py [n] [seed0]"""
 import os
 import sys
 
@@ -32,6 +32,12 @@ for it in range(n_cfg):
     with_ids = bool(rng.integers(0, 2))
     holes = bool(rng.integers(0, 2))
     chunk = int(rng.choice([0, 7, 64]))
+    if not with_att:
+        # additive-only towers go up to 512 tokens: beyond 64 launch_compact_rows takes compact_rows_kernel (a generator of
+        # its own: every other draw of the configuration stays what it was)
+        rng_s = np.random.default_rng(9000 + seed0 + it)
+        if rng_s.random() < 0.75:
+            S = int(rng_s.choice([65, 100, 129, 200, 512]))
     att = layers.MultiHeadAttention(h, D) if with_att else None
     enc = news_encoding.TextEncoder(pooler=layers.AdditiveAttention(D, A), p_dropout=0.0, out_features=E if with_head else D,
                                     in_features=D, head=with_head, att=att)

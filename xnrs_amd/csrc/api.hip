@@ -87,7 +87,9 @@ const char* xnrs_error_string(int32_t code) {
     case XNRS_EINVAL: return "invalid argument (shape or NULL pointer)";
     case XNRS_EHEADS: return "d_model is not divisible by n_heads";
     case XNRS_EWORKSPACE: return "workspace too small";
-    case XNRS_EUNSUPPORTED: return "shape outside the supported range (attention S <= 128, pooling N <= 512, long attention d_k <= 128)";
+    case XNRS_EUNSUPPORTED:
+      return "shape outside the supported range (attention S <= 128, pooling N <= 512, head width d_k <= 128, "
+             "personalized attention L <= 4096, CAUM pooling H <= 8192)";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
   }
 }

@@ -434,6 +434,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -482,11 +487,16 @@ __global__ __launch_bounds__(256) void caum_pool_fwd_kernel(const float* __restr
   }
 }
 
-// da_j = du . h_all[p, j]; ds_j = a_j (da_j - sum_j' a_j' da_j'); dh_all = a_j du; dt2 = ds_j w3; ds kept for dw3 / db3
+// da_j = du . h_all[p, j]; ds_j = a_j (da_j - c), c = sum_j a_j da_j / sum_j a_j; dh_all = a_j du; dt2 = ds_j w3; ds kept for dw3.
+// c is the a-weighted MEAN of da, taken in double: sum_j ds_j -- the pair's share of db3, a bias in front of a softmax, 0 in
+// exact arithmetic -- then cancels down to the rounding of c itself, although the fp32 weights do not sum to exactly 1.  That
+// share is evaluated here, in double over the unrounded terms (dbias_out[p]): summed from the rounded fp32 ds_j it carried
+// their rounding, ~2^-24 |ds|_2 per pair, several times what is left this way (tests/test_hip_length_limits.py).
 __global__ __launch_bounds__(256) void caum_pool_bwd_kernel(const float* __restrict__ t2, const float* __restrict__ w3,
                                                             const float* __restrict__ hall, const float* __restrict__ a,
                                                             const float* __restrict__ du, float* __restrict__ dt2,
-                                                            float* __restrict__ dhall, float* __restrict__ ds_out, int H, int A, int E) {
+                                                            float* __restrict__ dhall, float* __restrict__ ds_out,
+                                                            float* __restrict__ dbias_out, int H, int A, int E) {
   extern __shared__ float sc[];  // da / ds [H] | a [H]
   float* av = sc + H;
   const int64_t p = blockIdx.x;
@@ -504,14 +514,23 @@ __global__ __launch_bounds__(256) void caum_pool_bwd_kernel(const float* __restr
   }
   __syncthreads();
   if (wave == 0) {
-    float dot = 0.f;
-    for (int j = lane; j < H; j += 64) dot = fmaf(av[j], sc[j], dot);
-    dot = wave_sum(dot);
+    double dot = 0., suma = 0.;
     for (int j = lane; j < H; j += 64) {
-      const float ds = av[j] * (sc[j] - dot);
+      dot += (double)av[j] * (double)sc[j];
+      suma += (double)av[j];
+    }
+    dot = wave_sum(dot);
+    suma = wave_sum(suma);
+    const float c = (float)(dot / suma);  // (suma = 1 up to rounding: softmax weights)
+    double res = 0.;
+    for (int j = lane; j < H; j += 64) {
+      res += (double)av[j] * ((double)sc[j] - (double)c);
+      const float ds = av[j] * (sc[j] - c);
       sc[j] = ds;
       ds_out[p * H + j] = ds;
     }
+    res = wave_sum(res);
+    if (lane == 0) dbias_out[p] = (float)res;
   }
   __syncthreads();
   if (dhall)
@@ -520,16 +539,22 @@ __global__ __launch_bounds__(256) void caum_pool_bwd_kernel(const float* __restr
     for (int idx = threadIdx.x; idx < H * A; idx += blockDim.x) dt2[p * H * A + idx] = sc[idx / A] * w3[idx % A];
 }
 
-// partial[c][k] = sum over the rows of chunk c of ds[r] t2[r, k] (k < A), ds[r] (k == A), rows in order
+// partial[c][k] = sum over the rows of chunk c of ds[r] t2[r, k] (k < A), rows in order; k == A: the sum of the pairs' bias
+// shares dbias[p] over chunk c of the PAIRS (pairs_per each)
 __global__ __launch_bounds__(256) void caum_pool_dw_kernel(const float* __restrict__ ds, const float* __restrict__ t2,
-                                                           float* __restrict__ partial, int64_t R, int A, int64_t rows_per) {
+                                                           const float* __restrict__ dbias, float* __restrict__ partial, int64_t R,
+                                                           int A, int64_t rows_per, int64_t P, int64_t pairs_per) {
   const int64_t r0 = blockIdx.x * rows_per, r1 = r0 + rows_per < R ? r0 + rows_per : R;
+  const int64_t p0 = blockIdx.x * pairs_per, p1 = p0 + pairs_per < P ? p0 + pairs_per : P;
   for (int k = threadIdx.x; k <= A; k += blockDim.x) {
     float s = 0.f;
-    if (k < A)
+    if (k < A) {
       for (int64_t r = r0; r < r1; ++r) s = fmaf(ds[r], t2[r * A + k], s);
-    else
-      for (int64_t r = r0; r < r1; ++r) s += ds[r];
+    } else {
+      double sb = 0.;
+      for (int64_t p = p0; p < p1; ++p) sb += (double)dbias[p];
+      s = (float)sb;
+    }
     partial[(int64_t)blockIdx.x * (A + 1) + k] = s;
   }
 }
@@ -543,7 +568,7 @@ __global__ __launch_bounds__(256) void caum_pool_dw_final_kernel(const float* __
   if (k < A) {
     if (dw3) dw3[k] = s;
   } else if (db3) {
-    db3[0] = s;  // a bias in front of a softmax: sum_j ds_j cancels analytically, what is left is summation noise
+    db3[0] = s;  // a bias in front of a softmax: sum_j ds_j cancels analytically, what is left is the rounding of each pair's c
   }
 }
 
@@ -733,7 +758,7 @@ int32_t xnrs_caum_pool_fwd(const float* t2, const float* w3, const float* b3, co
 
 size_t xnrs_caum_pool_bwd_workspace_bytes(int64_t P, int32_t H, int32_t A) {
   if (P < 0 || H <= 0 || A <= 0) return 0;
-  return carve_total({(size_t)P * H * F32, (size_t)POOL_CHUNKS * (A + 1) * F32});
+  return carve_total({(size_t)P * H * F32, (size_t)POOL_CHUNKS * (A + 1) * F32, (size_t)P * F32});
 }
 
 int32_t xnrs_caum_pool_bwd(const float* t2, const float* w3, const float* h_all, const float* a, const float* du, float* d_t2,
@@ -751,14 +776,17 @@ int32_t xnrs_caum_pool_bwd(const float* t2, const float* w3, const float* h_all,
   Carver c;
   float* ds = at(ws, c.take((size_t)P * H * F32));
   float* partial = at(ws, c.take((size_t)POOL_CHUNKS * (A + 1) * F32));
+  float* dbias = at(ws, c.take((size_t)P * F32));
   hipLaunchKernelGGL(caum_pool_bwd_kernel, dim3((unsigned)P), dim3(256), (size_t)2 * H * F32, stream, t2, w3, h_all, a, du, d_t2,
-                     d_hall, ds, H, A, E);
+                     d_hall, ds, dbias, H, A, E);
   XNRS_TRY(hipGetLastError());
   if (d_w3 || d_b3) {
     const int64_t R = P * H;
     const int64_t rows_per = (R + POOL_CHUNKS - 1) / POOL_CHUNKS;
     const int nchunk = (int)((R + rows_per - 1) / rows_per);
-    hipLaunchKernelGGL(caum_pool_dw_kernel, dim3((unsigned)nchunk), dim3(256), 0, stream, ds, t2, partial, R, A, rows_per);
+    const int64_t pairs_per = (P + nchunk - 1) / nchunk;
+    hipLaunchKernelGGL(caum_pool_dw_kernel, dim3((unsigned)nchunk), dim3(256), 0, stream, ds, t2, dbias, partial, R, A, rows_per, P,
+                       pairs_per);
     XNRS_TRY(hipGetLastError());
     hipLaunchKernelGGL(caum_pool_dw_final_kernel, dim3((unsigned)((A + 256) / 256)), dim3(256), 0, stream, partial, nchunk, A, d_w3,
                        d_b3);

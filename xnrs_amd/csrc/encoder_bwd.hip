@@ -360,7 +360,12 @@ int32_t xnrs_seq_encoder_bwd_rows(const float* x, const float* m, const int32_t*
   const bool pooled = pool_kind != XNRS_POOL_NONE;
   const bool additive = pool_kind == XNRS_POOL_ADDITIVE;
   if (!pooled) head = nullptr;
+  if (att && att->n_heads <= 0) return XNRS_EINVAL;
   if (att && D % att->n_heads != 0) return XNRS_EHEADS;
+  // the forward's limits (seq_encode), checked here before the first launch: launch_mha_bwd and launch_additive_pool_bwd
+  // refuse the same shapes, but only after the head's products have been enqueued
+  if (att && (L > 128 || D / att->n_heads > 128)) return XNRS_EUNSUPPORTED;
+  if (pooled && L > 512) return XNRS_EUNSUPPORTED;
   if (additive && !pool) return XNRS_EINVAL;
   if (pool_kind == XNRS_POOL_MEAN && !m) return XNRS_EINVAL;
   const int A = additive ? pool->hidden : 0;

@@ -311,6 +311,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
     if (att->n_heads <= 0 || !att->wq || !att->wk || !att->wv || !att->wo) return XNRS_EINVAL;
     if (D % att->n_heads != 0) return XNRS_EHEADS;
     if (L > 128) return XNRS_EUNSUPPORTED;
+    if (train && D / att->n_heads > 128) return XNRS_EUNSUPPORTED;  // the backward kernels' limit (mha_bwd.hip MAX_FT)
   }
   const bool additive = pooled && pool_kind == XNRS_POOL_ADDITIVE;
   if (pooled) {
