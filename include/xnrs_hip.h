@@ -441,6 +441,23 @@ int32_t xnrs_infonce_bwd(const int64_t *labels, int64_t B, int32_t E, float temp
 int32_t xnrs_profile_enable(uint32_t stage_mask);
 int32_t xnrs_profile_read(double *ms, int64_t *launches, double *flops);
 
+/* ---- Q and K|V of a dense live-row pass in one launch (knob XNRS_GEMM_QKV_ONE_LAUNCH; no reference counterpart) ----
+ * Which route did a call take?  The launch timer cannot tell: stage 0 brackets the pass and reports the same executed
+ * FLOPs either way.  xnrs_qkv_launch_count returns the number of GEMM launches the live-row Q|K|V branch of the sequence
+ * encoder has issued since the last reset (process-global, relaxed atomic): one per pass on the one-launch route, two
+ * per pass otherwise (the knob at 0, and every call with ids: the one-launch entry serves dense rows only), none where the
+ * branch does not engage; reset != 0 clears it after reading.
+ * xnrs_qkv_one_launch_map is the kernel's block -> work rule, evaluated on the host (pure; tests enumerate it): for
+ * `block` of a grid sized for kv_row_tiles x kv_col_tiles K|V tiles and ceil(q_rows / q_tile_rows) x q_col_tiles Q tiles,
+ * given the device counts live_tiles and live_rows, it writes the section (0 K|V, 1 Q, -1 none) and the workgroup's
+ * index inside the section (both pointers nullable together) and returns the grid size (< 0: XNRS_EINVAL).  The K|V
+ * tiles come first and their section is rounded up to a multiple of 8 blocks, so both sections keep the XCD of the
+ * hardware's round-robin in the low three bits of their own index. */
+int32_t xnrs_qkv_launch_count(int32_t reset);
+int32_t xnrs_qkv_one_launch_map(int64_t block, int64_t live_tiles, int64_t live_rows, int32_t kv_row_tiles,
+                                int32_t kv_col_tiles, int64_t q_rows, int32_t q_tile_rows, int32_t q_col_tiles,
+                                int32_t *section, int32_t *index);
+
 /* Does the TRAINING forward fold the out-projection behind the pooling right now (knob XNRS_FOLD_TRAIN)?
  * The saved-activation blob of xnrs_seq_encoder_fwd_train* is laid out by that decision and xnrs_seq_encoder_bwd* reads it
  * under the decision of ITS call time: a caller that may reload the knobs between the two (tests, A/B tools) records this
@@ -488,7 +505,7 @@ int32_t xnrs_get_gemm_mode(void);
 /* ---- development knobs (no reference counterpart) ---------------------------------------------
  * Kernel-selection switches for A/B measurements and tests (XNRS_GEMM_PIPE, _BK, _BUF, _GROUP, _TILE,
  * XNRS_GEMM_SPLIT_MIN_TILES, XNRS_GEMM_DW, XNRS_MHA_LDS, XNRS_MHA_HEADWAVE, XNRS_MHA_PAIR, XNRS_MHA_BWD_FUSED,
- * XNRS_NEWS_FUSED, XNRS_NEWS_FUSED_NPW, XNRS_FOLD_OUT, XNRS_FOLD_TRAIN, XNRS_FC1_ROWDOT, XNRS_MHA_SKIP_MASKED, XNRS_BWD_SIDE_STREAM, XNRS_BWD_SIDE_MIN_ROWS; DESIGN.md section 6 -- and XNRS_GRU_LAYOUT).  The library reads
+ * XNRS_NEWS_FUSED, XNRS_NEWS_FUSED_NPW, XNRS_FOLD_OUT, XNRS_FOLD_TRAIN, XNRS_FC1_ROWDOT, XNRS_MHA_SKIP_MASKED, XNRS_GEMM_QKV_ONE_LAUNCH, XNRS_BWD_SIDE_STREAM, XNRS_BWD_SIDE_MIN_ROWS; DESIGN.md section 6 -- and XNRS_GRU_LAYOUT).  The library reads
  * them from the environment ONCE when it is loaded -- no launch calls getenv -- and again only when this function is
  * called.  None changes a result beyond summation / association order (XNRS_FOLD_*: whether the attention
  * out-projection is applied per token row, as the reference writes it, or once per sequence behind the additive

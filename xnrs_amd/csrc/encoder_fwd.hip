@@ -577,13 +577,22 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
         GemmArgs g = qkv_projection(cx, {cids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
         g.live_n = ltn;
         g.live_tiles = ltl;
-        XNRS_TRY(launch_gemm_f32(g, stream));
         GemmArgs q = gemm_linear(cx, {ids ? lrs : lrl, 1}, D, att->wq, att->bq, qkv, ld3, rows, D, D);
         q.c_scatter = 1;
         q.c_scatter_ids = lrl;
         q.m_dev = lrn;
         q.m_fill_hint = LR_FILL;
-        XNRS_TRY(launch_gemm_f32(q, stream));
+        // the two read the same x and write disjoint columns of the image: ONE grid, the Q tiles behind the K|V tiles, leaves
+        // one partly filled last round of workgroups instead of two and a launch boundary (XNRS_GEMM_QKV_ONE_LAUNCH=0: two
+        // launches; the same bits either way, and the same choice for every pass of the call whatever the data)
+        if (gemm_qkv_one_launch_ok(g, q)) {
+          XNRS_TRY(launch_gemm_qkv_one(g, q, stream));
+          qkv_launches_add(1);
+        } else {
+          XNRS_TRY(launch_gemm_f32(g, stream));
+          XNRS_TRY(launch_gemm_f32(q, stream));
+          qkv_launches_add(2);
+        }
       } else {
         GemmArgs g = qkv_projection(cx, {cids, L}, att, 0, qkv, ld3, rows, D, pqkv);
         if (lt_qkv) {  // the rows of the dead tiles stay unwritten: the attention kernel below never reads them

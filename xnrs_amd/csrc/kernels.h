@@ -49,6 +49,9 @@ struct Knobs {
                                 // same results)
   long long gemm_live_rows_min_rows = 16384;  // XNRS_GEMM_LIVE_ROWS_MIN_ROWS: token rows per encoder call from which the row lists
                                               // are built (on top of XNRS_GEMM_LIVE_TILES_MIN_ROWS)
+  bool gemm_qkv_one_launch = true;  // XNRS_GEMM_QKV_ONE_LAUNCH=0: a dense live-row pass over dense rows projects K|V and Q in two
+                                // launches instead of one grid (gemm_f32.hip: launch_gemm_qkv_one; bitwise the same results).  Calls
+                                // with ids take the two launches either way (DESIGN.md section 4.1 "One launch")
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
   int gru_layout = 0;           // XNRS_GRU_LAYOUT=1: the GRU recurrence as ONE launch of workgroups that own 32 batch rows for all
@@ -161,6 +164,42 @@ int gemm_pick_splits(int64_t M, int64_t N, int64_t K, bool dw_kernel = false);
 int gemm_group_tiles(int n_tiles, int bn, int64_t K, bool plain);
 size_t gemm_splitk_workspace_bytes(int64_t M, int64_t N, int64_t K);
 hipError_t launch_gemm_f32(const GemmArgs& a, hipStream_t stream, int* nsplit_used = nullptr);
+// ---- Q and K|V of a dense live-row pass in ONE grid (encoder_fwd.hip "lr_qkv").  `kv` is the K|V launch over the pass's live
+// row tiles (GemmArgs::live_tiles, main tile), `q` the Q launch over its live-row list (gathered rows, row-scattered C,
+// GemmArgs::m_dev), both exactly as they would go to launch_gemm_f32 one after the other.  The grid is the worst case of
+// both sections; the workgroups find their work from the two device counts:
+//   blocks [0, kv_wgs)             K|V tiles, kv_wgs = live tiles x column tiles -- the bigger tiles first
+//   blocks [kv_wgs, kv_pad)        nothing (kv_pad = kv_wgs rounded up to 8: both sections' XCD-aware walks take the XCD of a
+//                                  workgroup from the low 3 bits of ITS index, which must stay those of the hardware's)
+//   blocks [kv_pad, kv_pad+q_wgs)  Q tiles, q_wgs = ceil(live rows / q_bm) x column tiles -- they fill the K|V tail
+//   blocks past that               nothing
+// One rule for the kernel and the host (tests enumerate it without a GPU: xnrs_qkv_one_launch_map).
+struct QkvOneLaunchWork {
+  int section;  // 0: K|V, 1: Q, -1: no work
+  int index;    // the workgroup's index inside its section's tile sequence
+};
+__host__ __device__ inline QkvOneLaunchWork qkv_one_launch_map(int64_t block, int64_t live_n, int64_t m_dev, int kv_m_tiles,
+                                                               int kv_n_tiles, int64_t q_rows, int q_bm, int q_n_tiles) {
+  const int64_t lt = live_n < kv_m_tiles ? (live_n > 0 ? live_n : 0) : kv_m_tiles;
+  const int64_t kv_wgs = lt * kv_n_tiles, kv_pad = (kv_wgs + 7) & ~(int64_t)7;
+  if (block < kv_pad) return block >= 0 && block < kv_wgs ? QkvOneLaunchWork{0, (int)block} : QkvOneLaunchWork{-1, 0};
+  const int64_t rows = m_dev < q_rows ? (m_dev > 0 ? m_dev : 0) : q_rows;
+  const int64_t q_wgs = ((rows + q_bm - 1) / q_bm) * q_n_tiles;
+  return block - kv_pad < q_wgs ? QkvOneLaunchWork{1, (int)(block - kv_pad)} : QkvOneLaunchWork{-1, 0};
+}
+// the grid: every K|V tile (rounded up to 8) and every Q tile
+inline int64_t qkv_one_launch_grid(int kv_m_tiles, int kv_n_tiles, int64_t q_rows, int q_bm, int q_n_tiles) {
+  return (((int64_t)kv_m_tiles * kv_n_tiles + 7) & ~(int64_t)7) + ((q_rows + q_bm - 1) / q_bm) * q_n_tiles;
+}
+// can the pair go out as one grid (fp32 mode, the knob, dense K|V rows, the shapes and alignments of the two instantiations)?  If not, the
+// caller issues the two launches.
+bool gemm_qkv_one_launch_ok(const GemmArgs& kv, const GemmArgs& q);
+hipError_t launch_gemm_qkv_one(const GemmArgs& kv, const GemmArgs& q, hipStream_t stream);
+// the GEMM launches the "lr_qkv" branch has issued since the last reset: one per pass on the one-launch route, two otherwise
+// (calls with ids among them)
+// (xnrs_qkv_launch_count; the launch timer's FLOPs are the same on both routes and cannot tell)
+void qkv_launches_add(int n);
+int64_t qkv_launches_read(bool reset);
 // dW = dY^T . X with the transpose done in registers on the way to LDS (gemm_dw.hip); nsplit / k_per_split / slab_stride
 // as filled in by launch_gemm_f32
 bool gemm_dw_eligible(const GemmArgs& a);
