@@ -145,6 +145,38 @@ int32_t xnrs_text_encoder_fwd(const float *x, const float *m, const int32_t *ids
                               const xnrs_additive_params *pool, const xnrs_head_params *head, float *y,
                               float *hm, int64_t chunk, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- a news table STORED in bf16 (NewsStore.astype(torch.bfloat16)) -----------------------
+ * bf16 values are passed as const uint16_t * (the high half of the fp32 value; widening is bits << 16, exact).
+ *
+ * xnrs_linear_fwd_bf16: the twin of xnrs_linear_fwd over bf16 rows x (pitch K elements; gather_ids / gather_S as there),
+ * w, bias and y in fp32.  With K % 8 == 0, a 16-byte aligned x and a launch of at least XNRS_GEMM_SPLIT_MIN_TILES 128 x 128
+ * tiles (and XNRS_GEMM_A16 != 0) the product runs on the bf16 matrix cores against the exact three-way bf16 split of w --
+ * x.w = x.wh + x.wm + x.wl with fp32 accumulation: fp32-grade, whatever xnrs_set_gemm_mode says; one tile shape, so a row's
+ * bits do not depend on the batch.  Otherwise the rows are widened to fp32, 1024 at a time, and take xnrs_linear_fwd's route.
+ * ws: xnrs_linear_bf16_workspace_bytes(N, K) of scratch (the weight planes and the widening buffer). */
+size_t xnrs_linear_bf16_workspace_bytes(int32_t N, int32_t K);
+int32_t xnrs_linear_fwd_bf16(const uint16_t *x_bf16, const int32_t *gather_ids, int32_t gather_S, const float *w,
+                             const float *bias, float *y, int64_t M, int32_t N, int32_t K, int32_t act, void *ws,
+                             size_t ws_bytes, void *stream);
+
+/* xnrs_text_encoder_fwd over a bf16 TABLE: x is [n_table,S,D] bf16, m the table's fp32 mask, ids required (NULL ids:
+ * XNRS_EINVAL, nothing is written -- dense bf16 activations are not a feature).  Two routes:
+ *   direct    an attention tower with the additive pooler on the GEMM pipeline projects Q|K|V of every pass straight from the
+ *             bf16 rows (the product of xnrs_linear_fwd_bf16, over the live row tiles where the fp32 call would walk them);
+ *             everything behind the projection is the fp32 call's.  Results agree with the fp32 call on the widened table to
+ *             fp32 rounding (the bf16x3 bar).  XNRS_GEMM_A16=0, or a shape the kernel refuses: the widening route.
+ *   widening  everything else (attention-free towers, mean pooling, the fused short-title kernels): the rows of each pass are
+ *             widened into the workspace and the fp32 route runs on them -- bit for bit xnrs_text_encoder_fwd on the
+ *             widened table with the same ids.
+ * The whole table is never converted.  Workspace: xnrs_text_encoder_bf16_workspace_bytes (the fp32 call's plus one pass of
+ * fp32 rows and mask rows). */
+size_t xnrs_text_encoder_bf16_workspace_bytes(int64_t n_news, int32_t S, int32_t D, int32_t A, int32_t E,
+                                              int32_t has_att, int32_t pool_kind, int32_t has_head, int64_t chunk);
+int32_t xnrs_text_encoder_fwd_bf16(const uint16_t *x_bf16, const float *m, const int32_t *ids, int64_t n_news,
+                                   int32_t S, int32_t D, const xnrs_mha_params *att, int32_t pool_kind,
+                                   const xnrs_additive_params *pool, const xnrs_head_params *head, float *y,
+                                   float *hm, int64_t chunk, void *ws, size_t ws_bytes, void *stream);
+
 /* The folded fc1 of an (attention stage, additive pooler) pair, for xnrs_additive_params.w1_folded / b1_folded:
  *   w1f [A, D] = W1 . Wo      b1f [A] = W1 . bo + b1      (layers.py:154 behind layers.py:60, exact algebra)
  * ws: xnrs_fold_weights_workspace_bytes(D, A) of scratch. */
@@ -384,6 +416,16 @@ int32_t xnrs_gather_rows(const float *table, const int32_t *ids, float *out, int
  * pointers are 16-byte aligned, scalar accesses otherwise. */
 int32_t xnrs_dropout_rows(const float *x, const int32_t *ids, float *out, int64_t n, int64_t row_floats, float p,
                           uint64_t seed, const uint64_t *seed_dev, void *stream);
+
+/* The two calls above from a table stored in bf16 (row_elems bf16 values per row), widened on the way (bits << 16): out is fp32.
+ * xnrs_gather_rows_bf16 has the contract of xnrs_gather_rows; 16-byte loads of 8 elements and 16-byte stores when
+ * row_elems % 8 == 0 and both pointers are 16-byte aligned.  xnrs_dropout_rows_bf16 gathers, widens and drops in ONE launch:
+ * ids is required, and the keep mask is that of xnrs_dropout_rows for the same (seed, seed_dev, row i of the call, column j),
+ * so it equals xnrs_dropout_rows on the widened table bit for bit.  The other rules (p, n, row_elems) are the same. */
+int32_t xnrs_gather_rows_bf16(const uint16_t *table, const int32_t *ids, float *out, int64_t n, int64_t row_elems,
+                              void *stream);
+int32_t xnrs_dropout_rows_bf16(const uint16_t *table, const int32_t *ids, float *out, int64_t n, int64_t row_elems,
+                               float p, uint64_t seed, const uint64_t *seed_dev, void *stream);
 
 /* ---- device-side batch assembly and evaluation -----------------------
  * Click histories / positives / negatives live on the device as CSR arrays of ROWS into the resident news

@@ -26,7 +26,7 @@ namespace xnrs {
 
 // workspace carve for one chunk
 Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additive, bool head, bool pooled, int64_t chunk,
-               bool train, int n_heads) {
+               bool train, int n_heads, bool widen) {
   Plan p{};
   if (train) chunk = n_seq > 0 ? n_seq : 1;  // the saved activations of the whole batch live in one carve
   if (chunk <= 0) chunk = 65536 / L;  // <= 64k token rows per pass: 512 full 128-row GEMM tiles (whole rounds of workgroups)
@@ -76,6 +76,10 @@ Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additiv
   // folded out-projection ("fold" below): reserved whenever the shape is eligible, whatever the knob says
   // (training keeps W', b', the pooled O rows and the weight sums for the backward)
   p.fold = carve_fold(c, att && additive, n_seq, D, A);
+  // bf16 table: one pass of widened rows and mask rows, whatever route the call takes (behind every other region: the
+  // offsets of an fp32 call's carve are those of the plan without it)
+  p.off_x32 = c.take_if(widen, rows * (size_t)D * F32);
+  p.off_m32 = c.take_if(widen, rows * F32);
   p.total = c.total();
   return p;
 }
@@ -91,6 +95,8 @@ bool device_counts_ok(const float* x, int D, int A, const xnrs_mha_params* att, 
 }  // namespace xnrs
 
 namespace {
+
+constexpr int64_t LINEAR_BF16_WIDEN_ROWS = 1024;  // rows per pass of xnrs_linear_fwd_bf16's widening route
 
 // ---- "fold": the out-projection behind the pooling (inference).
 // The pooler never needs the attention OUTPUT rows Y_i = Wo O_i + bo one by one (layers.py:154 -> layers.py:60-65):
@@ -305,8 +311,10 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   // products over a list read their row count on the device (GemmArgs::m_dev)
   const int64_t* cnt = rl->counts_dev;
   const int64_t n_live = cnt ? n_seq * L : rl->n_live, n_kv = cnt ? n_seq * L : rl->n_kv;
+  const uint16_t* x16 = r.x16;
   if (n_seq == 0) return XNRS_OK;
-  if (n_seq < 0 || L <= 0 || D <= 0 || !x || !y) return XNRS_EINVAL;
+  if (n_seq < 0 || L <= 0 || D <= 0 || (!x && !x16) || !y) return XNRS_EINVAL;
+  if (x16 && (x || !ids || !m || !pooled || train || a_out)) return XNRS_EINVAL;  // a bf16 TABLE, inference: never dense rows
   if (att) {
     if (att->n_heads <= 0 || !att->wq || !att->wk || !att->wv || !att->wo) return XNRS_EINVAL;
     if (D % att->n_heads != 0) return XNRS_EHEADS;
@@ -326,7 +334,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   const int A = additive ? pool->hidden : 0;
   const int E = (pooled && head) ? head->out_features : D;
   const Plan p = make_plan(n_seq, L, D, A, E, att != nullptr, additive, pooled && head, pooled, r.chunk, train,
-                           att ? att->n_heads : 0);
+                           att ? att->n_heads : 0, x16 != nullptr);
   if (p.total > r.ws_bytes || (p.total > 0 && !r.ws)) return XNRS_EWORKSPACE;
   void* w = r.ws;
   float* stats = (train && att) ? at(w, p.off_stats) : nullptr;
@@ -380,14 +388,30 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       f.asum = at(w, p.fold.as);
       f.p = at(w, p.fold.po);
     }
+    if (x16) {  // bf16 table: the kernel runs pass by pass on the widened rows and the gathered mask rows (below)
+      f.x = at(w, p.off_x32);
+      f.ids = nullptr;
+      f.mask = at(w, p.off_m32);
+    }
     fused = p.off_nf != 0 && news_fused_ready(f);
   }
+  // bf16 table, widening route: pass [c0, c0 + nc) of the call's rows as fp32 in the workspace (mask_too: and its mask rows,
+  // for the one-launch kernels whose rows and mask share one id list)
+  auto widen_pass = [&](int64_t c0, int64_t nc, bool mask_too) -> hipError_t {
+    hipError_t e = launch_gather_rows_bf16(x16, ids + c0, 1, at(w, p.off_x32), nc, (int64_t)L * D, stream);
+    if (e == hipSuccess && mask_too) e = launch_gather_rows(m, ids + c0, at(w, p.off_m32), nc, L, stream);
+    return e;
+  };
   const bool fold = att && additive && fold_wanted(train ? knobs().fold_train : knobs().fold_out);
   float *pob = at(w, p.fold.po), *asum = at(w, p.fold.as);
   // inference, fp32 GEMM mode, 16-byte-aligned shapes the buffer-load kernel serves, no gathered rows: the pooler's fc2
   // dot is taken in the fc1 epilogue (fc1_product)
   // (every input path -- dense rows, id gather, padding-free -- takes it, so they stay bitwise equal)
-  const bool rowdot = additive && !train && !fused && fc1_rowdot_ok(x, att != nullptr, pool, D);
+  // (x16: the pooler of an attention-free tower reads the widened rows, 256-byte aligned in the workspace)
+  float* x32 = at(w, p.off_x32);
+  float* m32 = at(w, p.off_m32);
+  const float* xal = x16 ? x32 : x;  // the rows whose alignment the predicates below ask about
+  const bool rowdot = additive && !train && !fused && fc1_rowdot_ok(xal, att != nullptr, pool, D);
   Fc1 fc1{};
   XNRS_TRY_RC(fc1_pair(fold, att, additive ? pool : nullptr, D, w, p.fold, stream, &fc1));
   if (fold && fused) {  // the fused kernel's fc1 image is built from the folded pair
@@ -407,7 +431,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
                 (knobs().additive_fused == 2 || additive_fused_tiles(n_seq, L) >= 512);
   if (afused) {
     AdditiveFusedArgs af{};
-    af.x = x; af.ids = ids; af.mask = m;
+    af.x = x16 ? x32 : x; af.ids = x16 ? nullptr : ids; af.mask = x16 ? m32 : m;
     af.w1 = pool->w1; af.b1 = pool->b1; af.w2 = pool->w2; af.b2 = pool->b2;
     af.y = head ? pb : y;
     af.ldy = D;
@@ -418,14 +442,24 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
     if (afused) {
       const double fl = (double)n_seq * (2.0 * L * D * A + 2.0 * L * (A + D));
       ProfScope ps(3, fl, stream);
-      XNRS_TRY(launch_additive_fused(af, stream));
+      if (!x16) XNRS_TRY(launch_additive_fused(af, stream));
+      for (int64_t c0 = 0; x16 && c0 < n_seq; c0 += p.chunk) {  // bf16 table: pass by pass on the widened rows (the same bits)
+        AdditiveFusedArgs ac = af;
+        ac.n_seq = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
+        ac.y = af.y + c0 * (int64_t)D;
+        ac.hm = af.hm ? af.hm + c0 : nullptr;
+        XNRS_TRY(widen_pass(c0, ac.n_seq, true));
+        XNRS_TRY(launch_additive_fused(ac, stream));
+      }
     }
   }
 
   // bf16-split GEMM modes: split the weights ONCE per call (the chunk loop below reuses them ~20 times per step)
   const unsigned short* pqkv[3] = {nullptr, nullptr, nullptr};
   const unsigned short *po = nullptr, *p1 = nullptr;
-  if (gemm_mode() != 0) {
+  // (bf16 table: the direct route multiplies the bf16 rows with the planes of Wq | Wk | Wv in EVERY mode)
+  const bool want_a16 = x16 && att && additive && !fused && knobs().gemm_a16;
+  if (gemm_mode() != 0 || want_a16) {
     char* pw = at<char>(w, p.off_planes);
     auto prep = [&](const float* W, int N, int K) -> const unsigned short* {
       unsigned short* dst = reinterpret_cast<unsigned short*>(pw);
@@ -436,9 +470,16 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       pqkv[0] = prep(att->wq, D, D);
       pqkv[1] = prep(att->wk, D, D);
       pqkv[2] = prep(att->wv, D, D);
-      po = prep(att->wo, D, D);
+      if (gemm_mode() != 0) po = prep(att->wo, D, D);
     }
-    if (pooled && additive) p1 = prep(fc1.w, A, D);
+    if (pooled && additive && gemm_mode() != 0) p1 = prep(fc1.w, A, D);
+  }
+  // bf16 table, direct route: Q|K|V of every pass is ONE gemm_a16 product over the bf16 rows.  Decided once per call, from
+  // the shape of its first (largest) pass; a shape the kernel refuses takes the widening route.
+  bool direct = false;
+  if (want_a16 && pqkv[0] && pqkv[1] && pqkv[2]) {
+    const int64_t rows0 = (n_seq < p.chunk ? n_seq : p.chunk) * L;
+    direct = gemm_a16_ok(qkv_projection(nullptr, {ids, L}, att, 0, qkv, 3 * (int64_t)D, rows0, D, pqkv), x16);
   }
 
   // Short sequences: attention + additive pooling of ALL sequences in one launch (news_fused.hip); only the pooled
@@ -454,7 +495,16 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   if (fused) {
     const double fl = (double)n_seq * ((f.fold ? 6.0 : 8.0) * L * D * D + 4.0 * L * L * D + 2.0 * L * D * A + 2.0 * L * (A + D));
     ProfScope ps(6, fl, stream);
-    XNRS_TRY(launch_news_fused(f, stream));
+    if (!x16) XNRS_TRY(launch_news_fused(f, stream));
+    for (int64_t c0 = 0; x16 && c0 < n_seq; c0 += p.chunk) {  // bf16 table: pass by pass on the widened rows (the same bits)
+      NewsFusedArgs fc = f;
+      fc.n_seq = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
+      fc.p = f.p + c0 * f.ldp;
+      fc.hm = f.hm ? f.hm + c0 : nullptr;
+      fc.asum = f.asum ? f.asum + c0 : nullptr;
+      XNRS_TRY(widen_pass(c0, fc.n_seq, true));
+      XNRS_TRY(launch_news_fused(fc, stream));
+    }
   }
   // Live row tiles (inference, the news encoder's pooled calls with a mask; XNRS_GEMM_LIVE_TILES=0: off).  An all-masked
   // sequence -- an empty history slot, 49.5 % of the benchmark's -- has a result that needs none of its rows: every query
@@ -471,7 +521,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   // The choice never depends on the data (hipGraph) and changes no bit: a live sequence's rows are computed as before.
   const bool lt = r.live_tiles && knobs().gemm_live_tiles && !train && pooled && m && att && !fused && !afused &&
                   n_seq * (int64_t)L >= knobs().gemm_live_tiles_min_rows &&
-                  device_counts_ok(x, D, A, att, additive ? pool : nullptr);
+                  device_counts_ok(xal, D, A, att, additive ? pool : nullptr);
   bool lt_qkv = false;
   if (lt && knobs().mha_skip_masked) {
     MhaCoreArgs probe = mha_core_args(qkv + D, 3 * (int64_t)D, att, o, p.chunk, L, D);
@@ -497,7 +547,8 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   // the grids are sized for every row, the counts stay on the device (GemmArgs::m_dev): nothing depends on the data.
   const bool lr = lt && knobs().gemm_live_rows && p.off_lr_cnt != 0 && L <= 64 && n_seq * (int64_t)L <= 0x7fffffffLL &&
                   n_seq * (int64_t)L >= knobs().gemm_live_rows_min_rows;
-  const bool lr_qkv = lr && lt_qkv, lr_fc1 = lr && lt_fc1;
+  // (bf16 table, direct route: Q|K|V stays one product over the live row tiles -- no live-row Q list, no one-launch grid)
+  const bool lr_qkv = lr && lt_qkv && !direct, lr_fc1 = lr && lt_fc1;
   const int32_t *lr_loc = at<int32_t>(w, p.off_lr_loc), *lr_src = at<int32_t>(w, p.off_lr_src);
   const int64_t* lr_cnt = at<int64_t>(w, p.off_lr_cnt);
   constexpr float LR_FILL = 0.3f;  // tile choice only: the share of a pass's rows expected on the list (ragged titles x empty slots)
@@ -539,9 +590,15 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
     const int32_t* cids = ids ? ids + c0 : nullptr;
     const float* cx = ids ? x : x + c0 * (int64_t)L * D;      // table stays whole when gathering
     const float* cm = m ? (ids ? m : m + c0 * (int64_t)L) : nullptr;
+    const int32_t* xids = cids;       // gather for the token rows (the mask rows always follow cids)
+    if (x16) {  // bf16 table: the direct route reads it in the projection alone; every other call runs on this pass's widened rows
+      cx = direct ? nullptr : x32;
+      xids = direct ? cids : nullptr;
+      if (!direct) XNRS_TRY(widen_pass(c0, nc, false));
+    }
 
     const float* seq = cx;            // what the pooler sees
-    const int32_t* seq_ids = cids;    // gather for the pooler's value rows
+    const int32_t* seq_ids = xids;    // gather for the pooler's value rows
     if (att) {
       const int64_t ld3 = 3 * (int64_t)D;
       if (qkv_given) {
@@ -549,7 +606,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       } else if (live) {  // K|V of every row (kvl: of the rows of the non-empty news), Q of the live rows only (dead rows = 0)
         const double nl = (double)prof_count(0, cnt, 0, n_live, stream), nkv = (double)prof_count(0, cnt, 1, n_kv, stream);
         ProfScope ps(0, 2.0 * (kvl ? nkv : rows) * 2.0 * D * D + 2.0 * nl * (double)D * D, stream);
-        GemmArgs g = qkv_projection(cx, {cids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
+        GemmArgs g = qkv_projection(cx, {xids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
         if (kvl) {
           XNRS_TRY(launch_zero_dead_qkv(qkv, cm, cids, nc, L, D, stream));
           g.gather_ids = kvx;
@@ -574,10 +631,10 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
         }
       } else if (lr_qkv) {  // K|V of the live row tiles, Q of the live rows: a masked token's Q row stays unwritten, nobody reads it
         ProfScope ps(0, 2.0 * lt_rows * 2.0 * D * D + 2.0 * lr_rows * (double)D * D, stream);
-        GemmArgs g = qkv_projection(cx, {cids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
+        GemmArgs g = qkv_projection(cx, {xids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
         g.live_n = ltn;
         g.live_tiles = ltl;
-        GemmArgs q = gemm_linear(cx, {ids ? lrs : lrl, 1}, D, att->wq, att->bq, qkv, ld3, rows, D, D);
+        GemmArgs q = gemm_linear(cx, {xids ? lrs : lrl, 1}, D, att->wq, att->bq, qkv, ld3, rows, D, D);
         q.c_scatter = 1;
         q.c_scatter_ids = lrl;
         q.m_dev = lrn;
@@ -594,13 +651,14 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
           qkv_launches_add(2);
         }
       } else {
-        GemmArgs g = qkv_projection(cx, {cids, L}, att, 0, qkv, ld3, rows, D, pqkv);
+        GemmArgs g = qkv_projection(cx, {xids, L}, att, 0, qkv, ld3, rows, D, pqkv);
         if (lt_qkv) {  // the rows of the dead tiles stay unwritten: the attention kernel below never reads them
           g.live_n = ltn;
           g.live_tiles = ltl;
         }
         ProfScope ps(0, 2.0 * (lt_qkv ? lt_rows : (double)rows) * 3.0 * D * D, stream);
-        XNRS_TRY(launch_gemm_f32(g, stream));
+        if (direct) XNRS_TRY(launch_gemm_a16(g, x16, stream));
+        else XNRS_TRY(launch_gemm_f32(g, stream));
       }
 
       MhaCoreArgs ma = mha_core_args(qkv + D, ld3, att, o, nc, L, D);
@@ -838,6 +896,54 @@ int32_t xnrs_text_encoder_fwd(const float* x, const float* m, const int32_t* ids
   r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
   r.live_tiles = true;  // empty history slots are news: whole row tiles of a pass may hold nothing else
   return seq_encode(r, (hipStream_t)stream);
+}
+
+size_t xnrs_text_encoder_bf16_workspace_bytes(int64_t n_news, int32_t S, int32_t D, int32_t A, int32_t E, int32_t has_att,
+                                              int32_t pool_kind, int32_t has_head, int64_t chunk) {
+  return make_plan(n_news, S, D, A, E, has_att != 0, pool_kind == XNRS_POOL_ADDITIVE, has_head != 0, true, chunk, false, 0, true).total;
+}
+
+int32_t xnrs_text_encoder_fwd_bf16(const uint16_t* x_bf16, const float* m, const int32_t* ids, int64_t n_news, int32_t S, int32_t D,
+                                   const xnrs_mha_params* att, int32_t pool_kind, const xnrs_additive_params* pool,
+                                   const xnrs_head_params* head, float* y, float* hm, int64_t chunk, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  if (!ids || !x_bf16 || !m) return XNRS_EINVAL;  // a TABLE and its mask, gathered by id: dense bf16 activations are not a feature
+  if (n_news == 0) return XNRS_OK;
+  SeqEncode r = padded_call(nullptr, m, n_news, S, D, y, ws, ws_bytes);
+  r.x16 = x_bf16;
+  r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
+  r.live_tiles = true;
+  return seq_encode(r, (hipStream_t)stream);
+}
+
+size_t xnrs_linear_bf16_workspace_bytes(int32_t N, int32_t K) {
+  if (N <= 0 || K <= 0) return 0;
+  return carve_total({split_planes_bytes(N, K), (size_t)LINEAR_BF16_WIDEN_ROWS * (size_t)K * F32});
+}
+
+int32_t xnrs_linear_fwd_bf16(const uint16_t* x_bf16, const int32_t* gather_ids, int32_t gather_S, const float* w, const float* bias,
+                             float* y, int64_t M, int32_t N, int32_t K, int32_t act, void* ws, size_t ws_bytes, void* stream) {
+  if (!x_bf16 || !w || !y || M < 0 || N <= 0 || K <= 0 || act < 0 || act > 2) return XNRS_EINVAL;
+  if (gather_ids && gather_S <= 0) return XNRS_EINVAL;
+  if (M == 0) return XNRS_OK;
+  if (!ws || ws_bytes < xnrs_linear_bf16_workspace_bytes(N, K)) return XNRS_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  Carver c;
+  unsigned short* planes = at<unsigned short>(ws, c.take(split_planes_bytes(N, K)));
+  float* x32 = at(ws, c.take((size_t)LINEAR_BF16_WIDEN_ROWS * (size_t)K * F32));
+  GemmArgs g = gemm_linear(nullptr, {gather_ids, gather_S}, K, w, bias, y, N, M, N, K, act, planes);
+  if (gemm_a16_ok(g, x_bf16)) {
+    XNRS_TRY(launch_split_weights(w, N, K, planes, st));
+    return hip_rc(launch_gemm_a16(g, x_bf16, st));
+  }
+  // widening route: the rows as fp32, LINEAR_BF16_WIDEN_ROWS at a time, through the fp32 launcher (a row's bits do not
+  // depend on the rows beside it)
+  for (int64_t r0 = 0; r0 < M; r0 += LINEAR_BF16_WIDEN_ROWS) {
+    const int64_t nr = M - r0 < LINEAR_BF16_WIDEN_ROWS ? M - r0 : LINEAR_BF16_WIDEN_ROWS;
+    XNRS_TRY(launch_gather_rows_bf16(x_bf16, gather_ids, gather_ids ? gather_S : 1, x32, nr, K, st, r0));
+    XNRS_TRY(launch_gemm_f32(gemm_linear(x32, {}, K, w, bias, y + r0 * (int64_t)N, N, nr, N, K, act), st));
+  }
+  return XNRS_OK;
 }
 
 size_t xnrs_user_encoder_workspace_bytes(int64_t B, int32_t H, int32_t E, int32_t A, int32_t has_att, int32_t pool_kind,

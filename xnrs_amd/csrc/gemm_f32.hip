@@ -473,6 +473,7 @@ static Knobs read_knobs() {
   k.bwd_side_stream = num("XNRS_BWD_SIDE_STREAM", 1) != 0;
   k.bwd_side_min_rows = num("XNRS_BWD_SIDE_MIN_ROWS", 0);
   k.gru_layout = num("XNRS_GRU_LAYOUT", 0) == 1 ? 1 : 0;
+  k.gemm_a16 = num("XNRS_GEMM_A16", 1) != 0;
   const long long m = num("XNRS_GEMM_MODE", 0);
   k.gemm_mode_init = (m >= 0 && m <= 2) ? (int)m : 0;
   return k;

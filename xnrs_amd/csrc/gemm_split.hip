@@ -300,6 +300,188 @@ __global__ __launch_bounds__(256, MINW) void gemm_split_kernel(GemmArgs a, int m
   }
 }
 
+// ---- A stored in bf16 (a news table kept in bf16): C = act(A16 . W^T + bias), fp32-grade.
+// A bf16 value is ONE piece, so with W = Wh + Wm + Wl (exact, launch_split_weights)
+//   x . w = x.wh + x.wm + x.wl
+// is three v_mfma_f32_32x32x16_bf16 per tile and k step -- the product count of NPL = 2 with the accuracy of NPL = 3, and
+// nothing is narrowed: x is what the caller stored, W is represented exactly, the accumulation is fp32 in a fixed order.
+// The A side has no arithmetic at all: a thread's 8 consecutive k of a row are one 16-byte load and one ds_write_b128.
+// Same tile (128 x 128, 2 x 2 waves, BK = 16), LDS image and swizzle as gemm_split_kernel; one A plane + three B planes in
+// two stages are 32 KB.  Rows come through 64-bit row pointers (a table is larger than a buffer descriptor's window);
+// out-of-range rows and k select the address of the zero line.  The B planes are loaded as BPRE loads them.
+// LIVE: the row tiles of a device-built list only (GemmArgs::live_n / live_tiles, as in gemm_f32_body.h).
+// One tile shape: a row's bits do not depend on the batch it is in.  Needs K % 8 == 0 (a 16-byte chunk is wholly inside
+// or outside the contraction) and 16-byte aligned rows (gemm_a16_ok).
+// Compiler: 130 VGPRs, no scratch, 3 waves per SIMD; under __launch_bounds__(256, 4) it spills 2 VGPRs, so that variant
+// is not built (profiles/bf16_table_resource_usage.md).
+// Measured (MI355X, Q/K/V projection 65 500 x 2304 x 768 over gathered table rows, the weight-split launch included):
+// 290 TF algorithmic against 123 TF for the fp32 kernel on gathered fp32 rows, 176 / 232 TF for NPL = 3 / 2 through the
+// same entry; normwise error against fp64 1.1 - 2.3e-7 (fp32 kernel: 1.6 - 4.2e-7).  The benchmark's id-path step
+// 26.13 -> 14.87 ms (tools/bench_bf16_table.py, profiles/bf16_table_bench.json).
+template <bool LIVE, int MINW>
+__global__ __launch_bounds__(256, MINW) void gemm_a16_kernel(GemmArgs a, const unsigned short* __restrict__ A16, int m_tiles,
+                                                             int n_tiles_seg, int gn) {
+  constexpr int BM = 128, BN = 128, BK = 16;
+  __shared__ u32x4s As[2][BM * 2];     // [stage][row*2 + swizzled chunk], chunk = 8 bf16 of k
+  __shared__ u32x4s Bs[2][3][BN * 2];  // [stage][plane][...]
+  static_assert(sizeof(As) + sizeof(Bs) == 32768, "one A plane + three B planes, two stages");
+
+  int nwg = gridDim.x;
+  if constexpr (LIVE) {  // the listed row tiles (m_tiles was the grid's worst case); the workgroups past them leave at once
+    const int nl = __builtin_amdgcn_readfirstlane((int)load_dev_scalar(a.live_n));
+    m_tiles = nl < m_tiles ? (nl > 0 ? nl : 0) : m_tiles;
+    nwg = m_tiles * n_tiles_seg * a.nseg;
+    if ((int)blockIdx.x >= nwg) return;  // workgroup-uniform, before any barrier
+  }
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7;
+  const int q = nwg >> 3, r = nwg & 7;
+  const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int n_tiles = n_tiles_seg * a.nseg;  // grouped tile walk: see gemm_f32_kernel
+  const int grp = wgid / (gn * m_tiles);
+  const int rem = wgid - grp * gn * m_tiles;
+  const int gw = (n_tiles - grp * gn < gn) ? n_tiles - grp * gn : gn;
+  const int mt = rem / gw;
+  const int nt = grp * gn + (rem - mt * gw);
+  const int seg = nt / n_tiles_seg;
+  const int nts = nt - seg * n_tiles_seg;
+  int64_t m0 = (int64_t)mt * BM;
+  if constexpr (LIVE) m0 = (int64_t)__builtin_amdgcn_readfirstlane(a.live_tiles[mt]) * BM;
+  const int n0 = nts * BN;
+  const int kend = (int)a.K;
+
+  const float* __restrict__ bias = a.bias[seg];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // ---- staging map: thread -> row tid>>1, k half tid&1 (8 consecutive k = ONE 16-byte load of A, one per B plane)
+  const int srow = tid >> 1, shalf = tid & 1;
+  const int st_chunk = srow * 2 + (shalf ^ ((srow >> 3) & 1));
+  const unsigned short* pa;
+  bool a_ok = true;
+  {
+    int64_t gr = m0 + srow;
+    if (gr >= a.M) { a_ok = false; gr = a.M - 1; }
+    int64_t src = gr;
+    if (a.gather_ids) {
+      const int64_t n = gr / a.gather_S;
+      src = (int64_t)a.gather_ids[n] * a.gather_S + (gr - n * a.gather_S);
+    }
+    pa = A16 + src * a.lda + 8 * shalf;
+  }
+  // the pre-split weight planes of this thread's (column, k half): the loading of gemm_split_kernel<.., BPRE>
+  __amdgpu_buffer_rsrc_t rsP;
+  unsigned offP[3];
+  int kstepP;
+  {
+    int colc = n0 + srow;
+    if (colc >= a.Nseg) colc = a.Nseg - 1;  // clamped: the columns beyond Nseg are discarded by the epilogue
+    const int64_t kb = a.ldp / 16;
+    rsP = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.Wp[seg]), 0, (int)(3 * kb * a.Nseg * 32), 0x00020000);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) offP[p] = (unsigned)(((p * kb * a.Nseg + colc) * 16 + 8 * shalf) * 2);
+    kstepP = a.Nseg * 32;
+  }
+  u32x4s rap, rbp[3];  // the bf16 chunks of the NEXT stage as loaded
+  auto gloadA = [&](int k0) {
+    rap = *reinterpret_cast<const u32x4s*>((a_ok && k0 + 8 * shalf < kend) ? static_cast<const void*>(pa + k0)
+                                                                          : static_cast<const void*>(g_zero_line_split));
+  };
+  auto gloadB = [&](int k0) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+      rbp[p] = __builtin_bit_cast(u32x4s, __builtin_amdgcn_raw_buffer_load_b128(rsP, (int)offP[p], (k0 >> 4) * kstepP, 0));
+  };
+  auto storeA = [&](int buf) { As[buf][st_chunk] = rap; };
+  auto storeB = [&](int buf) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) Bs[buf][p][st_chunk] = rbp[p];
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+  const int frow = lane & 31, fh = lane >> 5;
+  int fchA[2], fchB[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int ar = wm * 64 + 32 * i + frow, br = wn * 64 + 32 * i + frow;
+    fchA[i] = ar * 2 + (fh ^ ((ar >> 3) & 1));
+    fchB[i] = br * 2 + (fh ^ ((br >> 3) & 1));
+  }
+
+  const int nk = (kend + BK - 1) / BK;
+  const int last = nk - 1;
+  auto ktile = [&](int t) { return (t < last ? t : last) * BK; };
+  if (nk > 0) {
+    gloadA(ktile(0));
+    gloadB(ktile(0));
+    storeA(0);
+    storeB(0);
+    gloadA(ktile(1));
+    gloadB(ktile(1));
+  }
+  __syncthreads();
+
+  // 12 MFMA slots per k step: (0,0) (0,1) (1,1) (1,0) x {Wh, Wm, Wl}; the next stage's LDS stores and the loads of the
+  // one after it ride behind slots 1..4
+  for (int t = 0; t < nk; ++t) {
+    const int buf = t & 1;
+    const int kn = ktile(t + 2);
+    bf16x8 fa[2], fb[2][3];
+    fa[0] = __builtin_bit_cast(bf16x8, As[buf][fchA[0]]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) fb[0][p] = __builtin_bit_cast(bf16x8, Bs[buf][p][fchB[0]]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) fb[1][p] = __builtin_bit_cast(bf16x8, Bs[buf][p][fchB[1]]);
+    fa[1] = __builtin_bit_cast(bf16x8, As[buf][fchA[1]]);
+#pragma unroll
+    for (int slot = 0; slot < 12; ++slot) {
+      const int tile = slot / 3, p = slot % 3;
+      const int ti = (tile == 0 || tile == 1) ? 0 : 1;
+      const int tj = (tile == 0 || tile == 3) ? 0 : 1;
+      acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ti], fb[tj][p], acc[ti][tj], 0, 0, 0);
+      if (slot == 1) storeA(buf ^ 1);
+      else if (slot == 2) gloadA(kn);
+      else if (slot == 3) storeB(buf ^ 1);
+      else if (slot == 4) gloadB(kn);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogue: C/D layout of the 32x32 tile: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
+  const int ccol = lane & 31;
+  const int crow = 4 * (lane >> 5);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int col = n0 + wn * 64 + 32 * j + ccol;
+    if (col >= a.Nseg) continue;
+    const float bv = bias ? bias[col] : 0.f;
+    const int64_t coff = (int64_t)seg * a.Nseg + col;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t row = m0 + wm * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + crow;
+        if (row < a.M) {
+          const float v = apply_act(acc[i][j][e] + bv, a.act);
+          if (a.nt_store) __builtin_nontemporal_store(v, &a.C[row * a.ldc + coff]);
+          else a.C[row * a.ldc + coff] = v;
+        }
+      }
+    }
+  }
+}
+
 // planes[p][k/16][n][16] of W[n][k]: the exact 3-way bf16 split (same arithmetic as split_phase), zero padded to ldp columns
 __global__ __launch_bounds__(256) void split_weights_kernel(const float* W, int64_t N, int64_t K, int64_t ldp, unsigned short* planes) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one thread per PAIR of k
@@ -356,6 +538,41 @@ hipError_t launch_gemm_split(const GemmArgs& a, int npl, hipStream_t stream) {
     else XNRS_LAUNCH_SPLIT(2, false, 3);
   }
 #undef XNRS_LAUNCH_SPLIT
+  return hipGetLastError();
+}
+
+// can gemm_a16_kernel take this launch?  Forward layout over bf16 rows A16 (pitch a.lda ELEMENTS; a.A is not read), every
+// segment's weights pre-split (GemmArgs::Wp), the plain epilogue.  Independent of xnrs_set_gemm_mode: the kernel is
+// fp32-grade in every mode.  false = the caller widens the rows and takes the fp32 route.
+bool gemm_a16_ok(const GemmArgs& a, const unsigned short* A16, bool check_size) {
+  if (!knobs().gemm_a16 || !A16 || a.a_col || a.b_kn || a.M <= 0 || a.Nseg <= 0 || a.nseg < 1 || a.nseg > 3) return false;
+  if (a.K < 8 || a.K % 8 != 0 || a.K >= (1ll << 31) || a.lda % 8 != 0 || a.lda < a.K) return false;
+  if ((reinterpret_cast<uintptr_t>(A16) & 15) != 0 || a.ldp != split_plane_ld(a.K)) return false;
+  if (a.gather_ids && a.gather_S <= 0) return false;
+  for (int s = 0; s < a.nseg; ++s)
+    if (!a.Wp[s] || (reinterpret_cast<uintptr_t>(a.Wp[s]) & 15) != 0) return false;
+  if ((int64_t)split_planes_bytes(a.Nseg, a.K) > (int64_t)SPLIT_OOB) return false;  // one buffer descriptor per segment
+  if (a.m_dev || a.c_scatter || a.rowdot_out || a.rowscale || a.aux_mode || a.accumulate || a.colsum || a.k_dev || a.C2 ||
+      (a.slabs && a.nsplit > 1))
+    return false;
+  if ((a.live_tiles != nullptr) != (a.live_n != nullptr)) return false;
+  const int64_t tiles = ((a.M + 127) / 128) * ((a.Nseg + 127) / 128) * a.nseg;
+  return (!check_size || tiles >= knobs().split_min_tiles) && tiles <= 0x7fffffffLL;
+}
+
+hipError_t launch_gemm_a16(const GemmArgs& a_in, const unsigned short* A16, hipStream_t stream) {
+  if (a_in.M <= 0 || a_in.Nseg <= 0) return hipSuccess;
+  if (!gemm_a16_ok(a_in, A16, false)) return hipErrorInvalidValue;  // (the size rule is the caller's: one choice per call)
+  GemmArgs a = a_in;
+  a.A = nullptr;
+  if (a.act == 2 && knobs().fast_tanh) a.act = ACT_TANH_FAST;
+  a.nt_store = a.M * a.ldc * 4 >= (64ll << 20) ? 1 : 0;
+  const int64_t m_tiles = (a.M + 127) / 128;
+  const int n_tiles_seg = (a.Nseg + 127) / 128;
+  const dim3 g((unsigned)(m_tiles * n_tiles_seg * a.nseg), 1);
+  const int gn = gemm_group_tiles(n_tiles_seg * a.nseg, 128, a.K, false);
+  if (a.live_tiles) hipLaunchKernelGGL((gemm_a16_kernel<true, 3>), g, dim3(256), 0, stream, a, A16, (int)m_tiles, n_tiles_seg, gn);
+  else hipLaunchKernelGGL((gemm_a16_kernel<false, 3>), g, dim3(256), 0, stream, a, A16, (int)m_tiles, n_tiles_seg, gn);
   return hipGetLastError();
 }
 

@@ -156,11 +156,12 @@ struct Plan {
   size_t off_lt_alive, off_lt_n, off_lt_tiles;  // live row tiles of the dense passes (launch_live_tiles)
   size_t off_lr_loc, off_lr_src, off_lr_cnt;    // live rows of the dense passes (launch_dense_row_lists); 0 = not reserved (L > 64)
   FoldRegions fold;
+  size_t off_x32, off_m32;  // bf16 table (SeqEncode::x16): one pass of widened fp32 token rows and of gathered mask rows
   size_t total;
 };
-// workspace (train: saved-activation) carve for one chunk
+// workspace (train: saved-activation) carve for one chunk; widen: the rows come from a bf16 table (SeqEncode::x16)
 Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additive, bool head, bool pooled, int64_t chunk,
-               bool train = false, int n_heads = 0);
+               bool train = false, int n_heads = 0, bool widen = false);
 
 // x:(n_seq,L,D) [or table + ids], m:(n_seq,L) [or table mask] -> y
 //   pooled == false: y:(n_seq,L,D) = att(x)            (MultiHeadAttention alone)
@@ -182,6 +183,10 @@ struct SeqEncode {
   bool train;                // keep the activations the backward reads (ws = the saved blob)
   const xnrs_row_lists* rl;  // nullable (training): live-row / K|V-row lists
   bool live_tiles;           // inference: the row-parallel products may skip row tiles that hold only all-masked sequences
+  // nullable, instead of x (inference, pooled, ids required): the table is STORED in bf16 [n_table, L, D].  An attention tower
+  // with the additive pooler on the GEMM pipeline projects Q|K|V straight from the bf16 rows (launch_gemm_a16); every other
+  // call widens the rows of each pass into the workspace and runs the fp32 route on them
+  const uint16_t* x16;
 };
 int32_t seq_encode(const SeqEncode& r, hipStream_t stream);
 

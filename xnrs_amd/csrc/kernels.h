@@ -54,6 +54,8 @@ struct Knobs {
                                 // with ids take the two launches either way (DESIGN.md section 4.1 "One launch")
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
+  bool gemm_a16 = true;         // XNRS_GEMM_A16=0: an encoder call on a bf16 news table widens the rows of every pass to fp32 and takes
+                                // the fp32 route instead of projecting Q|K|V straight from the bf16 rows (gemm_split.hip: gemm_a16_kernel)
   int gru_layout = 0;           // XNRS_GRU_LAYOUT=1: the GRU recurrence as ONE launch of workgroups that own 32 batch rows for all
                                 // steps (gru.hip) instead of one 2-D launch per step (0, default; the two are compared in DESIGN.md section 10b)
 };
@@ -212,6 +214,12 @@ hipError_t launch_gemm_split(const GemmArgs& a, int npl, hipStream_t stream);
 inline int64_t split_plane_ld(int64_t K) { return (K + 15) / 16 * 16; }
 inline size_t split_planes_bytes(int64_t N, int64_t K) { return (size_t)3 * (size_t)N * (size_t)split_plane_ld(K) * 2; }
 hipError_t launch_split_weights(const float* W, int64_t N, int64_t K, unsigned short* planes, hipStream_t stream);
+// forward-layout GEMM over rows STORED in bf16 (A16, pitch GemmArgs::lda elements; GemmArgs::A is not read) against the
+// pre-split weight planes GemmArgs::Wp: three bf16 MFMAs per tile and k step, fp32-grade whatever the GEMM mode
+// (gemm_split.hip: gemm_a16_kernel).  gemm_a16_ok: can the kernel take the launch (shape, alignment, plain epilogue, the
+// XNRS_GEMM_A16 and XNRS_GEMM_SPLIT_MIN_TILES knobs)?  If not the caller widens the rows and takes the fp32 route.
+bool gemm_a16_ok(const GemmArgs& a, const unsigned short* A16, bool check_size = true);
+hipError_t launch_gemm_a16(const GemmArgs& a, const unsigned short* A16, hipStream_t stream);
 // 0: exact fp32 MFMA (default); 1: bf16x3 split, six products; 2: bf16x2 split, three products.  Applies to the
 // forward (ROW x WT) layout only.  PROCESS-GLOBAL (one relaxed atomic int, initialised from XNRS_GEMM_MODE when the
 // library is loaded): every later launch from any thread uses the mode set last.
@@ -600,6 +608,13 @@ struct BatchArgs {
 // out[i, :] = table[ids[i], :] for rows of row_floats floats (whole news blocks)
 hipError_t launch_gather_rows(const float* table, const int32_t* ids, float* out, int64_t n, int64_t row_floats,
                               hipStream_t stream);
+// the same from a table stored in bf16, widened on the way (bits << 16): logical row i of row_elems elements is table row
+// ids[i / S] * S + i % S (ids nullable: row i; S >= 1).  row0: out rows 0 .. n are the logical rows row0 .. row0 + n
+hipError_t launch_gather_rows_bf16(const unsigned short* table, const int32_t* ids, int S, float* out, int64_t n, int64_t row_elems,
+                                   hipStream_t stream, int64_t row0 = 0);
+// ... and with the towers' input dropout in the same launch: the keep mask of launch_dropout_rows for the same (seed, row, column)
+hipError_t launch_dropout_rows_bf16(const unsigned short* table, const int32_t* ids, float* out, int64_t n, int64_t row_elems, float p,
+                                    uint64_t seed, const uint64_t* seed_dev, hipStream_t stream);
 hipError_t launch_poison(float* y, int64_t n, const int64_t* flags, int n_flags, int flag_stride, hipStream_t stream);
 // the caller's sticky device status word (xnrs_set_status_word; nullptr = none): kernels OR XNRS_STATUS_* bits into it when
 // they meet a violated precondition that no host code could check without a synchronisation

@@ -2,7 +2,7 @@
 custom_collate_fn + the `.to(device)` inside the encoders (xnrs/data/dataset.py:48-163, xnrs/utils.py:190-204)
 once the encoders are fast -- the host gather/pad/cat and the 4.6 MB/impression PCIe copy.
 
-* NewsStore      : flat [n_rows, S, D] fp32 token table + [n_rows, S] mask (+ optional category columns), row 0
+* NewsStore      : flat [n_rows, S, D] fp32 (or bf16: NewsStore.astype) token table + [n_rows, S] mask (+ optional category columns), row 0
                    is the EMPTY SLOT (all-zero tokens and mask: the zero padding of dataset.py:82-85); built from
                    the reference's in-memory format (mind.py:161-164: {news_id: {feat: (emb(1,S,D), mask(1,S))}}),
                    saved to / memory-mapped from a flat file (replaces the pandas pickle).
@@ -41,7 +41,35 @@ class NewsStore:
         self.texts = dict(texts or {})
         for k, (tx, tm) in self.texts.items():
             assert tx.dim() == 3 and tm.shape == tx.shape[:2] and tx.shape[0] == x.shape[0], k
+            assert tx.dtype == x.dtype, f"text feature {k!r} is {tx.dtype}, the primary feature {x.dtype}: one dtype per store"
         self.pad_row = 0
+
+    @property
+    def dtype(self) -> torch.dtype:
+        """Storage dtype of the token tables (torch.float32 or torch.bfloat16; every text feature shares it)."""
+        return self.x.dtype
+
+    def astype(self, dtype: torch.dtype, rows_per_chunk: int = 4096) -> "NewsStore":
+        """A store whose token tables (the primary feature and every entry of `texts`) are stored in `dtype`:
+        torch.bfloat16 halves the largest object on the device -- the encoders read bf16 rows directly or widen only the
+        rows of a pass (include/xnrs_hip.h: xnrs_text_encoder_fwd_bf16), never the table -- torch.float32 widens back
+        (exact).  Narrowing rounds to nearest even, as tensor.to(torch.bfloat16).  Masks, columns, ids and `feature` are
+        shared with this store, row 0 stays all zero.  Works on host and device, `rows_per_chunk` rows at a time: next to
+        the new table only one chunk of the conversion exists, never a second whole fp32 copy."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"NewsStore.astype: torch.float32 or torch.bfloat16, not {dtype}")
+        if dtype == self.x.dtype:
+            return self
+
+        def convert(t):
+            out = torch.empty(t.shape, dtype=dtype, device=t.device)
+            step = max(1, int(rows_per_chunk))
+            for lo in range(0, t.shape[0], step):
+                out[lo:lo + step].copy_(t[lo:lo + step])  # the copy converts (round to nearest even when narrowing)
+            return out
+
+        return NewsStore(convert(self.x), self.m, self.ids, self.columns,
+                         {k: (convert(tx), tm) for k, (tx, tm) in self.texts.items()}, self.feature)
 
     @property
     def n_rows(self) -> int:
@@ -125,7 +153,12 @@ class NewsStore:
         status word -- hip.check_status() raises at the caller's next sync point.  trusted=False: the old blocking check
         (two .item() reads, IndexError at once); trusted=True: no check at all."""
         tx, tm = self.text(feature or self.feature)
-        tx, tm = hip.dev_f32(tx, "news table"), hip.dev_f32(tm, "news table mask")
+        bf16 = tx.dtype == torch.bfloat16  # widened by the gather itself (ops.table_rows_f32): only the rows asked for
+        if not bf16:
+            tx = hip.dev_f32(tx, "news table")
+        elif not tx.is_cuda:
+            raise hip.XnrsHipError("NewsStore.gather: the table must live on the HIP device")
+        tm = hip.dev_f32(tm, "news table mask")
         if trusted is False:
             flat = self.check_rows(rows)
         else:
@@ -138,10 +171,14 @@ class NewsStore:
         if not flat.is_cuda:
             raise hip.XnrsHipError("NewsStore.gather: the rows must live on the HIP device")
         n, (S, D) = flat.numel(), tx.shape[1:]
-        x = torch.empty((n, S, D), dtype=torch.float32, device=tx.device)
         m = torch.empty((n, S), dtype=torch.float32, device=tx.device)
         st = hip.stream_ptr(tx.device)
-        hip.check(hip.lib().xnrs_gather_rows(hip.ptr(tx), hip.ptr(flat), hip.ptr(x), n, S * D, st), "xnrs_gather_rows(x)")
+        if bf16:
+            from . import ops
+            x = ops.table_rows_f32(tx, flat)
+        else:
+            x = torch.empty((n, S, D), dtype=torch.float32, device=tx.device)
+            hip.check(hip.lib().xnrs_gather_rows(hip.ptr(tx), hip.ptr(flat), hip.ptr(x), n, S * D, st), "xnrs_gather_rows(x)")
         hip.check(hip.lib().xnrs_gather_rows(hip.ptr(tm), hip.ptr(flat), hip.ptr(m), n, S, st), "xnrs_gather_rows(m)")
         return x.reshape(*rows.shape, S, D), m.reshape(*rows.shape, S, 1)
 
@@ -154,22 +191,33 @@ class NewsStore:
     #   <path>.x.f32  <path>.m.u8         primary text feature  [n_rows,S,D] fp32 / [n_rows,S] u8
     #   <path>.<feat>.x.f32 / .m.u8       further text features
     #   <path>.<col>.i32                  categorical columns
+    # a bf16 store (astype): header key "dtype": "bf16", tables as <path>.x.bf16 / <path>.<feat>.x.bf16 (2 bytes per
+    # element); an fp32 store is written as before, and a header without the key means fp32
     def _files(self, path: str):
-        yield self.feature, path + ".x.f32", path + ".m.u8"
+        ext = _X_EXT[self.x.dtype]
+        yield self.feature, f"{path}.x.{ext}", path + ".m.u8"
         for k in sorted(self.texts):
-            yield k, f"{path}.{k}.x.f32", f"{path}.{k}.m.u8"
+            yield k, f"{path}.{k}.x.{ext}", f"{path}.{k}.m.u8"
 
     def save(self, path: str, rows_per_chunk: int = 4096) -> None:
         header = {"magic": MAGIC, "n_rows": int(self.n_rows), "S": int(self.x.shape[1]), "D": int(self.x.shape[2]),
                   "ids": [str(i) for i in self.ids], "columns": sorted(self.columns), "feature": self.feature,
                   "texts": {k: {"S": int(tx.shape[1]), "D": int(tx.shape[2])} for k, (tx, tm) in sorted(self.texts.items())}}
+        if self.x.dtype == torch.bfloat16:
+            header["dtype"] = "bf16"
+        elif self.x.dtype != torch.float32:
+            raise ValueError(f"NewsStore.save: token tables of dtype {self.x.dtype} (torch.float32 or torch.bfloat16)")
         with open(path + ".json", "w") as f:
             json.dump(header, f)
         for feat, fx, fm in self._files(path):
             tx, tm = self.text(feat)
             with open(fx, "wb") as f:  # chunked: a 10-GB table never needs a second whole copy on the host
                 for lo in range(0, self.n_rows, rows_per_chunk):
-                    f.write(tx[lo:lo + rows_per_chunk].detach().cpu().numpy().astype(np.float32, copy=False).tobytes())
+                    chunk = tx[lo:lo + rows_per_chunk].detach().cpu().contiguous()
+                    if chunk.dtype == torch.bfloat16:  # the 16 stored bits as they are
+                        f.write(chunk.view(torch.int16).numpy().tobytes())
+                    else:
+                        f.write(chunk.numpy().astype(np.float32, copy=False).tobytes())
             tm.detach().cpu().numpy().astype(np.uint8).tofile(fm)
         for k, v in self.columns.items():
             v.detach().cpu().numpy().astype(np.int32).tofile(f"{path}.{k}.i32")
@@ -182,14 +230,18 @@ class NewsStore:
         if h.get("magic") not in (MAGIC, _MAGIC_V1):
             raise ValueError(f"{path}.json is not a {MAGIC} header")
         n = h["n_rows"]
-        feats = [(h.get("feature", "title_emb"), path + ".x.f32", path + ".m.u8", h["S"], h["D"])]
+        kind = h.get("dtype", "f32")  # (a header without the key: fp32)
+        if kind not in ("f32", "bf16"):
+            raise ValueError(f"{path}.json: unknown table dtype {kind!r}")
+        np_dtype = np.uint16 if kind == "bf16" else np.float32  # bf16 payloads are mapped as their 16 bits
+        feats = [(h.get("feature", "title_emb"), f"{path}.x.{kind}", path + ".m.u8", h["S"], h["D"])]
         for k, sd in sorted(h.get("texts", {}).items()):
-            feats.append((k, f"{path}.{k}.x.f32", f"{path}.{k}.m.u8", sd["S"], sd["D"]))
+            feats.append((k, f"{path}.{k}.x.{kind}", f"{path}.{k}.m.u8", sd["S"], sd["D"]))
         maps = {}
         for feat, fx, fm, S, D in feats:
-            if os.path.getsize(fx) != n * S * D * 4 or os.path.getsize(fm) != n * S:
+            if os.path.getsize(fx) != n * S * D * np.dtype(np_dtype).itemsize or os.path.getsize(fm) != n * S:
                 raise ValueError(f"news store payload size does not match its header ({feat})")
-            maps[feat] = (np.memmap(fx, dtype=np.float32, mode="r", shape=(n, S, D)),
+            maps[feat] = (np.memmap(fx, dtype=np_dtype, mode="r", shape=(n, S, D)),
                           np.memmap(fm, dtype=np.uint8, mode="r", shape=(n, S)))
         cols = {}
         for k in h["columns"]:
@@ -211,8 +263,8 @@ class NewsStore:
                 import warnings
                 with warnings.catch_warnings():
                     warnings.simplefilter("ignore")  # "non-writable array": the store is read-only by contract
-                    return torch.from_numpy(mx), torch.from_numpy(np.asarray(mm)).float()
-            return torch.from_numpy(np.array(mx)), torch.from_numpy(np.array(mm)).float()
+                    return _table_tensor(mx), torch.from_numpy(np.asarray(mm)).float()
+            return _table_tensor(np.array(mx)), torch.from_numpy(np.array(mm)).float()
 
         primary = feats[0][0]
         x, m = host(primary)
@@ -220,28 +272,39 @@ class NewsStore:
         return cls(x, m, h["ids"], cols, texts, primary)
 
     @classmethod
-    def load_to_device(cls, path: str, device, rows_per_chunk: int = 2048, stats: Optional[dict] = None):
+    def load_to_device(cls, path: str, device, rows_per_chunk: int = 2048, stats: Optional[dict] = None,
+                       dtype: Optional[torch.dtype] = None):
         """File -> HBM without a whole-table host copy (replaces the pandas pickle load of
         xnrs/data/mind.py:161-164): the device table is allocated once, the file is memory-mapped, and chunks of
         `rows_per_chunk` rows travel through TWO reused pinned staging buffers (the copy of chunk i overlaps the page-in
         of chunk i+1) straight into their rows of the table.  The u8 mask is widened to the fp32 0/1 mask the kernels
         read after it has landed (one elementwise cast of S bytes per row: data movement, not hot-path arithmetic).
-        `stats` (optional dict) receives bytes / seconds / GB/s."""
+        `stats` (optional dict) receives bytes / seconds / GB/s (the FILE's bytes, whatever `dtype`).
+        `dtype`: None keeps the file's; torch.bfloat16 on an fp32 file (or torch.float32 on a bf16 file) converts each chunk
+        on the device after it has landed -- into a small device staging buffer, never a whole table of the file's dtype
+        in HBM or on the host."""
         import time
         dev = torch.device(device)
         if dev.type != "cuda":
             raise hip.XnrsHipError("NewsStore.load_to_device: the target must be a HIP device")
         h, feats, maps, cols = cls._open(path)
         n = h["n_rows"]
+        file_dtype = torch.bfloat16 if h.get("dtype", "f32") == "bf16" else torch.float32
+        dtype = file_dtype if dtype is None else dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"NewsStore.load_to_device: torch.float32 or torch.bfloat16, not {dtype}")
         t0 = time.perf_counter()
         nbytes = 0
         copy_stream = torch.cuda.Stream(device=dev)
         out = {}
         for feat, fx, fm, S, D in feats:
             mx, mm = maps[feat]
-            tx = torch.empty((n, S, D), dtype=torch.float32, device=dev)
+            tx = torch.empty((n, S, D), dtype=dtype, device=dev)
             rpc = max(1, min(int(rows_per_chunk), n))
-            pinned = [torch.empty((rpc, S, D), dtype=torch.float32).pin_memory() for _ in range(2)]
+            pinned = [torch.empty((rpc, S, D), dtype=file_dtype).pin_memory() for _ in range(2)]
+            # converting load: a chunk lands in a device buffer of the file's dtype and is converted into its rows (both on
+            # the copy stream, in order: one buffer serves every chunk)
+            landed = torch.empty((rpc, S, D), dtype=file_dtype, device=dev) if dtype != file_dtype else None
             done = [torch.cuda.Event(), torch.cuda.Event()]
             used = [False, False]
             with torch.cuda.stream(copy_stream):
@@ -250,8 +313,14 @@ class NewsStore:
                     b = i & 1
                     if used[b]:
                         done[b].synchronize()  # the previous copy out of this staging buffer has landed
-                    np.copyto(pinned[b][:hi - lo].numpy(), mx[lo:hi])  # page-in: file -> pinned buffer
-                    tx[lo:hi].copy_(pinned[b][:hi - lo], non_blocking=True)
+                    stage = pinned[b][:hi - lo]
+                    np.copyto((stage.view(torch.int16) if file_dtype == torch.bfloat16 else stage).numpy(),
+                              mx[lo:hi].view(np.int16) if file_dtype == torch.bfloat16 else mx[lo:hi])  # page-in: file -> pinned buffer
+                    if landed is None:
+                        tx[lo:hi].copy_(stage, non_blocking=True)
+                    else:
+                        landed[:hi - lo].copy_(stage, non_blocking=True)
+                        tx[lo:hi].copy_(landed[:hi - lo])  # the conversion (round to nearest even when narrowing)
                     done[b].record(copy_stream)
                     used[b] = True
                 mu8 = torch.from_numpy(np.array(mm)).pin_memory()
@@ -266,6 +335,16 @@ class NewsStore:
         primary = feats[0][0]
         x, m = out.pop(primary)
         return cls(x, m, h["ids"], {k: v.to(dev) for k, v in cols.items()}, out, primary)
+
+
+_X_EXT = {torch.float32: "f32", torch.bfloat16: "bf16"}
+
+
+def _table_tensor(a: np.ndarray) -> torch.Tensor:
+    """Host tensor over a table payload: fp32 as it is, uint16 (a bf16 payload's 16 stored bits) viewed as torch.bfloat16."""
+    if a.dtype == np.uint16:
+        return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
+    return torch.from_numpy(a)
 
 
 def _csr(lists: List[List[int]]):

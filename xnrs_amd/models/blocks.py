@@ -168,6 +168,14 @@ class TextEncoder(_Tower):
             return y.reshape(b, n, self.out_dim), hm.reshape(b, n, 1)
         flat = ids.reshape(-1)
         encode = self._encoder_fn()
+        if table_x.dtype == torch.bfloat16 and (torch.is_grad_enabled() or self.training):
+            # training from a bf16 table: there is no bf16 backward -- the rows of the ids are widened into a dense fp32 copy
+            # (ops.table_rows_f32, never the table) and the dense training path runs on it, as behind the input dropout above
+            rows = torch.unique(flat, return_inverse=True) if dedup else (flat, None)
+            y, hm = encode(ops.table_rows_f32(table_x, rows[0]), ops.gather_rows(table_m, rows[0]), self)
+            if dedup:
+                y, hm = y[rows[1]], hm[rows[1]]
+            return y.reshape(b, n, self.out_dim), hm.reshape(b, n, 1)
         if dedup:
             uniq, inv = torch.unique(flat, return_inverse=True)  # index bookkeeping only
             y, hm = encode(table_x, table_m, self, ids=uniq)

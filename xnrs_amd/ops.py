@@ -145,8 +145,11 @@ def text_encoder_forward(x: torch.Tensor, m: torch.Tensor, att, pooler, head, id
     """TextEncoder.forward core (news_encoding.py:48-59) on (n_news,S,D)/(n_news,S) -> (y:(n,E'), hm:(n,)).
 
     With ``ids`` (int32, (n,)), ``x``/``m`` are the device-resident news-token table and its mask and
-    the rows are gathered inside the first GEMM's load phase."""
-    x = hip.dev_f32(x, "text encoder input")
+    the rows are gathered inside the first GEMM's load phase.  A table stored in bf16
+    (NewsStore.astype) goes to xnrs_text_encoder_fwd_bf16: Q|K|V straight from the bf16 rows, or the rows of a pass
+    widened in the workspace -- never the table."""
+    bf16_table = _is_bf16_table(x, ids)
+    x = _dev_bf16(x, "text encoder table") if bf16_table else hip.dev_f32(x, "text encoder input")
     n_tab, S, D = x.shape
     m2 = _mask2d(m, n_tab, S, "text encoder mask")
     if ids is not None:
@@ -162,13 +165,82 @@ def text_encoder_forward(x: torch.Tensor, m: torch.Tensor, att, pooler, head, id
     y = torch.empty((n, E), dtype=torch.float32, device=x.device)
     hm = torch.empty((n,), dtype=torch.float32, device=x.device)
     l = hip.lib()
-    nbytes = l.xnrs_text_encoder_workspace_bytes(n, S, D, A, E, int(att is not None), pool_kind, int(head is not None),
-                                                 chunk)
+    size_fn, fwd_fn = ((l.xnrs_text_encoder_bf16_workspace_bytes, l.xnrs_text_encoder_fwd_bf16) if bf16_table else
+                       (l.xnrs_text_encoder_workspace_bytes, l.xnrs_text_encoder_fwd))
+    nbytes = size_fn(n, S, D, A, E, int(att is not None), pool_kind, int(head is not None), chunk)
     ws = hip.workspace(x.device, nbytes)
-    hip.check(l.xnrs_text_encoder_fwd(hip.ptr(x), hip.ptr(m2), hip.ptr(ids), n, S, D, hip.ref(ap), pool_kind, hip.ref(pp),
-                                      hip.ref(hp), hip.ptr(y), hip.ptr(hm), chunk, hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
-              "xnrs_text_encoder_fwd")
+    hip.check(fwd_fn(hip.ptr(x), hip.ptr(m2), hip.ptr(ids), n, S, D, hip.ref(ap), pool_kind, hip.ref(pp),
+                     hip.ref(hp), hip.ptr(y), hip.ptr(hm), chunk, hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
+              "xnrs_text_encoder_fwd_bf16" if bf16_table else "xnrs_text_encoder_fwd")
     return y, hm
+
+
+def _is_bf16_table(x, ids) -> bool:
+    """Is x a news table stored in bf16, addressed by row ids?  (A dense bf16 batch is not a feature: it is widened whole
+    like any other non-fp32 input.)"""
+    return isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 and ids is not None
+
+
+def _dev_bf16(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise hip.XnrsHipError(f"{what}: tensor is on {t.device}; xnrs_amd runs on a HIP device only")
+    return t.contiguous()
+
+
+def table_rows_f32(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """table[ids] as dense fp32 rows, (ids.numel(), *table.shape[1:]) -- THE widening gather: every consumer of a bf16
+    table with ids other than the encoder's own entry widens only the rows it needs through it (one xnrs_gather_rows_bf16
+    launch; an fp32 table: xnrs_gather_rows).  No route converts a whole table."""
+    if table.dtype != torch.bfloat16:
+        return gather_rows(table, ids)
+    tab = _dev_bf16(table, "table_rows_f32 table")
+    if not ids.is_cuda:
+        raise hip.XnrsHipError("ids must live on the HIP device")
+    ids = ids.reshape(-1).to(torch.int32).contiguous()
+    out = torch.empty((ids.numel(),) + tuple(tab.shape[1:]), dtype=torch.float32, device=tab.device)
+    if out.numel():
+        hip.check(hip.lib().xnrs_gather_rows_bf16(hip.ptr(tab), hip.ptr(ids), hip.ptr(out), ids.numel(), tab[0].numel(),
+                                                  hip.stream_ptr(tab.device)), "xnrs_gather_rows_bf16")
+    return out
+
+
+def _widen_table_call(x, m, ids):
+    """(x, m, ids) of an encoder call for the consumers that have no bf16 entry of their own: a bf16 table with ids becomes
+    the dense fp32 rows of those ids and their mask rows (ids: None); anything else passes through."""
+    if not _is_bf16_table(x, ids):
+        return x, m, ids
+    flat = ids.reshape(-1)
+    md = None if m is None else gather_rows(m.reshape(x.shape[0], -1), flat)
+    return table_rows_f32(x, flat), md, None
+
+
+def linear_bf16(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = hip.ACT_NONE, *,
+                ids: Optional[torch.Tensor] = None, gather_s: int = 1, m_rows: Optional[int] = None):
+    """xnrs_linear_fwd_bf16 (inference): rows stored in bf16 against fp32 weights, fp32 out.  x:(..., K) bf16; with `ids`, x
+    is a table whose blocks of `gather_s` consecutive rows are gathered by id -> (ids.numel() * gather_s, N), or its first
+    `m_rows` rows (the last block then only in part)."""
+    x = _dev_bf16(x, "linear_bf16 input")
+    if x.dtype != torch.bfloat16:
+        raise hip.XnrsHipError("linear_bf16: the rows must be torch.bfloat16")
+    w = hip.dev_f32(weight, "linear weight")
+    b = None if bias is None else hip.dev_f32(bias, "linear bias")
+    N, K = w.shape
+    rows = None if ids is None else ids.reshape(-1).to(torch.int32).contiguous()
+    M = x.numel() // K if ids is None else rows.numel() * int(gather_s)
+    if m_rows is not None:
+        if not 0 <= int(m_rows) <= M:
+            raise ValueError(f"linear_bf16: m_rows = {m_rows} outside [0, {M}]")
+        M = int(m_rows)
+    if x.shape[-1] != K:
+        raise ValueError(f"linear_bf16: rows of {x.shape[-1]} elements against a weight of {K} columns")
+    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    l = hip.lib()
+    nbytes = l.xnrs_linear_bf16_workspace_bytes(N, K)
+    ws = hip.workspace(x.device, nbytes)
+    hip.check(l.xnrs_linear_fwd_bf16(hip.ptr(x), hip.ptr(rows), 0 if ids is None else int(gather_s), hip.ptr(w), hip.ptr(b),
+                                     hip.ptr(y), M, N, K, int(act), hip.ptr(ws), nbytes, hip.stream_ptr(x.device)),
+              "xnrs_linear_fwd_bf16")
+    return y
 
 
 def text_encoder_forward_unpadded(x: torch.Tensor, m: torch.Tensor, att, pooler, head, ids: Optional[torch.Tensor] = None,
@@ -177,6 +249,7 @@ def text_encoder_forward_unpadded(x: torch.Tensor, m: torch.Tensor, att, pooler,
     xnrs_text_encoder_fwd_unpadded): the unmasked token rows are compacted (index bookkeeping with torch, one
     host sync for the counts), K/V are projected for every row, everything else for the live rows only.
     Inference, additive pooler, 0/1 masks.  Same signature and results as text_encoder_forward."""
+    x, m, ids = _widen_table_call(x, m, ids)  # (a bf16 table: the rows of these ids, widened)
     x = hip.dev_f32(x, "text encoder input")
     n_tab, S, D = x.shape
     m2 = _mask2d(m, n_tab, S, "text encoder mask")
@@ -229,6 +302,7 @@ def text_encoder_forward_compact(x: torch.Tensor, m: torch.Tensor, att, pooler, 
     """The padding-free encoder with the row lists built on the DEVICE (include/xnrs_hip.h: xnrs_text_encoder_fwd_compact):
     same inputs and results as text_encoder_forward for 0/1 masks, no host sync anywhere -- the call can be captured in a
     hipGraph.  Raises XnrsHipError(code -4) for shapes / modes it does not serve (see compact_supported)."""
+    x, m, ids = _widen_table_call(x, m, ids)  # (a bf16 table: the rows of these ids, widened)
     x = hip.dev_f32(x, "text encoder input")
     n_tab, S, D = x.shape
     m2 = _mask2d(m, n_tab, S, "text encoder mask")
@@ -523,11 +597,18 @@ def gather_dropout(table: torch.Tensor, ids: torch.Tensor, p: float, seed: int):
     """nn.Dropout(p)(table[ids]) in one launch: table:(n_rows, ...), ids:(n,) -> dense dropped rows (n, ...).  Row i of the
     result draws its mask from (seed, i) -- its position in the call, not its table row -- so two occurrences of one news
     get two masks.  The device seed word (set_dropout_seed_word) is added to the seed."""
-    tab = hip.dev_f32(table, "gather_dropout table")
+    bf16 = table.dtype == torch.bfloat16  # a bf16 news table: gathered, widened and dropped in one launch, the same mask
+    tab = _dev_bf16(table, "gather_dropout table") if bf16 else hip.dev_f32(table, "gather_dropout table")
     if not ids.is_cuda:
         raise hip.XnrsHipError("ids must live on the HIP device")
     ids = ids.reshape(-1).to(torch.int32).contiguous()
     out = torch.empty((ids.numel(),) + tuple(tab.shape[1:]), dtype=torch.float32, device=tab.device)
+    if bf16:
+        if out.numel():
+            hip.check(hip.lib().xnrs_dropout_rows_bf16(hip.ptr(tab), hip.ptr(ids), hip.ptr(out), ids.numel(), tab[0].numel(),
+                                                       float(p), int(seed) % (1 << 64), hip.ptr(dropout_seed_word()),
+                                                       hip.stream_ptr(out.device)), "xnrs_dropout_rows_bf16")
+        return out
     return dropout_rows(tab, ids, out, p, seed, dropout_seed_word())
 
 
@@ -596,6 +677,7 @@ def text_encoder(x, m, enc, ids=None, chunk: int = 0):
     p, seed = _att_dropout(att)
     if _needs_grad(x, enc):
         from . import autograd
+        x, m, ids = _widen_table_call(x, m, ids)  # no bf16 backward: the training path runs on the widened rows of the ids
         return autograd.text_encoder(x, m, enc, ids, p, seed)
     return text_encoder_forward(x, m, att, pooler, head, ids=ids, chunk=chunk, dropout_p=p, seed=seed)
 
@@ -682,7 +764,9 @@ def personalized_forward(x, m, ids, q, q_idx, x_fc, head, keep: bool = False):
 
 
 def personalized(x, m, ids, q, q_idx, x_fc, head=None):
-    """-> (y, hm); through autograd when the input, the queries or the weights need a gradient."""
+    """-> (y, hm); through autograd when the input, the queries or the weights need a gradient.  A bf16 table with ids: the
+    personalized kernels read fp32 rows, so the rows of the ids are widened first (table_rows_f32)."""
+    x, m, ids = _widen_table_call(x, m, ids)
     if _needs_grad(x, q, x_fc, head):
         from . import autograd
         return autograd.personalized(x, m, ids, q, q_idx, x_fc, head)
