@@ -476,6 +476,9 @@ int32_t xnrs_infonce_bwd(const int64_t *labels, int64_t B, int32_t E, float temp
  *   7 weight-gradient GEMMs of the backward (dW = dY^T . X) | 8 input-gradient GEMMs (dX = dY . W)
  *   9 attention-core backward
  * (stage 3 also counts the one-launch additive encoder, additive_fused.hip: fc1 + pooling, stage 4 then stays empty)
+ * (stage 0 on the "fc1 in the tail" route, XNRS_GEMM_FC1_IN_TAIL below: its FLOPs are those of K|V + Q as ever, its time
+ * includes the fc1 tiles of the previous pass in the tail of the merged launch; while stage 3 is selected that route is
+ * not taken)
  * xnrs_profile_read synchronises the recorded events and returns, per stage, the summed launch
  * duration (ms), the number of launches and the summed ALGORITHMIC flops of those launches
  * (arrays of XNRS_PROFILE_STAGES entries), then clears the record. */
@@ -498,6 +501,27 @@ int32_t xnrs_profile_read(double *ms, int64_t *launches, double *flops);
 int32_t xnrs_qkv_launch_count(int32_t reset);
 int32_t xnrs_qkv_one_launch_map(int64_t block, int64_t live_tiles, int64_t live_rows, int32_t kv_row_tiles,
                                 int32_t kv_col_tiles, int64_t q_rows, int32_t q_tile_rows, int32_t q_col_tiles,
+                                int32_t *section, int32_t *index);
+
+/* ---- fc1 of the previous pass in the tail of that launch (knob XNRS_GEMM_FC1_IN_TAIL; no reference counterpart) ----
+ * Where a dense call takes the one-launch projection AND the pooler's fc1 walks the live-row list behind a folded
+ * out-projection (fp32 rows without ids, 33 <= S <= 64, inference, XNRS_FOLD_OUT on), the fc1 product of pass i-1 goes
+ * out as a third section of the projection launch of pass i; only the last pass of a call keeps an fc1 launch of its own.
+ * The same bits either way.  xnrs_fc1_in_tail_count returns the number of fc1 products that went out inside a projection
+ * launch since the last reset (process-global, relaxed atomic; the launch timer's FLOPs cannot tell the routes apart):
+ * passes - 1 per call on that route, 0 otherwise; reset != 0 clears it after reading.  xnrs_qkv_launch_count counts one
+ * per pass on this route too.
+ * Launch timer: stage 0 brackets the merged launch and reports the K|V + Q FLOPs as before, so its TIME on this route
+ * includes the fc1 tiles in the launch's tail (rates derived from it are slightly conservative).  A call made while
+ * stage 3 is selected takes the separate launches: an fc1 without a launch of its own has no time to report.
+ * xnrs_qkv_fc1_launch_map is the kernel's block -> work rule on the host (pure; tests enumerate it): the arguments of
+ * xnrs_qkv_one_launch_map plus the third section's device count (fc1_live_rows), its capacity (fc1_rows), tile height and
+ * column tiles.  Sections 0 and 1 are those of xnrs_qkv_one_launch_map for the same arguments; section 2 (fc1) starts at
+ * the end of the Q section rounded up to a multiple of 8 blocks.  Returns the grid size (< 0: XNRS_EINVAL). */
+int32_t xnrs_fc1_in_tail_count(int32_t reset);
+int32_t xnrs_qkv_fc1_launch_map(int64_t block, int64_t live_tiles, int64_t live_rows, int64_t fc1_live_rows,
+                                int32_t kv_row_tiles, int32_t kv_col_tiles, int64_t q_rows, int32_t q_tile_rows,
+                                int32_t q_col_tiles, int64_t fc1_rows, int32_t fc1_tile_rows, int32_t fc1_col_tiles,
                                 int32_t *section, int32_t *index);
 
 /* Does the TRAINING forward fold the out-projection behind the pooling right now (knob XNRS_FOLD_TRAIN)?

@@ -128,6 +128,29 @@ int32_t xnrs_qkv_one_launch_map(int64_t block, int64_t live_tiles, int64_t live_
   return (int32_t)grid;
 }
 
+int32_t xnrs_fc1_in_tail_count(int32_t reset) {
+  const int64_t n = xnrs::fc1_in_tail_read(reset != 0);
+  return n > 0x7fffffffLL ? 0x7fffffff : (int32_t)n;
+}
+
+int32_t xnrs_qkv_fc1_launch_map(int64_t block, int64_t live_tiles, int64_t live_rows, int64_t fc1_live_rows, int32_t kv_row_tiles,
+                                int32_t kv_col_tiles, int64_t q_rows, int32_t q_tile_rows, int32_t q_col_tiles, int64_t fc1_rows,
+                                int32_t fc1_tile_rows, int32_t fc1_col_tiles, int32_t* section, int32_t* index) {
+  if (kv_row_tiles < 0 || kv_col_tiles < 1 || q_rows < 0 || q_tile_rows < 1 || q_col_tiles < 1 || fc1_rows < 0 || fc1_tile_rows < 1 ||
+      fc1_col_tiles < 1)
+    return XNRS_EINVAL;
+  const int64_t grid =
+      xnrs::qkv_fc1_launch_grid(kv_row_tiles, kv_col_tiles, q_rows, q_tile_rows, q_col_tiles, fc1_rows, fc1_tile_rows, fc1_col_tiles);
+  if (grid > 0x7fffffffLL) return XNRS_EINVAL;
+  if (section && index) {
+    const xnrs::QkvOneLaunchWork w = xnrs::qkv_fc1_launch_map(block, live_tiles, live_rows, fc1_live_rows, kv_row_tiles, kv_col_tiles, q_rows,
+                                                              q_tile_rows, q_col_tiles, fc1_rows, fc1_tile_rows, fc1_col_tiles);
+    *section = w.section;
+    *index = w.index;
+  }
+  return (int32_t)grid;
+}
+
 int32_t xnrs_profile_enable(uint32_t stage_mask) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
   for (auto& r : g_prof) {

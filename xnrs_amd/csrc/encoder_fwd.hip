@@ -573,6 +573,48 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
         lr_host.clear();
     }
   }
+  // fc1 in the tail (XNRS_GEMM_FC1_IN_TAIL=0: off).  Where a pass takes the one-launch projection and its fc1 walks the
+  // live-row list over the O rows (folded out-projection), fc1 + pooling of pass i-1 wait until pass i has been projected:
+  //   launch{ K|V(i), Q(i), fc1(i-1) }  ->  pool(i-1)  ->  mha(i)          (after the last pass: fc1 and pool on their own)
+  // fc1 fills the tail of the projection grid instead of being a short launch of its own (gemm_f32.hip).  No new buffer:
+  // o and t of pass i-1 are read before mha(i) overwrites o, the image of pass i is written after mha(i-1) has read it, the
+  // row lists of every pass are in the workspace already.  Decided from shapes and knobs alone; a call with ids, a bf16
+  // table or the stage-3 timer on (an fc1 without a launch of its own has no time to report) keeps the sequence above.
+  const bool tail = lr_qkv && lr_fc1 && fold && pooled && !ids && !x16 && !qkv_given && !live && knobs().gemm_fc1_in_tail &&
+                    !prof_on(3);
+  // the pooling stage of one pass (what fc1 left in t -> pooled vector, history mask)
+  auto pool_pass = [&](int64_t c0, int64_t nc, const float* cm, const int32_t* cids, const float* seq, const int32_t* seq_ids) -> int32_t {
+    AdditivePoolArgs pa = additive_pool_args(t, rowdot, pool, seq, nc, L, D, A);
+    pa.skip_dead = lt_fc1 ? 1 : 0;
+    pa.skip_masked = lr_fc1 ? 1 : 0;
+    pa.mask = cm;
+    pa.mask_gather_ids = cids;
+    pa.x_gather_ids = seq_ids;
+    pa.y = fold ? pob + c0 * (int64_t)D : (head ? pb : y) + c0 * (int64_t)D;
+    pa.asum_out = fold ? asum + c0 : nullptr;
+    pa.a_out = a_save ? a_save : (a_out ? a_out + c0 * (int64_t)L : nullptr);
+    pa.hm_out = (cm && hm) ? hm + c0 : nullptr;
+    {
+      ProfScope ps(4, 2.0 * (double)(nc * L) * (double)(A + D), stream);
+      XNRS_TRY(launch_additive_pool(pa, stream));
+    }
+    if (a_save && a_out)
+      XNRS_TRY(hipMemcpyAsync(a_out, a_save, (size_t)(nc * L) * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    return XNRS_OK;
+  };
+  struct {
+    bool on = false;  // fc1 + pooling of a pass are outstanding
+    GemmArgs fg;
+    int64_t c0 = 0, nc = 0;
+    const float* cm = nullptr;
+  } pend;
+  // ... on their own: the last pass of a call, or a pass whose successor does not take the merged launch
+  auto drain = [&]() -> int32_t {
+    if (!pend.on) return XNRS_OK;
+    pend.on = false;
+    XNRS_TRY(launch_gemm_f32(pend.fg, stream));
+    return pool_pass(pend.c0, pend.nc, pend.cm, nullptr, o, nullptr);
+  };
   for (int64_t c0 = 0; !fused && !afused && c0 < n_seq; c0 += p.chunk) {
     const int64_t nc = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
     const int64_t rows = nc * L;
@@ -630,7 +672,6 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
           XNRS_TRY(launch_gemm_f32(q, stream));
         }
       } else if (lr_qkv) {  // K|V of the live row tiles, Q of the live rows: a masked token's Q row stays unwritten, nobody reads it
-        ProfScope ps(0, 2.0 * lt_rows * 2.0 * D * D + 2.0 * lr_rows * (double)D * D, stream);
         GemmArgs g = qkv_projection(cx, {xids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
         g.live_n = ltn;
         g.live_tiles = ltl;
@@ -642,13 +683,29 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
         // the two read the same x and write disjoint columns of the image: ONE grid, the Q tiles behind the K|V tiles, leaves
         // one partly filled last round of workgroups instead of two and a launch boundary (XNRS_GEMM_QKV_ONE_LAUNCH=0: two
         // launches; the same bits either way, and the same choice for every pass of the call whatever the data)
-        if (gemm_qkv_one_launch_ok(g, q)) {
-          XNRS_TRY(launch_gemm_qkv_one(g, q, stream));
-          qkv_launches_add(1);
-        } else {
-          XNRS_TRY(launch_gemm_f32(g, stream));
-          XNRS_TRY(launch_gemm_f32(q, stream));
-          qkv_launches_add(2);
+        const bool one = gemm_qkv_one_launch_ok(g, q);
+        // (fc1 in the tail) the outstanding fc1 rides in this launch if it can; otherwise it and its pooling run first, as before
+        const bool merged = tail && one && (!pend.on || gemm_fc1_in_tail_ok(pend.fg));
+        if (!merged) XNRS_TRY_RC(drain());
+        {
+          // (on the merged route the stage's time includes the fc1 tiles in the launch's tail; its FLOPs stay those of K|V + Q)
+          ProfScope ps(0, 2.0 * lt_rows * 2.0 * D * D + 2.0 * lr_rows * (double)D * D, stream);
+          if (merged) {
+            XNRS_TRY(launch_gemm_qkv_fc1(g, q, pend.on ? &pend.fg : nullptr, stream));
+            qkv_launches_add(1);
+            if (pend.on) fc1_in_tail_add(1);
+          } else if (one) {
+            XNRS_TRY(launch_gemm_qkv_one(g, q, stream));
+            qkv_launches_add(1);
+          } else {
+            XNRS_TRY(launch_gemm_f32(g, stream));
+            XNRS_TRY(launch_gemm_f32(q, stream));
+            qkv_launches_add(2);
+          }
+        }
+        if (pend.on) {  // (merged) the scores of the previous pass are out: pool it before the attention below overwrites its O rows
+          pend.on = false;
+          XNRS_TRY_RC(pool_pass(pend.c0, pend.nc, pend.cm, nullptr, o, nullptr));
         }
       } else {
         GemmArgs g = qkv_projection(cx, {xids, L}, att, 0, qkv, ld3, rows, D, pqkv);
@@ -725,6 +782,14 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
         fg.c_scatter_ids = lrl;
         fg.m_dev = lrn;
         fg.m_fill_hint = LR_FILL;
+        if (tail) {  // fc1 in the tail: this pass's fc1 goes out with the next pass's projection, its pooling right behind it
+          pend.on = true;
+          pend.fg = fg;
+          pend.c0 = c0;
+          pend.nc = nc;
+          pend.cm = cm;
+          continue;
+        }
         ProfScope ps(3, 2.0 * lr_rows * (double)D * A, stream);
         XNRS_TRY(launch_gemm_f32(fg, stream));
       } else {
@@ -736,22 +801,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
         ProfScope ps(3, 2.0 * (lt_fc1 ? lt_rows : (double)rows) * (double)D * A, stream);
         XNRS_TRY(launch_gemm_f32(fg, stream));
       }
-      AdditivePoolArgs pa = additive_pool_args(t, rowdot, pool, seq, nc, L, D, A);
-      pa.skip_dead = lt_fc1 ? 1 : 0;
-      pa.skip_masked = lr_fc1 ? 1 : 0;
-      pa.mask = cm;
-      pa.mask_gather_ids = cids;
-      pa.x_gather_ids = seq_ids;
-      pa.y = fold ? pob + c0 * (int64_t)D : pooled_dst;
-      pa.asum_out = fold ? asum + c0 : nullptr;
-      pa.a_out = a_save ? a_save : (a_out ? a_out + c0 * (int64_t)L : nullptr);
-      pa.hm_out = cm ? hm_dst : nullptr;
-      {
-        ProfScope ps(4, 2.0 * rows * (double)(A + D), stream);
-        XNRS_TRY(launch_additive_pool(pa, stream));
-      }
-      if (a_save && a_out)
-        XNRS_TRY(hipMemcpyAsync(a_out, a_save, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, stream));
+      XNRS_TRY_RC(pool_pass(c0, nc, cm, cids, seq, seq_ids));
     } else {
       MeanPoolArgs mp{};
       mp.x = seq;
@@ -770,6 +820,7 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
       }
     }
   }
+  XNRS_TRY_RC(drain());  // (fc1 in the tail) the last pass
   // pooled = Wo (sum_i a_i O_i) + bo (sum_i a_i): one out-projection per sequence (or folded into the head), then the head
   return pooled_tail(fold, pob, asum, att, pooled ? head : nullptr, pb, hb, y, n_seq, D, E, po, train, stream);
 }

@@ -164,6 +164,44 @@ __global__ __launch_bounds__(256, 4) void gemm_qkv_one_launch_kernel(const GemmA
     gemm_f32_body<2, 1, false, false, true, 5, 16, true, 4, true, 2, false, true, false>(q, q_m_tiles, q_n_tiles, q_gn, w.index, 0, As, Bs);
 }
 
+// ... and fc1 of the PREVIOUS pass behind them (kernels.h: qkv_fc1_launch_map; DESIGN.md section 4.1 "fc1 in the tail").  The
+// pooler's fc1 over a pass's live rows is 7 % of the projection's work on the smallest tile of the family: as a launch of its
+// own it is mostly ramp-up and tail (4.5 tiles per CU), and the projection launch above still ends in a partly filled round.
+// Here it is a third section of the next pass's projection grid: the body of the instantiation its own launch runs (GATH +
+// RDOT + MDEV, row-scattered row dots) on the same LDS arrays, its index inside the section as the workgroup index, the
+// section starting at a multiple of 8 -- every score comes from the same instruction sequence.  It reads the attention
+// output of the previous pass and writes that pass's scores; the two projection sections touch neither.
+// FTM x FTN: the third section's tile in units of 64 (every shape gives the same bits: the 32-column blocks of the row dots
+// do not depend on it); which shapes compile clean next to the two other bodies: profiles/fc1_in_tail_resource_usage.md.
+template <int FTM, int FTN>
+__global__ __launch_bounds__(256, 4) void gemm_qkv_fc1_launch_kernel(const GemmArgs kv, const GemmArgs q, const GemmArgs f, int kv_m_tiles,
+                                                                     int kv_n_tiles_seg, int kv_gn, int q_m_tiles, int q_n_tiles, int q_gn,
+                                                                     int f_m_tiles, int f_n_tiles, int f_gn) {
+  __shared__ __attribute__((aligned(16))) float As[gemm_f32_lds_floats<2, 16>()];
+  __shared__ __attribute__((aligned(16))) float Bs[gemm_f32_lds_floats<2, 16>()];
+  static_assert(sizeof(As) + sizeof(Bs) <= 32768, "four workgroups per CU");
+  static_assert(FTM >= 1 && FTM <= 2 && FTN >= 1 && FTN <= 2, "the third section's tiles fit the arrays of the first");
+  // the three device counts, as the bodies read them (wave-uniform); an empty third section (f.M == 0) has none
+  auto dev64 = [](const int64_t* p) {
+    const int64_t v = load_dev_scalar(p);
+    return ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+  };
+  const int64_t ln = __builtin_amdgcn_readfirstlane((int)load_dev_scalar(kv.live_n));
+  const int64_t md = dev64(q.m_dev);
+  const int64_t fd = f.M > 0 ? dev64(f.m_dev) : 0;
+  const QkvOneLaunchWork w = qkv_fc1_launch_map((int64_t)blockIdx.x, ln, md, fd, kv_m_tiles, kv_n_tiles_seg * kv.nseg, q.M, 128, q_n_tiles,
+                                                f.M, 64 * FTM, f_n_tiles);
+  if (w.section < 0) return;  // workgroup-uniform, before any barrier
+  // (nothing may follow the calls: a body returns early for its own reasons, see gemm_f32_body)
+  if (w.section == 0)
+    gemm_f32_body<2, 2, false, false, true, 5, 16, true, 4, false, 2, false, false, true>(kv, kv_m_tiles, kv_n_tiles_seg, kv_gn, w.index, 0,
+                                                                                        As, Bs);
+  else if (w.section == 1)
+    gemm_f32_body<2, 1, false, false, true, 5, 16, true, 4, true, 2, false, true, false>(q, q_m_tiles, q_n_tiles, q_gn, w.index, 0, As, Bs);
+  else
+    gemm_f32_body<FTM, FTN, false, false, true, 5, 16, true, 4, true, 2, true, true, false>(f, f_m_tiles, f_n_tiles, f_gn, w.index, 0, As, Bs);
+}
+
 // Wt[c][r] = W[r][c]: 32x32 tiles through LDS (padded rows), both sides coalesced
 __global__ __launch_bounds__(256) void transpose_kernel(const float* W, float* Wt, int rows, int cols) {
   __shared__ float tile[32][33];
@@ -466,6 +504,7 @@ static Knobs read_knobs() {
   {
     k.gemm_qkv_one_launch = num("XNRS_GEMM_QKV_ONE_LAUNCH", 1) != 0;
   }
+  k.gemm_fc1_in_tail = num("XNRS_GEMM_FC1_IN_TAIL", 1) != 0;
   k.gemm_live_tiles = num("XNRS_GEMM_LIVE_TILES", 1) != 0;
   k.gemm_live_tiles_min_rows = num("XNRS_GEMM_LIVE_TILES_MIN_ROWS", 16384);
   k.gemm_live_rows = num("XNRS_GEMM_LIVE_ROWS", 1) != 0;
@@ -612,6 +651,48 @@ hipError_t launch_gemm_qkv_one(const GemmArgs& kv_in, const GemmArgs& q_in, hipS
   const dim3 g((unsigned)qkv_one_launch_grid(kv_m_tiles, kv_n_tiles_seg * kv.nseg, q.M, 128, q_n_tiles));
   hipLaunchKernelGGL(gemm_qkv_one_launch_kernel, g, dim3(256), 0, stream, kv, q, kv_m_tiles, kv_n_tiles_seg, kv_gn, q_m_tiles, q_n_tiles,
                      q_gn);
+  return hipGetLastError();
+}
+
+// ---- ... with fc1 of the previous pass as a third section (kernels.h)
+static std::atomic<int64_t> g_fc1_in_tail{0};
+void fc1_in_tail_add(int n) { g_fc1_in_tail.fetch_add(n, std::memory_order_relaxed); }
+int64_t fc1_in_tail_read(bool reset) {
+  return reset ? g_fc1_in_tail.exchange(0, std::memory_order_relaxed) : g_fc1_in_tail.load(std::memory_order_relaxed);
+}
+
+// what launch_gemm_f32 asks of a launch before it takes the GATH + RDOT + MDEV instantiation with scattered row dots
+bool gemm_fc1_in_tail_ok(const GemmArgs& f) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (!knobs().gemm_fc1_in_tail || gemm_mode() != 0 || knobs().gemm_tile >= 0 || !knobs().gemm_buf) return false;
+  if (f.a_col || f.b_kn || f.M <= 0 || f.Nseg <= 0 || f.nseg != 1 || f.K < 4 || f.K >= (1ll << 31) || f.K % 4 != 0) return false;
+  if (f.lda % 4 != 0 || f.ldw % 4 != 0 || !al16(f.A) || !al16(f.W[0]) || (int64_t)f.Nseg * f.ldw * 4 > (int64_t)BUF_OOB) return false;
+  if ((f.slabs && f.nsplit > 1) || f.rowscale || f.colsum || f.k_dev || f.C2 || f.live_tiles || f.accumulate || f.aux_mode) return false;
+  if (!f.rowdot_out || !f.rowdot_w || (f.act != 2 && f.act != ACT_TANH_FAST)) return false;
+  if (!f.gather_ids || f.gather_S != 1 || !f.c_scatter || !f.m_dev) return false;
+  return (f.M + FC1_TAIL_BM - 1) / FC1_TAIL_BM * ((f.Nseg + FC1_TAIL_BN - 1) / FC1_TAIL_BN) <= 0x3fffffffLL;
+}
+
+hipError_t launch_gemm_qkv_fc1(const GemmArgs& kv_in, const GemmArgs& q_in, const GemmArgs* f_in, hipStream_t stream) {
+  if (!gemm_qkv_one_launch_ok(kv_in, q_in) || (f_in && !gemm_fc1_in_tail_ok(*f_in))) return hipErrorInvalidValue;
+  GemmArgs kv = kv_in, q = q_in, f{};  // f.M == 0: an empty third section, nothing of f is read
+  if (f_in) f = *f_in;
+  for (GemmArgs* a : {&kv, &q, &f}) {  // what launch_gemm_f32 fills in
+    if (a->act == 2 && knobs().fast_tanh) a->act = ACT_TANH_FAST;
+    a->k_per_split = a->K > 0 ? a->K : 1;
+    a->nt_store = (!a->accumulate && !a->c_scatter && a->M * a->ldc * 4 >= (64ll << 20)) ? 1 : 0;
+  }
+  constexpr int FTM = FC1_TAIL_BM / 64, FTN = FC1_TAIL_BN / 64;
+  const int kv_m_tiles = (int)((kv.M + 127) / 128), kv_n_tiles_seg = (kv.Nseg + 127) / 128;
+  const int q_m_tiles = (int)((q.M + 127) / 128), q_n_tiles = (q.Nseg + 63) / 64;
+  const int f_m_tiles = (int)((f.M + FC1_TAIL_BM - 1) / FC1_TAIL_BM), f_n_tiles = f_in ? (f.Nseg + FC1_TAIL_BN - 1) / FC1_TAIL_BN : 1;
+  const int kv_gn = gemm_group_tiles(kv_n_tiles_seg * kv.nseg, 128, kv.K, false);
+  const int q_gn = gemm_group_tiles(q_n_tiles, 64, q.K, false);
+  const int f_gn = gemm_group_tiles(f_n_tiles, FC1_TAIL_BN, f.K, false);
+  const int64_t grid = qkv_fc1_launch_grid(kv_m_tiles, kv_n_tiles_seg * kv.nseg, q.M, 128, q_n_tiles, f.M, FC1_TAIL_BM, f_n_tiles);
+  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((gemm_qkv_fc1_launch_kernel<FTM, FTN>), dim3((unsigned)grid), dim3(256), 0, stream, kv, q, f, kv_m_tiles, kv_n_tiles_seg,
+                     kv_gn, q_m_tiles, q_n_tiles, q_gn, f_m_tiles, f_n_tiles, f_gn);
   return hipGetLastError();
 }
 

@@ -52,6 +52,9 @@ struct Knobs {
   bool gemm_qkv_one_launch = true;  // XNRS_GEMM_QKV_ONE_LAUNCH=0: a dense live-row pass over dense rows projects K|V and Q in two
                                 // launches instead of one grid (gemm_f32.hip: launch_gemm_qkv_one; bitwise the same results).  Calls
                                 // with ids take the two launches either way (DESIGN.md section 4.1 "One launch")
+  bool gemm_fc1_in_tail = true;  // XNRS_GEMM_FC1_IN_TAIL=0: the pooler's fc1 of a dense live-row pass keeps its own launch instead of
+                                // riding as a third section in the one-launch projection of the NEXT pass (gemm_f32.hip:
+                                // launch_gemm_qkv_fc1; bitwise the same results; DESIGN.md section 4.1 "fc1 in the tail")
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
   bool gemm_a16 = true;         // XNRS_GEMM_A16=0: an encoder call on a bf16 news table widens the rows of every pass to fp32 and takes
@@ -177,7 +180,7 @@ hipError_t launch_gemm_f32(const GemmArgs& a, hipStream_t stream, int* nsplit_us
 //   blocks past that               nothing
 // One rule for the kernel and the host (tests enumerate it without a GPU: xnrs_qkv_one_launch_map).
 struct QkvOneLaunchWork {
-  int section;  // 0: K|V, 1: Q, -1: no work
+  int section;  // 0: K|V, 1: Q, -1: no work (2: fc1 of the previous pass, qkv_fc1_launch_map only)
   int index;    // the workgroup's index inside its section's tile sequence
 };
 __host__ __device__ inline QkvOneLaunchWork qkv_one_launch_map(int64_t block, int64_t live_n, int64_t m_dev, int kv_m_tiles,
@@ -202,6 +205,42 @@ hipError_t launch_gemm_qkv_one(const GemmArgs& kv, const GemmArgs& q, hipStream_
 // (xnrs_qkv_launch_count; the launch timer's FLOPs are the same on both routes and cannot tell)
 void qkv_launches_add(int n);
 int64_t qkv_launches_read(bool reset);
+// ---- ... with fc1 of the PREVIOUS pass in its tail (encoder_fwd.hip "fc1 in the tail").  `f` is the
+// pooler's fc1 launch over the previous pass's live-row list (gathered rows, row-scattered row dots, GemmArgs::m_dev) exactly
+// as it would go to launch_gemm_f32, or null (the first pass of a call: an empty third section).  A third section behind the
+// two of qkv_one_launch_map, which it leaves as they are:
+//   blocks [q_end, f0)         nothing (q_end = kv_pad + q_wgs, f0 = q_end rounded up to 8: the XCD rule again)
+//   blocks [f0, f0 + f_wgs)    fc1 tiles, f_wgs = ceil(fc1 live rows / f_bm) x column tiles (section 2)
+//   blocks past that           nothing
+// Section 2 exists in QkvOneLaunchWork for this rule only.
+__host__ __device__ inline QkvOneLaunchWork qkv_fc1_launch_map(int64_t block, int64_t live_n, int64_t m_dev, int64_t f_dev, int kv_m_tiles,
+                                                               int kv_n_tiles, int64_t q_rows, int q_bm, int q_n_tiles, int64_t f_rows,
+                                                               int f_bm, int f_n_tiles) {
+  const QkvOneLaunchWork w = qkv_one_launch_map(block, live_n, m_dev, kv_m_tiles, kv_n_tiles, q_rows, q_bm, q_n_tiles);
+  if (w.section >= 0) return w;
+  const int64_t lt = live_n < kv_m_tiles ? (live_n > 0 ? live_n : 0) : kv_m_tiles;
+  const int64_t rows = m_dev < q_rows ? (m_dev > 0 ? m_dev : 0) : q_rows;
+  const int64_t q_end = ((lt * kv_n_tiles + 7) & ~(int64_t)7) + ((rows + q_bm - 1) / q_bm) * q_n_tiles;
+  const int64_t f0 = (q_end + 7) & ~(int64_t)7;
+  const int64_t fr = f_dev < f_rows ? (f_dev > 0 ? f_dev : 0) : f_rows;
+  const int64_t f_wgs = ((fr + f_bm - 1) / f_bm) * f_n_tiles;
+  return block >= f0 && block - f0 < f_wgs ? QkvOneLaunchWork{2, (int)(block - f0)} : QkvOneLaunchWork{-1, 0};
+}
+// the grid: every tile of the three sections, the first two each rounded up to 8
+inline int64_t qkv_fc1_launch_grid(int kv_m_tiles, int kv_n_tiles, int64_t q_rows, int q_bm, int q_n_tiles, int64_t f_rows, int f_bm,
+                                   int f_n_tiles) {
+  return ((qkv_one_launch_grid(kv_m_tiles, kv_n_tiles, q_rows, q_bm, q_n_tiles) + 7) & ~(int64_t)7) +
+         ((f_rows + f_bm - 1) / f_bm) * f_n_tiles;
+}
+constexpr int FC1_TAIL_BM = 64, FC1_TAIL_BN = 64;  // the third section's tile (every tile shape gives the same bits)
+// can `f` ride in the projection launch of the next pass (the knob XNRS_GEMM_FC1_IN_TAIL, fp32 mode, the shape and
+// alignment of the GATH + RDOT + MDEV instantiation)?  If not the caller launches it on its own.
+bool gemm_fc1_in_tail_ok(const GemmArgs& f);
+// kv, q: as launch_gemm_qkv_one (gemm_qkv_one_launch_ok(kv, q) holds); f: nullable, gemm_fc1_in_tail_ok(*f) holds
+hipError_t launch_gemm_qkv_fc1(const GemmArgs& kv, const GemmArgs& q, const GemmArgs* f, hipStream_t stream);
+// the fc1 products that went out inside a projection launch since the last reset (xnrs_fc1_in_tail_count)
+void fc1_in_tail_add(int n);
+int64_t fc1_in_tail_read(bool reset);
 // dW = dY^T . X with the transpose done in registers on the way to LDS (gemm_dw.hip); nsplit / k_per_split / slab_stride
 // as filled in by launch_gemm_f32
 bool gemm_dw_eligible(const GemmArgs& a);
