@@ -623,6 +623,42 @@ int32_t xnrs_score_csr_mlp(const float *P, const int32_t *cand_rows, const int32
 /* y[r,:] = x[r,:] / ||x[r,:]|| (no epsilon, scoring.py:20-22); y may equal x */
 int32_t xnrs_l2_normalize_rows(const float *x, float *y, int64_t rows, int32_t E, void *stream);
 
+/* ---- top-k rows of a pre-encoded news table per user (recommendation; csrc/topk.hip) -------------------------------------
+ * rows:(B,k) int32, scores:(B,k) fp32 <- for every user the k eligible table rows of highest score, without a (B, n_rows)
+ * score matrix: a partial kernel ranks the score tiles of (user tile x table slice) while it forms them, a merge kernel
+ * merges the slices.  The three entry points mirror xnrs_score_csr / _bilinear / _mlp -- the same user-side GEMM into ws,
+ * the same meaning of table / P (already L2-normalised by the caller where the scorer normalises):
+ *   xnrs_topk          s = <table[n], u[b]>
+ *   xnrs_topk_bilinear s = <table[n], v[b]> + bias, v = u W[0]
+ *   xnrs_topk_mlp      s = w2 . tanh(q[b] + P[n]) + b2, q = u W1u^T + b1, P:(n_rows,H) = xnrs_mlp_scoring_news_proj of the table
+ * Order: higher score first; equal scores (==, so +0 and -0 tie) lower row first; a NaN score is never selected; -inf is a
+ * legal score.  The ranking is by the RAW score: there is no ReLU here (the evaluation's relu would tie every negative score).
+ * Eligible rows: [0, n_rows) minus pad_row (when >= 0) minus the user's exclusion list.  With fewer than k eligible rows the
+ * tail holds fillers -- row -1, score -inf -- behind every real entry.
+ * Exclusions: excl_off:(B+1) int64 and excl_rows: int32 form a CSR over the users, the offsets ABSOLUTE into excl_rows (a
+ * slice of a longer offset array works without a copy).  A list may be unsorted, hold duplicates and hold ids outside the
+ * table (compared, never dereferenced), at any length.  excl_off == NULL: no exclusions.
+ * Arithmetic: the inner-product forms are one fp32 fma chain over ascending feature index from 0 (the fp32 MFMA), the bias
+ * added last; the MLP form sums over h in ascending order.  A user's result therefore does not depend on B, on the user's
+ * position in the batch or on the slicing, and is bit for bit the same on every run.
+ * Limits: 1 <= k <= XNRS_TOPK_MAX_K, n_rows <= 2^31 - 1, any E, H >= 1, any B >= 0.  B == 0: XNRS_OK, nothing written;
+ * n_rows == 0: fillers.  Argument errors (XNRS_EINVAL) and a short workspace (XNRS_EWORKSPACE) are found on the host before
+ * any launch and write nothing.  ws: xnrs_topk_workspace_bytes(B, n_rows, proj_width, k), proj_width = 0 (xnrs_topk), E
+ * (bilinear), H (MLP).  xnrs_topk_slices: the number of table slices a call of this size uses, chosen from (B, n_rows) alone
+ * so that user tiles x slices fills the chip (a pure host call; 1 for a table of one 128-row chunk). */
+#define XNRS_TOPK_MAX_K 128
+size_t xnrs_topk_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t k);
+int32_t xnrs_topk_slices(int64_t B, int64_t n_rows);
+int32_t xnrs_topk(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const int64_t *excl_off,
+                  const int32_t *excl_rows, int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws,
+                  size_t ws_bytes, void *stream);
+int32_t xnrs_topk_bilinear(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const float *w,
+                           const float *bias, const int64_t *excl_off, const int32_t *excl_rows, int32_t pad_row, int32_t k,
+                           int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_topk_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, const float *u, int64_t B, const float *w1,
+                      const float *b1, const float *w2, const float *b2, const int64_t *excl_off, const int32_t *excl_rows,
+                      int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

@@ -129,6 +129,17 @@ inline GemmArgs gemm_kmajor_ab(const float* At, int64_t lda, const float* B, int
   return g;
 }
 
+// the dense projections of the scorers (scorers.hip, topk.hip)
+// C[M, N] = A[M, K] . op(W) (+ bias): W row-major [N][K] at pitch ldw (w_kn = 0: nn.Linear layout) or [K][N] at pitch ldw
+// (w_kn = 1); one launch, no split-K
+inline hipError_t sc_gemm(const float* A, int64_t lda, const float* W, int64_t ldw, int w_kn, const float* bias, float* C, int64_t ldc,
+                   int64_t M, int N, int64_t K, hipStream_t stream) {
+  GemmArgs g = w_kn ? gemm_kmajor_b(A, lda, W, ldw, C, ldc, M, N, K) : gemm_linear(A, {}, lda, W, bias, C, ldc, M, N, K);
+  g.bias[0] = bias;
+  g.ldw = ldw;
+  return launch_gemm_f32(g, stream);
+}
+
 // ---------------------------------------------------------------- folded out-projection (encoder_fwd.hip "fold")
 constexpr int FOLD_SPLITS = 8;  // K slices of the folded-weight product X . Wo (slabs: FOLD_SPLITS x M x D floats)
 inline bool fold_wanted(int knob) { return knob != 0; }  // knob: 0 never, anything else always

@@ -302,16 +302,6 @@ using namespace xnrs;
 
 namespace {
 
-// C[M, N] = A[M, K] . op(W) (+ bias): W row-major [N][K] at pitch ldw (w_kn = 0: nn.Linear layout) or [K][N] at pitch ldw
-// (w_kn = 1); one launch, no split-K
-hipError_t sc_gemm(const float* A, int64_t lda, const float* W, int64_t ldw, int w_kn, const float* bias, float* C, int64_t ldc,
-                   int64_t M, int N, int64_t K, hipStream_t stream) {
-  GemmArgs g = w_kn ? gemm_kmajor_b(A, lda, W, ldw, C, ldc, M, N, K) : gemm_linear(A, {}, lda, W, bias, C, ldc, M, N, K);
-  g.bias[0] = bias;
-  g.ldw = ldw;
-  return launch_gemm_f32(g, stream);
-}
-
 // dW[M, N] (pitch ldc) = dY[R, M]^T . X[R, N] over R rows (dY pitch lddy, X pitch ldx); one launch, no split-K
 hipError_t sc_gemm_dw(const float* dY, int64_t lddy, const float* X, int64_t ldx, float* dW, int64_t ldc, int M, int N, int64_t R,
                       hipStream_t stream) {

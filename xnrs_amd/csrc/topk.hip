@@ -1,0 +1,547 @@
+// Top-k news per user over a whole pre-encoded table: the scores of a (users x table rows) product are ranked while they are
+// formed, so the (B, n_rows) score matrix never exists.  Two launches per call (plus the user-side projection GEMM of the
+// bilinear / MLP scorer); results cross from one launch to the next at the kernel boundary only: no flags, no float atomics.
+//
+//   partial : grid = user tiles x table slices.  A workgroup takes TK_TILE users and one contiguous slice of table rows, walks
+//             the slice in chunks of TK_TILE rows, forms the chunk's score tile and keeps each user's k best of the slice so
+//             far as a sorted list of 64-bit keys in the workspace (the list of slice s of user b: part[(s * B + b) * k ..]).
+//             Only a score that beats the user's current k-th best (kept in LDS) is appended to the user's LDS candidate buffer
+//             (an integer LDS atomic hands out the slot); a full buffer, and the end of the slice, drop the candidates on the
+//             user's exclusion list (half a wave per user, one candidate per lane, the list read once for all of them), merge
+//             the rest into the list and raise the threshold.  Arrival order in the buffer
+//             varies from run to run; the merged list does not (the keys are totally ordered and a dropped candidate was
+//             already below k others).
+//   merge   : one wave per user merges the `slices` sorted lists into the final k and decodes rows and scores.
+//
+// Score tile
+//   inner product (dot, bilinear): the fp32 MFMA v_mfma_f32_32x32x2_f32 over ascending feature index, no split-K: bit for bit
+//             one fp32 fma chain from 0 per (user, row); the bias is added last.
+//   MLP     : w2 . tanh(q_b + P_n) + b2 on the VALU, h ascending, the tanhf of score_csr_mlp_kernel.
+// Either way the score of a (user, row) pair depends on nothing but that pair, so a user's result does not depend on B, on the
+// user's position in the batch or on the slicing, and is the same bits on every run.
+//
+// Order: key = (order-preserving score bits << 32) | ~row, so "higher score first, equal scores (-0 == +0) lower row first" is
+// one unsigned compare.  A NaN score is never selected; -inf is a legal score.  Missing entries (fewer than k eligible rows)
+// are fillers -- row -1, score -inf -- whose key lies below every real key.  The ranking is by the RAW score: no ReLU (the
+// evaluation's relu would tie every negative score).
+#include "host.h"
+
+namespace xnrs {
+
+namespace {
+
+constexpr int TK_TILE = 128;             // users per workgroup = table rows per chunk
+constexpr int TK_KT = 32;                // features per LDS stage
+constexpr int TK_PITCH = TK_TILE + 1;    // feature-major LDS tiles: conflict-free transposing writes (4 * pitch = 4 mod 32)
+constexpr int TK_CB = 32;                // candidate buffer entries per user
+constexpr int TK_WGS = 512;              // workgroups that fill the chip: 256 CUs x 2 resident (79 872 B of LDS each, 160 KB per CU)
+// the most slices of a call (a single user tile is the only case that wants more): the merge kernel folds a user's slice lists
+// one after the other, which with 512 lists takes longer than the partial kernel; 256 still gives every CU a workgroup
+constexpr int TK_MAX_SLICES = 256;
+constexpr uint64_t TK_FILLER = 0x007FFFFFull << 32;  // score -inf, row -1: below the key of row 2^31 - 2 at score -inf
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+__device__ __forceinline__ uint64_t tk_key(float s, uint32_t row) {
+  const uint32_t b = __float_as_uint(s == 0.f ? 0.f : s);  // -0 ties with +0
+  return ((uint64_t)((b & 0x80000000u) ? ~b : (b | 0x80000000u)) << 32) | (uint32_t)~row;
+}
+__device__ __forceinline__ float tk_score(uint64_t key) {
+  const uint32_t o = (uint32_t)(key >> 32);
+  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+// what one wave wrote to LDS / the workspace is read by its other lanes
+__device__ __forceinline__ void tk_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+// the same for LDS alone: a wave's LDS accesses are performed in program order, so the compiler must keep that order and no
+// wait is needed -- loads from global memory stay in flight across it
+__device__ __forceinline__ void tk_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// how many of the descending keys a[0, n), n <= MAXN (a power of two), are greater than key: a binary search of a fixed
+// number of branch-free steps, so that several searches side by side overlap their LDS latencies
+template <int MAXN>
+__device__ __forceinline__ int tk_count_greater(const uint64_t* a, int n, uint64_t key) {
+  int c = 0;
+#pragma unroll
+  for (int step = MAXN; step > 0; step >>= 1) {
+    const int t = c + step;
+    const uint64_t at = a[t <= n ? t - 1 : 0];
+    if (t <= n && at > key) c = t;
+  }
+  return c;
+}
+
+// rows [r0, r0 + 128) x features [k0, k0 + 32) of a row-major [n][W] matrix, four float4 per thread: eight consecutive
+// threads read 128 contiguous bytes of one row.  Rows past n and features past W read as 0.
+struct TkTile {
+  float4 v[4];
+};
+__device__ __forceinline__ void tk_load(TkTile& t, const float* x, int64_t n, int64_t r0, int W, int k0, int vec) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int idx = threadIdx.x + 256 * p;
+    const int64_t r = r0 + (idx >> 3);
+    const int k = k0 + (idx & 7) * 4;
+    float4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < n && k < W) {
+      const float* s = x + r * W + k;
+      if (vec) v = *reinterpret_cast<const float4*>(s);  // (W % 4 == 0 and a 16-B base: the four are inside the row)
+      else {
+        v.x = s[0];
+        if (k + 1 < W) v.y = s[1];
+        if (k + 2 < W) v.z = s[2];
+        if (k + 3 < W) v.w = s[3];
+      }
+    }
+    t.v[p] = v;
+  }
+}
+__device__ __forceinline__ void tk_store(const TkTile& t, float* lds) {  // lds[feature][row]
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int idx = threadIdx.x + 256 * p;
+    float* d = lds + (idx & 7) * 4 * TK_PITCH + (idx >> 3);
+    d[0] = t.v[p].x;
+    d[TK_PITCH] = t.v[p].y;
+    d[2 * TK_PITCH] = t.v[p].z;
+    d[3 * TK_PITCH] = t.v[p].w;
+  }
+}
+
+// x[b & 15]: a tree of selects on the bits of b (no register is indexed at run time)
+__device__ __forceinline__ float tk_pick16(const f32x16 x, int b) {
+  const bool b0 = b & 1, b1 = b & 2, b2 = b & 4, b3 = b & 8;
+  const float a0 = b0 ? x[1] : x[0], a1 = b0 ? x[3] : x[2], a2 = b0 ? x[5] : x[4], a3 = b0 ? x[7] : x[6];
+  const float a4 = b0 ? x[9] : x[8], a5 = b0 ? x[11] : x[10], a6 = b0 ? x[13] : x[12], a7 = b0 ? x[15] : x[14];
+  const float c0 = b1 ? a1 : a0, c1 = b1 ? a3 : a2, c2 = b1 ? a5 : a4, c3 = b1 ? a7 : a6;
+  const float d0 = b2 ? c1 : c0, d1 = b2 ? c3 : c2;
+  return b3 ? d1 : d0;
+}
+
+struct TopkArgs {
+  const float *table, *u, *w2, *bias;  // table:(n_rows, W), u:(B, W); w2:(W) in the MLP form
+  const int64_t* excl_off;
+  const int32_t* excl_rows;
+  int64_t n_rows, B, chunks_per_slice;
+  int W, k, pad_row, vec_t, vec_u;
+  uint64_t* part;
+};
+
+// One wave merges the candidate buffers of up to two users at once, one user per half-wave (32 lanes = TK_CB candidates, one
+// per lane): list[0, k) (sorted, in the workspace) <- the k greatest of list and the candidates buf[0, n) (unsorted, distinct
+// real keys) that are not on the user's exclusion list.  The exclusion list goes through LDS 64 ids at a time and every
+// candidate is compared with each (ids are compared, never dereferenced); an excluded candidate becomes key 0, below every
+// filler.  Every key's place is its count of greater keys: a list entry's index (fillers are told apart by it) plus the
+// surviving candidates above it, a candidate's rank among the candidates plus the list entries above it.
+struct TkHalf {  // the LDS of one half-wave
+  uint64_t stage[XNRS_TOPK_MAX_K], sorted[TK_CB];
+  int32_t excl[64];
+};
+// what a merge reads from global memory, fetched while the merge before it computes
+struct TkFetch {
+  uint64_t key[XNRS_TOPK_MAX_K / 32];  // list[hl + 32 t]
+  int32_t id0, id1;                    // excl_rows[lo + hl], [lo + hl + 32]; -1 past the end
+  int64_t lo, hi;
+  int uc;      // the half's user in the tile (an idle half addresses user 0 and writes nothing)
+  int active;  // (an int: no padding bytes to carry around)
+};
+__device__ __forceinline__ int32_t tk_excl_id(const TopkArgs& a, int64_t e, int64_t hi) { return e < hi ? a.excl_rows[e] : -1; }
+__device__ __forceinline__ TkFetch tk_fetch(const TopkArgs& a, int64_t u0, const uint64_t* lists, int k, int ul, int hl) {
+  TkFetch f;
+  const bool active = ul >= 0;  // (tk_pop_pair: a negative user is none)
+  f.active = active;
+  f.uc = active ? ul : 0;
+  const uint64_t* list = lists + (int64_t)f.uc * k;
+#pragma unroll
+  for (int t = 0; t < XNRS_TOPK_MAX_K / 32; ++t) f.key[t] = active && hl + 32 * t < k ? list[hl + 32 * t] : 0;
+  f.lo = f.hi = 0;
+  if (a.excl_off && active) {
+    f.lo = a.excl_off[u0 + f.uc];
+    f.hi = a.excl_off[u0 + f.uc + 1];
+  }
+  f.id0 = tk_excl_id(a, f.lo + hl, f.hi);
+  f.id1 = tk_excl_id(a, f.lo + hl + 32, f.hi);
+  return f;
+}
+__device__ __forceinline__ void tk_merge_pair(const TopkArgs& a, const TkFetch& f, uint64_t* lists, int k, TkHalf& w, uint64_t* bufs,
+                                              uint64_t* thr, int* cnt, int hl, int h) {
+  uint64_t* list = lists + (int64_t)f.uc * k;
+  uint64_t* buf = bufs + f.uc * TK_CB;
+  const int n = !f.active ? 0 : cnt[f.uc] < TK_CB ? cnt[f.uc] : TK_CB;
+#pragma unroll
+  for (int t = 0; t < XNRS_TOPK_MAX_K / 32; ++t)
+    if (hl + 32 * t < k) w.stage[hl + 32 * t] = f.key[t];
+  uint64_t cand = hl < n ? buf[hl] : 0;
+  if (a.excl_off) {
+    const int32_t row = (int32_t)~(uint32_t)cand;  // (-1 without a candidate)
+    int32_t id0 = f.id0, id1 = f.id1;
+    bool hit = false;
+    for (int64_t base = f.lo; __any(base < f.hi); base += 64) {
+      if (base != f.lo) {
+        id0 = tk_excl_id(a, base + hl, f.hi);
+        id1 = tk_excl_id(a, base + hl + 32, f.hi);
+      }
+      tk_lds_sync();
+      w.excl[hl] = id0;
+      w.excl[hl + 32] = id1;
+      tk_lds_sync();
+#pragma unroll
+      for (int e = 0; e < 64; ++e) hit |= w.excl[e] == row;
+    }
+    if (hit && row >= 0) cand = 0;
+  }
+  if (f.active) buf[hl] = cand;
+  tk_lds_sync();
+  int rank = 0;
+  if (cand) {
+#pragma unroll 8
+    for (int j = 0; j < TK_CB; ++j) rank += buf[j] > cand;
+    w.sorted[rank] = cand;
+  }
+  const int alive = __popc((uint32_t)(__ballot(cand != 0) >> (32 * h)));
+  tk_lds_sync();
+  uint64_t key[XNRS_TOPK_MAX_K / 32];
+  int place[XNRS_TOPK_MAX_K / 32];
+#pragma unroll
+  for (int t = 0; t < XNRS_TOPK_MAX_K / 32; ++t) {  // (four searches side by side)
+    const int i = hl + 32 * t;
+    key[t] = f.active && i < k ? w.stage[i] : 0;
+    place[t] = i + tk_count_greater<TK_CB>(w.sorted, alive, key[t]);
+  }
+  const int cand_place = rank + tk_count_greater<XNRS_TOPK_MAX_K>(w.stage, k, cand);
+#pragma unroll
+  for (int t = 0; t < XNRS_TOPK_MAX_K / 32; ++t)
+    if (key[t] && place[t] < k) {
+      if (place[t] != hl + 32 * t) list[place[t]] = key[t];
+      if (place[t] == k - 1) thr[f.uc] = key[t];
+    }
+  if (cand && cand_place < k) {
+    list[cand_place] = cand;
+    if (cand_place == k - 1) thr[f.uc] = cand;
+  }
+  if (f.active && hl == 0) cnt[f.uc] = 0;
+  // (stage / sorted / excl may be written again; the list's stores complete by the workgroup barrier that ends the phase,
+  // before any later merge of the same user fetches it)
+  tk_lds_sync();
+}
+
+// the two lowest set bits of `todo`, taken out of it: the lower for half 0, the other (or -1: none) for half 1
+__device__ __forceinline__ int tk_pop_pair(uint32_t& todo, int h) {
+  const int j0 = __ffs(todo) - 1;
+  todo &= todo - 1;
+  const int j1 = todo ? __ffs(todo) - 1 : -1;
+  todo &= todo - 1;  // (0 stays 0)
+  return h ? j1 : j0;
+}
+
+// the merges of one wave: its users (wave, wave + 4, ...) whose buffer is full -- at the end of the slice: not empty -- two at a
+// time, the next two users' lists on their way while these two merge
+__device__ __forceinline__ void tk_merge_phase(const TopkArgs& a, int64_t u0, uint64_t* lists, int k, int nu, bool final, TkHalf* w,
+                                               uint64_t* bufs, uint64_t* thr, int* cnt, int wave, int lane) {
+  const int hl = lane & 31, h = lane >> 5;
+  const int mine = wave + 4 * hl;
+  const int c = h == 0 && mine < nu ? cnt[mine] : 0;
+  uint32_t todo = (uint32_t)__ballot(final ? c > 0 : c >= TK_CB);
+  if (!todo) return;
+  TkFetch cur = tk_fetch(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), hl);
+  for (;;) {
+    const bool more = todo != 0;
+    TkFetch nxt = cur;
+    if (more) nxt = tk_fetch(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), hl);
+    tk_merge_pair(a, cur, lists, k, w[h], bufs, thr, cnt, hl, h);
+    if (!more) break;
+    cur = nxt;
+  }
+}
+
+// (two workgroups per CU for the MFMA form; the MLP form's 64 tanhf per feature want more than 256 registers)
+template <bool MLP>
+__global__ __launch_bounds__(256, MLP ? 1 : 2) void topk_partial_kernel(TopkArgs a) {
+  __shared__ float At[TK_KT * TK_PITCH], Bt[TK_KT * TK_PITCH];  // table rows / users of one stage, feature-major
+  __shared__ float w2s[TK_KT];
+  __shared__ uint64_t buf[TK_TILE * TK_CB], thr[TK_TILE];
+  __shared__ TkHalf halves[4][2];
+  __shared__ int cnt[TK_TILE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
+  const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;  // the wave's 64 x 64 part of the score tile
+  const int64_t u0 = (int64_t)blockIdx.x * TK_TILE;
+  const int nu = a.B - u0 < TK_TILE ? (int)(a.B - u0) : TK_TILE;
+  const int k = a.k;
+  uint64_t* lists = a.part + ((int64_t)blockIdx.y * a.B + u0) * k;
+  for (int i = tid; i < nu * k; i += 256) lists[i] = TK_FILLER;
+  for (int i = tid; i < TK_TILE; i += 256) {
+    thr[i] = TK_FILLER;
+    cnt[i] = 0;
+  }
+  __syncthreads();
+  const float bias = a.bias ? a.bias[0] : 0.f;
+  const int64_t chunks = (a.n_rows + TK_TILE - 1) / TK_TILE;
+  const int64_t c_lo = (int64_t)blockIdx.y * a.chunks_per_slice;
+  const int64_t c_hi = c_lo + a.chunks_per_slice < chunks ? c_lo + a.chunks_per_slice : chunks;
+  for (int64_t c = c_lo; c < c_hi; ++c) {
+    const int64_t r0 = c * TK_TILE;
+    f32x16 acc[2][2];  // [row block][user block]: element j of a lane is row 8 (j / 4) + 4 half + j % 4, user l32
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[i >> 1][i & 1][j] = 0.f;
+    TkTile ta, tb;
+    // the MFMA form loads the next stage while it computes this one; the MLP form is bound by its tanhf and keeps the registers
+    if (!MLP) {
+      tk_load(ta, a.table, a.n_rows, r0, a.W, 0, a.vec_t);
+      tk_load(tb, a.u, a.B, u0, a.W, 0, a.vec_u);
+    }
+    for (int k0 = 0; k0 < a.W; k0 += TK_KT) {
+      if (MLP) {
+        tk_load(ta, a.table, a.n_rows, r0, a.W, k0, a.vec_t);
+        tk_load(tb, a.u, a.B, u0, a.W, k0, a.vec_u);
+      }
+      __syncthreads();  // (the previous stage has been read)
+      tk_store(ta, At);
+      tk_store(tb, Bt);
+      if (MLP && tid < TK_KT) w2s[tid] = k0 + tid < a.W ? a.w2[k0 + tid] : 0.f;
+      __syncthreads();
+      if (!MLP && k0 + TK_KT < a.W) {
+        tk_load(ta, a.table, a.n_rows, r0, a.W, k0 + TK_KT, a.vec_t);
+        tk_load(tb, a.u, a.B, u0, a.W, k0 + TK_KT, a.vec_u);
+      }
+      const int kn = a.W - k0 < TK_KT ? a.W - k0 : TK_KT;
+      if (!MLP) {
+        for (int kk = 0; kk < kn; kk += 2) {  // (an odd width ends on a zero feature: the tile is zero-filled)
+          const float* ap = At + (kk + half) * TK_PITCH + rw + l32;
+          const float* bp = Bt + (kk + half) * TK_PITCH + uw + l32;
+          const float a0 = ap[0], a1 = ap[32], b0 = bp[0], b1 = bp[32];
+          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+      } else {
+        for (int kk = 0; kk < kn; ++kk) {
+          const float q0 = Bt[kk * TK_PITCH + uw + l32], q1 = Bt[kk * TK_PITCH + uw + 32 + l32], w = w2s[kk];
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+              const float p = At[kk * TK_PITCH + rw + rb * 32 + (j >> 2) * 8 + half * 4 + (j & 3)];
+              acc[rb][0][j] = fmaf(w, tanhf(q0 + p), acc[rb][0][j]);
+              acc[rb][1][j] = fmaf(w, tanhf(q1 + p), acc[rb][1][j]);
+            }
+        }
+      }
+    }
+    // ---- selection: append what beats the threshold, merge full buffers, go round again while a buffer overflowed
+    uint64_t pend = 0;  // bit ub * 32 + rb * 16 + j: a score at or above the threshold as the chunk begins
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub) {
+      const int ul = uw + ub * 32 + l32;
+      const float tS = ul < nu ? tk_score(thr[ul]) : __builtin_inff();
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const float s = acc[rb][ub][j] + bias;
+          acc[rb][ub][j] = s;
+          if (ul < nu && s >= tS) pend |= 1ull << (ub * 32 + rb * 16 + j);  // (false for a NaN)
+        }
+    }
+    for (;;) {
+      int overflow = 0;
+      for (uint64_t todo = pend; todo; todo &= todo - 1) {
+        const int b = __ffsll((unsigned long long)todo) - 1;
+        // element b of the lane's 64 scores
+        const float s = (b & 32) ? ((b & 16) ? tk_pick16(acc[1][1], b) : tk_pick16(acc[0][1], b))
+                                 : ((b & 16) ? tk_pick16(acc[1][0], b) : tk_pick16(acc[0][0], b));
+        const int ul = uw + (b >> 5) * 32 + l32;
+        const int64_t row = r0 + rw + ((b >> 4) & 1) * 32 + ((b & 15) >> 2) * 8 + half * 4 + (b & 3);
+        const uint64_t key = tk_key(s, (uint32_t)row);
+        bool keep = false;
+        if (row < a.n_rows && row != a.pad_row && key > thr[ul]) {
+          const int slot = atomicAdd(&cnt[ul], 1);
+          if (slot < TK_CB) buf[ul * TK_CB + slot] = key;
+          else keep = true;
+        }
+        if (keep) overflow = 1;
+        else pend &= ~(1ull << b);
+      }
+      const int again = __syncthreads_or(overflow);
+      tk_merge_phase(a, u0, lists, k, nu, false, halves[wave], buf, thr, cnt, wave, lane);
+      __syncthreads();
+      if (!again) break;
+    }
+  }
+  tk_merge_phase(a, u0, lists, k, nu, true, halves[wave], buf, thr, cnt, wave, lane);  // the slice is done: what is still buffered
+}
+
+// rows[b, :], scores[b, :] <- the k greatest keys of the `slices` sorted lists of user b; one wave per user
+__global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* part, int slices, int64_t B, int k, int32_t* rows,
+                                                         float* scores) {
+  __shared__ uint64_t lds[4][3][XNRS_TOPK_MAX_K];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+  if (b >= B) return;  // (no workgroup barrier below)
+  uint64_t *cur = lds[wave][0], *in = lds[wave][1], *nxt = lds[wave][2];
+  for (int i = lane; i < k; i += 64) cur[i] = part[b * k + i];
+  for (int s = 1; s < slices; ++s) {
+    const uint64_t* list = part + ((int64_t)s * B + b) * k;
+    for (int i = lane; i < k; i += 64) in[i] = list[i];
+    tk_wave_sync();
+    // two sorted lists: a key's place is its index plus the other list's count of greater keys.  Real keys are distinct;
+    // two fillers may land on one place, with the same value
+    for (int i = lane; i < k; i += 64) {
+      const int rc = i + tk_count_greater<XNRS_TOPK_MAX_K>(in, k, cur[i]);
+      if (rc < k) nxt[rc] = cur[i];
+      const int ri = i + tk_count_greater<XNRS_TOPK_MAX_K>(cur, k, in[i]);
+      if (ri < k) nxt[ri] = in[i];
+    }
+    tk_wave_sync();
+    uint64_t* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  tk_wave_sync();
+  for (int i = lane; i < k; i += 64) {
+    rows[b * k + i] = (int32_t)~(uint32_t)cur[i];
+    scores[b * k + i] = tk_score(cur[i]);
+  }
+}
+
+int64_t tk_chunks_per_slice(int64_t B, int64_t n_rows) {
+  const int64_t tiles = (B + TK_TILE - 1) / TK_TILE, chunks = (n_rows + TK_TILE - 1) / TK_TILE;
+  if (tiles <= 0 || chunks <= 0) return 1;
+  int64_t want = (TK_WGS + tiles - 1) / tiles;
+  if (want > TK_MAX_SLICES) want = TK_MAX_SLICES;
+  if (want > chunks) want = chunks;
+  return (chunks + want - 1) / want;
+}
+
+bool tk_vec_ok(const float* p, int W) { return W % 4 == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+struct TopkCall {
+  const float* table;  // (n_rows, W): the vectors of the inner-product forms, P of the MLP form
+  int64_t n_rows;
+  int32_t W;
+  int64_t B;
+  const int64_t* excl_off;
+  const int32_t* excl_rows;
+  int32_t pad_row, k;
+  int32_t *rows;
+  float* scores;
+  void* ws;
+  size_t ws_bytes;
+  int32_t proj_width;
+};
+
+// the argument checks every entry point shares; XNRS_OK with *run = false: nothing to do
+int32_t tk_check(const TopkCall& c, const float* u, bool* run) {
+  *run = false;
+  if (c.k < 1 || c.k > XNRS_TOPK_MAX_K || c.W <= 0 || c.B < 0 || c.n_rows < 0 || c.n_rows > 0x7fffffffLL) return XNRS_EINVAL;
+  if (c.B == 0) return XNRS_OK;
+  if (!c.rows || !c.scores || !u || (c.n_rows > 0 && !c.table) || (c.excl_off && !c.excl_rows)) return XNRS_EINVAL;
+  const size_t need = xnrs_topk_workspace_bytes(c.B, c.n_rows, c.proj_width, c.k);
+  if (!c.ws || c.ws_bytes < need) return XNRS_EWORKSPACE;
+  *run = true;
+  return XNRS_OK;
+}
+
+// the two launches; up:(B, W) the user side as the kernel reads it (u, v = u W[0], q = u W1u^T + b1)
+hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const float* bias, hipStream_t stream) {
+  const int64_t cps = tk_chunks_per_slice(c.B, c.n_rows);
+  const int32_t slices = xnrs_topk_slices(c.B, c.n_rows);
+  TopkArgs a{};
+  a.table = c.table;
+  a.u = up;
+  a.w2 = w2;
+  a.bias = bias;
+  a.excl_off = c.excl_off;
+  a.excl_rows = c.excl_rows;
+  a.n_rows = c.n_rows;
+  a.B = c.B;
+  a.chunks_per_slice = cps;
+  a.W = c.W;
+  a.k = c.k;
+  a.pad_row = c.pad_row;
+  a.vec_t = tk_vec_ok(c.table, c.W);
+  a.vec_u = tk_vec_ok(up, c.W);
+  a.part = at<uint64_t>(c.ws, align_up((size_t)c.B * c.proj_width * F32));
+  const int64_t tiles = (c.B + TK_TILE - 1) / TK_TILE;
+  if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)tiles, (unsigned)slices);
+  if (w2) hipLaunchKernelGGL(topk_partial_kernel<true>, grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(topk_partial_kernel<false>, grid, dim3(256), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, stream, a.part, slices, c.B, c.k, c.rows,
+                     c.scores);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+}  // namespace xnrs
+
+using namespace xnrs;
+
+extern "C" {
+
+int32_t xnrs_topk_slices(int64_t B, int64_t n_rows) {
+  const int64_t chunks = (n_rows + TK_TILE - 1) / TK_TILE;
+  if (B <= 0 || chunks <= 0) return 1;
+  const int64_t cps = tk_chunks_per_slice(B, n_rows);
+  return (int32_t)((chunks + cps - 1) / cps);
+}
+
+size_t xnrs_topk_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t k) {
+  if (B <= 0 || n_rows < 0 || proj_width < 0 || k < 1 || k > XNRS_TOPK_MAX_K) return 0;
+  // the projected user side [B, proj_width] | the partial lists [slices, B, k] of 64-bit keys
+  return carve_total({(size_t)B * proj_width * F32, (size_t)xnrs_topk_slices(B, n_rows) * B * k * sizeof(uint64_t)});
+}
+
+int32_t xnrs_topk(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* excl_off,
+                  const int32_t* excl_rows, int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes,
+                  void* stream) {
+  const TopkCall c{table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, 0};
+  bool run;
+  XNRS_TRY_RC(tk_check(c, u, &run));
+  if (run) XNRS_TRY(tk_launch(c, u, nullptr, nullptr, (hipStream_t)stream));
+  return XNRS_OK;
+}
+
+int32_t xnrs_topk_bilinear(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
+                           const float* bias, const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t k,
+                           int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const TopkCall c{table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, E};
+  bool run;
+  XNRS_TRY_RC(tk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w) return XNRS_EINVAL;
+  float* v = static_cast<float*>(ws);
+  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, B, E, E, stream));  // v_b = W[0]^T u_b, as xnrs_score_csr_bilinear
+  XNRS_TRY(tk_launch(c, v, nullptr, bias, stream));
+  return XNRS_OK;
+}
+
+int32_t xnrs_topk_mlp(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
+                      const float* b1, const float* w2, const float* b2, const int64_t* excl_off, const int32_t* excl_rows,
+                      int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (E <= 0) return XNRS_EINVAL;
+  const TopkCall c{P, n_rows, H, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, H};
+  bool run;
+  XNRS_TRY_RC(tk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w1 || !w2) return XNRS_EINVAL;
+  float* q = static_cast<float*>(ws);
+  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_score_csr_mlp
+  XNRS_TRY(tk_launch(c, q, w2, b2, stream));
+  return XNRS_OK;
+}
+
+}  // extern "C"

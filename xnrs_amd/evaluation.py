@@ -176,3 +176,67 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
     out = {k: float(v) for k, v in zip(METRIC_NAMES, mean.tolist())}
     hip.check_status(dev)  # (the read above was the epoch's sync point: what the sync-free encoders could not raise, raises here)
     return out
+
+
+def _history_csr(behaviors: Behaviors, sess: torch.Tensor, first):
+    """(excl_off:(B+1) int64 absolute into excl_rows, excl_rows int32): the FULL histories of the sessions.  A contiguous run
+    of sessions from session `first` on (an int) is a slice of hist_off over the whole hist_val (no copy); any other selection
+    (`first` None) gathers its lists."""
+    off, val = behaviors.hist_off, behaviors.hist_val
+    if first is not None:
+        return off[first:first + sess.numel() + 1], val
+    start, n = off[sess], off[sess + 1] - off[sess]
+    new_off = torch.zeros(sess.numel() + 1, dtype=torch.int64, device=off.device)
+    torch.cumsum(n, 0, out=new_off[1:])
+    idx = torch.arange(int(new_off[-1]), device=off.device) + torch.repeat_interleave(start - new_off[:-1], n)
+    return new_off, val[idx]
+
+
+@torch.no_grad()
+def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions=None, batch: int = 4096,
+              exclude_history: bool = True):
+    """For every session the k news of the WHOLE table its user scores highest -> (rows:(n,k) int32, scores:(n,k) fp32) on the
+    device, best first (include/xnrs_hip.h: xnrs_topk -- higher raw score first, equal scores lower row first, no ReLU; with
+    fewer than k eligible news the tail is row -1 / score -inf).
+
+    Once per call the news table is encoded (encode_news_table) and handed to the scorer (prepare_csr); per batch of sessions
+    the user tower runs over the last `l_hist` clicks as DeviceBatcher builds them (encode_user, as evaluate) and the scorer's
+    topk(table, u, k, ...) ranks the table without a (sessions, n_rows) score matrix.  store.pad_row is never recommended;
+    with `exclude_history` neither is any news of the session's FULL history (hist_off / hist_val, not only the last l_hist).
+    `sessions`: session indices (None = all); row i of the result is session sessions[i].
+
+    One process, one device: rank-sharded recommendation is out of scope.  A scorer without topk / prepare_csr, a model
+    whose news vectors depend on the user (NPA) and CAUM (no candidate-independent user vector) raise NotImplementedError."""
+    scorer = getattr(model, "rec_model", None)
+    prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, "topk", None)
+    if prepare is None or topk is None:
+        raise NotImplementedError(f"recommend(): the scorer {type(scorer).__name__} has no top-k path over a news table "
+                                  "(prepare_csr / topk); ranking it with a plain dot product would recommend another model's news")
+    if getattr(model, "user_dependent_news", False):
+        raise NotImplementedError(f"recommend(): the news vectors of {type(model).__name__} depend on the user, so no table of "
+                                  "news vectors exists to rank")
+    vecs, hm = encode_news_table(model, store)
+    table = prepare(vecs)
+    batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
+    dev = vecs.device
+    uidx = None
+    if getattr(model, "uses_user_index", False):
+        uidx = getattr(behaviors, "user_index", None)
+        if uidx is None:
+            raise ValueError(f"recommend(): {type(model).__name__} needs the user index of every session (sessions without "
+                             "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+        uidx = uidx.to(dev)
+    every = sessions is None
+    sessions = torch.arange(len(behaviors), device=dev) if every else torch.as_tensor(sessions, dtype=torch.int64, device=dev)
+    rows = torch.empty((sessions.numel(), k), dtype=torch.int32, device=dev)
+    scores = torch.empty((sessions.numel(), k), dtype=torch.float32, device=dev)
+    for lo in range(0, sessions.numel(), batch):
+        sess = sessions[lo:lo + batch]
+        hist = batcher.eval_batch(sess)[0]
+        h = vecs[hist.long()]
+        m = hm[hist.long()]
+        u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
+        excl = _history_csr(behaviors, sess, lo if every else None) if exclude_history else (None, None)
+        rows[lo:lo + batch], scores[lo:lo + batch] = topk(table, u, k, excl[0], excl[1], store.pad_row)
+    hip.check_status(dev)
+    return rows, scores

@@ -205,7 +205,9 @@ class UserEncoder(_Tower):
 
 # Scorers.  Besides forward, each one answers the evaluation epoch's two questions (xnrs_amd.evaluation.evaluate): what to do
 # ONCE per epoch with the table of pre-encoded news vectors (prepare_csr), and how to score impressions given as CSR
-# candidate lists against that table (score_csr(table, rows, sess, u, relu)).
+# candidate lists against that table (score_csr(table, rows, sess, u, relu)) -- and recommendation's one
+# (xnrs_amd.evaluation.recommend): which k rows of that table each user gets (topk(table, u, k, excl_off, excl_rows, pad_row),
+# ranked by the raw score, no ReLU).
 class DotScoring(nn.Module):
     """Reference: xnrs/models/components/scoring.py:6-23.  u:(B,1,D), c:(B,N,D) -> (B,N,1)."""
 
@@ -222,6 +224,9 @@ class DotScoring(nn.Module):
     def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
         from ..evaluation import score_csr
         return score_csr(table, rows, sess, ops.l2_normalize_rows(u) if self.normalize else u, relu=relu)
+
+    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+        return ops.topk_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, k, excl_off, excl_rows, pad_row)
 
 
 class BilinScoring(nn.Module):
@@ -243,6 +248,10 @@ class BilinScoring(nn.Module):
     def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
         u = ops.l2_normalize_rows(u) if self.normalize else u
         return ops.score_csr_bilinear(table, rows, sess, u, self.bilin.weight, self.bilin.bias, relu=relu)
+
+    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+        u = ops.l2_normalize_rows(u) if self.normalize else u
+        return ops.topk_bilinear(table, u, self.bilin.weight, self.bilin.bias, k, excl_off, excl_rows, pad_row)
 
 
 def _is_tanh(activation) -> bool:
@@ -273,6 +282,10 @@ class FCScoring(nn.Module):
 
     def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
         return ops.score_csr_mlp(table, rows, sess, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, relu=relu)
+
+    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+        return ops.topk_mlp(table, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, k, excl_off, excl_rows,
+                            pad_row)
 
 
 # ------------------------------------------------------------------------------------------- bi-encoder shell

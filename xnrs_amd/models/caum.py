@@ -78,6 +78,7 @@ class CAUMScoring(DotScoring):
     # batch), so evaluation.evaluate() raises NotImplementedError for this scorer before it encodes anything
     prepare_csr = None
     score_csr = None
+    topk = None
 
 
 class CAUMNewsEncoder(nn.Module):

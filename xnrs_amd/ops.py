@@ -531,6 +531,62 @@ def score_csr_mlp(P, cand_rows, cand_sess, u, w1, b1, w2, b2, relu: bool = True)
     return r
 
 
+def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, k: int, excl_off, excl_rows, pad_row: int):
+    """The call every top-k entry point shares behind its own leading arguments `head` -> (rows:(B,k) int32, scores:(B,k))."""
+    dev = table.device
+    if (excl_off is None) != (excl_rows is None):
+        raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
+    if excl_off is not None:
+        if excl_off.dtype != torch.int64 or excl_rows.dtype != torch.int32 or excl_off.numel() != B + 1:
+            raise RuntimeError(f"exclusions: excl_off (B+1,) int64 and excl_rows int32, got {tuple(excl_off.shape)} {excl_off.dtype} "
+                               f"and {excl_rows.dtype} for {B} users")
+        if excl_off.device != dev or excl_rows.device != dev or not (excl_off.is_contiguous() and excl_rows.is_contiguous()):
+            raise hip.XnrsHipError(f"exclusions must be contiguous tensors on {dev}")
+    k = int(k)
+    rows = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    l = hip.lib()
+    nbytes = l.xnrs_topk_workspace_bytes(B, table.shape[0], proj_width, k)
+    ws = hip.workspace(dev, nbytes)
+    hip.check(getattr(l, entry)(*head, hip.ptr(excl_off), hip.ptr(excl_rows), int(pad_row), k,
+                                hip.ptr(rows), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
+    return rows, scores
+
+
+def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """Per user the k rows of `table` with the highest u . table[row] (include/xnrs_hip.h: xnrs_topk) -> (rows, scores)."""
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    B = u.shape[0]
+    return _topk("xnrs_topk", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, k, excl_off, excl_rows, pad_row)
+
+
+def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """As topk_dot with the score u W[0] table[row] + bias (xnrs_topk_bilinear)."""
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    w = hip.dev_f32(w, "bilinear weight")
+    b = None if b is None else hip.dev_f32(b, "bilinear bias")
+    B = u.shape[0]
+    return _topk("xnrs_topk_bilinear", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E, k,
+                 excl_off, excl_rows, pad_row)
+
+
+def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """As topk_dot with the score w2 . tanh(W1u u + b1 + P[row]) + b2, P = mlp_news_proj(table) (xnrs_topk_mlp)."""
+    P = hip.dev_f32(P, "projected news table")
+    E = w1.shape[1] // 2
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    w1, b1, w2, b2, H = _mlp_weights(E, w1, b1, w2, b2)
+    if P.dim() != 2 or P.shape[1] != H:
+        raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
+    B = u.shape[0]
+    return _topk("xnrs_topk_mlp", P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2),
+                                      hip.ptr(b2)), B, H, k, excl_off, excl_rows, pad_row)
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
