@@ -659,6 +659,42 @@ int32_t xnrs_topk_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, cons
                       const float *b1, const float *w2, const float *b2, const int64_t *excl_off, const int32_t *excl_rows,
                       int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- where given rows rank within the whole table per user (full-corpus evaluation; csrc/topk.hip) ------------------------
+ * The sweep of xnrs_topk* that counts instead of selects, again without a (B, n_rows) score matrix.  table / P, u, the
+ * weights, the exclusion CSR and pad_row mean what they mean for xnrs_topk*: the same tensors serve both calls.
+ * Queries: tgt_off:(B+1) int64 and tgt_rows: int32 form a CSR of target rows over the users, the offsets ABSOLUTE into
+ * tgt_rows like excl_off.  ranks: int32 and scores: fp32 are indexed like tgt_rows; a call writes positions
+ * [tgt_off[0], tgt_off[B]) and nothing else.  A user may have zero, one or any number of targets; duplicate targets are
+ * separate queries with the same answer.  For query e = (user b, row t):
+ *   scores[e] = the raw score of (b, t): the very bits xnrs_topk* forms for that pair (one score-tile function, the same
+ *               instruction, for the targets and for the sweep)
+ *   ranks[e]  = the number of eligible rows n != t that come before (b, t) in the order of xnrs_topk: a higher score, or an
+ *               equal score (==, so -0 ties +0) in a lower row.  A NaN-scored row is never counted; -inf is a legal score.
+ * Eligible rows are those of xnrs_topk: [0, n_rows) minus pad_row minus the user's exclusion list (unsorted, duplicates,
+ * foreign ids, any length; compared, never dereferenced; a duplicate is not counted twice).  THE TARGET ITSELF IS RANKED
+ * EVEN WHEN IT IS ON ITS OWN USER'S EXCLUSION LIST: the list removes competitors, not the query.  So for an eligible target
+ * ranks[e] < k exactly when xnrs_topk* with the same arguments returns t, and it returns t at position ranks[e] with
+ * scores[e].  Rank -1 and score NaN: t outside [0, n_rows) (never dereferenced), t == pad_row, a NaN score.
+ * A query's result does not depend on B, on the user's position in the batch or on the slicing, and is the same on every
+ * run (integer counts; no float atomics).  No host synchronisation: the target counts are read on the device only.
+ * Limits as xnrs_topk: n_rows <= 2^31 - 1, any E, H >= 1, any B >= 0.  B == 0 or an empty target span: XNRS_OK, nothing
+ * written; n_rows == 0: every query -1 / NaN.  Argument errors (XNRS_EINVAL) and a short workspace (XNRS_EWORKSPACE) are
+ * found on the host before any launch and write nothing.  ws: xnrs_rank_workspace_bytes(B, proj_width) -- the projected
+ * user side only -- proj_width = 0 (xnrs_rank: no workspace, ws may be NULL), E (bilinear), H (MLP); a pure host call.  The
+ * grid of the sweep is user tiles x xnrs_topk_slices(B, n_rows). */
+size_t xnrs_rank_workspace_bytes(int64_t B, int32_t proj_width);
+int32_t xnrs_rank(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const int64_t *tgt_off,
+                  const int32_t *tgt_rows, const int64_t *excl_off, const int32_t *excl_rows, int32_t pad_row,
+                  int32_t *ranks, float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_rank_bilinear(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const float *w,
+                           const float *bias, const int64_t *tgt_off, const int32_t *tgt_rows, const int64_t *excl_off,
+                           const int32_t *excl_rows, int32_t pad_row, int32_t *ranks, float *scores, void *ws,
+                           size_t ws_bytes, void *stream);
+int32_t xnrs_rank_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, const float *u, int64_t B, const float *w1,
+                      const float *b1, const float *w2, const float *b2, const int64_t *tgt_off, const int32_t *tgt_rows,
+                      const int64_t *excl_off, const int32_t *excl_rows, int32_t pad_row, int32_t *ranks, float *scores,
+                      void *ws, size_t ws_bytes, void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

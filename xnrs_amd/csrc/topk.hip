@@ -79,17 +79,20 @@ __device__ __forceinline__ int tk_count_greater(const uint64_t* a, int n, uint64
 
 // rows [r0, r0 + 128) x features [k0, k0 + 32) of a row-major [n][W] matrix, four float4 per thread: eight consecutive
 // threads read 128 contiguous bytes of one row.  Rows past n and features past W read as 0.
+// With GATHER the 128 rows are gather[0, 128) (LDS; a negative id reads as 0) instead of r0 + [0, 128).
 struct TkTile {
   float4 v[4];
 };
-__device__ __forceinline__ void tk_load(TkTile& t, const float* x, int64_t n, int64_t r0, int W, int k0, int vec) {
+template <bool GATHER = false>
+__device__ __forceinline__ void tk_load(TkTile& t, const float* x, int64_t n, int64_t r0, int W, int k0, int vec,
+                                        const int32_t* gather = nullptr) {
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     const int idx = threadIdx.x + 256 * p;
-    const int64_t r = r0 + (idx >> 3);
+    const int64_t r = GATHER ? (int64_t)gather[idx >> 3] : r0 + (idx >> 3);
     const int k = k0 + (idx & 7) * 4;
     float4 v = {0.f, 0.f, 0.f, 0.f};
-    if (r < n && k < W) {
+    if ((!GATHER || r >= 0) && r < n && k < W) {
       const float* s = x + r * W + k;
       if (vec) v = *reinterpret_cast<const float4*>(s);  // (W % 4 == 0 and a 16-B base: the four are inside the row)
       else {
@@ -124,14 +127,79 @@ __device__ __forceinline__ float tk_pick16(const f32x16 x, int b) {
   return b3 ? d1 : d0;
 }
 
-struct TopkArgs {
+// what a score tile reads, and what every kernel over score tiles is told about the call
+struct TkOperands {
   const float *table, *u, *w2, *bias;  // table:(n_rows, W), u:(B, W); w2:(W) in the MLP form
   const int64_t* excl_off;
   const int32_t* excl_rows;
   int64_t n_rows, B, chunks_per_slice;
-  int W, k, pad_row, vec_t, vec_u;
+  int W, pad_row, vec_t, vec_u;
+};
+struct TopkArgs : TkOperands {
+  int k;
   uint64_t* part;
 };
+
+// The score tile, the ONE definition of every kernel that ranks: acc <- the scores, before the bias, of table rows
+// r0 + [0, 128) (GATHER: rows gather[0, 128)) x users u0 + [0, 128).  acc[row block][user block]: element j of a lane is row
+// 8 (j / 4) + 4 half + j % 4 of the wave's row block, user l32 of its user block.  A (row, user) score depends on nothing but
+// that pair: not on the other rows and users of the tile, nor on where in the tile the pair sits.  All 256 threads call it;
+// it begins and ends between workgroup barriers of its own, and on return At / Bt / w2s may still be read by other waves.
+template <bool MLP, bool GATHER>
+__device__ __forceinline__ void tk_score_tile(const TkOperands& a, int64_t r0, const int32_t* gather, int64_t u0, float* At, float* Bt,
+                                              float* w2s, f32x16 (&acc)[2][2]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
+  const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;  // the wave's 64 x 64 part of the score tile
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[i >> 1][i & 1][j] = 0.f;
+  TkTile ta, tb;
+  // the MFMA form loads the next stage while it computes this one; the MLP form is bound by its tanhf and keeps the registers
+  if (!MLP) {
+    tk_load<GATHER>(ta, a.table, a.n_rows, r0, a.W, 0, a.vec_t, gather);
+    tk_load(tb, a.u, a.B, u0, a.W, 0, a.vec_u);
+  }
+  for (int k0 = 0; k0 < a.W; k0 += TK_KT) {
+    if (MLP) {
+      tk_load<GATHER>(ta, a.table, a.n_rows, r0, a.W, k0, a.vec_t, gather);
+      tk_load(tb, a.u, a.B, u0, a.W, k0, a.vec_u);
+    }
+    __syncthreads();  // (the previous stage has been read)
+    tk_store(ta, At);
+    tk_store(tb, Bt);
+    if (MLP && tid < TK_KT) w2s[tid] = k0 + tid < a.W ? a.w2[k0 + tid] : 0.f;
+    __syncthreads();
+    if (!MLP && k0 + TK_KT < a.W) {
+      tk_load<GATHER>(ta, a.table, a.n_rows, r0, a.W, k0 + TK_KT, a.vec_t, gather);
+      tk_load(tb, a.u, a.B, u0, a.W, k0 + TK_KT, a.vec_u);
+    }
+    const int kn = a.W - k0 < TK_KT ? a.W - k0 : TK_KT;
+    if (!MLP) {
+      for (int kk = 0; kk < kn; kk += 2) {  // (an odd width ends on a zero feature: the tile is zero-filled)
+        const float* ap = At + (kk + half) * TK_PITCH + rw + l32;
+        const float* bp = Bt + (kk + half) * TK_PITCH + uw + l32;
+        const float a0 = ap[0], a1 = ap[32], b0 = bp[0], b1 = bp[32];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+      }
+    } else {
+      for (int kk = 0; kk < kn; ++kk) {
+        const float q0 = Bt[kk * TK_PITCH + uw + l32], q1 = Bt[kk * TK_PITCH + uw + 32 + l32], w = w2s[kk];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const float p = At[kk * TK_PITCH + rw + rb * 32 + (j >> 2) * 8 + half * 4 + (j & 3)];
+            acc[rb][0][j] = fmaf(w, tanhf(q0 + p), acc[rb][0][j]);
+            acc[rb][1][j] = fmaf(w, tanhf(q1 + p), acc[rb][1][j]);
+          }
+      }
+    }
+  }
+}
 
 // One wave merges the candidate buffers of up to two users at once, one user per half-wave (32 lanes = TK_CB candidates, one
 // per lane): list[0, k) (sorted, in the workspace) <- the k greatest of list and the candidates buf[0, n) (unsorted, distinct
@@ -286,56 +354,8 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void topk_partial_kernel(TopkArgs
   const int64_t c_hi = c_lo + a.chunks_per_slice < chunks ? c_lo + a.chunks_per_slice : chunks;
   for (int64_t c = c_lo; c < c_hi; ++c) {
     const int64_t r0 = c * TK_TILE;
-    f32x16 acc[2][2];  // [row block][user block]: element j of a lane is row 8 (j / 4) + 4 half + j % 4, user l32
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[i >> 1][i & 1][j] = 0.f;
-    TkTile ta, tb;
-    // the MFMA form loads the next stage while it computes this one; the MLP form is bound by its tanhf and keeps the registers
-    if (!MLP) {
-      tk_load(ta, a.table, a.n_rows, r0, a.W, 0, a.vec_t);
-      tk_load(tb, a.u, a.B, u0, a.W, 0, a.vec_u);
-    }
-    for (int k0 = 0; k0 < a.W; k0 += TK_KT) {
-      if (MLP) {
-        tk_load(ta, a.table, a.n_rows, r0, a.W, k0, a.vec_t);
-        tk_load(tb, a.u, a.B, u0, a.W, k0, a.vec_u);
-      }
-      __syncthreads();  // (the previous stage has been read)
-      tk_store(ta, At);
-      tk_store(tb, Bt);
-      if (MLP && tid < TK_KT) w2s[tid] = k0 + tid < a.W ? a.w2[k0 + tid] : 0.f;
-      __syncthreads();
-      if (!MLP && k0 + TK_KT < a.W) {
-        tk_load(ta, a.table, a.n_rows, r0, a.W, k0 + TK_KT, a.vec_t);
-        tk_load(tb, a.u, a.B, u0, a.W, k0 + TK_KT, a.vec_u);
-      }
-      const int kn = a.W - k0 < TK_KT ? a.W - k0 : TK_KT;
-      if (!MLP) {
-        for (int kk = 0; kk < kn; kk += 2) {  // (an odd width ends on a zero feature: the tile is zero-filled)
-          const float* ap = At + (kk + half) * TK_PITCH + rw + l32;
-          const float* bp = Bt + (kk + half) * TK_PITCH + uw + l32;
-          const float a0 = ap[0], a1 = ap[32], b0 = bp[0], b1 = bp[32];
-          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-      } else {
-        for (int kk = 0; kk < kn; ++kk) {
-          const float q0 = Bt[kk * TK_PITCH + uw + l32], q1 = Bt[kk * TK_PITCH + uw + 32 + l32], w = w2s[kk];
-#pragma unroll
-          for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-              const float p = At[kk * TK_PITCH + rw + rb * 32 + (j >> 2) * 8 + half * 4 + (j & 3)];
-              acc[rb][0][j] = fmaf(w, tanhf(q0 + p), acc[rb][0][j]);
-              acc[rb][1][j] = fmaf(w, tanhf(q1 + p), acc[rb][1][j]);
-            }
-        }
-      }
-    }
+    f32x16 acc[2][2];
+    tk_score_tile<MLP, false>(a, r0, nullptr, u0, At, Bt, w2s, acc);
     // ---- selection: append what beats the threshold, merge full buffers, go round again while a buffer overflowed
     uint64_t pend = 0;  // bit ub * 32 + rb * 16 + j: a score at or above the threshold as the chunk begins
 #pragma unroll
@@ -412,6 +432,168 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* part, i
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- rank
+// Where a user's target rows rank within the whole table: the sweep of topk_partial_kernel that COUNTS instead of selects.
+//
+//   target : grid = user tiles.  Round j gathers target j of each of the tile's users into one 128-row tile, forms that tile's
+//            scores with tk_score_tile -- the function and the instruction of the sweep -- and keeps the diagonal: the score of
+//            (user i, its own target).  It writes scores[] and starts ranks[] at 0, or at -1 for a query without an answer.
+//            The round count (the most targets of a user of the tile) is found in the kernel.
+//   sweep  : the grid, the slices and the score tiles of topk_partial_kernel.  Ineligible scores of a tile become NaN in the
+//            registers (a NaN is greater than nothing and equal to nothing); then every lane counts, for each target of its
+//            users, those of its 32 rows that come before the target in the order of tk_key -- s > s_t, or s == s_t in a
+//            lower row.  The target's own row holds the very bits of s_t, so it never counts itself.  Counts are integers:
+//            the first RK_SLOTS targets of a user add up in LDS across the chunks of the slice and reach ranks[] in one
+//            global integer atomic per slice, the others take one per chunk.
+//   Exclusions: a bitmap of the chunk, users x rows, in LDS, filled by walking each user's list (half a wave per user); ids
+//            are compared, duplicates set a set bit again.
+constexpr int RK_SLOTS = 4;
+
+struct RankArgs : TkOperands {
+  const int64_t* tgt_off;
+  const int32_t* tgt_rows;
+  int32_t* ranks;
+  float* scores;
+};
+
+template <bool MLP>
+__global__ __launch_bounds__(256, MLP ? 1 : 2) void rank_target_kernel(RankArgs a) {
+  __shared__ float At[TK_KT * TK_PITCH], Bt[TK_KT * TK_PITCH];
+  __shared__ float w2s[TK_KT];
+  __shared__ int64_t t_lo[TK_TILE], t_n[TK_TILE];
+  __shared__ int32_t gather[TK_TILE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
+  const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;
+  const int64_t u0 = (int64_t)blockIdx.x * TK_TILE;
+  const int nu = a.B - u0 < TK_TILE ? (int)(a.B - u0) : TK_TILE;
+  if (tid < TK_TILE) {
+    const int64_t lo = tid < nu ? a.tgt_off[u0 + tid] : 0, hi = tid < nu ? a.tgt_off[u0 + tid + 1] : 0;
+    t_lo[tid] = lo;
+    t_n[tid] = hi > lo ? hi - lo : 0;
+  }
+  __syncthreads();
+  int64_t rounds = 0;
+#pragma unroll 8
+  for (int i = 0; i < TK_TILE; ++i) rounds = t_n[i] > rounds ? t_n[i] : rounds;  // (uniform: every thread reads the same LDS)
+  const float bias = a.bias ? a.bias[0] : 0.f;
+  const float nan = __builtin_nanf("");
+  for (int64_t j = 0; j < rounds; ++j) {
+    if (tid < TK_TILE) {
+      int32_t g = -1;  // no target in this round, or one that is never dereferenced: outside the table, the pad row
+      if (j < t_n[tid]) {
+        const int32_t t = a.tgt_rows[t_lo[tid] + j];
+        if (t >= 0 && t < a.n_rows && t != a.pad_row) g = t;
+      }
+      gather[tid] = g;
+    }
+    __syncthreads();
+    f32x16 acc[2][2];
+    tk_score_tile<MLP, true>(a, 0, gather, u0, At, Bt, w2s, acc);
+    // the diagonal: row i of the tile is the target of user i.  It lies in the waves whose row half is their user half, in
+    // block [b][b], in the lanes whose half holds row l32 of the block: 8 (j / 4) + 4 half + j % 4 == l32
+    if (rw == uw && ((l32 >> 2) & 1) == half) {
+      const int el = (l32 >> 3) * 4 + (l32 & 3);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int ul = uw + b * 32 + l32;
+        const float s = tk_pick16(acc[b][b], el) + bias;
+        if (j < t_n[ul]) {
+          const bool ok = gather[ul] >= 0 && s == s;
+          a.scores[t_lo[ul] + j] = ok ? s : nan;
+          a.ranks[t_lo[ul] + j] = ok ? 0 : -1;
+        }
+      }
+    }
+    __syncthreads();  // (gather is written again)
+  }
+}
+
+template <bool MLP>
+__global__ __launch_bounds__(256, MLP ? 1 : 2) void rank_sweep_kernel(RankArgs a) {
+  __shared__ float At[TK_KT * TK_PITCH], Bt[TK_KT * TK_PITCH];
+  __shared__ float w2s[TK_KT];
+  __shared__ uint32_t excl[4 * TK_TILE];      // bit r % 32 of excl[(r / 32) * 128 + user]: row r of the chunk is excluded
+  __shared__ int32_t slot[RK_SLOTS * TK_TILE];  // slot[i * 128 + user]: the slice's count for target i of the user
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
+  const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;
+  const int64_t u0 = (int64_t)blockIdx.x * TK_TILE;
+  const int nu = a.B - u0 < TK_TILE ? (int)(a.B - u0) : TK_TILE;
+  for (int i = tid; i < RK_SLOTS * TK_TILE; i += 256) slot[i] = 0;
+  int64_t e_lo[2], e_hi[2];  // the targets of the lane's two users
+#pragma unroll
+  for (int ub = 0; ub < 2; ++ub) {
+    const int ul = uw + ub * 32 + l32;
+    e_lo[ub] = ul < nu ? a.tgt_off[u0 + ul] : 0;
+    e_hi[ub] = ul < nu ? a.tgt_off[u0 + ul + 1] : 0;
+  }
+  const float bias = a.bias ? a.bias[0] : 0.f;
+  const float nan = __builtin_nanf("");
+  const int64_t chunks = (a.n_rows + TK_TILE - 1) / TK_TILE;
+  const int64_t c_lo = (int64_t)blockIdx.y * a.chunks_per_slice;
+  const int64_t c_hi = c_lo + a.chunks_per_slice < chunks ? c_lo + a.chunks_per_slice : chunks;
+  for (int64_t c = c_lo; c < c_hi; ++c) {
+    const int64_t r0 = c * TK_TILE;
+    if (a.excl_off) {
+      __syncthreads();  // (the bitmap of the chunk before has been read)
+      for (int i = tid; i < 4 * TK_TILE; i += 256) excl[i] = 0;
+      __syncthreads();
+      for (int ul = tid >> 5; ul < nu; ul += 8) {
+        const int64_t hi = a.excl_off[u0 + ul + 1];
+        for (int64_t e = a.excl_off[u0 + ul] + l32; e < hi; e += 32) {
+          const int64_t d = (int64_t)a.excl_rows[e] - r0;
+          if (d >= 0 && d < TK_TILE) atomicOr(&excl[(int)(d >> 5) * TK_TILE + ul], 1u << (d & 31));
+        }
+      }
+      // (the barriers of the score tile stand between these writes and the reads below)
+    }
+    f32x16 acc[2][2];
+    tk_score_tile<MLP, false>(a, r0, nullptr, u0, At, Bt, w2s, acc);
+    // ---- what may be counted: the bias added as the selection adds it, everything else NaN
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub) {
+      const int ul = uw + ub * 32 + l32;
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) {
+        const uint32_t word = a.excl_off ? excl[((rw >> 5) + rb) * TK_TILE + ul] : 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int bit = (j >> 2) * 8 + half * 4 + (j & 3);
+          const int64_t row = r0 + rw + rb * 32 + bit;
+          const bool ok = row < a.n_rows && row != a.pad_row && !((word >> bit) & 1u);
+          acc[rb][ub][j] = ok ? acc[rb][ub][j] + bias : nan;
+        }
+      }
+    }
+    // ---- count
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub) {
+      const int ul = uw + ub * 32 + l32;
+      for (int64_t e = e_lo[ub]; e < e_hi[ub]; ++e) {
+        const float st = a.scores[e];
+        if (!(st == st)) continue;  // rank -1: no answer
+        // the lane's row of element (rb, j) is below the target's row when 32 rb + 8 (j / 4) + j % 4 < d
+        int64_t d64 = (int64_t)a.tgt_rows[e] - (r0 + rw + half * 4);
+        const int d = d64 < 0 ? 0 : d64 > 64 ? 64 : (int)d64;
+        int n = 0;
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const float s = acc[rb][ub][j];
+            n += (s > st) || (s == st && rb * 32 + (j >> 2) * 8 + (j & 3) < d);
+          }
+        if (n) {
+          if (e - e_lo[ub] < RK_SLOTS) atomicAdd(&slot[(int)(e - e_lo[ub]) * TK_TILE + ul], n);
+          else atomicAdd(&a.ranks[e], n);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < RK_SLOTS * TK_TILE; i += 256)
+    if (slot[i]) atomicAdd(&a.ranks[a.tgt_off[u0 + (i & (TK_TILE - 1))] + (i >> 7)], slot[i]);  // (counted: the user and the target exist)
+}
+
 int64_t tk_chunks_per_slice(int64_t B, int64_t n_rows) {
   const int64_t tiles = (B + TK_TILE - 1) / TK_TILE, chunks = (n_rows + TK_TILE - 1) / TK_TILE;
   if (tiles <= 0 || chunks <= 0) return 1;
@@ -482,6 +664,65 @@ hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const 
   return hipGetLastError();
 }
 
+struct RankCall {
+  const float* table;
+  int64_t n_rows;
+  int32_t W;
+  int64_t B;
+  const int64_t *tgt_off, *excl_off;
+  const int32_t *tgt_rows, *excl_rows;
+  int32_t pad_row;
+  int32_t* ranks;
+  float* scores;
+  void* ws;
+  size_t ws_bytes;
+  int32_t proj_width;
+};
+
+int32_t rk_check(const RankCall& c, const float* u, bool* run) {
+  *run = false;
+  if (c.W <= 0 || c.B < 0 || c.n_rows < 0 || c.n_rows > 0x7fffffffLL) return XNRS_EINVAL;
+  if (c.B == 0) return XNRS_OK;
+  if (!c.ranks || !c.scores || !c.tgt_off || !c.tgt_rows || !u || (c.n_rows > 0 && !c.table) || (c.excl_off && !c.excl_rows))
+    return XNRS_EINVAL;
+  const size_t need = xnrs_rank_workspace_bytes(c.B, c.proj_width);
+  if (need && (!c.ws || c.ws_bytes < need)) return XNRS_EWORKSPACE;
+  *run = true;
+  return XNRS_OK;
+}
+
+// the two launches; up, w2, bias as tk_launch
+hipError_t rk_launch(const RankCall& c, const float* up, const float* w2, const float* bias, hipStream_t stream) {
+  RankArgs a{};
+  a.table = c.table;
+  a.u = up;
+  a.w2 = w2;
+  a.bias = bias;
+  a.excl_off = c.excl_off;
+  a.excl_rows = c.excl_rows;
+  a.n_rows = c.n_rows;
+  a.B = c.B;
+  a.chunks_per_slice = tk_chunks_per_slice(c.B, c.n_rows);
+  a.W = c.W;
+  a.pad_row = c.pad_row;
+  a.vec_t = tk_vec_ok(c.table, c.W);
+  a.vec_u = tk_vec_ok(up, c.W);
+  a.tgt_off = c.tgt_off;
+  a.tgt_rows = c.tgt_rows;
+  a.ranks = c.ranks;
+  a.scores = c.scores;
+  const int64_t tiles = (c.B + TK_TILE - 1) / TK_TILE;
+  if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (w2) hipLaunchKernelGGL(rank_target_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(rank_target_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || c.n_rows == 0) return e;  // (an empty table: every query has its -1 / NaN)
+  const dim3 grid((unsigned)tiles, (unsigned)xnrs_topk_slices(c.B, c.n_rows));
+  if (w2) hipLaunchKernelGGL(rank_sweep_kernel<true>, grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(rank_sweep_kernel<false>, grid, dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 }  // namespace xnrs
@@ -541,6 +782,54 @@ int32_t xnrs_topk_mlp(const float* P, int64_t n_rows, int32_t E, int32_t H, cons
   float* q = static_cast<float*>(ws);
   XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_score_csr_mlp
   XNRS_TRY(tk_launch(c, q, w2, b2, stream));
+  return XNRS_OK;
+}
+
+size_t xnrs_rank_workspace_bytes(int64_t B, int32_t proj_width) {
+  if (B <= 0 || proj_width <= 0) return 0;
+  return carve_total({(size_t)B * proj_width * F32});  // the projected user side [B, proj_width]
+}
+
+int32_t xnrs_rank(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* tgt_off,
+                  const int32_t* tgt_rows, const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t* ranks,
+                  float* scores, void* ws, size_t ws_bytes, void* stream) {
+  const RankCall c{table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, 0};
+  bool run;
+  XNRS_TRY_RC(rk_check(c, u, &run));
+  if (run) XNRS_TRY(rk_launch(c, u, nullptr, nullptr, (hipStream_t)stream));
+  return XNRS_OK;
+}
+
+int32_t xnrs_rank_bilinear(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
+                           const float* bias, const int64_t* tgt_off, const int32_t* tgt_rows, const int64_t* excl_off,
+                           const int32_t* excl_rows, int32_t pad_row, int32_t* ranks, float* scores, void* ws, size_t ws_bytes,
+                           void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const RankCall c{table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, E};
+  bool run;
+  XNRS_TRY_RC(rk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w) return XNRS_EINVAL;
+  float* v = static_cast<float*>(ws);
+  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, B, E, E, stream));  // v_b = W[0]^T u_b, as xnrs_topk_bilinear
+  XNRS_TRY(rk_launch(c, v, nullptr, bias, stream));
+  return XNRS_OK;
+}
+
+int32_t xnrs_rank_mlp(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
+                      const float* b1, const float* w2, const float* b2, const int64_t* tgt_off, const int32_t* tgt_rows,
+                      const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t* ranks, float* scores,
+                      void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (E <= 0) return XNRS_EINVAL;
+  const RankCall c{P, n_rows, H, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, H};
+  bool run;
+  XNRS_TRY_RC(rk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w1 || !w2) return XNRS_EINVAL;
+  float* q = static_cast<float*>(ws);
+  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_topk_mlp
+  XNRS_TRY(rk_launch(c, q, w2, b2, stream));
   return XNRS_OK;
 }
 

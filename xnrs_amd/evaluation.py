@@ -178,11 +178,10 @@ def evaluate(model, store: NewsStore, behaviors: Behaviors, l_hist: int, batch: 
     return out
 
 
-def _history_csr(behaviors: Behaviors, sess: torch.Tensor, first):
-    """(excl_off:(B+1) int64 absolute into excl_rows, excl_rows int32): the FULL histories of the sessions.  A contiguous run
-    of sessions from session `first` on (an int) is a slice of hist_off over the whole hist_val (no copy); any other selection
+def _session_csr(off: torch.Tensor, val: torch.Tensor, sess: torch.Tensor, first):
+    """(off:(B+1) int64 absolute into rows, rows int32): the lists of the sessions out of the CSR (off, val).  A contiguous
+    run of sessions from session `first` on (an int) is a slice of `off` over the whole `val` (no copy); any other selection
     (`first` None) gathers its lists."""
-    off, val = behaviors.hist_off, behaviors.hist_val
     if first is not None:
         return off[first:first + sess.numel() + 1], val
     start, n = off[sess], off[sess + 1] - off[sess]
@@ -190,6 +189,11 @@ def _history_csr(behaviors: Behaviors, sess: torch.Tensor, first):
     torch.cumsum(n, 0, out=new_off[1:])
     idx = torch.arange(int(new_off[-1]), device=off.device) + torch.repeat_interleave(start - new_off[:-1], n)
     return new_off, val[idx]
+
+
+def _history_csr(behaviors: Behaviors, sess: torch.Tensor, first):
+    """The FULL histories of the sessions as an exclusion CSR (_session_csr of hist_off / hist_val)."""
+    return _session_csr(behaviors.hist_off, behaviors.hist_val, sess, first)
 
 
 @torch.no_grad()
@@ -240,3 +244,138 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
         rows[lo:lo + batch], scores[lo:lo + batch] = topk(table, u, k, excl[0], excl[1], store.pad_row)
     hip.check_status(dev)
     return rows, scores
+
+
+def _ranking_model_parts(model, behaviors: Behaviors, who: str):
+    """(prepare_csr, rank, user index or None) of a model whose clicked news can be ranked within the table, or the refusal
+    -- before anything is encoded."""
+    scorer = getattr(model, "rec_model", None)
+    prepare, rank = getattr(scorer, "prepare_csr", None), getattr(scorer, "rank", None)
+    if prepare is None or rank is None:
+        raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no ranking path over a news table "
+                                  "(prepare_csr / rank); ranking it with a plain dot product would evaluate another model")
+    if getattr(model, "user_dependent_news", False):
+        raise NotImplementedError(f"{who}: the news vectors of {type(model).__name__} depend on the user, so no table of "
+                                  "news vectors exists to rank")
+    uidx = None
+    if getattr(model, "uses_user_index", False):
+        uidx = getattr(behaviors, "user_index", None)
+        if uidx is None:
+            raise ValueError(f"{who}: {type(model).__name__} needs the user index of every session (sessions without "
+                             "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    return prepare, rank, uidx
+
+
+@torch.no_grad()
+def rank_clicked(model, store: NewsStore, behaviors: Behaviors, l_hist: int, sessions=None, batch: int = 4096,
+                 exclude_history: bool = True):
+    """Where every clicked news ranks among ALL news of the table for its session's user -> (query_session int64, query_row
+    int32, rank int32, score fp32) on the device, one entry per (session, clicked news) in session order (pos_off / pos_val;
+    a session without a click gives no query).
+
+    rank = the number of eligible news that come before the clicked one in the order of recommend() (include/xnrs_hip.h:
+    xnrs_rank -- higher raw score first, equal scores lower row first, no ReLU), so rank < k exactly when recommend(k) lists
+    the news, at position rank.  Eligible: every news but store.pad_row and, with `exclude_history`, the session's FULL
+    history; the clicked news itself is ranked even when it is in that history.  rank -1 / score NaN: the clicked news is
+    the pad row, or its score is NaN.
+
+    Once per call the news table is encoded (encode_news_table) and handed to the scorer (prepare_csr); per batch of sessions
+    the user tower runs as in recommend() and the scorer's rank(table, u, ...) sweeps the table without a (sessions, n_rows)
+    score matrix.  `sessions`: session indices (None = all; a range of step 1 is taken as a slice, without gathering).
+    Refusals as recommend()."""
+    prepare, rank_fn, uidx = _ranking_model_parts(model, behaviors, "rank_clicked()")
+    vecs, hm = encode_news_table(model, store)
+    table = prepare(vecs)
+    batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
+    dev = vecs.device
+    if uidx is not None:
+        uidx = uidx.to(dev)
+    first = None  # the first session of a contiguous run
+    if sessions is None:
+        sessions = range(len(behaviors))
+    if isinstance(sessions, range) and sessions.step == 1:
+        first = sessions.start
+        sessions = torch.arange(sessions.start, max(sessions.stop, sessions.start), device=dev)
+    else:
+        sessions = torch.as_tensor(sessions, dtype=torch.int64, device=dev)
+    pos_off, pos_val = behaviors.pos_off, behaviors.pos_val
+    n_pos = pos_off[sessions + 1] - pos_off[sessions]
+    q_sess = torch.repeat_interleave(sessions, n_pos)
+    if first is not None:  # one pair of outputs indexed like pos_val; every batch writes its own span
+        ranks = torch.full((pos_val.numel(),), -1, dtype=torch.int32, device=dev)
+        scores = torch.full((pos_val.numel(),), float("nan"), dtype=torch.float32, device=dev)
+    parts = []
+    for lo in range(0, sessions.numel(), batch):
+        sess = sessions[lo:lo + batch]
+        hist = batcher.eval_batch(sess)[0]
+        h = vecs[hist.long()]
+        m = hm[hist.long()]
+        u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
+        at = None if first is None else first + lo
+        excl = _history_csr(behaviors, sess, at) if exclude_history else (None, None)
+        tgt = _session_csr(pos_off, pos_val, sess, at)
+        if first is not None:
+            rank_fn(table, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row, out=(ranks, scores))
+        else:
+            parts.append((tgt[1],) + tuple(rank_fn(table, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row)))
+    hip.check_status(dev)
+    if first is not None:
+        a, b = (int(v) for v in pos_off[[first, first + sessions.numel()]].tolist())
+        return q_sess, pos_val[a:b], ranks[a:b], scores[a:b]
+    if not parts:
+        return (q_sess, pos_val[:0], torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev))
+    return (q_sess,) + tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+
+
+def full_ranking_sums(rank: torch.Tensor, ks) -> torch.Tensor:
+    """fp64 sums over the queries with rank >= 0: [n_queries, hit@k for k in ks, ndcg@k for k in ks, reciprocal rank, rank].
+    Post-processing of an integer vector (ranks are 0-based: the best news has rank 0)."""
+    r = rank[rank >= 0].double()
+    out = [torch.tensor(float(r.numel()), dtype=torch.float64, device=rank.device)]
+    out += [(r < k).double().sum() for k in ks]
+    out += [torch.where(r < k, 1.0 / torch.log2(2.0 + r), torch.zeros_like(r)).sum() for k in ks]  # one relevant item: DCG / 1
+    out += [(1.0 / (1.0 + r)).sum(), r.sum()]
+    return torch.stack(out)
+
+
+def full_ranking_metrics(sums: torch.Tensor, ks) -> Dict[str, float]:
+    """The dict of evaluate_full_ranking out of full_ranking_sums (added over the ranks of a job)."""
+    v = sums.tolist()
+    n, nk = v[0], len(ks)
+    d = max(n, 1.0)
+    out = {f"hit@{k}": v[1 + i] / d for i, k in enumerate(ks)}
+    out.update({f"ndcg@{k}": v[1 + nk + i] / d for i, k in enumerate(ks)})
+    out.update({"mrr": v[1 + 2 * nk] / d, "mean_rank": v[2 + 2 * nk] / d, "n_queries": int(n)})
+    return out
+
+
+@torch.no_grad()
+def evaluate_full_ranking(model, store: NewsStore, behaviors: Behaviors, l_hist: int, ks=(5, 10, 100), sessions=None,
+                          batch: int = 4096, exclude_history: bool = True, distributed: bool = False) -> Dict[str, float]:
+    """Full-corpus ranking metrics of the clicked news (rank_clicked): hit@k (= recall@k: one relevant news per query),
+    ndcg@k (1 / log2(2 + rank) when rank < k), mrr (1 / (1 + rank)), mean_rank (0-based) and n_queries, averaged in fp64
+    over the queries with rank >= 0.
+
+    `distributed=True` (opt-in, never automatic: every rank of the default process group must then make this call) shards
+    the sessions over the ranks (distributed.shard_range); every rank encodes the whole table, and ONE fp64 all-reduce adds
+    the sums and the count, so every rank returns the same dict, equal to the single-process one up to the order of that
+    final sum."""
+    _ranking_model_parts(model, behaviors, "evaluate_full_ranking()")
+    ks = tuple(int(k) for k in ks)
+    on = False
+    if distributed:
+        rank, world, on = _dist_rank_world(True)
+    if on:
+        from .distributed import shard_range
+        n = len(behaviors) if sessions is None else len(sessions)
+        lo, hi = shard_range(n, rank, world)
+        if sessions is None:
+            sessions = range(lo, hi)
+        else:
+            sessions = sessions[lo:hi]
+    _, _, ranks, _ = rank_clicked(model, store, behaviors, l_hist, sessions, batch, exclude_history)
+    sums = full_ranking_sums(ranks, ks)
+    if on:
+        import torch.distributed as dist
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+    return full_ranking_metrics(sums, ks)

@@ -79,6 +79,7 @@ class CAUMScoring(DotScoring):
     prepare_csr = None
     score_csr = None
     topk = None
+    rank = None
 
 
 class CAUMNewsEncoder(nn.Module):

@@ -587,6 +587,78 @@ def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_ro
                                       hip.ptr(b2)), B, H, k, excl_off, excl_rows, pad_row)
 
 
+def _csr_check(what: str, off, rows, B: int, dev):
+    if off.dtype != torch.int64 or rows.dtype != torch.int32 or off.numel() != B + 1:
+        raise RuntimeError(f"{what}: offsets (B+1,) int64 and rows int32, got {tuple(off.shape)} {off.dtype} "
+                           f"and {rows.dtype} for {B} users")
+    if off.device != dev or rows.device != dev or not (off.is_contiguous() and rows.is_contiguous()):
+        raise hip.XnrsHipError(f"{what} must be contiguous tensors on {dev}")
+
+
+def _rank(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, tgt_off, tgt_rows, excl_off, excl_rows,
+          pad_row: int, out):
+    """The call every rank entry point shares behind its own leading arguments `head` -> (ranks int32, scores fp32), both
+    indexed like tgt_rows.  The call writes the positions [tgt_off[0], tgt_off[B]) only: fresh outputs start at -1 / NaN
+    everywhere else, the tensors of `out` = (ranks, scores) keep what they held."""
+    dev = table.device
+    if (excl_off is None) != (excl_rows is None):
+        raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
+    _csr_check("targets", tgt_off, tgt_rows, B, dev)
+    if excl_off is not None:
+        _csr_check("exclusions", excl_off, excl_rows, B, dev)
+    if out is None:
+        ranks = torch.full((tgt_rows.numel(),), -1, dtype=torch.int32, device=dev)
+        scores = torch.full((tgt_rows.numel(),), float("nan"), dtype=torch.float32, device=dev)
+    else:
+        ranks, scores = out
+        for t, dt in ((ranks, torch.int32), (scores, torch.float32)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() != tgt_rows.numel():
+                raise RuntimeError(f"out: (ranks int32, scores fp32), contiguous on {dev}, one entry per target row "
+                                   f"({tgt_rows.numel()}); got {tuple(t.shape)} {t.dtype} on {t.device}")
+    l = hip.lib()
+    nbytes = l.xnrs_rank_workspace_bytes(B, proj_width)
+    ws = hip.workspace(dev, nbytes)
+    hip.check(getattr(l, entry)(*head, hip.ptr(tgt_off), hip.ptr(tgt_rows), hip.ptr(excl_off), hip.ptr(excl_rows), int(pad_row),
+                                hip.ptr(ranks), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
+    return ranks, scores
+
+
+def rank_dot(table, u, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None):
+    """For every (user, target row) of the CSR tgt_off / tgt_rows: how many eligible rows of `table` come before the target
+    in the order of topk_dot, and the target's score (include/xnrs_hip.h: xnrs_rank) -> (ranks, scores)."""
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    B = u.shape[0]
+    return _rank("xnrs_rank", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, tgt_off, tgt_rows, excl_off, excl_rows,
+                 pad_row, out)
+
+
+def rank_bilinear(table, u, w, b, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None):
+    """As rank_dot with the score u W[0] table[row] + bias (xnrs_rank_bilinear)."""
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    w = hip.dev_f32(w, "bilinear weight")
+    b = None if b is None else hip.dev_f32(b, "bilinear bias")
+    B = u.shape[0]
+    return _rank("xnrs_rank_bilinear", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E,
+                 tgt_off, tgt_rows, excl_off, excl_rows, pad_row, out)
+
+
+def rank_mlp(P, u, w1, b1, w2, b2, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None):
+    """As rank_dot with the score w2 . tanh(W1u u + b1 + P[row]) + b2, P = mlp_news_proj(table) (xnrs_rank_mlp)."""
+    P = hip.dev_f32(P, "projected news table")
+    E = w1.shape[1] // 2
+    u = hip.dev_f32(u, "user vectors").reshape(-1, E)
+    w1, b1, w2, b2, H = _mlp_weights(E, w1, b1, w2, b2)
+    if P.dim() != 2 or P.shape[1] != H:
+        raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
+    B = u.shape[0]
+    return _rank("xnrs_rank_mlp", P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2),
+                                      hip.ptr(b2)), B, H, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, out)
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
