@@ -424,9 +424,8 @@ bool additive_fused_plan(int S, int D, int A, int* nn_out, int* pp_out) {
 }
 
 bool additive_fused_ready(const AdditiveFusedArgs& a) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return additive_fused_plan(a.S, a.D, a.A, nullptr, nullptr) && a.x && a.w1 && a.w2 && a.y && al16(a.x) && al16(a.w1) &&
-         al16(a.y) && a.ldy % 4 == 0;
+  return additive_fused_plan(a.S, a.D, a.A, nullptr, nullptr) && a.x && a.w1 && a.w2 && a.y && aligned16(a.x) && aligned16(a.w1) &&
+         aligned16(a.y) && a.ldy % 4 == 0;
 }
 
 namespace {

@@ -85,10 +85,9 @@ Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additiv
 }
 
 bool device_counts_ok(const float* x, int D, int A, const xnrs_mha_params* att, const xnrs_additive_params* pool) {
-  auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (!knobs().gemm_buf || gemm_mode() != 0 || D % 4 != 0 || D < 4 || (A > 0 && A % 4 != 0)) return false;
-  if (!al16(x) || (pool && !al16(pool->w1))) return false;
-  if (att && !(al16(att->wq) && al16(att->wk) && al16(att->wv) && al16(att->wo))) return false;
+  if (!aligned16(x) || (pool && !aligned16(pool->w1))) return false;
+  if (att && !(aligned16(att->wq) && aligned16(att->wk) && aligned16(att->wv) && aligned16(att->wo))) return false;
   return (int64_t)D * D * 4 <= (1ll << 30) && (int64_t)A * D * 4 <= (1ll << 30);
 }
 
@@ -157,11 +156,10 @@ int32_t fc1_pair(bool fold, const xnrs_mha_params* att, const xnrs_additive_para
 
 // the fused row dots ride on the raw-buffer-load forward kernel: 16-byte aligned operands
 bool fc1_rowdot_ok(const float* x, bool att, const xnrs_additive_params* pool, int D) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // (rows of any count / any gather: beyond the 1-GB descriptor window or with row ids the launcher takes the
   // pointer-gather variant of the same kernel)
   return knobs().fc1_rowdot && knobs().gemm_buf && gemm_mode() == 0 && pool && pool->w2 && D % 4 == 0 && D >= 4 &&
-         al16(pool->w1) && (att || al16(x)) && (int64_t)pool->hidden * D * 4 <= (1ll << 30);
+         aligned16(pool->w1) && (att || aligned16(x)) && (int64_t)pool->hidden * D * 4 <= (1ll << 30);
 }
 inline int n_epart(int A) { return (A + 31) / 32; }  // partial fc2 dots per row: one per 32 hidden columns
 
@@ -290,60 +288,126 @@ int32_t pooled_tail(bool fold, const float* pob, const float* asum, const xnrs_m
   return XNRS_OK;
 }
 
-}  // namespace
+// where the pooled vectors of a call go: the fold buffer (pooled_tail follows), else the head's input, else the caller's y
+inline float* pooled_dst(bool fold, float* pob, const xnrs_head_params* head, float* pb, float* y) { return fold ? pob : (head ? pb : y); }
+// This product runs over a row list IN PLACE: A rows gathered through `src` (one row per id), C rows (or row dots) scattered
+// through `dst` (nullptr: `src`); n = the list's length (its CAPACITY with the length on the device, n_dev), fill = its expected share
+inline void over_row_list(GemmArgs* g, const int32_t* src, const int32_t* dst, int64_t n, const int64_t* n_dev, float fill) {
+  g->gather_ids = src; g->gather_S = 1; g->c_scatter = 1; g->c_scatter_ids = dst;
+  g->M = n; g->m_dev = n_dev; g->m_fill_hint = fill;
+}
+inline void over_live_tiles(GemmArgs* g, const int64_t* n, const int32_t* tiles) { g->live_n = n; g->live_tiles = tiles; }
+constexpr float LR_FILL = 0.3f;  // tile choice only: the share of a pass's rows expected on the list (ragged titles x empty slots)
 
-int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
-  const float *x = r.x, *m = r.m;
-  const int32_t* ids = r.ids;
-  const int64_t n_seq = r.n_seq;
-  const int L = r.L, D = r.D, pool_kind = r.pool_kind;
-  const xnrs_mha_params* att = r.att;
-  const xnrs_additive_params* pool = r.pool;
-  const xnrs_head_params* head = r.head;
-  const bool pooled = r.pooled, train = r.train;
-  float *y = r.y, *a_out = r.a_out, *hm = r.hm;
-  const xnrs_row_lists no_lists{};
-  const xnrs_row_lists* rl = r.rl ? r.rl : &no_lists;
-  const int32_t *live_rows = rl->live_rows, *live_src_rows = rl->live_src_rows, *kv_rows = rl->kv_rows,
-                *kv_src_rows = rl->kv_src_rows;
-  const float* qkv_shared = rl->qkv_shared;
-  // counts on the device (xnrs_row_lists::counts_dev): the list lengths below are then CAPACITIES (every row), the
-  // products over a list read their row count on the device (GemmArgs::m_dev)
-  const int64_t* cnt = rl->counts_dev;
-  const int64_t n_live = cnt ? n_seq * L : rl->n_live, n_kv = cnt ? n_seq * L : rl->n_kv;
-  const uint16_t* x16 = r.x16;
-  if (n_seq == 0) return XNRS_OK;
-  if (n_seq < 0 || L <= 0 || D <= 0 || (!x && !x16) || !y) return XNRS_EINVAL;
-  if (x16 && (x || !ids || !m || !pooled || train || a_out)) return XNRS_EINVAL;  // a bf16 TABLE, inference: never dense rows
-  if (att) {
-    if (att->n_heads <= 0 || !att->wq || !att->wk || !att->wv || !att->wo) return XNRS_EINVAL;
-    if (D % att->n_heads != 0) return XNRS_EHEADS;
-    if (L > 128) return XNRS_EUNSUPPORTED;
-    if (train && D / att->n_heads > 128) return XNRS_EUNSUPPORTED;  // the backward kernels' limit (mha_bwd.hip MAX_FT)
+// ---- the padded pipeline (seq_encode): check -> plan -> route -> weights -> (one-launch kernel | pass loop) -> tail
+inline bool is_additive(const SeqEncode& r) { return r.pooled && r.pool_kind == XNRS_POOL_ADDITIVE; }
+inline int hidden_of(const SeqEncode& r) { return is_additive(r) ? r.pool->hidden : 0; }
+inline int width_of(const SeqEncode& r) { return (r.pooled && r.head) ? r.head->out_features : r.D; }
+// the argument checks of a padded call, in the order the tests pin (which code a bad call returns)
+int32_t check_seq_encode(const SeqEncode& r) {
+  if (r.n_seq < 0 || r.L <= 0 || r.D <= 0 || (!r.x && !r.x16) || !r.y) return XNRS_EINVAL;
+  if (r.x16 && (r.x || !r.ids || !r.m || !r.pooled || r.train || r.a_out)) return XNRS_EINVAL;  // a bf16 TABLE, inference: never dense rows
+  if (r.att) {
+    if (r.att->n_heads <= 0 || !r.att->wq || !r.att->wk || !r.att->wv || !r.att->wo) return XNRS_EINVAL;
+    if (r.D % r.att->n_heads != 0) return XNRS_EHEADS;
+    if (r.L > 128) return XNRS_EUNSUPPORTED;
+    if (r.train && r.D / r.att->n_heads > 128) return XNRS_EUNSUPPORTED;  // the backward kernels' limit (mha_bwd.hip MAX_FT)
   }
-  const bool additive = pooled && pool_kind == XNRS_POOL_ADDITIVE;
-  if (pooled) {
-    if (pool_kind != XNRS_POOL_ADDITIVE && pool_kind != XNRS_POOL_MEAN) return XNRS_EINVAL;
-    if (additive && (!pool || !pool->w1 || !pool->w2 || pool->hidden <= 0)) return XNRS_EINVAL;
-    if (pool_kind == XNRS_POOL_MEAN && !m) return XNRS_EINVAL;
-    if (L > 512) return XNRS_EUNSUPPORTED;
-    if (head && (!head->w0 || !head->w2 || head->out_features <= 0 || head->activation < 0 || head->activation > 2))
+  if (r.pooled) {
+    if (r.pool_kind != XNRS_POOL_ADDITIVE && r.pool_kind != XNRS_POOL_MEAN) return XNRS_EINVAL;
+    if (is_additive(r) && (!r.pool || !r.pool->w1 || !r.pool->w2 || r.pool->hidden <= 0)) return XNRS_EINVAL;
+    if (r.pool_kind == XNRS_POOL_MEAN && !r.m) return XNRS_EINVAL;
+    if (r.L > 512) return XNRS_EUNSUPPORTED;
+    if (r.head && (!r.head->w0 || !r.head->w2 || r.head->out_features <= 0 || r.head->activation < 0 || r.head->activation > 2))
       return XNRS_EINVAL;
   }
-  if (ids && !m && pooled && pool_kind == XNRS_POOL_MEAN) return XNRS_EINVAL;
-  const int A = additive ? pool->hidden : 0;
-  const int E = (pooled && head) ? head->out_features : D;
-  const Plan p = make_plan(n_seq, L, D, A, E, att != nullptr, additive, pooled && head, pooled, r.chunk, train,
-                           att ? att->n_heads : 0, x16 != nullptr);
-  if (p.total > r.ws_bytes || (p.total > 0 && !r.ws)) return XNRS_EWORKSPACE;
-  void* w = r.ws;
-  float* stats = (train && att) ? at(w, p.off_stats) : nullptr;
-  float* a_save = (train && additive) ? at(w, p.off_a) : nullptr;
-  // (training) the Q|K|V image of another forward over the same input and weights: read it, project nothing (xnrs_row_lists)
-  const bool qkv_given = train && att && qkv_shared;
-  float* qkv = qkv_given ? const_cast<float*>(qkv_shared) : at(w, p.off_qkv);
-  float *o = at(w, p.off_o), *yb = at(w, p.off_y), *t = at(w, p.off_t), *pb = at(w, p.off_p), *hb = at(w, p.off_h);
+  return (r.ids && !r.m && r.pooled && r.pool_kind == XNRS_POOL_MEAN) ? XNRS_EINVAL : XNRS_OK;
+}
 
+// ---- Route: every decision of a padded call, each taken ONCE, in make_route, from arguments, plan, knobs, GEMM mode and the timer's
+// stage mask -- never from data (hipGraph).  qkv_given, live, kvl require train, every other one !train.  Per stage, first match:
+struct Route {
+  bool fused, afused;  // the whole call as ONE kernel: news_fused.hip, additive_fused.hip
+  // project: image given | training lists (kvl: K|V over a list too) | live rows ("lr_qkv"; tail: the launch carries the
+  //   previous fc1) | dense (lt_qkv: live row tiles; direct: from the bf16 rows, a16: their weight planes are wanted)
+  bool qkv_given, live, kvl, lr_qkv, tail, lt_qkv, direct, a16;
+  bool fold;  // out-project: folded away ("fold") | training lists (live) | dense
+  // fc1: training lists (live) | live rows (lr_fc1; tail: deferred) | dense (lt_fc1: live row tiles; rowdot: fc2 in the epilogue)
+  bool lr_fc1, lt_fc1, rowdot;
+  bool skip_dead, read_counts;  // attend: zeros for an all-masked sequence; timer: the list counts of every pass are read back once
+};
+
+// Short sequences: attention + additive pooling of ALL sequences in one launch (news_fused.hip); only the pooled
+// vectors leave the CU.  Inference only (nothing is saved for a backward), fp32 arithmetic only.
+// Dispatch (measured, tools/bench_news_fused.py at D = 320; profiles/r02_news_fused_dispatch_sweep.txt): a workgroup owns
+// news padded to 32 token rows each, so the kernel wins from ~26 tokens (<= 19 % padding) upwards and once there are
+// enough news to fill the CUs -- with 1 news per workgroup (two workgroups per CU) from ~200, with 2 news per workgroup
+// (every weight fragment feeds 4 row tiles) from 512: 256 x 30 tokens 116 vs 149 us for the pipeline, 512 x 30: 177 vs
+// 217 us, 1024 x 30: 325 vs 329 us.  From ~1500 news on the pipeline is ahead again since it folds the out-projection
+// behind the pooling (fold_out_projection above; the fused kernel computes it per token): 2048 x 30: 623 vs 592 us,
+// 28 160 x 30: 8.2 vs 7.1 ms; 64 x 30: 111 vs 104 us, 1024 x 20: 318 vs 255 us.  XNRS_NEWS_FUSED=2 forces the kernel
+// for every eligible shape (tests), 0 turns it off.
+// Short sequences go through the fused kernel; everything else folds the out-projection behind the pooling.
+// The predicate covers EVERY precondition of the launch (shape, 16-byte aligned operands, 160 KB of dynamic LDS on the
+// current device: news_fused_ready), so a batch the kernel cannot take runs on the pipeline instead of failing.
+bool news_fused_route(const SeqEncode& r, const Plan& p, int A, bool fold, NewsFusedArgs* f) {
+  const xnrs_mha_params* att = r.att;
+  const int L = r.L, D = r.D;
+  if (!(att && is_additive(r) && !r.train && !r.a_out && att->dropout_p == 0.f && gemm_mode() == 0 && knobs().news_fused &&
+        news_fused_plan(L, D, att->n_heads, A, nullptr) && (D / att->n_heads) * att->n_heads == D &&
+        (knobs().news_fused == 2 || (L >= 26 && r.n_seq >= 192))))
+    return false;
+  f->x = r.x; f->ids = r.ids; f->mask = r.m;
+  f->wq = att->wq; f->bq = att->bq; f->wk = att->wk; f->bk = att->bk; f->wv = att->wv; f->bv = att->bv;
+  f->wo = att->wo; f->bo = att->bo;
+  f->w1 = r.pool->w1; f->b1 = r.pool->b1; f->w2 = r.pool->w2; f->b2 = r.pool->b2;
+  f->img = at(r.ws, p.off_nf);
+  f->p = pooled_dst(fold, at(r.ws, p.fold.po), r.head, at(r.ws, p.off_p), r.y);
+  f->ldp = D; f->hm = r.m ? r.hm : nullptr; f->n_seq = r.n_seq;
+  f->S = L; f->D = D; f->n_heads = att->n_heads; f->d_k = D / att->n_heads; f->A = A; f->scaled = att->scaled;
+  f->npw = knobs().news_fused_npw ? knobs().news_fused_npw : (r.n_seq < 512 ? 1 : 2);
+  if (fold) {  // the kernel pools the attention rows; Wo is applied once per news (pooled_tail)
+    f->fold = 1; f->o_scratch = at(r.ws, p.off_nfo); f->asum = at(r.ws, p.fold.as);
+  }
+  if (r.x16) {  // bf16 table: the kernel runs pass by pass on the widened rows and the gathered mask rows (run_one_launch)
+    f->x = at(r.ws, p.off_x32); f->ids = nullptr; f->mask = at(r.ws, p.off_m32);
+  }
+  return p.off_nf != 0 && news_fused_ready(*f);
+}
+
+// Additive-only towers (no self-attention: StandardRec / BaseRec / NAML / LSTUR news encoders) from a batch that fills
+// the chip: fc1 + tanh + fc2 + exp + mask + normalise + weighted sum as ONE persistent launch (additive_fused.hip).  Its
+// result equals the GEMM + pooling pipeline's bit for bit (same MFMA fragments and k order, same reduction orders), so
+// the choice may depend on the batch size without a news vector ever changing: from two 256-row tiles per CU on the
+// fused launch wins (tools/bench_af.py, settled clocks: 2 560 news x 50 x 768 -- two tiles per CU -- 0.447 vs 0.469 ms for
+// the pipeline; 12 800 news -- ten per CU -- 2.13 vs 2.33 ms, i.e. 0.98 of the plain fc1 GEMM of the same shape with the
+// pooling included); below that the pipeline's smaller tiles fill the chip better.
+bool additive_fused_route(const SeqEncode& r, const Plan& p, int A, bool rowdot, AdditiveFusedArgs* af) {
+  if (!(!r.att && is_additive(r) && !r.train && !r.a_out && gemm_mode() == 0 && knobs().additive_fused &&
+        additive_fused_plan(r.L, r.D, A, nullptr, nullptr) && rowdot &&
+        (knobs().additive_fused == 2 || additive_fused_tiles(r.n_seq, r.L) >= 512)))
+    return false;
+  af->x = r.x16 ? at(r.ws, p.off_x32) : r.x; af->ids = r.x16 ? nullptr : r.ids; af->mask = r.x16 ? at(r.ws, p.off_m32) : r.m;
+  af->w1 = r.pool->w1; af->b1 = r.pool->b1; af->w2 = r.pool->w2; af->b2 = r.pool->b2;
+  af->y = pooled_dst(false, nullptr, r.head, at(r.ws, p.off_p), r.y);
+  af->ldy = r.D; af->hm = r.m ? r.hm : nullptr; af->n_seq = r.n_seq;
+  af->S = r.L; af->D = r.D; af->A = A;
+  return additive_fused_ready(*af);
+}
+// the pre-split planes of Wq, Wk, Wv, Wo (i = 0..3), then W1, in the plan's planes region (prepare_weights fills them)
+inline unsigned short* weight_plane(const SeqEncode& r, const Plan& p, int i) {
+  return at<unsigned short>(r.ws, p.off_planes + (size_t)i * align_up(split_planes_bytes(r.D, r.D)));
+}
+
+// *nf / *af: the arguments of the one-launch kernel the route names (w1 / b1: prepare_weights puts the folded pair there)
+Route make_route(const SeqEncode& r, const Plan& p, NewsFusedArgs* nf, AdditiveFusedArgs* af) {
+  const xnrs_row_lists rl = r.rl ? *r.rl : xnrs_row_lists{};
+  const int L = r.L, D = r.D, A = hidden_of(r);
+  const bool additive = is_additive(r);
+  const int64_t n_rows = r.n_seq * (int64_t)L;
+  Route rt{};
+  // (training) the Q|K|V image of another forward over the same input and weights: read it, project nothing (xnrs_row_lists)
+  rt.qkv_given = r.train && r.att && rl.qkv_shared;
   // Training forward over the UNMASKED token rows (optional, exact): a masked token row has pooling weight exp(e) * 0, so
   // its query projection, its out-projection row and its fc1 row never reach the output or any gradient (K and V stay
   // dense: padded tokens are keys, layers.py:142-144).  Those three products run over the live rows in place (A rows
@@ -352,160 +416,28 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   // exactly as if the rows had been computed and then multiplied by the zero weight.
   // An attention-FREE additive tower (StandardRec, NAML's views) takes the same list for its one row-parallel product:
   // fc1 runs over the live token rows of x, T of the masked rows is zero.
-  const bool live = train && additive && m && live_rows && (cnt || (n_live >= 0 && n_live < n_seq * L)) &&
-                    !(ids && !live_src_rows);
-  if (cnt && live && !device_counts_ok(x, D, A, att, pool)) return XNRS_EUNSUPPORTED;
-  const int32_t* lvx = live ? (ids ? live_src_rows : live_rows) : nullptr;  // rows of x (table rows with ids)
+  rt.live = r.train && additive && r.m && rl.live_rows && (rl.counts_dev || (rl.n_live >= 0 && rl.n_live < n_rows)) &&
+            !(r.ids && !rl.live_src_rows);
   // ... and K|V over the token rows of the NON-EMPTY news only (kv_rows, optional, exact): the keys and values of a news
   // are read by that news' own queries alone, and an all-masked news has no live query, so its K and V rows (zeroed
   // here: its attention rows then come out as finite zeros) reach neither the output nor a gradient.
-  const bool kvl = live && kv_rows && (cnt || (n_kv >= 0 && n_kv < n_seq * L)) && !(ids && !kv_src_rows);
-  const int32_t* kvx = kvl ? (ids ? kv_src_rows : kv_rows) : nullptr;
-
-  // Short sequences go through the fused kernel (below); everything else folds the out-projection behind the pooling.
-  // The predicate covers EVERY precondition of the launch (shape, 16-byte aligned operands, 160 KB of dynamic LDS on the
-  // current device: news_fused_ready), so a batch the kernel cannot take runs on the pipeline instead of failing.
-  NewsFusedArgs f{};
-  bool fused = att && additive && !train && !a_out && att->dropout_p == 0.f && gemm_mode() == 0 &&
-               knobs().news_fused && news_fused_plan(L, D, att->n_heads, A, nullptr) &&
-               (D / att->n_heads) * att->n_heads == D &&
-               (knobs().news_fused == 2 || (L >= 26 && n_seq >= 192));
-  if (fused) {
-    f.x = x; f.ids = ids; f.mask = m;
-    f.wq = att->wq; f.bq = att->bq; f.wk = att->wk; f.bk = att->bk; f.wv = att->wv; f.bv = att->bv;
-    f.wo = att->wo; f.bo = att->bo;
-    f.w1 = pool->w1; f.b1 = pool->b1; f.w2 = pool->w2; f.b2 = pool->b2;
-    f.img = at(w, p.off_nf);
-    f.p = head ? pb : y;
-    f.ldp = D;
-    f.hm = m ? hm : nullptr;
-    f.n_seq = n_seq;
-    f.S = L; f.D = D; f.n_heads = att->n_heads; f.d_k = D / att->n_heads; f.A = A; f.scaled = att->scaled;
-    f.npw = knobs().news_fused_npw ? knobs().news_fused_npw : (n_seq < 512 ? 1 : 2);
-    if (fold_wanted(knobs().fold_out)) {  // the kernel pools the attention rows; Wo is applied once per news below
-      f.fold = 1;
-      f.o_scratch = at(w, p.off_nfo);
-      f.asum = at(w, p.fold.as);
-      f.p = at(w, p.fold.po);
-    }
-    if (x16) {  // bf16 table: the kernel runs pass by pass on the widened rows and the gathered mask rows (below)
-      f.x = at(w, p.off_x32);
-      f.ids = nullptr;
-      f.mask = at(w, p.off_m32);
-    }
-    fused = p.off_nf != 0 && news_fused_ready(f);
-  }
-  // bf16 table, widening route: pass [c0, c0 + nc) of the call's rows as fp32 in the workspace (mask_too: and its mask rows,
-  // for the one-launch kernels whose rows and mask share one id list)
-  auto widen_pass = [&](int64_t c0, int64_t nc, bool mask_too) -> hipError_t {
-    hipError_t e = launch_gather_rows_bf16(x16, ids + c0, 1, at(w, p.off_x32), nc, (int64_t)L * D, stream);
-    if (e == hipSuccess && mask_too) e = launch_gather_rows(m, ids + c0, at(w, p.off_m32), nc, L, stream);
-    return e;
-  };
-  const bool fold = att && additive && fold_wanted(train ? knobs().fold_train : knobs().fold_out);
-  float *pob = at(w, p.fold.po), *asum = at(w, p.fold.as);
+  rt.kvl = rt.live && rl.kv_rows && (rl.counts_dev || (rl.n_kv >= 0 && rl.n_kv < n_rows)) && !(r.ids && !rl.kv_src_rows);
+  rt.fold = r.att && additive && fold_wanted(r.train ? knobs().fold_train : knobs().fold_out);  // ("fold", above)
+  rt.fused = news_fused_route(r, p, A, rt.fold, nf);
   // inference, fp32 GEMM mode, 16-byte-aligned shapes the buffer-load kernel serves, no gathered rows: the pooler's fc2
   // dot is taken in the fc1 epilogue (fc1_product)
   // (every input path -- dense rows, id gather, padding-free -- takes it, so they stay bitwise equal)
   // (x16: the pooler of an attention-free tower reads the widened rows, 256-byte aligned in the workspace)
-  float* x32 = at(w, p.off_x32);
-  float* m32 = at(w, p.off_m32);
-  const float* xal = x16 ? x32 : x;  // the rows whose alignment the predicates below ask about
-  const bool rowdot = additive && !train && !fused && fc1_rowdot_ok(xal, att != nullptr, pool, D);
-  Fc1 fc1{};
-  XNRS_TRY_RC(fc1_pair(fold, att, additive ? pool : nullptr, D, w, p.fold, stream, &fc1));
-  if (fold && fused) {  // the fused kernel's fc1 image is built from the folded pair
-    f.w1 = fc1.w;
-    f.b1 = fc1.b;
-  }
-
-  // Additive-only towers (no self-attention: StandardRec / BaseRec / NAML / LSTUR news encoders) from a batch that fills
-  // the chip: fc1 + tanh + fc2 + exp + mask + normalise + weighted sum as ONE persistent launch (additive_fused.hip).  Its
-  // result equals the GEMM + pooling pipeline's bit for bit (same MFMA fragments and k order, same reduction orders), so
-  // the choice may depend on the batch size without a news vector ever changing: from two 256-row tiles per CU on the
-  // fused launch wins (tools/bench_af.py, settled clocks: 2 560 news x 50 x 768 -- two tiles per CU -- 0.447 vs 0.469 ms for
-  // the pipeline; 12 800 news -- ten per CU -- 2.13 vs 2.33 ms, i.e. 0.98 of the plain fc1 GEMM of the same shape with the
-  // pooling included); below that the pipeline's smaller tiles fill the chip better.
-  bool afused = !att && additive && !train && !a_out && gemm_mode() == 0 && knobs().additive_fused &&
-                additive_fused_plan(L, D, A, nullptr, nullptr) && rowdot &&
-                (knobs().additive_fused == 2 || additive_fused_tiles(n_seq, L) >= 512);
-  if (afused) {
-    AdditiveFusedArgs af{};
-    af.x = x16 ? x32 : x; af.ids = x16 ? nullptr : ids; af.mask = x16 ? m32 : m;
-    af.w1 = pool->w1; af.b1 = pool->b1; af.w2 = pool->w2; af.b2 = pool->b2;
-    af.y = head ? pb : y;
-    af.ldy = D;
-    af.hm = m ? hm : nullptr;
-    af.n_seq = n_seq;
-    af.S = L; af.D = D; af.A = A;
-    afused = additive_fused_ready(af);
-    if (afused) {
-      const double fl = (double)n_seq * (2.0 * L * D * A + 2.0 * L * (A + D));
-      ProfScope ps(3, fl, stream);
-      if (!x16) XNRS_TRY(launch_additive_fused(af, stream));
-      for (int64_t c0 = 0; x16 && c0 < n_seq; c0 += p.chunk) {  // bf16 table: pass by pass on the widened rows (the same bits)
-        AdditiveFusedArgs ac = af;
-        ac.n_seq = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
-        ac.y = af.y + c0 * (int64_t)D;
-        ac.hm = af.hm ? af.hm + c0 : nullptr;
-        XNRS_TRY(widen_pass(c0, ac.n_seq, true));
-        XNRS_TRY(launch_additive_fused(ac, stream));
-      }
-    }
-  }
-
-  // bf16-split GEMM modes: split the weights ONCE per call (the chunk loop below reuses them ~20 times per step)
-  const unsigned short* pqkv[3] = {nullptr, nullptr, nullptr};
-  const unsigned short *po = nullptr, *p1 = nullptr;
+  const float* xal = r.x16 ? at(r.ws, p.off_x32) : r.x;  // the rows whose alignment the predicates ask about
+  rt.rowdot = additive && !r.train && !rt.fused && fc1_rowdot_ok(xal, r.att != nullptr, r.pool, r.D);
+  rt.afused = additive_fused_route(r, p, A, rt.rowdot, af);
   // (bf16 table: the direct route multiplies the bf16 rows with the planes of Wq | Wk | Wv in EVERY mode)
-  const bool want_a16 = x16 && att && additive && !fused && knobs().gemm_a16;
-  if (gemm_mode() != 0 || want_a16) {
-    char* pw = at<char>(w, p.off_planes);
-    auto prep = [&](const float* W, int N, int K) -> const unsigned short* {
-      unsigned short* dst = reinterpret_cast<unsigned short*>(pw);
-      pw += align_up(split_planes_bytes(N, K));
-      return launch_split_weights(W, N, K, dst, stream) == hipSuccess ? dst : nullptr;
-    };
-    if (att) {
-      pqkv[0] = prep(att->wq, D, D);
-      pqkv[1] = prep(att->wk, D, D);
-      pqkv[2] = prep(att->wv, D, D);
-      if (gemm_mode() != 0) po = prep(att->wo, D, D);
-    }
-    if (pooled && additive && gemm_mode() != 0) p1 = prep(fc1.w, A, D);
-  }
+  rt.a16 = r.x16 && r.att && additive && !rt.fused && knobs().gemm_a16;
   // bf16 table, direct route: Q|K|V of every pass is ONE gemm_a16 product over the bf16 rows.  Decided once per call, from
   // the shape of its first (largest) pass; a shape the kernel refuses takes the widening route.
-  bool direct = false;
-  if (want_a16 && pqkv[0] && pqkv[1] && pqkv[2]) {
-    const int64_t rows0 = (n_seq < p.chunk ? n_seq : p.chunk) * L;
-    direct = gemm_a16_ok(qkv_projection(nullptr, {ids, L}, att, 0, qkv, 3 * (int64_t)D, rows0, D, pqkv), x16);
-  }
-
-  // Short sequences: attention + additive pooling of ALL sequences in one launch (news_fused.hip); only the pooled
-  // vectors leave the CU.  Inference only (nothing is saved for a backward), fp32 arithmetic only.
-  // Dispatch (measured, tools/bench_news_fused.py at D = 320; profiles/r02_news_fused_dispatch_sweep.txt): a workgroup owns
-  // news padded to 32 token rows each, so the kernel wins from ~26 tokens (<= 19 % padding) upwards and once there are
-  // enough news to fill the CUs -- with 1 news per workgroup (two workgroups per CU) from ~200, with 2 news per workgroup
-  // (every weight fragment feeds 4 row tiles) from 512: 256 x 30 tokens 116 vs 149 us for the pipeline, 512 x 30: 177 vs
-  // 217 us, 1024 x 30: 325 vs 329 us.  From ~1500 news on the pipeline is ahead again since it folds the out-projection
-  // behind the pooling (fold_out_projection above; the fused kernel computes it per token): 2048 x 30: 623 vs 592 us,
-  // 28 160 x 30: 8.2 vs 7.1 ms; 64 x 30: 111 vs 104 us, 1024 x 20: 318 vs 255 us.  XNRS_NEWS_FUSED=2 forces the kernel
-  // for every eligible shape (tests), 0 turns it off.
-  if (fused) {
-    const double fl = (double)n_seq * ((f.fold ? 6.0 : 8.0) * L * D * D + 4.0 * L * L * D + 2.0 * L * D * A + 2.0 * L * (A + D));
-    ProfScope ps(6, fl, stream);
-    if (!x16) XNRS_TRY(launch_news_fused(f, stream));
-    for (int64_t c0 = 0; x16 && c0 < n_seq; c0 += p.chunk) {  // bf16 table: pass by pass on the widened rows (the same bits)
-      NewsFusedArgs fc = f;
-      fc.n_seq = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
-      fc.p = f.p + c0 * f.ldp;
-      fc.hm = f.hm ? f.hm + c0 : nullptr;
-      fc.asum = f.asum ? f.asum + c0 : nullptr;
-      XNRS_TRY(widen_pass(c0, fc.n_seq, true));
-      XNRS_TRY(launch_news_fused(fc, stream));
-    }
-  }
+  const unsigned short* pl[3] = {weight_plane(r, p, 0), weight_plane(r, p, 1), weight_plane(r, p, 2)};
+  const int64_t rows0 = (r.n_seq < p.chunk ? r.n_seq : p.chunk) * r.L;
+  rt.direct = rt.a16 && gemm_a16_ok(qkv_projection(nullptr, {r.ids, r.L}, r.att, 0, at(r.ws, p.off_qkv), 3 * (int64_t)r.D, rows0, r.D, pl), r.x16);
   // Live row tiles (inference, the news encoder's pooled calls with a mask; XNRS_GEMM_LIVE_TILES=0: off).  An all-masked
   // sequence -- an empty history slot, 49.5 % of the benchmark's -- has a result that needs none of its rows: every query
   // row is masked, the pooler multiplies every row by 0, the pooled vector is 0.  Its rows are contiguous, so whole
@@ -519,21 +451,16 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   // on (default 16 384 = 128 tiles: the list then pays for itself from ~9 dead tiles, 3.6 us each at D = 768 for the two
   // products).
   // The choice never depends on the data (hipGraph) and changes no bit: a live sequence's rows are computed as before.
-  const bool lt = r.live_tiles && knobs().gemm_live_tiles && !train && pooled && m && att && !fused && !afused &&
-                  n_seq * (int64_t)L >= knobs().gemm_live_tiles_min_rows &&
-                  device_counts_ok(xal, D, A, att, additive ? pool : nullptr);
-  bool lt_qkv = false;
+  const bool lt = r.live_tiles && knobs().gemm_live_tiles && !r.train && r.pooled && r.m && r.att && !rt.fused && !rt.afused &&
+                  n_rows >= knobs().gemm_live_tiles_min_rows &&
+                  device_counts_ok(xal, D, A, r.att, additive ? r.pool : nullptr);
+  MhaCoreArgs probe{};
   if (lt && knobs().mha_skip_masked) {
-    MhaCoreArgs probe = mha_core_args(qkv + D, 3 * (int64_t)D, att, o, p.chunk, L, D);
-    probe.q = qkv;
-    probe.mask = m;
-    probe.skip_dead = 1;
-    lt_qkv = mha_core_skips_dead(probe);
+    probe = mha_core_args(at(r.ws, p.off_qkv) + D, 3 * (int64_t)D, r.att, at(r.ws, p.off_o), p.chunk, L, D);
+    probe.q = at(r.ws, p.off_qkv); probe.mask = r.m; probe.skip_dead = 1;
   }
-  const bool lt_fc1 = lt && additive && rowdot;
-  const int64_t lt_cap = live_tiles_cap(p.chunk, L, LIVE_TILE_BM);
-  const int64_t* lt_n = at<int64_t>(w, p.off_lt_n);
-  const int32_t* lt_tiles = at<int32_t>(w, p.off_lt_tiles);
+  rt.lt_qkv = probe.skip_dead && mha_core_skips_dead(probe);
+  rt.lt_fc1 = lt && additive && rt.rowdot;
   // Live rows (the second half of the same saving; XNRS_GEMM_LIVE_ROWS=0: off).  A masked token row of a LIVE sequence stays
   // a key and a value (the mask is a query-row mask, layers.py:142-144), but its Q row feeds only its own attention row and
   // its fc1 row only its own score -- and both poolers multiply that row by exactly 0.  So wherever a product walks the
@@ -545,34 +472,11 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   //          masked token's score (AdditivePoolArgs::skip_masked), so its summation order -- and every bit -- is unchanged.
   // The lists of every pass come from the ONE list launch of the call (launch_dense_row_lists writes the tile lists too);
   // the grids are sized for every row, the counts stay on the device (GemmArgs::m_dev): nothing depends on the data.
-  const bool lr = lt && knobs().gemm_live_rows && p.off_lr_cnt != 0 && L <= 64 && n_seq * (int64_t)L <= 0x7fffffffLL &&
-                  n_seq * (int64_t)L >= knobs().gemm_live_rows_min_rows;
+  const bool lr = lt && knobs().gemm_live_rows && p.off_lr_cnt != 0 && L <= 64 && n_rows <= 0x7fffffffLL &&
+                  n_rows >= knobs().gemm_live_rows_min_rows;
   // (bf16 table, direct route: Q|K|V stays one product over the live row tiles -- no live-row Q list, no one-launch grid)
-  const bool lr_qkv = lr && lt_qkv && !direct, lr_fc1 = lr && lt_fc1;
-  const int32_t *lr_loc = at<int32_t>(w, p.off_lr_loc), *lr_src = at<int32_t>(w, p.off_lr_src);
-  const int64_t* lr_cnt = at<int64_t>(w, p.off_lr_cnt);
-  constexpr float LR_FILL = 0.3f;  // tile choice only: the share of a pass's rows expected on the list (ragged titles x empty slots)
-  if (lr_qkv || lr_fc1)
-    XNRS_TRY(launch_dense_row_lists(m, ids, n_seq, p.chunk, L, LIVE_TILE_BM, at<int32_t>(w, p.off_lr_loc), at<int32_t>(w, p.off_lr_src),
-                                    at<int64_t>(w, p.off_lr_cnt), at<uint8_t>(w, p.off_lt_alive), at<int64_t>(w, p.off_lt_n),
-                                    at<int32_t>(w, p.off_lt_tiles), stream));
-  else if (lt_qkv || lt_fc1)
-    XNRS_TRY(launch_live_tiles(m, ids, n_seq, p.chunk, L, LIVE_TILE_BM, at<uint8_t>(w, p.off_lt_alive), at<int64_t>(w, p.off_lt_n),
-                               at<int32_t>(w, p.off_lt_tiles), stream));
-  // launch timer on: the live-tile (and live-row) counts of every pass, read back ONCE per call (the timer is a measurement
-  // aid that synchronises anyway; nothing is read while it is off) -- stages 0 and 3 then report EXECUTED FLOPs
-  std::vector<int64_t> lt_host, lr_host;
-  if ((lt_qkv && prof_on(0)) || (lt_fc1 && prof_on(3))) {
-    lt_host.resize((size_t)((n_seq + p.chunk - 1) / p.chunk));
-    if (hipStreamSynchronize(stream) != hipSuccess ||
-        hipMemcpy(lt_host.data(), lt_n, lt_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
-      lt_host.clear();
-    if (lr_qkv || lr_fc1) {
-      lr_host.resize(3 * lt_host.size());
-      if (lt_host.empty() || hipMemcpy(lr_host.data(), lr_cnt, lr_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        lr_host.clear();
-    }
-  }
+  rt.lr_qkv = lr && rt.lt_qkv && !rt.direct;
+  rt.lr_fc1 = lr && rt.lt_fc1;
   // fc1 in the tail (XNRS_GEMM_FC1_IN_TAIL=0: off).  Where a pass takes the one-launch projection and its fc1 walks the
   // live-row list over the O rows (folded out-projection), fc1 + pooling of pass i-1 wait until pass i has been projected:
   //   launch{ K|V(i), Q(i), fc1(i-1) }  ->  pool(i-1)  ->  mha(i)          (after the last pass: fc1 and pool on their own)
@@ -580,249 +484,356 @@ int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
   // o and t of pass i-1 are read before mha(i) overwrites o, the image of pass i is written after mha(i-1) has read it, the
   // row lists of every pass are in the workspace already.  Decided from shapes and knobs alone; a call with ids, a bf16
   // table or the stage-3 timer on (an fc1 without a launch of its own has no time to report) keeps the sequence above.
-  const bool tail = lr_qkv && lr_fc1 && fold && pooled && !ids && !x16 && !qkv_given && !live && knobs().gemm_fc1_in_tail &&
-                    !prof_on(3);
-  // the pooling stage of one pass (what fc1 left in t -> pooled vector, history mask)
-  auto pool_pass = [&](int64_t c0, int64_t nc, const float* cm, const int32_t* cids, const float* seq, const int32_t* seq_ids) -> int32_t {
-    AdditivePoolArgs pa = additive_pool_args(t, rowdot, pool, seq, nc, L, D, A);
-    pa.skip_dead = lt_fc1 ? 1 : 0;
-    pa.skip_masked = lr_fc1 ? 1 : 0;
-    pa.mask = cm;
-    pa.mask_gather_ids = cids;
-    pa.x_gather_ids = seq_ids;
-    pa.y = fold ? pob + c0 * (int64_t)D : (head ? pb : y) + c0 * (int64_t)D;
-    pa.asum_out = fold ? asum + c0 : nullptr;
-    pa.a_out = a_save ? a_save : (a_out ? a_out + c0 * (int64_t)L : nullptr);
-    pa.hm_out = (cm && hm) ? hm + c0 : nullptr;
-    {
-      ProfScope ps(4, 2.0 * (double)(nc * L) * (double)(A + D), stream);
-      XNRS_TRY(launch_additive_pool(pa, stream));
-    }
-    if (a_save && a_out)
-      XNRS_TRY(hipMemcpyAsync(a_out, a_save, (size_t)(nc * L) * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    return XNRS_OK;
-  };
-  struct {
-    bool on = false;  // fc1 + pooling of a pass are outstanding
-    GemmArgs fg;
-    int64_t c0 = 0, nc = 0;
-    const float* cm = nullptr;
-  } pend;
-  // ... on their own: the last pass of a call, or a pass whose successor does not take the merged launch
-  auto drain = [&]() -> int32_t {
-    if (!pend.on) return XNRS_OK;
-    pend.on = false;
-    XNRS_TRY(launch_gemm_f32(pend.fg, stream));
-    return pool_pass(pend.c0, pend.nc, pend.cm, nullptr, o, nullptr);
-  };
-  for (int64_t c0 = 0; !fused && !afused && c0 < n_seq; c0 += p.chunk) {
-    const int64_t nc = (n_seq - c0 < p.chunk) ? (n_seq - c0) : p.chunk;
-    const int64_t rows = nc * L;
-    // this pass's live row tiles, and the rows they hold for the launch timer (executed FLOPs: live tiles x tile height)
-    const int64_t* ltn = lt_n + c0 / p.chunk;
-    const int32_t* ltl = lt_tiles + (c0 / p.chunk) * lt_cap;
-    const double lt_rows = (double)LIVE_TILE_BM *
-                           (double)(lt_host.empty() ? (rows + LIVE_TILE_BM - 1) / LIVE_TILE_BM : lt_host[(size_t)(c0 / p.chunk)]);
-    // this pass's live rows: the list in its own row space, in x's (the table's with ids), the count, and -- timer -- its value
-    const int32_t* lrl = lr_loc + (c0 / p.chunk) * p.chunk * L;
-    const int32_t* lrs = lr_src + (c0 / p.chunk) * p.chunk * L;
-    const int64_t* lrn = lr_cnt + 3 * (c0 / p.chunk);
-    const double lr_rows = lr_host.empty() ? (double)rows : (double)lr_host[(size_t)(3 * (c0 / p.chunk))];
-    // this chunk's view of the inputs
-    const int32_t* cids = ids ? ids + c0 : nullptr;
-    const float* cx = ids ? x : x + c0 * (int64_t)L * D;      // table stays whole when gathering
-    const float* cm = m ? (ids ? m : m + c0 * (int64_t)L) : nullptr;
-    const int32_t* xids = cids;       // gather for the token rows (the mask rows always follow cids)
-    if (x16) {  // bf16 table: the direct route reads it in the projection alone; every other call runs on this pass's widened rows
-      cx = direct ? nullptr : x32;
-      xids = direct ? cids : nullptr;
-      if (!direct) XNRS_TRY(widen_pass(c0, nc, false));
-    }
+  rt.tail = rt.lr_qkv && rt.lr_fc1 && rt.fold && r.pooled && !r.ids && !r.x16 && knobs().gemm_fc1_in_tail && !prof_on(3);
+  // launch timer on: the live-tile (and live-row) counts of every pass, read back ONCE per call (the timer is a measurement
+  // aid that synchronises anyway; nothing is read while it is off) -- stages 0 and 3 then report EXECUTED FLOPs
+  rt.read_counts = (rt.lt_qkv && prof_on(0)) || (rt.lt_fc1 && prof_on(3));
+  // an all-masked sequence: zeros instead of attention over keys nobody weights (kernels.h).  Training over row lists,
+  // and (round 4) every POOLED call with a mask: both poolers multiply a masked row by exactly 0 (layers.py:33,62-65), so
+  // the pooled vector is bit for bit the same whether such a row holds the uniform average of V or zeros -- the empty
+  // history slots of the benchmark batch (49.5 % of its news) cost the attention core nothing.  MultiHeadAttention
+  // alone (pooled == false) returns its masked rows to the caller and computes them.
+  rt.skip_dead = rt.live || (r.pooled && r.m && knobs().mha_skip_masked);
+  return rt;
+}
 
-    const float* seq = cx;            // what the pooler sees
-    const int32_t* seq_ids = xids;    // gather for the pooler's value rows
-    if (att) {
-      const int64_t ld3 = 3 * (int64_t)D;
-      if (qkv_given) {
-        // nothing to project
-      } else if (live) {  // K|V of every row (kvl: of the rows of the non-empty news), Q of the live rows only (dead rows = 0)
-        const double nl = (double)prof_count(0, cnt, 0, n_live, stream), nkv = (double)prof_count(0, cnt, 1, n_kv, stream);
-        ProfScope ps(0, 2.0 * (kvl ? nkv : rows) * 2.0 * D * D + 2.0 * nl * (double)D * D, stream);
-        GemmArgs g = qkv_projection(cx, {xids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
-        if (kvl) {
-          XNRS_TRY(launch_zero_dead_qkv(qkv, cm, cids, nc, L, D, stream));
-          g.gather_ids = kvx;
-          g.gather_S = 1;
-          g.c_scatter = 1;
-          g.c_scatter_ids = kv_rows;
-          g.M = n_kv;
-          g.m_dev = cnt ? cnt + 1 : nullptr;
-          g.m_fill_hint = 0.6f;
-          if (n_kv > 0) XNRS_TRY(launch_gemm_f32(g, stream));
-        } else {
-          XNRS_TRY(launch_gemm_f32(g, stream));
-          XNRS_TRY(launch_zero_cols(qkv, ld3, D, rows, stream));
-        }
-        if (n_live > 0) {
-          GemmArgs q = gemm_linear(cx, {lvx, 1}, D, att->wq, att->bq, qkv, ld3, n_live, D, D, XNRS_ACT_NONE, pqkv[0]);
-          q.c_scatter = 1;
-          q.c_scatter_ids = live_rows;
-          q.m_dev = cnt;
-          q.m_fill_hint = 0.4f;
-          XNRS_TRY(launch_gemm_f32(q, stream));
-        }
-      } else if (lr_qkv) {  // K|V of the live row tiles, Q of the live rows: a masked token's Q row stays unwritten, nobody reads it
-        GemmArgs g = qkv_projection(cx, {xids, L}, att, 1, qkv + D, ld3, rows, D, pqkv);
-        g.live_n = ltn;
-        g.live_tiles = ltl;
-        GemmArgs q = gemm_linear(cx, {xids ? lrs : lrl, 1}, D, att->wq, att->bq, qkv, ld3, rows, D, D);
-        q.c_scatter = 1;
-        q.c_scatter_ids = lrl;
-        q.m_dev = lrn;
-        q.m_fill_hint = LR_FILL;
-        // the two read the same x and write disjoint columns of the image: ONE grid, the Q tiles behind the K|V tiles, leaves
-        // one partly filled last round of workgroups instead of two and a launch boundary (XNRS_GEMM_QKV_ONE_LAUNCH=0: two
-        // launches; the same bits either way, and the same choice for every pass of the call whatever the data)
-        const bool one = gemm_qkv_one_launch_ok(g, q);
-        // (fc1 in the tail) the outstanding fc1 rides in this launch if it can; otherwise it and its pooling run first, as before
-        const bool merged = tail && one && (!pend.on || gemm_fc1_in_tail_ok(pend.fg));
-        if (!merged) XNRS_TRY_RC(drain());
-        {
-          // (on the merged route the stage's time includes the fc1 tiles in the launch's tail; its FLOPs stay those of K|V + Q)
-          ProfScope ps(0, 2.0 * lt_rows * 2.0 * D * D + 2.0 * lr_rows * (double)D * D, stream);
-          if (merged) {
-            XNRS_TRY(launch_gemm_qkv_fc1(g, q, pend.on ? &pend.fg : nullptr, stream));
-            qkv_launches_add(1);
-            if (pend.on) fc1_in_tail_add(1);
-          } else if (one) {
-            XNRS_TRY(launch_gemm_qkv_one(g, q, stream));
-            qkv_launches_add(1);
-          } else {
-            XNRS_TRY(launch_gemm_f32(g, stream));
-            XNRS_TRY(launch_gemm_f32(q, stream));
-            qkv_launches_add(2);
-          }
-        }
-        if (pend.on) {  // (merged) the scores of the previous pass are out: pool it before the attention below overwrites its O rows
-          pend.on = false;
-          XNRS_TRY_RC(pool_pass(pend.c0, pend.nc, pend.cm, nullptr, o, nullptr));
-        }
-      } else {
-        GemmArgs g = qkv_projection(cx, {xids, L}, att, 0, qkv, ld3, rows, D, pqkv);
-        if (lt_qkv) {  // the rows of the dead tiles stay unwritten: the attention kernel below never reads them
-          g.live_n = ltn;
-          g.live_tiles = ltl;
-        }
-        ProfScope ps(0, 2.0 * (lt_qkv ? lt_rows : (double)rows) * 3.0 * D * D, stream);
-        if (direct) XNRS_TRY(launch_gemm_a16(g, x16, stream));
-        else XNRS_TRY(launch_gemm_f32(g, stream));
-      }
+// ---- the context of one call: what its stages share, resolved once (prepare_weights and run_passes complete it)
+struct Call {
+  const SeqEncode& r;
+  hipStream_t stream;
+  const Plan p;
+  const Route rt;
+  NewsFusedArgs nf; AdditiveFusedArgs af;  // the launch of Route::fused / afused
+  const int L = r.L, D = r.D, A = hidden_of(r);
+  const xnrs_mha_params* att = r.att;
+  // training lists (xnrs_row_lists; lvx, kvx: as rows of x, table rows with ids).  Counts on the device (counts_dev): the list
+  // lengths are then CAPACITIES (every row), the products over a list read their row count on the device (GemmArgs::m_dev)
+  const xnrs_row_lists rl = r.rl ? *r.rl : xnrs_row_lists{};
+  const int32_t *lvx = rt.live ? (r.ids ? rl.live_src_rows : rl.live_rows) : nullptr, *kvx = rt.kvl ? (r.ids ? rl.kv_src_rows : rl.kv_rows) : nullptr;
+  const int64_t* cnt = rl.counts_dev;
+  const int64_t n_live = cnt ? r.n_seq * L : rl.n_live, n_kv = cnt ? r.n_seq * L : rl.n_kv;
+  float *qkv = rt.qkv_given ? const_cast<float*>(rl.qkv_shared) : at(r.ws, p.off_qkv), *o = at(r.ws, p.off_o), *yb = at(r.ws, p.off_y);
+  float *t = at(r.ws, p.off_t), *pb = at(r.ws, p.off_p), *hb = at(r.ws, p.off_h), *pob = at(r.ws, p.fold.po), *asum = at(r.ws, p.fold.as);
+  float *stats = (r.train && att) ? at(r.ws, p.off_stats) : nullptr, *a_save = (r.train && is_additive(r)) ? at(r.ws, p.off_a) : nullptr;
+  float *x32 = at(r.ws, p.off_x32), *m32 = at(r.ws, p.off_m32);
+  const int64_t lt_cap = live_tiles_cap(p.chunk, L, LIVE_TILE_BM);
+  uint8_t* lt_alive = at<uint8_t>(r.ws, p.off_lt_alive);
+  int64_t *lt_n = at<int64_t>(r.ws, p.off_lt_n), *lr_cnt = at<int64_t>(r.ws, p.off_lr_cnt);
+  int32_t *lt_tiles = at<int32_t>(r.ws, p.off_lt_tiles), *lr_loc = at<int32_t>(r.ws, p.off_lr_loc), *lr_src = at<int32_t>(r.ws, p.off_lr_src);
+  std::vector<int64_t> lt_host{}, lr_host{};  // launch timer: host copies of the counts (empty: not read)
+  Fc1 fc1{};
+  const unsigned short *pqkv[3] = {nullptr, nullptr, nullptr}, *po = nullptr, *p1 = nullptr;
+};
 
-      MhaCoreArgs ma = mha_core_args(qkv + D, ld3, att, o, nc, L, D);
-      ma.q = qkv;
-      ma.mask = cm;
-      ma.mask_gather_ids = cids;
-      ma.dropout_p = att->dropout_p;
-      // the kernels count (sequence, head) pairs from the launch's first sequence (kernels.h drop_uniform): a pass that starts
-      // at sequence c0 continues the counter at pair c0 * heads, so sequence c0 + i draws what it draws in an unchunked call.
-      ma.seed = att->seed + (uint64_t)c0 * (uint64_t)att->n_heads * 0x9E3779B97F4A7C15ull;
-      ma.seed_dev = att->seed_dev;
-      ma.stats = stats;
-      // an all-masked sequence: zeros instead of attention over keys nobody weights (kernels.h).  Training over row lists,
-      // and (round 4) every POOLED call with a mask: both poolers multiply a masked row by exactly 0 (layers.py:33,62-65), so
-      // the pooled vector is bit for bit the same whether such a row holds the uniform average of V or zeros -- the empty
-      // history slots of the benchmark batch (49.5 % of its news) cost the attention core nothing.  MultiHeadAttention
-      // alone (pooled == false) returns its masked rows to the caller and computes them.
-      ma.skip_dead = (live || (pooled && cm && knobs().mha_skip_masked)) ? 1 : 0;
-      if (lt_qkv && !mha_core_skips_dead(ma)) return XNRS_EUNSUPPORTED;  // (never: the two are decided by one rule)
-      {
-        ProfScope ps(1, 4.0 * rows * (double)L * D, stream);
-        XNRS_TRY(launch_mha_core(ma, stream));
-      }
+// plane i of the region <- the split of W [N][D]; nullptr if the split did not launch (a product then does without the plane)
+const unsigned short* split_plane(const Call& c, const float* W, int N, int i) {
+  return launch_split_weights(W, N, c.D, weight_plane(c.r, c.p, i), c.stream) == hipSuccess ? weight_plane(c.r, c.p, i) : nullptr;
+}
+// The weights of a call: the fold-weight build, then -- it reads fc1.w -- the split planes.
+int32_t prepare_weights(Call* c) {
+  const Route& rt = c->rt;
+  XNRS_TRY_RC(fc1_pair(rt.fold, c->att, is_additive(c->r) ? c->r.pool : nullptr, c->D, c->r.ws, c->p.fold, c->stream, &c->fc1));
+  if (rt.fold && rt.fused) {  // the fused kernel's fc1 image is built from the folded pair
+    c->nf.w1 = c->fc1.w; c->nf.b1 = c->fc1.b;
+  }
+  // bf16-split GEMM modes: split the weights ONCE per call (the pass loop reuses them ~20 times per step)
+  if (gemm_mode() == 0 && !rt.a16) return XNRS_OK;
+  if (c->att) {  // (direct route: launch_gemm_a16 refuses a product whose plane is missing)
+    const float* W[3] = {c->att->wq, c->att->wk, c->att->wv};
+    for (int i = 0; i < 3; ++i) c->pqkv[i] = split_plane(*c, W[i], c->D, i);
+    if (gemm_mode() != 0) c->po = split_plane(*c, c->att->wo, c->D, 3);
+  }
+  if (c->A && gemm_mode() != 0) c->p1 = split_plane(*c, c->fc1.w, c->A, c->att ? 4 : 0);
+  return XNRS_OK;
+}
 
-      float* dst = pooled ? yb : y + c0 * (int64_t)L * D;
-      if (fold) {
-        dst = o;  // the pooler works on the O rows (fold_out_projection); masked rows of O are finite and carry weight 0
-      } else if (live) {
-        ProfScope ps(2, 2.0 * (double)prof_count(2, cnt, 0, n_live, stream) * (double)D * D, stream);
-        XNRS_TRY(hipMemsetAsync(dst, 0, (size_t)rows * D * sizeof(float), stream));
-        if (n_live > 0) {
-          GemmArgs og = gemm_linear(o, {live_rows, 1}, D, att->wo, att->bo, dst, D, n_live, D, D, XNRS_ACT_NONE, po);
-          og.c_scatter = 1;
-          og.m_dev = cnt;
-          og.m_fill_hint = 0.4f;
-          XNRS_TRY(launch_gemm_f32(og, stream));
-        }
-      } else {
-        ProfScope ps(2, 2.0 * rows * (double)D * D, stream);
-        XNRS_TRY(launch_gemm_f32(gemm_linear(o, {}, D, att->wo, att->bo, dst, D, rows, D, D, XNRS_ACT_NONE, po), stream));
-      }
-      seq = dst;
-      seq_ids = nullptr;
-    }
-    if (!pooled) continue;
+// ---- Pass: the view of the sequences [c0, c0 + nc) of a call (make_pass)
+struct Pass {
+  int64_t c0, nc, rows;
+  const float *cx, *cm;        // the pass's token rows (the whole table when gathering) and mask rows
+  const int32_t *cids, *xids;  // gather for the mask rows; gather for the token rows
+  // what the pooler sees, and the gather for it: the token rows, behind an attention tower its output (out_project)
+  const float* seq; const int32_t* seq_ids;
+  // its live row tiles (count, list; timer: the rows they hold) and live rows (in its own row space, in x's, count; timer: its value)
+  const int64_t *ltn, *lrn;
+  const int32_t *ltl, *lrl, *lrs;
+  double lt_rows, lr_rows;
+};
 
-    float* pooled_dst = (head ? pb : y) + c0 * (int64_t)D;
-    float* hm_dst = hm ? hm + c0 : nullptr;
-    if (additive) {
-      if (live) {  // with attention seq is the dense attention output; without, the rows of x (table rows with ids: lvx)
-        ProfScope ps(3, 2.0 * (double)prof_count(3, cnt, 0, n_live, stream) * (double)D * A, stream);
-        XNRS_TRY(hipMemsetAsync(t, 0, (size_t)rows * A * sizeof(float), stream));
-        if (n_live > 0) {
-          GemmArgs fg = fc1_product(seq, {att ? live_rows : lvx, 1}, fc1, t, n_live, D, A, false, pool, p1);
-          fg.c_scatter = 1;
-          fg.c_scatter_ids = live_rows;
-          fg.m_dev = cnt;
-          fg.m_fill_hint = 0.4f;
-          XNRS_TRY(launch_gemm_f32(fg, stream));
-        }
-      } else if (lr_fc1) {  // the scores of the live rows, in place; the pooler below reads no other
-        GemmArgs fg = fc1_product(seq, {seq_ids ? lrs : lrl, 1}, fc1, t, rows, D, A, true, pool, p1);
-        fg.c_scatter = 1;
-        fg.c_scatter_ids = lrl;
-        fg.m_dev = lrn;
-        fg.m_fill_hint = LR_FILL;
-        if (tail) {  // fc1 in the tail: this pass's fc1 goes out with the next pass's projection, its pooling right behind it
-          pend.on = true;
-          pend.fg = fg;
-          pend.c0 = c0;
-          pend.nc = nc;
-          pend.cm = cm;
-          continue;
-        }
-        ProfScope ps(3, 2.0 * lr_rows * (double)D * A, stream);
-        XNRS_TRY(launch_gemm_f32(fg, stream));
-      } else {
-        GemmArgs fg = fc1_product(seq, {seq_ids, L}, fc1, t, rows, D, A, rowdot, pool, p1);
-        if (lt_fc1) {  // the scores of the dead tiles stay unwritten: the pooler below leaves their sequences first
-          fg.live_n = ltn;
-          fg.live_tiles = ltl;
-        }
-        ProfScope ps(3, 2.0 * (lt_fc1 ? lt_rows : (double)rows) * (double)D * A, stream);
-        XNRS_TRY(launch_gemm_f32(fg, stream));
-      }
-      XNRS_TRY_RC(pool_pass(c0, nc, cm, cids, seq, seq_ids));
+// The pass from sequence c0 on (`step` sequences, fewer in the last).  bf16 table: every route but the direct one runs on its WIDENED
+// rows, enqueued here -- before anything reads x32 / m32, which the next pass reuses (a one-launch kernel: and its gathered mask rows)
+int32_t make_pass(const Call& c, int64_t c0, int64_t step, Pass* ps) {
+  const SeqEncode& r = c.r;
+  const int64_t i = c0 / c.p.chunk;
+  ps->c0 = c0; ps->nc = (r.n_seq - c0 < step) ? (r.n_seq - c0) : step; ps->rows = ps->nc * c.L;
+  ps->ltn = c.lt_n + i; ps->ltl = c.lt_tiles + i * c.lt_cap;
+  ps->lt_rows = (double)LIVE_TILE_BM * (double)(c.lt_host.empty() ? (ps->rows + LIVE_TILE_BM - 1) / LIVE_TILE_BM : c.lt_host[(size_t)i]);
+  ps->lrl = c.lr_loc + i * c.p.chunk * c.L; ps->lrs = c.lr_src + i * c.p.chunk * c.L; ps->lrn = c.lr_cnt + 3 * i;
+  ps->lr_rows = c.lr_host.empty() ? (double)ps->rows : (double)c.lr_host[(size_t)(3 * i)];
+  ps->cids = r.ids ? r.ids + c0 : nullptr; ps->xids = ps->cids;  // gathers for the mask rows and the token rows
+  ps->cx = r.ids ? r.x : r.x + c0 * (int64_t)c.L * c.D;  // table stays whole when gathering
+  ps->cm = r.m ? (r.ids ? r.m : r.m + c0 * (int64_t)c.L) : nullptr;
+  if (r.x16) {  // bf16 table: the direct route reads it in the projection alone; every other call runs on the widened rows
+    ps->cx = c.rt.direct ? nullptr : c.x32; ps->xids = c.rt.direct ? ps->cids : nullptr;
+    if (!c.rt.direct) XNRS_TRY(launch_gather_rows_bf16(r.x16, r.ids + c0, 1, c.x32, ps->nc, (int64_t)c.L * c.D, c.stream));
+    if (c.rt.fused || c.rt.afused) XNRS_TRY(launch_gather_rows(r.m, r.ids + c0, c.m32, ps->nc, c.L, c.stream));
+  }
+  ps->seq = ps->cx; ps->seq_ids = ps->xids;
+  return XNRS_OK;
+}
+
+// The whole call as one kernel (Route::fused / afused).  bf16 table: pass by pass on the widened rows (the same bits).
+int32_t run_one_launch(const Call& c) {
+  const double L = c.L, D = c.D, A = c.A;
+  const double fl = c.rt.fused ? (double)c.r.n_seq * ((c.nf.fold ? 6.0 : 8.0) * L * D * D + 4.0 * L * L * D + 2.0 * L * D * A + 2.0 * L * (A + D))
+                               : (double)c.r.n_seq * (2.0 * L * D * A + 2.0 * L * (A + D));
+  ProfScope ps(c.rt.fused ? 6 : 3, fl, c.stream);
+  const int64_t step = c.r.x16 ? c.p.chunk : c.r.n_seq;
+  Pass pass;
+  for (int64_t c0 = 0; c0 < c.r.n_seq; c0 += step) {
+    XNRS_TRY_RC(make_pass(c, c0, step, &pass));
+    if (c.rt.fused) {
+      NewsFusedArgs f = c.nf;
+      f.n_seq = pass.nc; f.p = c.nf.p + c0 * c.nf.ldp;
+      f.hm = c.nf.hm ? c.nf.hm + c0 : nullptr; f.asum = c.nf.asum ? c.nf.asum + c0 : nullptr;
+      XNRS_TRY(launch_news_fused(f, c.stream));
     } else {
-      MeanPoolArgs mp{};
-      mp.x = seq;
-      mp.ldx = D;
-      mp.mask = cm;
-      mp.mask_gather_ids = cids;
-      mp.x_gather_ids = seq_ids;
-      mp.y = pooled_dst;
-      mp.hm_out = hm_dst;
-      mp.n_seq = nc;
-      mp.N = L;
-      mp.D = D;
-      {
-        ProfScope ps(4, 2.0 * rows * (double)D, stream);
-        XNRS_TRY(launch_mean_pool(mp, stream));
-      }
+      AdditiveFusedArgs a = c.af;
+      a.n_seq = pass.nc; a.y = c.af.y + c0 * (int64_t)c.D; a.hm = c.af.hm ? c.af.hm + c0 : nullptr;
+      XNRS_TRY(launch_additive_fused(a, c.stream));
     }
   }
-  XNRS_TRY_RC(drain());  // (fc1 in the tail) the last pass
+  return XNRS_OK;
+}
+
+// ---- pool: what fc1 left in t -> pooled vector, history mask | masked mean
+int32_t pool_additive(const Call& c, const Pass& pass) {
+  AdditivePoolArgs pa = additive_pool_args(c.t, c.rt.rowdot, c.r.pool, pass.seq, pass.nc, c.L, c.D, c.A);
+  pa.skip_dead = c.rt.lt_fc1 ? 1 : 0; pa.skip_masked = c.rt.lr_fc1 ? 1 : 0;
+  pa.mask = pass.cm; pa.mask_gather_ids = pass.cids; pa.x_gather_ids = pass.seq_ids;
+  pa.y = pooled_dst(c.rt.fold, c.pob, c.r.head, c.pb, c.r.y) + pass.c0 * (int64_t)c.D;
+  pa.asum_out = c.rt.fold ? c.asum + pass.c0 : nullptr;
+  pa.a_out = c.a_save ? c.a_save : (c.r.a_out ? c.r.a_out + pass.c0 * (int64_t)c.L : nullptr);
+  pa.hm_out = (pass.cm && c.r.hm) ? c.r.hm + pass.c0 : nullptr;
+  {
+    ProfScope ps(4, 2.0 * (double)pass.rows * (double)(c.A + c.D), c.stream);
+    XNRS_TRY(launch_additive_pool(pa, c.stream));
+  }
+  if (c.a_save && c.r.a_out)  // (after the pool)
+    XNRS_TRY(hipMemcpyAsync(c.r.a_out, c.a_save, (size_t)pass.rows * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
+  return XNRS_OK;
+}
+int32_t pool_mean(const Call& c, const Pass& pass) {
+  MeanPoolArgs mp{};
+  mp.x = pass.seq; mp.ldx = c.D; mp.x_gather_ids = pass.seq_ids;
+  mp.mask = pass.cm; mp.mask_gather_ids = pass.cids;
+  mp.y = pooled_dst(false, nullptr, c.r.head, c.pb, c.r.y) + pass.c0 * (int64_t)c.D;
+  mp.hm_out = c.r.hm ? c.r.hm + pass.c0 : nullptr;
+  mp.n_seq = pass.nc; mp.N = c.L; mp.D = c.D;
+  ProfScope ps(4, 2.0 * pass.rows * (double)c.D, c.stream);
+  return hip_rc(launch_mean_pool(mp, c.stream));
+}
+
+// ---- fc1 in the tail (Route::tail): the deferred fc1 + pooling of the previous pass,
+//   launch{ K|V(i), Q(i), fc1(i-1) }  ->  pool(i-1)  ->  mha(i)          (after the last pass: fc1 and pool on their own)
+struct DeferredFc1 {
+  bool on = false;  // fc1 + pooling of a pass are outstanding
+  GemmArgs fg; Pass pass;  // its fc1 goes out with the next pass's projection, its pooling right behind it
+  void defer(const GemmArgs& g, const Pass& of) { on = true; fg = g; pass = of; }
+  // rode: the projection launch carried fc1, its scores are out -- pool the pass before the next attention overwrites its O
+  // rows.  Else fc1 and pooling on their own: the last pass of a call, or a successor that does not take the merged launch
+  int32_t flush(const Call& c, bool rode) {
+    if (!on) return XNRS_OK;
+    on = false;
+    if (!rode) XNRS_TRY(launch_gemm_f32(fg, c.stream));
+    return pool_additive(c, pass);
+  }
+};
+
+// ---- project: [Q|]K|V of a pass into the image c.qkv
+// (training lists) K|V of every row (kvl: of the rows of the non-empty news), Q of the live rows only (dead rows = 0)
+int32_t project_train_lists(const Call& c, const Pass& pass) {
+  const int D = c.D;
+  const int64_t ld3 = 3 * (int64_t)D;
+  const double nl = (double)prof_count(0, c.cnt, 0, c.n_live, c.stream), nkv = (double)prof_count(0, c.cnt, 1, c.n_kv, c.stream);
+  ProfScope ps(0, 2.0 * (c.rt.kvl ? nkv : pass.rows) * 2.0 * D * D + 2.0 * nl * (double)D * D, c.stream);
+  GemmArgs g = qkv_projection(pass.cx, {pass.xids, c.L}, c.att, 1, c.qkv + D, ld3, pass.rows, D, c.pqkv);
+  if (c.rt.kvl) {
+    XNRS_TRY(launch_zero_dead_qkv(c.qkv, pass.cm, pass.cids, pass.nc, c.L, D, c.stream));
+    over_row_list(&g, c.kvx, c.rl.kv_rows, c.n_kv, c.cnt ? c.cnt + 1 : nullptr, 0.6f);
+    if (c.n_kv > 0) XNRS_TRY(launch_gemm_f32(g, c.stream));
+  } else {
+    XNRS_TRY(launch_gemm_f32(g, c.stream));
+    XNRS_TRY(launch_zero_cols(c.qkv, ld3, D, pass.rows, c.stream));
+  }
+  if (c.n_live <= 0) return XNRS_OK;
+  GemmArgs q = gemm_linear(pass.cx, {}, D, c.att->wq, c.att->bq, c.qkv, ld3, 0, D, D, XNRS_ACT_NONE, c.pqkv[0]);
+  over_row_list(&q, c.lvx, c.rl.live_rows, c.n_live, c.cnt, 0.4f);
+  return hip_rc(launch_gemm_f32(q, c.stream));
+}
+// (live rows, "lr_qkv") K|V of the live row tiles, Q of the live rows: a masked token's Q row stays unwritten, nobody reads it
+int32_t project_live_rows(const Call& c, const Pass& pass, DeferredFc1* prev) {
+  const int D = c.D;
+  GemmArgs g = qkv_projection(pass.cx, {pass.xids, c.L}, c.att, 1, c.qkv + D, 3 * (int64_t)D, pass.rows, D, c.pqkv);
+  over_live_tiles(&g, pass.ltn, pass.ltl);
+  GemmArgs q = gemm_linear(pass.cx, {}, D, c.att->wq, c.att->bq, c.qkv, 3 * (int64_t)D, 0, D, D);
+  over_row_list(&q, pass.xids ? pass.lrs : pass.lrl, pass.lrl, pass.rows, pass.lrn, LR_FILL);
+  // the two read the same x and write disjoint columns of the image: ONE grid, the Q tiles behind the K|V tiles, leaves
+  // one partly filled last round of workgroups instead of two and a launch boundary (XNRS_GEMM_QKV_ONE_LAUNCH=0: two
+  // launches; the same bits either way, and the same choice for every pass of the call whatever the data)
+  const bool one = gemm_qkv_one_launch_ok(g, q);
+  // (fc1 in the tail) the outstanding fc1 rides in this launch if it can; otherwise it and its pooling run first, as before
+  const bool merged = c.rt.tail && one && (!prev->on || gemm_fc1_in_tail_ok(prev->fg));
+  if (!merged) XNRS_TRY_RC(prev->flush(c, false));
+  {
+    // (on the merged route the stage's time includes the fc1 tiles in the launch's tail; its FLOPs stay those of K|V + Q)
+    ProfScope ps(0, 2.0 * pass.lt_rows * 2.0 * D * D + 2.0 * pass.lr_rows * (double)D * D, c.stream);
+    if (merged) {
+      XNRS_TRY(launch_gemm_qkv_fc1(g, q, prev->on ? &prev->fg : nullptr, c.stream));
+      if (prev->on) fc1_in_tail_add(1);
+    } else if (one) {
+      XNRS_TRY(launch_gemm_qkv_one(g, q, c.stream));
+    } else {
+      XNRS_TRY(launch_gemm_f32(g, c.stream));
+      XNRS_TRY(launch_gemm_f32(q, c.stream));
+    }
+    qkv_launches_add(one ? 1 : 2);
+  }
+  return prev->flush(c, true);
+}
+int32_t project(const Call& c, const Pass& pass, DeferredFc1* prev) {
+  if (c.rt.qkv_given) return XNRS_OK;  // nothing to project
+  if (c.rt.live) return project_train_lists(c, pass);
+  if (c.rt.lr_qkv) return project_live_rows(c, pass, prev);
+  // (dense) Q|K|V as one product
+  GemmArgs g = qkv_projection(pass.cx, {pass.xids, c.L}, c.att, 0, c.qkv, 3 * (int64_t)c.D, pass.rows, c.D, c.pqkv);
+  if (c.rt.lt_qkv) over_live_tiles(&g, pass.ltn, pass.ltl);  // dead tiles stay unwritten: the attention kernel never reads their rows
+  ProfScope ps(0, 2.0 * (c.rt.lt_qkv ? pass.lt_rows : (double)pass.rows) * 3.0 * c.D * c.D, c.stream);
+  return hip_rc(c.rt.direct ? launch_gemm_a16(g, c.r.x16, c.stream) : launch_gemm_f32(g, c.stream));
+}
+
+// ---- attend: O = softmax(rowmask(QK^T/sqrt(dk))) V over the image
+int32_t attend(const Call& c, const Pass& pass) {
+  MhaCoreArgs ma = mha_core_args(c.qkv + c.D, 3 * (int64_t)c.D, c.att, c.o, pass.nc, c.L, c.D);
+  ma.q = c.qkv; ma.mask = pass.cm; ma.mask_gather_ids = pass.cids; ma.dropout_p = c.att->dropout_p;
+  // the kernels count (sequence, head) pairs from the launch's first sequence (kernels.h drop_uniform): a pass that starts
+  // at sequence c0 continues the counter at pair c0 * heads, so sequence c0 + i draws what it draws in an unchunked call.
+  ma.seed = c.att->seed + (uint64_t)pass.c0 * (uint64_t)c.att->n_heads * 0x9E3779B97F4A7C15ull;
+  ma.seed_dev = c.att->seed_dev; ma.stats = c.stats; ma.skip_dead = c.rt.skip_dead ? 1 : 0;
+  if (c.rt.lt_qkv && !mha_core_skips_dead(ma)) return XNRS_EUNSUPPORTED;  // (never: the two are decided by one rule)
+  ProfScope ps(1, 4.0 * pass.rows * (double)c.L * c.D, c.stream);
+  return hip_rc(launch_mha_core(ma, c.stream));
+}
+
+// ---- out-project: Y = O.Wo^T + bo; what the pooler sees from here on (pass->seq)
+// (training lists) over the live rows in place, the dead rows zeroed
+int32_t out_project_train_lists(const Call& c, const Pass& pass, float* dst) {
+  const int D = c.D;
+  ProfScope ps(2, 2.0 * (double)prof_count(2, c.cnt, 0, c.n_live, c.stream) * (double)D * D, c.stream);
+  XNRS_TRY(hipMemsetAsync(dst, 0, (size_t)pass.rows * D * sizeof(float), c.stream));
+  if (c.n_live <= 0) return XNRS_OK;
+  GemmArgs og = gemm_linear(c.o, {}, D, c.att->wo, c.att->bo, dst, D, 0, D, D, XNRS_ACT_NONE, c.po);
+  over_row_list(&og, c.rl.live_rows, nullptr, c.n_live, c.cnt, 0.4f);
+  return hip_rc(launch_gemm_f32(og, c.stream));
+}
+int32_t out_project(const Call& c, Pass* pass) {
+  // fold: the pooler works on the O rows (fold_out_projection); masked rows of O are finite and carry weight 0
+  float* dst = c.rt.fold ? c.o : (c.r.pooled ? c.yb : c.r.y + pass->c0 * (int64_t)c.L * c.D);
+  pass->seq = dst; pass->seq_ids = nullptr;
+  if (c.rt.fold) return XNRS_OK;
+  if (c.rt.live) return out_project_train_lists(c, *pass, dst);
+  ProfScope ps(2, 2.0 * pass->rows * (double)c.D * c.D, c.stream);
+  return hip_rc(launch_gemm_f32(gemm_linear(c.o, {}, c.D, c.att->wo, c.att->bo, dst, c.D, pass->rows, c.D, c.D, XNRS_ACT_NONE, c.po), c.stream));
+}
+
+// ---- fc1: T = tanh(seq.W1^T + b1), or the fc2 dots of its rows (rowdot)
+// (training lists) with attention seq is the dense attention output; without, the rows of x (table rows with ids: lvx)
+int32_t fc1_train_lists(const Call& c, const Pass& pass) {
+  ProfScope ps(3, 2.0 * (double)prof_count(3, c.cnt, 0, c.n_live, c.stream) * (double)c.D * c.A, c.stream);
+  XNRS_TRY(hipMemsetAsync(c.t, 0, (size_t)pass.rows * c.A * sizeof(float), c.stream));
+  if (c.n_live <= 0) return XNRS_OK;
+  GemmArgs fg = fc1_product(pass.seq, {}, c.fc1, c.t, 0, c.D, c.A, false, c.r.pool, c.p1);
+  over_row_list(&fg, c.att ? c.rl.live_rows : c.lvx, c.rl.live_rows, c.n_live, c.cnt, 0.4f);
+  return hip_rc(launch_gemm_f32(fg, c.stream));
+}
+// (live rows, "lr_fc1") the scores of the live rows, in place; the pooler reads no other
+GemmArgs fc1_live_rows_args(const Call& c, const Pass& pass) {
+  GemmArgs fg = fc1_product(pass.seq, {}, c.fc1, c.t, 0, c.D, c.A, true, c.r.pool, c.p1);
+  over_row_list(&fg, pass.seq_ids ? pass.lrs : pass.lrl, pass.lrl, pass.rows, pass.lrn, LR_FILL);
+  return fg;
+}
+int32_t fc1_stage(const Call& c, const Pass& pass) {
+  if (c.rt.live) return fc1_train_lists(c, pass);
+  if (c.rt.lr_fc1) {
+    ProfScope ps(3, 2.0 * pass.lr_rows * (double)c.D * c.A, c.stream);
+    return hip_rc(launch_gemm_f32(fc1_live_rows_args(c, pass), c.stream));
+  }
+  // (dense) every row
+  GemmArgs fg = fc1_product(pass.seq, {pass.seq_ids, c.L}, c.fc1, c.t, pass.rows, c.D, c.A, c.rt.rowdot, c.r.pool, c.p1);
+  if (c.rt.lt_fc1) over_live_tiles(&fg, pass.ltn, pass.ltl);  // their scores stay unwritten: the pooler leaves their sequences first
+  ProfScope ps(3, 2.0 * (c.rt.lt_fc1 ? pass.lt_rows : (double)pass.rows) * (double)c.D * c.A, c.stream);
+  return hip_rc(launch_gemm_f32(fg, c.stream));
+}
+
+// ---- the pass loop: the pipeline diagram at the top of this file, once per pass
+int32_t run_passes(Call* call) {
+  const Call& c = *call;
+  const SeqEncode& r = c.r;
+  if (c.rt.lr_qkv || c.rt.lr_fc1)
+    XNRS_TRY(launch_dense_row_lists(r.m, r.ids, r.n_seq, c.p.chunk, r.L, LIVE_TILE_BM, c.lr_loc, c.lr_src, c.lr_cnt, c.lt_alive, c.lt_n,
+                                    c.lt_tiles, c.stream));
+  else if (c.rt.lt_qkv || c.rt.lt_fc1)
+    XNRS_TRY(launch_live_tiles(r.m, r.ids, r.n_seq, c.p.chunk, r.L, LIVE_TILE_BM, c.lt_alive, c.lt_n, c.lt_tiles, c.stream));
+  if (c.rt.read_counts) {
+    call->lt_host.resize((size_t)((r.n_seq + c.p.chunk - 1) / c.p.chunk));
+    if (hipStreamSynchronize(c.stream) != hipSuccess ||
+        hipMemcpy(call->lt_host.data(), c.lt_n, c.lt_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
+      call->lt_host.clear();
+    if (c.rt.lr_qkv || c.rt.lr_fc1) {
+      call->lr_host.resize(3 * c.lt_host.size());
+      if (c.lt_host.empty() || hipMemcpy(call->lr_host.data(), c.lr_cnt, c.lr_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        call->lr_host.clear();
+    }
+  }
+  DeferredFc1 prev;  // (fc1 in the tail)
+  Pass pass;
+  for (int64_t c0 = 0; c0 < r.n_seq; c0 += c.p.chunk) {
+    XNRS_TRY_RC(make_pass(c, c0, c.p.chunk, &pass));
+    if (c.att) {
+      XNRS_TRY_RC(project(c, pass, &prev));  // (fc1 in the tail: ... with fc1 of the previous pass, then its pooling)
+      XNRS_TRY_RC(attend(c, pass));
+      XNRS_TRY_RC(out_project(c, &pass));
+    }
+    if (!r.pooled) continue;
+    if (!is_additive(r)) {
+      XNRS_TRY_RC(pool_mean(c, pass));
+    } else if (c.rt.tail) {
+      prev.defer(fc1_live_rows_args(c, pass), pass);
+    } else {
+      XNRS_TRY_RC(fc1_stage(c, pass));
+      XNRS_TRY_RC(pool_additive(c, pass));
+    }
+  }
+  return prev.flush(c, false);  // (fc1 in the tail) the last pass
+}
+
+}  // namespace
+
+int32_t xnrs::seq_encode(const SeqEncode& r, hipStream_t stream) {
+  if (r.n_seq == 0) return XNRS_OK;
+  XNRS_TRY_RC(check_seq_encode(r));
+  const Plan p = make_plan(r.n_seq, r.L, r.D, hidden_of(r), width_of(r), r.att != nullptr, is_additive(r), r.pooled && r.head, r.pooled,
+                           r.chunk, r.train, r.att ? r.att->n_heads : 0, r.x16 != nullptr);
+  if (p.total > r.ws_bytes || (p.total > 0 && !r.ws)) return XNRS_EWORKSPACE;
+  NewsFusedArgs nf{}; AdditiveFusedArgs af{};
+  const Route rt = make_route(r, p, &nf, &af);
+  Call c{r, stream, p, rt, nf, af};
+  if (c.cnt && rt.live && !device_counts_ok(r.x, r.D, c.A, r.att, r.pool)) return XNRS_EUNSUPPORTED;
+  XNRS_TRY_RC(prepare_weights(&c));
+  XNRS_TRY_RC((rt.fused || rt.afused) ? run_one_launch(c) : run_passes(&c));
   // pooled = Wo (sum_i a_i O_i) + bo (sum_i a_i): one out-projection per sequence (or folded into the head), then the head
-  return pooled_tail(fold, pob, asum, att, pooled ? head : nullptr, pb, hb, y, n_seq, D, E, po, train, stream);
+  return pooled_tail(rt.fold, c.pob, c.asum, r.att, r.pooled ? r.head : nullptr, c.pb, c.hb, r.y, r.n_seq, r.D, width_of(r), c.po,
+                     r.train, stream);
 }
 
 namespace {
@@ -890,6 +901,12 @@ SeqEncode padded_call(const float* x, const float* m, int64_t n_seq, int L, int 
   r.x = x; r.m = m; r.n_seq = n_seq; r.L = L; r.D = D; r.y = y; r.ws = ws; r.ws_bytes = ws_bytes;
   return r;
 }
+int32_t news_encode(SeqEncode r, const int32_t* ids, const xnrs_mha_params* att, int32_t pool_kind, const xnrs_additive_params* pool,
+                    const xnrs_head_params* head, float* hm, int64_t chunk, void* stream) {
+  r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
+  r.live_tiles = true;  // empty history slots are news: whole row tiles of a pass may hold nothing else
+  return seq_encode(r, (hipStream_t)stream);
+}
 
 }  // namespace
 
@@ -943,10 +960,7 @@ int32_t xnrs_text_encoder_fwd(const float* x, const float* m, const int32_t* ids
                               void* stream) {
   if (n_news == 0) return XNRS_OK;
   if (!m) return XNRS_EINVAL;  // TextEncoder always receives a token mask (news_encoding.py:41-50)
-  SeqEncode r = padded_call(x, m, n_news, S, D, y, ws, ws_bytes);
-  r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
-  r.live_tiles = true;  // empty history slots are news: whole row tiles of a pass may hold nothing else
-  return seq_encode(r, (hipStream_t)stream);
+  return news_encode(padded_call(x, m, n_news, S, D, y, ws, ws_bytes), ids, att, pool_kind, pool, head, hm, chunk, stream);
 }
 
 size_t xnrs_text_encoder_bf16_workspace_bytes(int64_t n_news, int32_t S, int32_t D, int32_t A, int32_t E, int32_t has_att,
@@ -962,9 +976,7 @@ int32_t xnrs_text_encoder_fwd_bf16(const uint16_t* x_bf16, const float* m, const
   if (n_news == 0) return XNRS_OK;
   SeqEncode r = padded_call(nullptr, m, n_news, S, D, y, ws, ws_bytes);
   r.x16 = x_bf16;
-  r.ids = ids; r.att = att; r.pooled = true; r.pool_kind = pool_kind; r.pool = pool; r.head = head; r.hm = hm; r.chunk = chunk;
-  r.live_tiles = true;
-  return seq_encode(r, (hipStream_t)stream);
+  return news_encode(r, ids, att, pool_kind, pool, head, hm, chunk, stream);
 }
 
 size_t xnrs_linear_bf16_workspace_bytes(int32_t N, int32_t K) {
@@ -1070,7 +1082,7 @@ int32_t xnrs_text_encoder_fwd_unpadded(const float* x, const int32_t* ids, int64
   AdditivePoolArgs pa = additive_pool_args(tc, rowdot, pool, vals, n_news, S, D, A);
   pa.row_off = row_off;
   pa.row_ids = val_ids;
-  pa.y = fold ? pob : (head ? pb : y);
+  pa.y = pooled_dst(fold, pob, head, pb, y);
   pa.asum_out = fold ? asum : nullptr;
   pa.hm_out = hm;
   {
@@ -1155,7 +1167,7 @@ int32_t xnrs_text_encoder_fwd_compact(const float* x, const float* m, const int3
     pa.row_off = roff;
     pa.row_ids = val_ids;
     pa.poison = cnt + 2;  // a mask value other than 0 / 1: NaN out, not a silently different result
-    pa.y = (fold ? pob : (head ? pb : y)) + c0 * (int64_t)D;
+    pa.y = pooled_dst(fold, pob, head, pb, y) + c0 * (int64_t)D;
     pa.asum_out = fold ? asum + c0 : nullptr;
     pa.hm_out = hm ? hm + c0 : nullptr;
     {

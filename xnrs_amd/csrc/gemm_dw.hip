@@ -400,9 +400,8 @@ __global__ __launch_bounds__(512, 2) void gemm_dw256_kernel(GemmArgs a, int n_ti
 // XNRS_GEMM_DW=2 sends every eligible launch (tests), 0 none.
 bool gemm_dw_eligible(const GemmArgs& a) {
   if (!a.gather_ids && !(knobs().gemm_dw >= 3 || (knobs().gemm_dw == 2 && gemm_dw_big_tile(a)))) return false;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (!a.a_col || !a.b_kn || a.nseg != 1 || a.accumulate || a.aux_mode || a.act || a.bias[0]) return false;
-  if (a.M % 4 != 0 || a.Nseg % 4 != 0 || a.lda % 4 != 0 || a.ldw % 4 != 0 || !al16(a.A) || !al16(a.W[0])) return false;
+  if (a.M % 4 != 0 || a.Nseg % 4 != 0 || a.lda % 4 != 0 || a.ldw % 4 != 0 || !aligned16(a.A) || !aligned16(a.W[0])) return false;
   if (a.M < 64 || a.Nseg < 64 || a.K >= (1ll << 31)) return false;
   if (a.K < 8192) return false;  // short contractions: few slices, the 64 x 64 tiles of the generic kernel fill the chip better
   if (a.gather_ids && (a.gather_S != 1 || !a.b_gather_ids || a.b_gather_S != 1)) return false;  // dY: dense, or both

@@ -524,35 +524,37 @@ void reload_knobs() { g_knobs = read_knobs(); }
 int gemm_mode() { return g_gemm_mode.load(std::memory_order_relaxed); }
 void set_gemm_mode(int mode) { g_gemm_mode.store((mode >= 0 && mode <= 2) ? mode : 0, std::memory_order_relaxed); }
 
+// what a forward launcher fills in (kernels.h: "filled in by the launcher"), for a launch without split-K
+static void complete_args(GemmArgs* a) {
+  if (a->act == 2 && knobs().fast_tanh) a->act = ACT_TANH_FAST;
+  a->k_per_split = a->K > 0 ? a->K : 1;
+  // an output of hundreds of MB (the Q/K/V image of a 65 500-row pass: 604 MB) is written once and read by the next
+  // kernel from HBM anyway: non-temporal stores keep it from evicting the operand panels (-0.5 % on the Q/K/V GEMM)
+  a->nt_store = (!a->accumulate && !a->c_scatter && a->M * a->ldc * 4 >= (64ll << 20)) ? 1 : 0;
+}
+
 hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t stream, int* nsplit_used) {
   GemmArgs a = a_in;
   if (a.M <= 0 || a.Nseg <= 0) return hipSuccess;
-  if (a.act == 2 && knobs().fast_tanh) a.act = ACT_TANH_FAST;
+  complete_args(&a);
   if (a.K >= (1ll << 31)) return hipErrorInvalidValue;  // 32-bit contraction indices in the kernel
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // 16-byte vector loads need the contiguous dimension of each operand on 16-B boundaries
-  bool vec = (a.lda % 4 == 0) && (a.ldw % 4 == 0) && al16(a.A);
+  bool vec = (a.lda % 4 == 0) && (a.ldw % 4 == 0) && aligned16(a.A);
   vec = vec && (a.a_col ? (a.M % 4 == 0) : (a.K % 4 == 0));
   vec = vec && (a.b_kn ? (a.Nseg % 4 == 0) : (a.K % 4 == 0));
-  for (int s = 0; s < a.nseg; ++s) vec = vec && al16(a.W[s]);
+  for (int s = 0; s < a.nseg; ++s) vec = vec && aligned16(a.W[s]);
 
   int nsplit = 1;
   if (a.slabs && a.nsplit > 1) {
     nsplit = a.nsplit;
     const int64_t per = ((a.K + nsplit - 1) / nsplit + KALIGN - 1) / KALIGN * KALIGN;  // tile-aligned slices
-    a.k_per_split = per;
     nsplit = (int)((a.K + per - 1) / per);
+    if (nsplit > 1) a.k_per_split = per;  // (one slice: the whole contraction, as complete_args left it)
     a.slab_stride = a.M * a.ldc;
     if (a.nseg != 1 || a.ldc != a.Nseg) return hipErrorInvalidValue;
   }
-  if (nsplit <= 1) {
-    nsplit = 1;
-    a.k_per_split = a.K > 0 ? a.K : 1;
-  }
+  if (nsplit <= 1) nsplit = 1;
   if (nsplit_used) *nsplit_used = nsplit;
-  // an output of hundreds of MB (the Q/K/V image of a 65 500-row pass: 604 MB) is written once and read by the next
-  // kernel from HBM anyway: non-temporal stores keep it from evicting the operand panels (-0.5 % on the Q/K/V GEMM)
-  a.nt_store = (!a.accumulate && !a.c_scatter && a.M * a.ldc * 4 >= (64ll << 20)) ? 1 : 0;
   if (a.colsum && !(a.a_col && a.b_kn)) return hipErrorInvalidValue;  // fused column sums: dW layout only
   if (a.k_dev && !(a.a_col && a.b_kn)) return hipErrorInvalidValue;   // device contraction length: dW layout only
   if (a.colsum_out && !a.colsum) return hipErrorInvalidValue;
@@ -560,7 +562,7 @@ hipError_t launch_gemm_f32(const GemmArgs& a_in, hipStream_t stream, int* nsplit
                                                                                                    // destinations: split-K dW only
   bool cs_copy = false;  // one slice: its partial IS the bias gradient (written in place when 16-byte aligned)
   if (a.colsum && a.colsum_out && nsplit == 1) {
-    if (al16(a.colsum_out)) a.colsum = a.colsum_out;
+    if (aligned16(a.colsum_out)) a.colsum = a.colsum_out;
     else cs_copy = true;
   }
   if (a.rowdot_out && (a.a_col || a.b_kn || a.nseg != 1 || nsplit != 1 || !a.rowdot_w || a.accumulate || a.aux_mode ||
@@ -612,11 +614,10 @@ int64_t qkv_launches_read(bool reset) {
 // the conditions under which launch_gemm_f32 runs a forward launch on the 16-byte-vector, buffer-load kernels; *gath: A through
 // row pointers (launch_cfg: gathered rows, or an A beyond the descriptor window)
 static bool qkv_section_ok(const GemmArgs& a, bool* gath) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (a.a_col || a.b_kn || a.M <= 0 || a.Nseg <= 0 || a.nseg < 1 || a.K < 4 || a.K >= (1ll << 31) || a.K % 4 != 0) return false;
-  if (a.lda % 4 != 0 || a.ldw % 4 != 0 || !al16(a.A)) return false;
+  if (a.lda % 4 != 0 || a.ldw % 4 != 0 || !aligned16(a.A)) return false;
   for (int s = 0; s < a.nseg; ++s)
-    if (!al16(a.W[s])) return false;
+    if (!aligned16(a.W[s])) return false;
   if ((a.slabs && a.nsplit > 1) || a.rowdot_out || a.rowscale || a.colsum || a.k_dev || a.C2) return false;
   if (!knobs().gemm_buf || (int64_t)a.Nseg * a.ldw * 4 > (int64_t)BUF_OOB) return false;
   *gath = a.gather_ids || a.M * a.lda * 4 > (int64_t)BUF_OOB;
@@ -639,11 +640,7 @@ bool gemm_qkv_one_launch_ok(const GemmArgs& kv, const GemmArgs& q) {
 hipError_t launch_gemm_qkv_one(const GemmArgs& kv_in, const GemmArgs& q_in, hipStream_t stream) {
   if (!gemm_qkv_one_launch_ok(kv_in, q_in)) return hipErrorInvalidValue;
   GemmArgs kv = kv_in, q = q_in;
-  for (GemmArgs* a : {&kv, &q}) {  // what launch_gemm_f32 fills in
-    if (a->act == 2 && knobs().fast_tanh) a->act = ACT_TANH_FAST;
-    a->k_per_split = a->K;
-    a->nt_store = (!a->accumulate && !a->c_scatter && a->M * a->ldc * 4 >= (64ll << 20)) ? 1 : 0;
-  }
+  for (GemmArgs* a : {&kv, &q}) complete_args(a);  // (K >= 4 here, gemm_qkv_one_launch_ok: k_per_split = K)
   const int kv_m_tiles = (int)((kv.M + 127) / 128), kv_n_tiles_seg = (kv.Nseg + 127) / 128;
   const int q_m_tiles = (int)((q.M + 127) / 128), q_n_tiles = (q.Nseg + 63) / 64;
   const int kv_gn = gemm_group_tiles(kv_n_tiles_seg * kv.nseg, 128, kv.K, false);
@@ -663,10 +660,9 @@ int64_t fc1_in_tail_read(bool reset) {
 
 // what launch_gemm_f32 asks of a launch before it takes the GATH + RDOT + MDEV instantiation with scattered row dots
 bool gemm_fc1_in_tail_ok(const GemmArgs& f) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (!knobs().gemm_fc1_in_tail || gemm_mode() != 0 || knobs().gemm_tile >= 0 || !knobs().gemm_buf) return false;
   if (f.a_col || f.b_kn || f.M <= 0 || f.Nseg <= 0 || f.nseg != 1 || f.K < 4 || f.K >= (1ll << 31) || f.K % 4 != 0) return false;
-  if (f.lda % 4 != 0 || f.ldw % 4 != 0 || !al16(f.A) || !al16(f.W[0]) || (int64_t)f.Nseg * f.ldw * 4 > (int64_t)BUF_OOB) return false;
+  if (f.lda % 4 != 0 || f.ldw % 4 != 0 || !aligned16(f.A) || !aligned16(f.W[0]) || (int64_t)f.Nseg * f.ldw * 4 > (int64_t)BUF_OOB) return false;
   if ((f.slabs && f.nsplit > 1) || f.rowscale || f.colsum || f.k_dev || f.C2 || f.live_tiles || f.accumulate || f.aux_mode) return false;
   if (!f.rowdot_out || !f.rowdot_w || (f.act != 2 && f.act != ACT_TANH_FAST)) return false;
   if (!f.gather_ids || f.gather_S != 1 || !f.c_scatter || !f.m_dev) return false;
@@ -677,11 +673,7 @@ hipError_t launch_gemm_qkv_fc1(const GemmArgs& kv_in, const GemmArgs& q_in, cons
   if (!gemm_qkv_one_launch_ok(kv_in, q_in) || (f_in && !gemm_fc1_in_tail_ok(*f_in))) return hipErrorInvalidValue;
   GemmArgs kv = kv_in, q = q_in, f{};  // f.M == 0: an empty third section, nothing of f is read
   if (f_in) f = *f_in;
-  for (GemmArgs* a : {&kv, &q, &f}) {  // what launch_gemm_f32 fills in
-    if (a->act == 2 && knobs().fast_tanh) a->act = ACT_TANH_FAST;
-    a->k_per_split = a->K > 0 ? a->K : 1;
-    a->nt_store = (!a->accumulate && !a->c_scatter && a->M * a->ldc * 4 >= (64ll << 20)) ? 1 : 0;
-  }
+  for (GemmArgs* a : {&kv, &q, &f}) complete_args(a);  // (the empty third section: K = 0, k_per_split = 1)
   constexpr int FTM = FC1_TAIL_BM / 64, FTN = FC1_TAIL_BN / 64;
   const int kv_m_tiles = (int)((kv.M + 127) / 128), kv_n_tiles_seg = (kv.Nseg + 127) / 128;
   const int q_m_tiles = (int)((q.M + 127) / 128), q_n_tiles = (q.Nseg + 63) / 64;

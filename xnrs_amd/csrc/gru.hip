@@ -226,8 +226,6 @@ __global__ __launch_bounds__(256) void gru_lengths_kernel(const float* __restric
   len[b] = n < 0 ? 0 : (n > T ? T : n);
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 dim3 step_grid(int B, int Hd) { return dim3((unsigned)((B + TILE - 1) / TILE), (unsigned)((Hd + TILE - 1) / TILE)); }
 
 }  // namespace
@@ -326,7 +324,7 @@ int32_t gru_forward(const float* x, const float* m, int32_t ldm, const float* h0
   a.B = (int32_t)B;
   a.T = T;
   a.Hd = Hd;
-  a.vec = (Hd % 4 == 0 && al16(p->w_hh) && (!h0 || al16(h0))) ? 1 : 0;
+  a.vec = (Hd % 4 == 0 && aligned16(p->w_hh) && (!h0 || aligned16(h0))) ? 1 : 0;
   XNRS_TRY(launch_gru_lengths(m, ldm, at<int32_t>(buf, r.len), B, T, stream));
   XNRS_TRY(launch_gemm_f32(gemm_linear(x, {}, E, p->w_ih, p->b_ih, a.g, 3 * (int64_t)Hd, B * T, 3 * Hd, E), stream));
   XNRS_TRY(launch_gru_fwd(a, stream));

@@ -8,6 +8,7 @@ namespace xnrs {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }  // host: on a 16-byte boundary (nullptr is)
 
 // ---------------------------------------------------------------- development knobs
 // Kernel-selection switches for in-process A/B runs (tools/) and tests.  They are read from the XNRS_* environment

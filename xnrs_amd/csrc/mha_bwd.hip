@@ -543,14 +543,13 @@ static hipError_t launch_dq(const MhaBwdArgs& a, bool vec, hipStream_t stream) {
 hipError_t launch_mha_bwd(const MhaBwdArgs& a, hipStream_t stream) {
   if (a.n_seq <= 0 || a.S <= 0) return hipSuccess;
   if (a.S > 128 || a.d_k > 16 * MAX_FT) return hipErrorInvalidValue;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = (a.d_k % 4 == 0) && (a.ld % 4 == 0) && (a.lddo % 4 == 0) && (a.ldd % 4 == 0) && al16(a.q) && al16(a.k) &&
-                   al16(a.v) && al16(a.d_o) && al16(a.dq) && al16(a.dk) && al16(a.dv);
+  const bool vec = (a.d_k % 4 == 0) && (a.ld % 4 == 0) && (a.lddo % 4 == 0) && (a.ldd % 4 == 0) && aligned16(a.q) && aligned16(a.k) &&
+                   aligned16(a.v) && aligned16(a.d_o) && aligned16(a.dq) && aligned16(a.dk) && aligned16(a.dv);
   if (a.n_heads * a.d_k > 2048) return hipErrorInvalidValue;
   const int64_t n_rows = a.n_seq * a.S;
   hipError_t e = hipSuccess;
   const int KT = (a.S + 15) / 16;
-  const bool fused = vec && a.S <= 64 && a.d_k <= 64 && a.ldo % 4 == 0 && al16(a.o) && knobs().mha_bwd_fused;
+  const bool fused = vec && a.S <= 64 && a.d_k <= 64 && a.ldo % 4 == 0 && aligned16(a.o) && knobs().mha_bwd_fused;
   if (!fused) {  // the fused kernel takes delta = rowsum(dO * O) while it stages dO
     const unsigned dgrid = (unsigned)(n_rows < 65536 ? n_rows : 65536);
     hipLaunchKernelGGL(mha_delta_kernel, dim3(dgrid), dim3(256), 0, stream, a, n_rows);

@@ -742,10 +742,9 @@ bool news_fused_ready(const NewsFusedArgs& a) {
   NewsFusedPlan p;
   const int npw = a.npw == 1 ? 1 : 2;
   if (!news_fused_plan(a.S, a.D, a.n_heads, a.A, &p, npw) || a.d_k * a.n_heads != a.D) return false;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al16(a.x) || !al16(a.wq) || !al16(a.wk) || !al16(a.wv) || !al16(a.wo) || !al16(a.w1) || !a.img || !al16(a.img))
+  if (!aligned16(a.x) || !aligned16(a.wq) || !aligned16(a.wk) || !aligned16(a.wv) || !aligned16(a.wo) || !aligned16(a.w1) || !a.img || !aligned16(a.img))
     return false;
-  if (a.fold && (!a.o_scratch || !a.asum || !al16(a.o_scratch))) return false;
+  if (a.fold && (!a.o_scratch || !a.asum || !aligned16(a.o_scratch))) return false;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return false;
   return nf_attr_ok(a.d_k / 4, npw, a.fold != 0, dev);

@@ -140,9 +140,8 @@ __global__ __launch_bounds__(256) void additive_pool_bwd_kernel(AdditivePoolBwdA
 hipError_t launch_additive_pool_bwd(const AdditivePoolBwdArgs& a, hipStream_t stream) {
   if (a.n_seq <= 0) return hipSuccess;
   if (a.N > POOLB_MAX_N || a.N <= 0) return hipErrorInvalidValue;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = a.D % 4 == 0 && a.A % 4 == 0 && a.ldx % 4 == 0 && (!a.dx || (a.lddx % 4 == 0 && al16(a.dx))) && al16(a.x) &&
-                   al16(a.dp) && al16(a.t) && al16(a.w2) && al16(a.dpre);
+  const bool vec = a.D % 4 == 0 && a.A % 4 == 0 && a.ldx % 4 == 0 && (!a.dx || (a.lddx % 4 == 0 && aligned16(a.dx))) && aligned16(a.x) &&
+                   aligned16(a.dp) && aligned16(a.t) && aligned16(a.w2) && aligned16(a.dpre);
   if (vec) hipLaunchKernelGGL(additive_pool_bwd_kernel<true>, dim3((unsigned)a.n_seq), dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(additive_pool_bwd_kernel<false>, dim3((unsigned)a.n_seq), dim3(256), 0, stream, a);
   return hipGetLastError();
