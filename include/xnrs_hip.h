@@ -524,6 +524,15 @@ int32_t xnrs_qkv_fc1_launch_map(int64_t block, int64_t live_tiles, int64_t live_
                                 int32_t q_col_tiles, int64_t fc1_rows, int32_t fc1_tile_rows, int32_t fc1_col_tiles,
                                 int32_t *section, int32_t *index);
 
+/* ---- attention rows nobody reads are not stored (knob XNRS_MHA_LIVE_O; no reference counterpart) -----------------
+ * Where the fc1 of a dense inference pass walks the live-row list over the attention rows (folded out-projection,
+ * 33 <= S <= 64: dense rows, ids, a bf16 table's direct route), fc1 and the pooler are the only readers of those rows and
+ * both read the rows of unmasked tokens alone.  The attention core then stores nothing for a masked query: not the zeros
+ * of an all-masked news or query tile, not the uniform average of V of a masked query next to live ones.  The same bits
+ * in every output either way.  xnrs_mha_live_o_count returns the number of attention launches that ran that way since the
+ * last reset (process-global, relaxed atomic): one per pass on that route, 0 otherwise; reset != 0 clears it after reading. */
+int32_t xnrs_mha_live_o_count(int32_t reset);
+
 /* Does the TRAINING forward fold the out-projection behind the pooling right now (knob XNRS_FOLD_TRAIN)?
  * The saved-activation blob of xnrs_seq_encoder_fwd_train* is laid out by that decision and xnrs_seq_encoder_bwd* reads it
  * under the decision of ITS call time: a caller that may reload the knobs between the two (tests, A/B tools) records this

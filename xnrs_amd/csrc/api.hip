@@ -133,6 +133,11 @@ int32_t xnrs_fc1_in_tail_count(int32_t reset) {
   return n > 0x7fffffffLL ? 0x7fffffff : (int32_t)n;
 }
 
+int32_t xnrs_mha_live_o_count(int32_t reset) {
+  const int64_t n = xnrs::mha_live_o_read(reset != 0);
+  return n > 0x7fffffffLL ? 0x7fffffff : (int32_t)n;
+}
+
 int32_t xnrs_qkv_fc1_launch_map(int64_t block, int64_t live_tiles, int64_t live_rows, int64_t fc1_live_rows, int32_t kv_row_tiles,
                                 int32_t kv_col_tiles, int64_t q_rows, int32_t q_tile_rows, int32_t q_col_tiles, int64_t fc1_rows,
                                 int32_t fc1_tile_rows, int32_t fc1_col_tiles, int32_t* section, int32_t* index) {

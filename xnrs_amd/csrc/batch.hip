@@ -16,6 +16,7 @@
 //   dropout_rows   : the towers' input dropout (news_encoding.py:51, user_encoding.py:69) on dense rows, or fused with
 //                    gather_rows for the id path: the dropped batch is materialised in the launch that gathers it.
 #include <atomic>
+#include <type_traits>
 
 #include "host.h"
 
@@ -503,31 +504,11 @@ __global__ __launch_bounds__(1024) void compact_rows_kernel(const float* __restr
 // word in LDS; counts are popcounts, and the lists are written by the same flattened sweep (a live token's place = the
 // news' offset + the popcount of the bits below it).  378 -> 249 us per call of 25 600 news x 50 in five passes (it sits on
 // the critical path of the device-compacted encoder; one workgroup per pass is what bounds it now: the passes' rounds of
-// 1 024 news run one after the other).
-//
-// DENSE: the same sweep for the DENSE encoder passes (encoder_fwd.hip "live rows"): rows stay where they are, so what a pass
-// needs is the ascending list of its unmasked token rows in the pass's own row space (dl.live_loc: where Q and the scores are
-// written, and where the O rows are read), the same tokens' rows in the gathered table when there are ids (live_all, else not
-// written), their number (counts[0]), and the live 128-row tile list of launch_live_tiles (list_live_tiles below) -- ONE list
-// launch per encoder call.  row_off / kv_src / kv_block are not written; a mask value other than 0 / 1 is legal there (a
-// row is live iff mask != 0, the dense path's own rule), so counts[2] is not written either.
-struct DenseLists {
-  int32_t* live_loc;  // [passes * chunk * S]
-  uint8_t* alive;     // [n_news] scratch
-  int64_t* n_tiles;   // [passes]
-  int32_t* tiles;     // [passes * cap]
-  int64_t cap;
-  int BM;
-};
-__device__ void list_live_tiles(const uint8_t* __restrict__ alive, int64_t cn, int L, int BM, int32_t* __restrict__ tiles,
-                                int64_t* __restrict__ n_out, int* s_wsum, int* s_carry);
-
-template <bool DENSE>
+// 1 024 news run one after the other).  (The dense encoder passes have a list kernel of their own: dense_row_lists_kernel.)
 __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __restrict__ mask, const int32_t* __restrict__ ids,
                                                                int64_t n_news, int64_t chunk, int S, int64_t* __restrict__ row_off_all,
                                                                int32_t* __restrict__ live_all, int32_t* __restrict__ kvs_all,
-                                                               int32_t* __restrict__ kvb_all, int64_t* __restrict__ counts_all,
-                                                               DenseLists dl) {
+                                                               int32_t* __restrict__ kvb_all, int64_t* __restrict__ counts_all) {
   __shared__ unsigned long long s_bits[1024];
   __shared__ int64_t s_row[1024];
   __shared__ int s_ex[2][1024];
@@ -536,16 +517,14 @@ __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __res
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t news0 = (int64_t)blockIdx.x * chunk;
   const int cn = (int)(n_news - news0 < chunk ? n_news - news0 : chunk);
-  int64_t* row_off = DENSE ? nullptr : row_off_all + (int64_t)blockIdx.x * (chunk + 1);
-  int32_t* live_src = live_all ? live_all + (int64_t)blockIdx.x * chunk * S : nullptr;
-  int32_t* kv_src = DENSE ? nullptr : kvs_all + (int64_t)blockIdx.x * chunk * S;
-  int32_t* kv_block = DENSE ? nullptr : kvb_all + (int64_t)blockIdx.x * chunk;
+  int64_t* row_off = row_off_all + (int64_t)blockIdx.x * (chunk + 1);
+  int32_t* live_src = live_all + (int64_t)blockIdx.x * chunk * S;
+  int32_t* kv_src = kvs_all + (int64_t)blockIdx.x * chunk * S;
+  int32_t* kv_block = kvb_all + (int64_t)blockIdx.x * chunk;
   int64_t* counts = counts_all + 3 * (int64_t)blockIdx.x;
-  int32_t* live_loc = DENSE ? dl.live_loc + (int64_t)blockIdx.x * chunk * S : nullptr;
-  uint8_t* alive = DENSE ? dl.alive + news0 : nullptr;
   int bad = 0;
   if (tid < 2) s_carry[tid] = 0;
-  if (!DENSE && tid == 0) row_off[0] = 0;
+  if (tid == 0) row_off[0] = 0;
   for (int base = 0; base < cn; base += 1024) {
     const int nn = cn - base < 1024 ? cn - base : 1024;
     s_bits[tid] = 0ull;
@@ -590,12 +569,8 @@ __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __res
       s_ex[which][tid] = before + incl[which] - v[which];
     }
     if (tid < nn) {
-      if constexpr (DENSE) {
-        alive[base + tid] = bits != 0ull ? 1 : 0;
-      } else {
-        row_off[base + tid + 1] = s_ex[0][tid] + cnt;
-        kv_block[base + tid] = s_ex[1][tid] / S;  // (an empty news: the block the next non-empty one gets -- never read)
-      }
+      row_off[base + tid + 1] = s_ex[0][tid] + cnt;
+      kv_block[base + tid] = s_ex[1][tid] / S;  // (an empty news: the block the next non-empty one gets -- never read)
     }
     __syncthreads();
     if (tid == 1023) {
@@ -608,28 +583,10 @@ __global__ __launch_bounds__(1024) void compact_rows64_kernel(const float* __res
       const unsigned long long b = s_bits[jj];
       if (b == 0ull) continue;
       const int32_t src = (int32_t)(s_row[jj] * S + sl);
-      if constexpr (DENSE) {
-        if ((b >> sl) & 1ull) {
-          const int at = s_ex[0][jj] + __popcll(b & ((1ull << sl) - 1ull));
-          live_loc[at] = (int32_t)((base + jj) * S + sl);
-          if (live_src) live_src[at] = src;
-        }
-      } else {
-        kv_src[s_ex[1][jj] + sl] = src;
-        if ((b >> sl) & 1ull) live_src[s_ex[0][jj] + __popcll(b & ((1ull << sl) - 1ull))] = src;
-      }
+      kv_src[s_ex[1][jj] + sl] = src;
+      if ((b >> sl) & 1ull) live_src[s_ex[0][jj] + __popcll(b & ((1ull << sl) - 1ull))] = src;
     }
     __syncthreads();
-  }
-  if constexpr (DENSE) {  // (the loop's last barrier has passed: s_carry is final, the alive flags of this pass are visible)
-    if (tid == 0) {
-      counts[0] = s_carry[0];
-      counts[1] = s_carry[1];
-      s_carry[0] = 0;
-    }
-    __syncthreads();
-    list_live_tiles(alive, cn, S, dl.BM, dl.tiles + (int64_t)blockIdx.x * dl.cap, dl.n_tiles + blockIdx.x, s_wsum[0], &s_carry[0]);
-    return;
   }
   bad = __syncthreads_or(bad);
   if (tid == 0) {
@@ -798,8 +755,8 @@ hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_
   const int64_t passes = (n_news + chunk - 1) / chunk;
   if (passes > 0x7fffffffLL) return hipErrorInvalidValue;
   if (S <= 64)
-    hipLaunchKernelGGL(compact_rows64_kernel<false>, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_news, chunk, S,
-                       row_off, live_src, kv_src, kv_block, counts, DenseLists{});
+    hipLaunchKernelGGL(compact_rows64_kernel, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_news, chunk, S, row_off,
+                       live_src, kv_src, kv_block, counts);
   else
     hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_news, chunk, S, row_off,
                        live_src, kv_src, kv_block, counts);
@@ -815,6 +772,9 @@ hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_
 //   alive [n_seq] bytes     scratch: 1 = the sequence has an unmasked token (a thread per sequence walks its mask row)
 //   n_tiles [pass]          number of live tiles of the pass (device scalar the GEMMs read)
 //   tiles [pass * cap ..]   their indices; cap = tiles of a full pass
+__device__ void list_live_tiles(const uint8_t* __restrict__ alive, int64_t cn, int L, int BM, int32_t* __restrict__ tiles,
+                                int64_t* __restrict__ n_out, int* s_wsum, int* s_carry);
+
 __global__ __launch_bounds__(1024) void live_tiles_kernel(const float* __restrict__ mask, const int32_t* __restrict__ ids,
                                                            int64_t n_seq, int64_t chunk, int L, int BM, int64_t cap,
                                                            uint8_t* __restrict__ alive_all, int64_t* __restrict__ n_tiles,
@@ -881,6 +841,132 @@ hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_se
   return hipGetLastError();
 }
 
+// ---- live rows AND live row tiles of the DENSE encoder passes in one launch (encoder_fwd.hip "live rows"; S <= 64).
+// Rows stay where they are, so what a pass needs is the ascending list of its unmasked token rows in the pass's own row space
+// (live_loc: where Q and the scores are written, and where the O rows are read), the same tokens' rows in the gathered table
+// when there are ids (live_src, else not written), their number (counts[0]; counts[1] = S x its non-empty news), and the
+// live 128-row tile list of launch_live_tiles.  A mask value other than 0 / 1 is legal (a row is live iff mask != 0, the
+// dense path's own rule).
+// This used to be one 1 024-thread workgroup per pass (compact_rows64_kernel's sweep): 20 workgroups on 256 CUs, 61-69 us at
+// the head of every encoder call with nothing beside it.  Now a pass is cut into slices of DL_SLICE news, a workgroup each.
+// No workgroup waits for another and no atomic decides a place: a slice finds its offset in the pass's list by COUNTING the
+// live tokens of the news before it in the same pass (at most chunk x S mask floats, 262 KB at the benchmark's pass, out of
+// L2), a wave per news row and one ballot per row -- so the list order, and every byte written, is what the one workgroup
+// wrote.  The workgroup of a pass's LAST slice has then seen every news of the pass: it alone writes the alive flags, the
+// two counts and -- from those flags -- the tile list (list_live_tiles).
+constexpr int DL_SLICE = 64;  // news per workgroup: 4 rows per wave of its own, and at most chunk / 16 rows per wave to count
+constexpr int DL_ROWS = 16;   // mask rows a wave has in flight (8 waves per SIMD: two workgroups per CU, every slice of a call resident at once)
+__global__ __launch_bounds__(1024, 8) void dense_row_lists_kernel(const float* __restrict__ mask, const int32_t* __restrict__ ids,
+                                                                int64_t n_news, int64_t chunk, int S, int nsl,
+                                                                int32_t* __restrict__ live_loc_all, int32_t* __restrict__ live_src_all,
+                                                                int64_t* __restrict__ counts_all, uint8_t* __restrict__ alive_all,
+                                                                int64_t* __restrict__ n_tiles, int32_t* __restrict__ tiles_all,
+                                                                int64_t cap, int BM) {
+  __shared__ unsigned long long s_bits[DL_SLICE];  // the live tokens of the slice's news
+  __shared__ int32_t s_row[DL_SLICE];              // their mask rows
+  __shared__ int s_ex[DL_SLICE];                   // their first places in the pass's list
+  __shared__ int s_part[2][16];                    // per wave: live tokens / non-empty news BEFORE the slice
+  __shared__ int s_wsum[16];
+  __shared__ int s_carry;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the rows a wave walks are addressed from SGPRs)
+  const int64_t pass = blockIdx.x / nsl;
+  const int slice = blockIdx.x % nsl;
+  const int64_t news0 = pass * chunk;
+  const int cn = (int)(n_news - news0 < chunk ? n_news - news0 : chunk);
+  const int j0 = slice * DL_SLICE;
+  if (j0 >= cn) return;  // (a short last pass has fewer slices; uniform)
+  const int j1 = j0 + DL_SLICE < cn ? j0 + DL_SLICE : cn;
+  const bool last = j1 == cn;
+  if (tid < DL_SLICE) {
+    s_bits[tid] = 0ull;
+    s_row[tid] = 0;
+  }
+  __syncthreads();
+  // the news [0, j1) of the pass, a wave per row, DL_ROWS rows per trip.  Every load of a trip is UNCONDITIONAL (row and token
+  // clamped, the value dropped afterwards): behind a "load or constant" select the compiler branches around each load and
+  // waits for it, and the sweep -- 82 rows per wave for the last slice of a 1 310-news pass -- becomes 82 dependent round
+  // trips to memory (that, not the one workgroup per pass, was most of the old kernel's 61-69 us).
+  int before = 0, kept = 0;  // (wave-uniform)
+  const int lc = lane < S ? lane : S - 1;
+  auto sweep = [&](auto gathered) {
+    for (int jb = wave; jb < j1; jb += 16 * DL_ROWS) {
+      int32_t row[DL_ROWS];  // (a news index or an id: 32 bits, the launcher checks n_news)
+      float mv[DL_ROWS];
+#pragma unroll
+      for (int u = 0; u < DL_ROWS; ++u) {
+        const int jc = jb + 16 * u < j1 ? jb + 16 * u : j1 - 1;
+        if constexpr (decltype(gathered)::value)
+          row[u] = ids[news0 + jc];
+        else
+          row[u] = (int32_t)(news0 + jc);
+      }
+#pragma unroll
+      for (int u = 0; u < DL_ROWS; ++u) mv[u] = mask[(int64_t)row[u] * S + lc];
+#pragma unroll
+      for (int u = 0; u < DL_ROWS; ++u) {
+        const int j = jb + 16 * u;
+        const unsigned long long b = __ballot(lane < S && mv[u] != 0.f);
+        if (j >= j1) continue;  // (uniform)
+        if (j < j0) {
+          before += __popcll(b);
+          kept += b != 0ull ? 1 : 0;
+        } else if (lane == 0) {
+          s_bits[j - j0] = b;
+          s_row[j - j0] = row[u];
+        }
+        if (last && lane == 0) alive_all[news0 + j] = b != 0ull ? 1 : 0;
+      }
+    }
+  };
+  if (ids)
+    sweep(std::true_type{});
+  else
+    sweep(std::false_type{});
+  if (lane == 0) {
+    s_part[0][wave] = before;
+    s_part[1][wave] = kept;
+  }
+  __syncthreads();
+  if (wave == 0) {  // the slice's own news: lane = news, an inclusive scan of the counts behind the tokens before the slice
+    const unsigned long long bits = s_bits[lane];
+    const int cnt = __popcll(bits);
+    int x = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int up = __shfl_up(x, off);
+      if (lane >= off) x += up;
+    }
+    int base = 0, kbase = 0;
+    for (int w = 0; w < 16; ++w) {
+      base += s_part[0][w];
+      kbase += s_part[1][w];
+    }
+    s_ex[lane] = base + x - cnt;
+    const int kown = __popcll(__ballot(bits != 0ull));
+    if (last && lane == 63) {
+      int64_t* counts = counts_all + 3 * pass;
+      counts[0] = base + x;
+      counts[1] = (int64_t)(kbase + kown) * S;
+    }
+  }
+  __syncthreads();
+  int32_t* live_loc = live_loc_all + pass * chunk * S;
+  int32_t* live_src = live_src_all ? live_src_all + pass * chunk * S : nullptr;
+  const int n_el = (j1 - j0) * S;
+  for (int i = tid; i < n_el; i += 1024) {  // the flattened sweep: a live token's place = its news' + the live tokens below it
+    const int jj = i / S, sl = i - jj * S;
+    const unsigned long long b = s_bits[jj];
+    if (!((b >> sl) & 1ull)) continue;
+    const int at = s_ex[jj] + __popcll(b & ((1ull << sl) - 1ull));
+    live_loc[at] = (int32_t)((j0 + jj) * S + sl);
+    if (live_src) live_src[at] = (int32_t)((int64_t)s_row[jj] * S + sl);
+  }
+  if (!last) return;  // (uniform)
+  if (tid == 0) s_carry = 0;
+  __syncthreads();  // (the alive flags of the whole pass were written by this workgroup: visible to it behind the barrier)
+  list_live_tiles(alive_all + news0, cn, S, BM, tiles_all + pass * cap, n_tiles + pass, s_wsum, &s_carry);
+}
+
 // the lists of the dense passes' live rows AND live row tiles in one launch (S <= 64; kernels.h)
 hipError_t launch_dense_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM,
                                   int32_t* live_loc, int32_t* live_src, int64_t* counts, uint8_t* alive, int64_t* n_tiles,
@@ -888,9 +974,13 @@ hipError_t launch_dense_row_lists(const float* mask, const int32_t* ids, int64_t
   if (n_seq <= 0 || chunk <= 0 || L <= 0 || BM <= 0) return hipSuccess;
   const int64_t passes = (n_seq + chunk - 1) / chunk;
   const int64_t cap = live_tiles_cap(chunk, L, BM);
-  if (L > 64 || passes > 0x7fffffffLL || cap > 0x7fffffffLL || chunk * L > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(compact_rows64_kernel<true>, dim3((unsigned)passes), dim3(1024), 0, stream, mask, ids, n_seq, chunk, L,
-                     nullptr, ids ? live_src : nullptr, nullptr, nullptr, counts, DenseLists{live_loc, alive, n_tiles, tiles, cap, BM});
+  if (L > 64 || passes > 0x7fffffffLL || cap > 0x7fffffffLL || chunk * L > 0x7fffffffLL || n_seq > 0x7fffffffLL) return hipErrorInvalidValue;
+  // one workgroup per slice of DL_SLICE news of a pass; the grid is sized from the shapes alone (hipGraph)
+  const int64_t per_pass = chunk < n_seq ? chunk : n_seq;
+  const int64_t nsl = (per_pass + DL_SLICE - 1) / DL_SLICE;
+  if (passes * nsl > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dense_row_lists_kernel, dim3((unsigned)(passes * nsl)), dim3(1024), 0, stream, mask, ids, n_seq, chunk, L,
+                     (int)nsl, live_loc, ids ? live_src : nullptr, counts, alive, n_tiles, tiles, cap, BM);
   return hipGetLastError();
 }
 

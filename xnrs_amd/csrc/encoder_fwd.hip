@@ -335,6 +335,7 @@ struct Route {
   // fc1: training lists (live) | live rows (lr_fc1; tail: deferred) | dense (lt_fc1: live row tiles; rowdot: fc2 in the epilogue)
   bool lr_fc1, lt_fc1, rowdot;
   bool skip_dead, read_counts;  // attend: zeros for an all-masked sequence; timer: the list counts of every pass are read back once
+  bool o_live;  // attend: the O row of a masked query is not stored at all (every reader of O walks the live rows)
 };
 
 // Short sequences: attention + additive pooling of ALL sequences in one launch (news_fused.hip); only the pooled
@@ -494,6 +495,17 @@ Route make_route(const SeqEncode& r, const Plan& p, NewsFusedArgs* nf, AdditiveF
   // history slots of the benchmark batch (49.5 % of its news) cost the attention core nothing.  MultiHeadAttention
   // alone (pooled == false) returns its masked rows to the caller and computes them.
   rt.skip_dead = rt.live || (r.pooled && r.m && knobs().mha_skip_masked);
+  // O rows nobody reads (XNRS_MHA_LIVE_O=0: off).  With the out-projection folded away the pooler works on the O rows, and
+  // on the live-row route O has exactly two readers: fc1 walks the pass's live-row list (fc1_live_rows_args), and the pooler
+  // leaves an all-masked sequence behind its mask and then reads the rows with a non-zero weight only -- a masked row's
+  // weight is its mask value, 0 (pool_score.hip: skip_masked, s_idx).  So the attention kernel stores NOTHING for a masked
+  // query (MhaCoreArgs::o_live_only): at the benchmark's history passes 49.5 % of the news are empty slots and a title fills
+  // 27.5 of its 50 rows, i.e. ~145 MB of zeros and averages per pass that went to HBM to be overwritten by the next pass.
+  // Only where the attention launch goes to the kernel that honours skip_dead (lt_qkv: decided by mha_core_skips_dead above).
+  // A dense reader of O keeps every write: the out-projection GEMM (XNRS_FOLD_OUT=0), the live-TILE fc1 without the row list
+  // (lt_fc1 alone: its tiles hold masked rows), MultiHeadAttention alone (the caller reads the rows), training (the backward).
+  // (and never with dropout: the kernel's dropout instantiations do not take the flag)
+  rt.o_live = rt.lr_fc1 && rt.lt_qkv && rt.fold && r.pooled && !r.train && rt.skip_dead && r.att->dropout_p == 0.f && knobs().mha_live_o;
   return rt;
 }
 
@@ -720,9 +732,13 @@ int32_t attend(const Call& c, const Pass& pass) {
   // at sequence c0 continues the counter at pair c0 * heads, so sequence c0 + i draws what it draws in an unchunked call.
   ma.seed = c.att->seed + (uint64_t)pass.c0 * (uint64_t)c.att->n_heads * 0x9E3779B97F4A7C15ull;
   ma.seed_dev = c.att->seed_dev; ma.stats = c.stats; ma.skip_dead = c.rt.skip_dead ? 1 : 0;
+  // (Route::o_live) fc1 and the pooler read the O rows of unmasked tokens only: the others are not stored
+  ma.o_live_only = c.rt.o_live ? 1 : 0;
   if (c.rt.lt_qkv && !mha_core_skips_dead(ma)) return XNRS_EUNSUPPORTED;  // (never: the two are decided by one rule)
   ProfScope ps(1, 4.0 * pass.rows * (double)c.L * c.D, c.stream);
-  return hip_rc(launch_mha_core(ma, c.stream));
+  XNRS_TRY(launch_mha_core(ma, c.stream));
+  if (c.rt.o_live) mha_live_o_add(1);
+  return XNRS_OK;
 }
 
 // ---- out-project: Y = O.Wo^T + bo; what the pooler sees from here on (pass->seq)

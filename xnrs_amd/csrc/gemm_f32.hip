@@ -501,6 +501,7 @@ static Knobs read_knobs() {
   k.additive_fused = (int)num("XNRS_ADDITIVE_FUSED", 1);
   k.af_fbuf = num("XNRS_AF_FBUF", 1) == 2 ? 2 : 1;
   k.mha_skip_masked = num("XNRS_MHA_SKIP_MASKED", 1) != 0;
+  k.mha_live_o = num("XNRS_MHA_LIVE_O", 1) != 0;
   {
     k.gemm_qkv_one_launch = num("XNRS_GEMM_QKV_ONE_LAUNCH", 1) != 0;
   }

@@ -58,6 +58,9 @@ struct Knobs {
                                 // launch_gemm_qkv_fc1; bitwise the same results; DESIGN.md section 4.1 "fc1 in the tail")
   bool mha_skip_masked = true;  // XNRS_MHA_SKIP_MASKED=0: pooled encoder calls compute the attention rows of all-masked sequences
                                 // and query tiles too (the pooler multiplies them by 0: bitwise the same pooled vectors)
+  bool mha_live_o = true;       // XNRS_MHA_LIVE_O=0: the attention core of a dense live-row pass stores the O rows of masked queries
+                                // too (zeros / the uniform average of V), although fc1 and the pooler walk the unmasked rows only
+                                // (encoder_fwd.hip Route::o_live; bitwise the same results)
   bool gemm_a16 = true;         // XNRS_GEMM_A16=0: an encoder call on a bf16 news table widens the rows of every pass to fp32 and takes
                                 // the fp32 route instead of projecting Q|K|V straight from the bf16 rows (gemm_split.hip: gemm_a16_kernel)
   int gru_layout = 0;           // XNRS_GRU_LAYOUT=1: the GRU recurrence as ONE launch of workgroups that own 32 batch rows for all
@@ -298,10 +301,18 @@ struct MhaCoreArgs {
   // whose consumers give masked rows a zero weight (the training forward over live rows, encoder_fwd.hip): such rows reach
   // neither the output nor a gradient, and with K = V = 0 (xnrs_row_lists) zeros are what the kernel would compute.
   int32_t skip_dead;
+  // 1 (optional; honoured where skip_dead is -- mha_core_skips_dead -- and never together with stats): the O row of a
+  // MASKED query is not stored at all -- neither the zeros of an all-masked sequence or query tile nor the uniform average
+  // of V that a masked query of a live tile computes.  For callers whose every reader of O walks the unmasked rows only
+  // (encoder_fwd.hip Route::o_live): those rows of `out` keep whatever they held.  0: every row is written, as before.
+  int32_t o_live_only;
 };
 hipError_t launch_mha_core(const MhaCoreArgs& a, hipStream_t stream);
 // would this launch go to the kernel that honours skip_dead, i.e. reads NO q / k / v row of an all-masked sequence?
 bool mha_core_skips_dead(const MhaCoreArgs& a);
+// the attention launches that went out with o_live_only since the last reset (xnrs_mha_live_o_count)
+void mha_live_o_add(int n);
+int64_t mha_live_o_read(bool reset);
 
 // backward of the attention core: recomputes P from Q, K and the saved row statistics
 struct MhaBwdArgs {
@@ -675,7 +686,7 @@ constexpr int LIVE_TILE_BM = 128;  // the forward GEMM's main tile height (GemmA
 inline int64_t live_tiles_cap(int64_t chunk, int L, int BM) { return (chunk * L + BM - 1) / BM; }
 hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM, uint8_t* alive,
                              int64_t* n_tiles, int32_t* tiles, hipStream_t stream);
-// launch_live_tiles AND the live rows of every dense pass in ONE launch (L <= 64; batch.hip compact_rows64_kernel<true>): pass p
+// launch_live_tiles AND the live rows of every dense pass in ONE launch (L <= 64; batch.hip dense_row_lists_kernel): pass p
 // writes counts[3 * p] = its unmasked token rows (mask != 0) and their ascending list at [p * chunk * L ..] -- live_loc in the
 // pass's own row space (news j of the pass, token s: j * L + s), live_src (written only with ids) as rows of the gathered table
 hipError_t launch_dense_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM,

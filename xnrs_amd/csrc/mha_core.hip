@@ -18,6 +18,7 @@
 //     16 consecutive floats.
 //   * the output comes out as O^T[dv = 16*dt + 4g + r][query c]: 4 consecutive dv per lane -> one
 //     16-byte store per lane straight into the (M, D) "concat heads" layout (layers.py:153).
+#include <atomic>
 #include <cstdlib>
 
 #include "kernels.h"
@@ -538,6 +539,10 @@ __global__ __launch_bounds__(256, (KTM * NFB <= 9 ? 8 : 5)) void mha_core_pair_k
     const int64_t mrow = a.mask_gather_ids ? (int64_t)a.mask_gather_ids[seq] * S : (int64_t)seq * S;
     mq = a.mask[mrow + query];
   }
+  // (o_live_only) the O row of a masked query has no reader: it is not stored -- not as zeros below, not as the uniform
+  // average of V at the end (kernels.h; kernel argument: uniform).  Inference only, so the dropout instantiations -- the
+  // launcher refuses the flag with dropout -- compile to what they were
+  const bool o_live = !DROP && a.o_live_only && a.skip_dead && a.mask && !a.q_off;
   if (a.skip_dead && a.mask && !a.q_off) {  // (kernel argument: uniform)
     if (!__syncthreads_or(qvalid && mq != 0.f)) {  // every query row of this sequence is masked: zeros, nothing read
       if (qvalid) {
@@ -545,7 +550,7 @@ __global__ __launch_bounds__(256, (KTM * NFB <= 9 ? 8 : 5)) void mha_core_pair_k
 #pragma unroll
         for (int dt = 0; dt < NFB; ++dt) {
           const int dv0 = dt * 16 + 4 * g;
-          if (dv0 < dk) *reinterpret_cast<f32x4*>(orow + dv0) = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (!o_live && dv0 < dk) *reinterpret_cast<f32x4*>(orow + dv0) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         if (a.stats && g == 0) {
           float* sp = a.stats + (((int64_t)seq * a.n_heads + hd) * (int64_t)S + query) * 2;
@@ -636,7 +641,7 @@ __global__ __launch_bounds__(256, (KTM * NFB <= 9 ? 8 : 5)) void mha_core_pair_k
 #pragma unroll
       for (int dt = 0; dt < NFB; ++dt) {
         const int dv0 = dt * 16 + 4 * g;
-        if (dv0 < dk) *reinterpret_cast<f32x4*>(orow0 + dv0) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (!o_live && dv0 < dk) *reinterpret_cast<f32x4*>(orow0 + dv0) = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       if (a.stats && g == 0) {
         float* sp = a.stats + (((int64_t)seq * a.n_heads + hd) * (int64_t)S + query) * 2;
@@ -774,10 +779,11 @@ __global__ __launch_bounds__(256, (KTM * NFB <= 9 ? 8 : 5)) void mha_core_pair_k
   }
   const int hoff = hd * dk;
   float* orow = a.out + (q0 + query) * a.ldo + hoff;
+  const bool stored = qvalid && !(o_live && mq == 0.f);  // (o_live_only: a masked query of a live tile)
 #pragma unroll
   for (int dt = 0; dt < NFB; ++dt) {
     const int dv0 = dt * 16 + 4 * g;
-    if (qvalid && dv0 < dk) *reinterpret_cast<f32x4*>(orow + dv0) = o[dt];
+    if (stored && dv0 < dk) *reinterpret_cast<f32x4*>(orow + dv0) = o[dt];
   }
 }
 
@@ -855,6 +861,12 @@ bool mha_core_skips_dead(const MhaCoreArgs& a) {
   return a.skip_dead && a.mask && !a.q_off && a.S <= 128 && mha_pick(a).pair;
 }
 
+static std::atomic<int64_t> g_mha_live_o{0};
+void mha_live_o_add(int n) { g_mha_live_o.fetch_add(n, std::memory_order_relaxed); }
+int64_t mha_live_o_read(bool reset) {
+  return reset ? g_mha_live_o.exchange(0, std::memory_order_relaxed) : g_mha_live_o.load(std::memory_order_relaxed);
+}
+
 hipError_t launch_mha_core(const MhaCoreArgs& a, hipStream_t stream) {
   if (a.n_seq <= 0 || a.S <= 0) return hipSuccess;
   if (a.S > 128) return hipErrorInvalidValue;
@@ -862,6 +874,8 @@ hipError_t launch_mha_core(const MhaCoreArgs& a, hipStream_t stream) {
   const bool vec = pk.vec, fast = pk.fast, use_lds = pk.use_lds;
   const int KT = pk.KT;
   if (a.q_off && (!fast || a.stats || a.dropout_p > 0.f || a.ldq % 4 != 0)) return hipErrorInvalidValue;
+  // o_live_only: only where the launch goes to the kernel that honours it, and never with the training statistics or dropout
+  if (a.o_live_only && (a.stats || a.dropout_p > 0.f || !mha_core_skips_dead(a))) return hipErrorInvalidValue;
   if (pk.pair) {
     const bool tail = pk.tail;
     const int KTM = pk.KTM;
