@@ -668,6 +668,42 @@ int32_t xnrs_topk_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, cons
                       const float *b1, const float *w2, const float *b2, const int64_t *excl_off, const int32_t *excl_rows,
                       int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- deep top-k: the same lists up to k = 1024 (candidate generation; csrc/topk.hip) ---------------------------------------
+ * xnrs_topk_deep / _bilinear / _mlp take the argument lists of xnrs_topk / _bilinear / _mlp and keep their contract word for
+ * word -- order, fillers, eligibility, the exclusion CSR with absolute offsets, pad_row, the NaN / +-inf / +-0 rules, the
+ * arithmetic, refusals on the host before any launch that write nothing, no host synchronisation, hipGraph-capturable, no
+ * allocation, no float atomics -- with the limit 1 <= k <= XNRS_TOPK_DEEP_MAX_K.  On top of it:
+ *   same bits : scores are formed by the score-tile function of xnrs_topk* and by nothing else; for k <= XNRS_TOPK_MAX_K a call
+ *               runs the two launches of xnrs_topk* and returns their rows and scores bit for bit.
+ *   prefix    : deep(k)[:, :j] == deep(j) for every j <= k, so deep(1024)[:, :128] == xnrs_topk*(128).
+ *   rank      : for an eligible row t of user b, xnrs_rank* over the same arguments gives ranks < k exactly when deep(k) lists
+ *               t, at position ranks with the bits of scores.
+ *   A user's result does not depend on B, on the user's position in the batch or on the slicing, and is the same on every run.
+ * For k > XNRS_TOPK_MAX_K the launches are the user-side GEMM where the scorer has one, then the partial and the merge kernel
+ * of xnrs_topk* instantiated for lists of up to 1024 keys: the partial kernel stages a list in LDS (8 KB per half-wave, 135 KB
+ * per workgroup: one workgroup per CU) and moves only the keys a list holds so far, the merge kernel holds three lists per
+ * wave (96 KB per workgroup).  The inner-product
+ * forms sweep the table twice: a first sweep with the kernels of xnrs_topk* keeps ceil(k / (slices - 1)) keys per slice, a
+ * one-thread-per-user kernel turns them into a key that k rows of the user are known to reach, and the second sweep starts its
+ * thresholds there (the floor removes only rows that cannot be among the k: the result does not depend on it).  Results cross
+ * from launch to launch at kernel boundaries only.
+ * ws: xnrs_topk_deep_workspace_bytes(B, n_rows, proj_width, k) = align(B * proj_width * 4) + align(B * 8) + align(slices * B *
+ * k * 8), align = up to 256 B, slices = xnrs_topk_slices(B, n_rows) <= 256: it grows with n_rows through the slice count alone
+ * and never holds a (B, n_rows) array; for k <= XNRS_TOPK_MAX_K it is xnrs_topk_workspace_bytes (no B * 8 term).  A pure host
+ * call; 0 for k outside the limit. */
+#define XNRS_TOPK_DEEP_MAX_K 1024
+size_t xnrs_topk_deep_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t k);
+int32_t xnrs_topk_deep(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const int64_t *excl_off,
+                       const int32_t *excl_rows, int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws,
+                       size_t ws_bytes, void *stream);
+int32_t xnrs_topk_deep_bilinear(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const float *w,
+                                const float *bias, const int64_t *excl_off, const int32_t *excl_rows, int32_t pad_row,
+                                int32_t k, int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_topk_deep_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, const float *u, int64_t B, const float *w1,
+                           const float *b1, const float *w2, const float *b2, const int64_t *excl_off,
+                           const int32_t *excl_rows, int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws,
+                           size_t ws_bytes, void *stream);
+
 /* ---- where given rows rank within the whole table per user (full-corpus evaluation; csrc/topk.hip) ------------------------
  * The sweep of xnrs_topk* that counts instead of selects, again without a (B, n_rows) score matrix.  table / P, u, the
  * weights, the exclusion CSR and pad_row mean what they mean for xnrs_topk*: the same tensors serve both calls.

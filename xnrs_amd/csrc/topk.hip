@@ -12,6 +12,8 @@
 //             varies from run to run; the merged list does not (the keys are totally ordered and a dropped candidate was
 //             already below k others).
 //   merge   : one wave per user merges the `slices` sorted lists into the final k and decodes rows and scores.
+// xnrs_topk_deep* (k up to 1024) runs the same two kernels instantiated for longer lists (KCAP), for the inner-product forms
+// behind a first sweep that finds each user a threshold to start from (tk_launch, topk_floor_kernel).
 //
 // Score tile
 //   inner product (dot, bilinear): the fp32 MFMA v_mfma_f32_32x32x2_f32 over ascending feature index, no split-K: bit for bit
@@ -138,6 +140,7 @@ struct TkOperands {
 struct TopkArgs : TkOperands {
   int k;
   uint64_t* part;
+  const uint64_t* floor;  // xnrs_topk_deep*, k > XNRS_TOPK_MAX_K: per user a key below which nothing is wanted (topk_floor_kernel), or NULL
 };
 
 // The score tile, the ONE definition of every kernel that ranks: acc <- the scores, before the bias, of table rows
@@ -207,10 +210,18 @@ __device__ __forceinline__ void tk_score_tile(const TkOperands& a, int64_t r0, c
 // candidate is compared with each (ids are compared, never dereferenced); an excluded candidate becomes key 0, below every
 // filler.  Every key's place is its count of greater keys: a list entry's index (fillers are told apart by it) plus the
 // surviving candidates above it, a candidate's rank among the candidates plus the list entries above it.
-struct TkHalf {  // the LDS of one half-wave
-  uint64_t stage[XNRS_TOPK_MAX_K], sorted[TK_CB];
+template <int KCAP>
+struct TkListLen {};  // (empty: the lists of xnrs_topk* are filled with fillers and always k long)
+template <>
+struct TkListLen<XNRS_TOPK_DEEP_MAX_K> {
+  int32_t nreal[32];  // of the first half of a wave: how many keys the list of the wave's user wave + 4 j holds so far
+};
+template <int KCAP>
+struct TkHalfT : TkListLen<KCAP> {  // the LDS of one half-wave; KCAP: the longest list it stages
+  uint64_t stage[KCAP], sorted[TK_CB];
   int32_t excl[64];
 };
+using TkHalf = TkHalfT<XNRS_TOPK_MAX_K>;
 // what a merge reads from global memory, fetched while the merge before it computes
 struct TkFetch {
   uint64_t key[XNRS_TOPK_MAX_K / 32];  // list[hl + 32 t]
@@ -299,6 +310,92 @@ __device__ __forceinline__ void tk_merge_pair(const TopkArgs& a, const TkFetch& 
   tk_lds_sync();
 }
 
+// The same merge for a list of up to KCAP > XNRS_TOPK_MAX_K keys (xnrs_topk_deep*).  Such a list does not fit the registers
+// of a fetch ahead, so it goes from the workspace straight into LDS and its entries are placed 256 at a time (eight searches
+// side by side).  Every entry is read from LDS, which holds the whole list before the first store to the workspace.
+// A list in the workspace is not filled with fillers first: nreal[] says how many keys it holds, only those are read, moved
+// and written, and the kernel ends every list that is not full with one filler (the merge kernel reads up to it).  So a
+// merge costs what the list holds, not k -- after the floor of the first sweep that is a few dozen keys.
+template <int KCAP>
+__device__ __forceinline__ void tk_merge_pair_deep(const TopkArgs& a, int64_t u0, uint64_t* lists, int k, int ul, TkHalfT<KCAP>& w,
+                                                   int32_t* nreal, uint64_t* bufs, uint64_t* thr, int* cnt, int hl, int h) {
+  const bool active = ul >= 0;  // (tk_pop_pair: a negative user is none; an idle half addresses user 0 and writes nothing)
+  const int uc = active ? ul : 0;
+  uint64_t* list = lists + (int64_t)uc * k;
+  uint64_t* buf = bufs + uc * TK_CB;
+  const int n = !active ? 0 : cnt[uc] < TK_CB ? cnt[uc] : TK_CB;
+  const int nl = active ? nreal[uc >> 2] : 0;                  // the keys of the list
+  const int nl2 = max(__shfl(nl, 0), __shfl(nl, 32));          // ... of the longer list of the two halves: uniform loop bounds
+  int64_t lo = 0, hi = 0;
+  if (a.excl_off && active) {
+    lo = a.excl_off[u0 + uc];
+    hi = a.excl_off[u0 + uc + 1];
+  }
+  int32_t id0 = tk_excl_id(a, lo + hl, hi), id1 = tk_excl_id(a, lo + hl + 32, hi);  // (on their way with the list)
+  for (int i0 = hl; i0 < nl2; i0 += 256) {  // eight loads in flight per lane
+    uint64_t t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = i0 + 32 * j < nl ? list[i0 + 32 * j] : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (i0 + 32 * j < nl) w.stage[i0 + 32 * j] = t[j];
+  }
+  uint64_t cand = hl < n ? buf[hl] : 0;
+  if (a.excl_off) {
+    const int32_t row = (int32_t)~(uint32_t)cand;  // (-1 without a candidate)
+    bool hit = false;
+    for (int64_t base = lo; __any(base < hi); base += 64) {
+      if (base != lo) {
+        id0 = tk_excl_id(a, base + hl, hi);
+        id1 = tk_excl_id(a, base + hl + 32, hi);
+      }
+      tk_lds_sync();
+      w.excl[hl] = id0;
+      w.excl[hl + 32] = id1;
+      tk_lds_sync();
+#pragma unroll
+      for (int e = 0; e < 64; ++e) hit |= w.excl[e] == row;
+    }
+    if (hit && row >= 0) cand = 0;
+  }
+  if (active) buf[hl] = cand;
+  tk_lds_sync();
+  int rank = 0;
+  if (cand) {
+#pragma unroll 8
+    for (int j = 0; j < TK_CB; ++j) rank += buf[j] > cand;
+    w.sorted[rank] = cand;
+  }
+  const int alive = __popc((uint32_t)(__ballot(cand != 0) >> (32 * h)));
+  tk_lds_sync();
+  const int cand_place = rank + tk_count_greater<KCAP>(w.stage, nl, cand);
+  for (int i0 = 0; i0 < nl2; i0 += 256) {
+    uint64_t key[8];
+    int place[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int i = i0 + hl + 32 * t;
+      key[t] = i < nl ? w.stage[i] : 0;
+      place[t] = i + tk_count_greater<TK_CB>(w.sorted, alive, key[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+      if (key[t] && place[t] < k) {
+        if (place[t] != i0 + hl + 32 * t) list[place[t]] = key[t];
+        if (place[t] == k - 1) thr[uc] = key[t];
+      }
+  }
+  if (cand && cand_place < k) {
+    list[cand_place] = cand;
+    if (cand_place == k - 1) thr[uc] = cand;
+  }
+  if (active && hl == 0) {
+    cnt[uc] = 0;
+    nreal[uc >> 2] = nl + alive < k ? nl + alive : k;
+  }
+  tk_lds_sync();  // (as tk_merge_pair: the LDS of the half may be written again)
+}
+
 // the two lowest set bits of `todo`, taken out of it: the lower for half 0, the other (or -1: none) for half 1
 __device__ __forceinline__ int tk_pop_pair(uint32_t& todo, int h) {
   const int j0 = __ffs(todo) - 1;
@@ -309,32 +406,39 @@ __device__ __forceinline__ int tk_pop_pair(uint32_t& todo, int h) {
 }
 
 // the merges of one wave: its users (wave, wave + 4, ...) whose buffer is full -- at the end of the slice: not empty -- two at a
-// time, the next two users' lists on their way while these two merge
-__device__ __forceinline__ void tk_merge_phase(const TopkArgs& a, int64_t u0, uint64_t* lists, int k, int nu, bool final, TkHalf* w,
+// time, the next two users' lists on their way while these two merge (KCAP > XNRS_TOPK_MAX_K: without the fetch ahead)
+template <int KCAP>
+__device__ __forceinline__ void tk_merge_phase(const TopkArgs& a, int64_t u0, uint64_t* lists, int k, int nu, bool final, TkHalfT<KCAP>* w,
                                                uint64_t* bufs, uint64_t* thr, int* cnt, int wave, int lane) {
   const int hl = lane & 31, h = lane >> 5;
   const int mine = wave + 4 * hl;
   const int c = h == 0 && mine < nu ? cnt[mine] : 0;
   uint32_t todo = (uint32_t)__ballot(final ? c > 0 : c >= TK_CB);
   if (!todo) return;
-  TkFetch cur = tk_fetch(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), hl);
-  for (;;) {
-    const bool more = todo != 0;
-    TkFetch nxt = cur;
-    if (more) nxt = tk_fetch(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), hl);
-    tk_merge_pair(a, cur, lists, k, w[h], bufs, thr, cnt, hl, h);
-    if (!more) break;
-    cur = nxt;
+  if constexpr (KCAP > XNRS_TOPK_MAX_K) {
+    while (todo) tk_merge_pair_deep<KCAP>(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), w[h], w[0].nreal, bufs, thr, cnt, hl, h);
+  } else {
+    TkFetch cur = tk_fetch(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), hl);
+    for (;;) {
+      const bool more = todo != 0;
+      TkFetch nxt = cur;
+      if (more) nxt = tk_fetch(a, u0, lists, k, wave + 4 * tk_pop_pair(todo, h), hl);
+      tk_merge_pair(a, cur, lists, k, w[h], bufs, thr, cnt, hl, h);
+      if (!more) break;
+      cur = nxt;
+    }
   }
 }
 
-// (two workgroups per CU for the MFMA form; the MLP form's 64 tanhf per feature want more than 256 registers)
-template <bool MLP>
-__global__ __launch_bounds__(256, MLP ? 1 : 2) void topk_partial_kernel(TopkArgs a) {
+// (two workgroups per CU for the MFMA form; the MLP form's 64 tanhf per feature want more than 256 registers.  KCAP: the
+// longest list of the call -- XNRS_TOPK_MAX_K for xnrs_topk*; the 1024 of xnrs_topk_deep* stages 8 KB per half-wave, 135 KB of
+// LDS in all, and is alone on its CU)
+template <bool MLP, int KCAP = XNRS_TOPK_MAX_K>
+__global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void topk_partial_kernel(TopkArgs a) {
   __shared__ float At[TK_KT * TK_PITCH], Bt[TK_KT * TK_PITCH];  // table rows / users of one stage, feature-major
   __shared__ float w2s[TK_KT];
   __shared__ uint64_t buf[TK_TILE * TK_CB], thr[TK_TILE];
-  __shared__ TkHalf halves[4][2];
+  __shared__ TkHalfT<KCAP> halves[4][2];
   __shared__ int cnt[TK_TILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
   const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;  // the wave's 64 x 64 part of the score tile
@@ -342,9 +446,16 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void topk_partial_kernel(TopkArgs
   const int nu = a.B - u0 < TK_TILE ? (int)(a.B - u0) : TK_TILE;
   const int k = a.k;
   uint64_t* lists = a.part + ((int64_t)blockIdx.y * a.B + u0) * k;
-  for (int i = tid; i < nu * k; i += 256) lists[i] = TK_FILLER;
+  if constexpr (KCAP > XNRS_TOPK_MAX_K) {
+    if (tid < TK_TILE) halves[tid & 3][0].nreal[tid >> 2] = 0;  // (the lists start empty, and are not filled)
+  } else {
+    for (int i = tid; i < nu * k; i += 256) lists[i] = TK_FILLER;
+  }
   for (int i = tid; i < TK_TILE; i += 256) {
-    thr[i] = TK_FILLER;
+    uint64_t t0 = TK_FILLER;
+    if constexpr (KCAP > XNRS_TOPK_MAX_K)
+      if (a.floor && i < nu) t0 = a.floor[u0 + i];  // the threshold starts where the first sweep proved k rows to be
+    thr[i] = t0;
     cnt[i] = 0;
   }
   __syncthreads();
@@ -391,45 +502,119 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void topk_partial_kernel(TopkArgs
         else pend &= ~(1ull << b);
       }
       const int again = __syncthreads_or(overflow);
-      tk_merge_phase(a, u0, lists, k, nu, false, halves[wave], buf, thr, cnt, wave, lane);
+      tk_merge_phase<KCAP>(a, u0, lists, k, nu, false, halves[wave], buf, thr, cnt, wave, lane);
       __syncthreads();
       if (!again) break;
     }
   }
-  tk_merge_phase(a, u0, lists, k, nu, true, halves[wave], buf, thr, cnt, wave, lane);  // the slice is done: what is still buffered
+  tk_merge_phase<KCAP>(a, u0, lists, k, nu, true, halves[wave], buf, thr, cnt, wave, lane);  // the slice is done: what is still buffered
+  if constexpr (KCAP > XNRS_TOPK_MAX_K) {
+    __syncthreads();
+    if (tid < nu) {  // a filler ends a list that is not full
+      const int n = halves[tid & 3][0].nreal[tid >> 2];
+      if (n < k) lists[(int64_t)tid * k + n] = TK_FILLER;
+    }
+  }
 }
 
-// rows[b, :], scores[b, :] <- the k greatest keys of the `slices` sorted lists of user b; one wave per user
+// dst[0, n) <- the keys of a deep list up to its filler (or all k), 256 at a time -> n; all 64 lanes of a wave
+__device__ __forceinline__ int tk_load_list(const uint64_t* list, int k, uint64_t* dst, int lane) {
+  for (int i0 = 0; i0 < k; i0 += 256) {
+    uint64_t t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = i0 + 64 * j + lane < k ? list[i0 + 64 * j + lane] : TK_FILLER;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint64_t end = __ballot(t[j] == TK_FILLER);
+      const int n = end ? __ffsll((unsigned long long)end) - 1 : 64;  // (the keys of these 64 before the first filler)
+      if (lane < n) dst[i0 + 64 * j + lane] = t[j];
+      if (end) return i0 + 64 * j + n;
+    }
+  }
+  return k;
+}
+
+// rows[b, :], scores[b, :] <- the k greatest keys of the `slices` sorted lists of user b; one wave per user (KCAP = 1024: 96 KB)
+template <int KCAP>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* part, int slices, int64_t B, int k, int32_t* rows,
                                                          float* scores) {
-  __shared__ uint64_t lds[4][3][XNRS_TOPK_MAX_K];
+  __shared__ uint64_t lds[4][3][KCAP];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t b = (int64_t)blockIdx.x * 4 + wave;
   if (b >= B) return;  // (no workgroup barrier below)
   uint64_t *cur = lds[wave][0], *in = lds[wave][1], *nxt = lds[wave][2];
-  for (int i = lane; i < k; i += 64) cur[i] = part[b * k + i];
-  for (int s = 1; s < slices; ++s) {
-    const uint64_t* list = part + ((int64_t)s * B + b) * k;
-    for (int i = lane; i < k; i += 64) in[i] = list[i];
-    tk_wave_sync();
-    // two sorted lists: a key's place is its index plus the other list's count of greater keys.  Real keys are distinct;
-    // two fillers may land on one place, with the same value
-    for (int i = lane; i < k; i += 64) {
-      const int rc = i + tk_count_greater<XNRS_TOPK_MAX_K>(in, k, cur[i]);
-      if (rc < k) nxt[rc] = cur[i];
-      const int ri = i + tk_count_greater<XNRS_TOPK_MAX_K>(cur, k, in[i]);
-      if (ri < k) nxt[ri] = in[i];
+  if constexpr (KCAP > XNRS_TOPK_MAX_K) {
+    // long lists that the floor of the first sweep leaves mostly empty, each ended by a filler when it is not full (what lies
+    // behind that filler was never written): only the real keys are loaded, searched and placed.  cur[0, nc) and in[0, ni)
+    // are the real keys; what lies past them is never read
+    int nc = tk_load_list(part + b * k, k, cur, lane);
+    for (int s = 1; s < slices; ++s) {
+      tk_wave_sync();  // (the searches of the round before have read `in`)
+      const int ni = tk_load_list(part + ((int64_t)s * B + b) * k, k, in, lane);
+      tk_wave_sync();
+      for (int i = lane; i < nc; i += 64) {
+        const int rc = i + tk_count_greater<KCAP>(in, ni, cur[i]);
+        if (rc < k) nxt[rc] = cur[i];
+      }
+      for (int i = lane; i < ni; i += 64) {
+        const int ri = i + tk_count_greater<KCAP>(cur, nc, in[i]);
+        if (ri < k) nxt[ri] = in[i];
+      }
+      nc = nc + ni < k ? nc + ni : k;
+      tk_wave_sync();
+      uint64_t* t = cur;
+      cur = nxt;
+      nxt = t;
     }
     tk_wave_sync();
-    uint64_t* t = cur;
-    cur = nxt;
-    nxt = t;
+    for (int i = lane; i < k; i += 64) {
+      const uint64_t key = i < nc ? cur[i] : TK_FILLER;
+      rows[b * k + i] = (int32_t)~(uint32_t)key;
+      scores[b * k + i] = tk_score(key);
+    }
+  } else {
+    for (int i = lane; i < k; i += 64) cur[i] = part[b * k + i];
+    for (int s = 1; s < slices; ++s) {
+      const uint64_t* list = part + ((int64_t)s * B + b) * k;
+      for (int i = lane; i < k; i += 64) in[i] = list[i];
+      tk_wave_sync();
+      // two sorted lists: a key's place is its index plus the other list's count of greater keys.  Real keys are distinct;
+      // two fillers may land on one place, with the same value
+      for (int i = lane; i < k; i += 64) {
+        const int rc = i + tk_count_greater<KCAP>(in, k, cur[i]);
+        if (rc < k) nxt[rc] = cur[i];
+        const int ri = i + tk_count_greater<KCAP>(cur, k, in[i]);
+        if (ri < k) nxt[ri] = in[i];
+      }
+      tk_wave_sync();
+      uint64_t* t = cur;
+      cur = nxt;
+      nxt = t;
+    }
+    tk_wave_sync();
+    for (int i = lane; i < k; i += 64) {
+      rows[b * k + i] = (int32_t)~(uint32_t)cur[i];
+      scores[b * k + i] = tk_score(cur[i]);
+    }
   }
-  tk_wave_sync();
-  for (int i = lane; i < k; i += 64) {
-    rows[b * k + i] = (int32_t)~(uint32_t)cur[i];
-    scores[b * k + i] = tk_score(cur[i]);
+}
+
+// floor[b] <- a key that at least k eligible rows of user b are known to reach, less one -- so that "key > floor" admits them
+// all -- from the first sweep's lists of kl keys per slice: the lowest kl-th key among the slices whose list is full, when those
+// lists hold k keys between them; the filler (no floor) when they do not.  One thread per user.
+__global__ __launch_bounds__(256) void topk_floor_kernel(const uint64_t* part, int slices, int64_t B, int kl, int k, uint64_t* floor) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  uint64_t lowest = ~0ull;
+  int64_t full = 0;
+  for (int s = 0; s < slices; ++s) {
+    const uint64_t last = part[((int64_t)s * B + b) * kl + kl - 1];
+    if (last > TK_FILLER) {  // (a real key: the slice has kl eligible rows)
+      ++full;
+      lowest = last < lowest ? last : lowest;
+    }
   }
+  floor[b] = full * kl >= k ? lowest - 1 : TK_FILLER;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- rank
@@ -618,21 +803,37 @@ struct TopkCall {
   void* ws;
   size_t ws_bytes;
   int32_t proj_width;
+  bool deep;  // xnrs_topk_deep*: k up to XNRS_TOPK_DEEP_MAX_K
 };
+
+// the projected user side [B, proj_width] | k > XNRS_TOPK_MAX_K: the floor keys [B] | the partial lists [slices, B, k] of 64-bit keys
+size_t tk_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t k, int32_t max_k) {
+  if (B <= 0 || n_rows < 0 || proj_width < 0 || k < 1 || k > max_k) return 0;
+  return carve_total({(size_t)B * proj_width * F32, k > XNRS_TOPK_MAX_K ? (size_t)B * sizeof(uint64_t) : 0,
+                      (size_t)xnrs_topk_slices(B, n_rows) * B * k * sizeof(uint64_t)});
+}
 
 // the argument checks every entry point shares; XNRS_OK with *run = false: nothing to do
 int32_t tk_check(const TopkCall& c, const float* u, bool* run) {
   *run = false;
-  if (c.k < 1 || c.k > XNRS_TOPK_MAX_K || c.W <= 0 || c.B < 0 || c.n_rows < 0 || c.n_rows > 0x7fffffffLL) return XNRS_EINVAL;
+  const int32_t max_k = c.deep ? XNRS_TOPK_DEEP_MAX_K : XNRS_TOPK_MAX_K;
+  if (c.k < 1 || c.k > max_k || c.W <= 0 || c.B < 0 || c.n_rows < 0 || c.n_rows > 0x7fffffffLL) return XNRS_EINVAL;
   if (c.B == 0) return XNRS_OK;
   if (!c.rows || !c.scores || !u || (c.n_rows > 0 && !c.table) || (c.excl_off && !c.excl_rows)) return XNRS_EINVAL;
-  const size_t need = xnrs_topk_workspace_bytes(c.B, c.n_rows, c.proj_width, c.k);
+  const size_t need = tk_workspace_bytes(c.B, c.n_rows, c.proj_width, c.k, max_k);
   if (!c.ws || c.ws_bytes < need) return XNRS_EWORKSPACE;
   *run = true;
   return XNRS_OK;
 }
 
-// the two launches; up:(B, W) the user side as the kernel reads it (u, v = u W[0], q = u W1u^T + b1)
+// the launches; up:(B, W) the user side as the kernel reads it (u, v = u W[0], q = u W1u^T + b1).  k <= XNRS_TOPK_MAX_K runs
+// the two kernels of xnrs_topk* whichever entry point was called.  A longer list runs their XNRS_TOPK_DEEP_MAX_K instantiations,
+// which move a list of k keys through LDS on every merge: the inner-product forms therefore sweep the table twice.  The first
+// sweep, with the kernels of xnrs_topk*, keeps kl = ceil(k / (slices - 1)) keys per slice -- one slice may be short -- and
+// topk_floor_kernel turns them into a key that k rows of the user are known to reach; the second sweep starts its thresholds
+// there, so that about k rows of the whole table pass instead of about k (1 + ln(slice rows / k)) per slice.  The floor only
+// removes rows that cannot be among the k, so the result does not depend on it.  The MLP form sweeps once: its tanhf cost more
+// than its merges.  The first sweep's lists lie where the second sweep's will (they are dead by then).
 hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const float* bias, hipStream_t stream) {
   const int64_t cps = tk_chunks_per_slice(c.B, c.n_rows);
   const int32_t slices = xnrs_topk_slices(c.B, c.n_rows);
@@ -651,17 +852,70 @@ hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const 
   a.pad_row = c.pad_row;
   a.vec_t = tk_vec_ok(c.table, c.W);
   a.vec_u = tk_vec_ok(up, c.W);
-  a.part = at<uint64_t>(c.ws, align_up((size_t)c.B * c.proj_width * F32));
+  const bool deep = c.k > XNRS_TOPK_MAX_K;
+  Carver carve;
+  carve.take((size_t)c.B * c.proj_width * F32);
+  uint64_t* floor = at<uint64_t>(c.ws, carve.take_if(deep, (size_t)c.B * sizeof(uint64_t)));
+  a.part = at<uint64_t>(c.ws, carve.take(0));
   const int64_t tiles = (c.B + TK_TILE - 1) / TK_TILE;
   if (tiles > 0x7fffffffLL) return hipErrorInvalidValue;
   const dim3 grid((unsigned)tiles, (unsigned)slices);
-  if (w2) hipLaunchKernelGGL(topk_partial_kernel<true>, grid, dim3(256), 0, stream, a);
+  const int kl = slices > 1 ? (c.k + slices - 2) / (slices - 1) : 0;
+  if (deep && !w2 && kl >= 1 && kl <= XNRS_TOPK_MAX_K) {
+    a.k = kl;
+    hipLaunchKernelGGL(topk_partial_kernel<false>, grid, dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(topk_floor_kernel, dim3((unsigned)((c.B + 255) / 256)), dim3(256), 0, stream, a.part, slices, c.B, kl, c.k, floor);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    a.k = c.k;
+    a.floor = floor;
+  }
+  if (deep && w2) hipLaunchKernelGGL((topk_partial_kernel<true, XNRS_TOPK_DEEP_MAX_K>), grid, dim3(256), 0, stream, a);
+  else if (deep) hipLaunchKernelGGL((topk_partial_kernel<false, XNRS_TOPK_DEEP_MAX_K>), grid, dim3(256), 0, stream, a);
+  else if (w2) hipLaunchKernelGGL(topk_partial_kernel<true>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(topk_partial_kernel<false>, grid, dim3(256), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, stream, a.part, slices, c.B, c.k, c.rows,
-                     c.scores);
+  const dim3 mgrid((unsigned)((c.B + 3) / 4));
+  if (deep) hipLaunchKernelGGL(topk_merge_kernel<XNRS_TOPK_DEEP_MAX_K>, mgrid, dim3(256), 0, stream, a.part, slices, c.B, c.k, c.rows, c.scores);
+  else hipLaunchKernelGGL(topk_merge_kernel<XNRS_TOPK_MAX_K>, mgrid, dim3(256), 0, stream, a.part, slices, c.B, c.k, c.rows, c.scores);
   return hipGetLastError();
+}
+
+// the bodies of xnrs_topk / _bilinear / _mlp and of their xnrs_topk_deep twins (c.deep)
+int32_t tk_dot(const TopkCall& c, const float* u, hipStream_t stream) {
+  bool run;
+  XNRS_TRY_RC(tk_check(c, u, &run));
+  if (run) XNRS_TRY(tk_launch(c, u, nullptr, nullptr, stream));
+  return XNRS_OK;
+}
+
+int32_t tk_bilinear(const TopkCall& c, const float* u, const float* w, const float* bias, hipStream_t stream) {
+  const int32_t E = c.W;
+  bool run;
+  XNRS_TRY_RC(tk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w) return XNRS_EINVAL;
+  float* v = static_cast<float*>(c.ws);
+  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, c.B, E, E, stream));  // v_b = W[0]^T u_b, as xnrs_score_csr_bilinear
+  XNRS_TRY(tk_launch(c, v, nullptr, bias, stream));
+  return XNRS_OK;
+}
+
+int32_t tk_mlp(const TopkCall& c, int32_t E, const float* u, const float* w1, const float* b1, const float* w2, const float* b2,
+               hipStream_t stream) {
+  const int32_t H = c.W;
+  if (E <= 0) return XNRS_EINVAL;
+  bool run;
+  XNRS_TRY_RC(tk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w1 || !w2) return XNRS_EINVAL;
+  float* q = static_cast<float*>(c.ws);
+  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, c.B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_score_csr_mlp
+  XNRS_TRY(tk_launch(c, q, w2, b2, stream));
+  return XNRS_OK;
 }
 
 struct RankCall {
@@ -739,50 +993,51 @@ int32_t xnrs_topk_slices(int64_t B, int64_t n_rows) {
 }
 
 size_t xnrs_topk_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t k) {
-  if (B <= 0 || n_rows < 0 || proj_width < 0 || k < 1 || k > XNRS_TOPK_MAX_K) return 0;
-  // the projected user side [B, proj_width] | the partial lists [slices, B, k] of 64-bit keys
-  return carve_total({(size_t)B * proj_width * F32, (size_t)xnrs_topk_slices(B, n_rows) * B * k * sizeof(uint64_t)});
+  return tk_workspace_bytes(B, n_rows, proj_width, k, XNRS_TOPK_MAX_K);
 }
 
 int32_t xnrs_topk(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* excl_off,
                   const int32_t* excl_rows, int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes,
                   void* stream) {
-  const TopkCall c{table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, 0};
-  bool run;
-  XNRS_TRY_RC(tk_check(c, u, &run));
-  if (run) XNRS_TRY(tk_launch(c, u, nullptr, nullptr, (hipStream_t)stream));
-  return XNRS_OK;
+  return tk_dot({table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, 0, false}, u, (hipStream_t)stream);
 }
 
 int32_t xnrs_topk_bilinear(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
                            const float* bias, const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t k,
-                           int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const TopkCall c{table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, E};
-  bool run;
-  XNRS_TRY_RC(tk_check(c, u, &run));
-  if (!run) return XNRS_OK;
-  if (!w) return XNRS_EINVAL;
-  float* v = static_cast<float*>(ws);
-  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, B, E, E, stream));  // v_b = W[0]^T u_b, as xnrs_score_csr_bilinear
-  XNRS_TRY(tk_launch(c, v, nullptr, bias, stream));
-  return XNRS_OK;
+                           int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return tk_bilinear({table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, E, false}, u, w, bias,
+                     (hipStream_t)stream);
 }
 
 int32_t xnrs_topk_mlp(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
                       const float* b1, const float* w2, const float* b2, const int64_t* excl_off, const int32_t* excl_rows,
-                      int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (E <= 0) return XNRS_EINVAL;
-  const TopkCall c{P, n_rows, H, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, H};
-  bool run;
-  XNRS_TRY_RC(tk_check(c, u, &run));
-  if (!run) return XNRS_OK;
-  if (!w1 || !w2) return XNRS_EINVAL;
-  float* q = static_cast<float*>(ws);
-  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_score_csr_mlp
-  XNRS_TRY(tk_launch(c, q, w2, b2, stream));
-  return XNRS_OK;
+                      int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return tk_mlp({P, n_rows, H, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, H, false}, E, u, w1, b1, w2, b2,
+                (hipStream_t)stream);
+}
+
+size_t xnrs_topk_deep_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t k) {
+  return tk_workspace_bytes(B, n_rows, proj_width, k, XNRS_TOPK_DEEP_MAX_K);
+}
+
+int32_t xnrs_topk_deep(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* excl_off,
+                       const int32_t* excl_rows, int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws,
+                       size_t ws_bytes, void* stream) {
+  return tk_dot({table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, 0, true}, u, (hipStream_t)stream);
+}
+
+int32_t xnrs_topk_deep_bilinear(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
+                                const float* bias, const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t k,
+                                int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return tk_bilinear({table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, E, true}, u, w, bias,
+                     (hipStream_t)stream);
+}
+
+int32_t xnrs_topk_deep_mlp(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
+                           const float* b1, const float* w2, const float* b2, const int64_t* excl_off, const int32_t* excl_rows,
+                           int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return tk_mlp({P, n_rows, H, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, H, true}, E, u, w1, b1, w2, b2,
+                (hipStream_t)stream);
 }
 
 size_t xnrs_rank_workspace_bytes(int64_t B, int32_t proj_width) {

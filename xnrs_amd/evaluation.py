@@ -196,21 +196,12 @@ def _history_csr(behaviors: Behaviors, sess: torch.Tensor, first):
     return _session_csr(behaviors.hist_off, behaviors.hist_val, sess, first)
 
 
-@torch.no_grad()
-def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions=None, batch: int = 4096,
-              exclude_history: bool = True):
-    """For every session the k news of the WHOLE table its user scores highest -> (rows:(n,k) int32, scores:(n,k) fp32) on the
-    device, best first (include/xnrs_hip.h: xnrs_topk -- higher raw score first, equal scores lower row first, no ReLU; with
-    fewer than k eligible news the tail is row -1 / score -inf).
+TOPK_MAX_K, TOPK_DEEP_MAX_K = hip._CONSTANTS["TOPK_MAX_K"], hip._CONSTANTS["TOPK_DEEP_MAX_K"]  # include/xnrs_hip.h
 
-    Once per call the news table is encoded (encode_news_table) and handed to the scorer (prepare_csr); per batch of sessions
-    the user tower runs over the last `l_hist` clicks as DeviceBatcher builds them (encode_user, as evaluate) and the scorer's
-    topk(table, u, k, ...) ranks the table without a (sessions, n_rows) score matrix.  store.pad_row is never recommended;
-    with `exclude_history` neither is any news of the session's FULL history (hist_off / hist_val, not only the last l_hist).
-    `sessions`: session indices (None = all); row i of the result is session sessions[i].
 
-    One process, one device: rank-sharded recommendation is out of scope.  A scorer without topk / prepare_csr, a model
-    whose news vectors depend on the user (NPA) and CAUM (no candidate-independent user vector) raise NotImplementedError."""
+def _recommending_model_parts(model, behaviors: Behaviors, k: int):
+    """(prepare_csr, the scorer's top-k call for this k, user index or None) of a model that can rank the table on its own, or
+    the refusal -- before anything is encoded."""
     scorer = getattr(model, "rec_model", None)
     prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, "topk", None)
     if prepare is None or topk is None:
@@ -218,22 +209,34 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
                                   "(prepare_csr / topk); ranking it with a plain dot product would recommend another model's news")
     if getattr(model, "user_dependent_news", False):
         raise NotImplementedError(f"recommend(): the news vectors of {type(model).__name__} depend on the user, so no table of "
-                                  "news vectors exists to rank")
-    vecs, hm = encode_news_table(model, store)
-    table = prepare(vecs)
-    batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
-    dev = vecs.device
+                                  "news vectors exists to rank; give it a candidate generator -- recommend(model, ..., "
+                                  "generator=a model that ranks the table, pool=...) -- and it re-ranks the generator's list")
+    if k > TOPK_MAX_K:
+        topk = getattr(scorer, "topk_deep", None)
+        if topk is None:
+            raise NotImplementedError(f"recommend(): the scorer {type(scorer).__name__} has no topk_deep, so it lists at most "
+                                      f"k = {TOPK_MAX_K} news per session, not {k}")
     uidx = None
     if getattr(model, "uses_user_index", False):
         uidx = getattr(behaviors, "user_index", None)
         if uidx is None:
             raise ValueError(f"recommend(): {type(model).__name__} needs the user index of every session (sessions without "
                              "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    return prepare, topk, uidx
+
+
+def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions, batch: int,
+                        exclude_history: bool):
+    """The table of `model` encoded once, then per batch of sessions (lo, sess, hist rows, top-k rows, top-k scores)."""
+    prepare, topk, uidx = parts
+    vecs, hm = encode_news_table(model, store)
+    table = prepare(vecs)
+    batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
+    dev = vecs.device
+    if uidx is not None:
         uidx = uidx.to(dev)
     every = sessions is None
     sessions = torch.arange(len(behaviors), device=dev) if every else torch.as_tensor(sessions, dtype=torch.int64, device=dev)
-    rows = torch.empty((sessions.numel(), k), dtype=torch.int32, device=dev)
-    scores = torch.empty((sessions.numel(), k), dtype=torch.float32, device=dev)
     for lo in range(0, sessions.numel(), batch):
         sess = sessions[lo:lo + batch]
         hist = batcher.eval_batch(sess)[0]
@@ -241,7 +244,87 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
         m = hm[hist.long()]
         u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
         excl = _history_csr(behaviors, sess, lo if every else None) if exclude_history else (None, None)
-        rows[lo:lo + batch], scores[lo:lo + batch] = topk(table, u, k, excl[0], excl[1], store.pad_row)
+        yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row))
+
+
+def _rerank(rows: torch.Tensor, r: torch.Tensor, k: int):
+    """Per session the k best of the scored candidates rows:(b, pool) int32 (-1: no candidate), r:(b, pool), in the order of
+    xnrs_topk: higher score first, equal scores (-0 == +0) lower table row first, a NaN never, fillers -1 / -inf behind.
+    Two stable device sorts over at most 1024 entries per session: by row, then by score descending."""
+    ok = (rows >= 0) & ~torch.isnan(r)
+    score = torch.where(ok, r + 0.0, torch.full_like(r, float("-inf")))  # (-0 + 0 == +0: the sort sees one zero)
+    by_row = torch.where(ok, rows, torch.full_like(rows, torch.iinfo(torch.int32).max)).argsort(dim=1, stable=True)
+    by_score = score.gather(1, by_row).argsort(dim=1, descending=True, stable=True)
+    idx = by_row.gather(1, by_score)[:, :k]
+    ok = ok.gather(1, idx)
+    return (torch.where(ok, rows.gather(1, idx), torch.full_like(idx, -1, dtype=torch.int32)),
+            torch.where(ok, r.gather(1, idx), torch.full_like(score[:, :k], float("-inf"))))
+
+
+@torch.no_grad()
+def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions=None, batch: int = 4096,
+              exclude_history: bool = True, generator=None, pool=None):
+    """For every session the k news of the WHOLE table its user scores highest -> (rows:(n,k) int32, scores:(n,k) fp32) on the
+    device, best first (include/xnrs_hip.h: xnrs_topk -- higher raw score first, equal scores lower row first, no ReLU; with
+    fewer than k eligible news the tail is row -1 / score -inf).  k <= 128 runs the scorer's topk, 129 <= k <= 1024 its
+    topk_deep (xnrs_topk_deep: the same order and bits, longer lists); a larger k raises ValueError.
+
+    Once per call the news table is encoded (encode_news_table) and handed to the scorer (prepare_csr); per batch of sessions
+    the user tower runs over the last `l_hist` clicks as DeviceBatcher builds them (encode_user, as evaluate) and the scorer's
+    topk(table, u, k, ...) ranks the table without a (sessions, n_rows) score matrix.  store.pad_row is never recommended;
+    with `exclude_history` neither is any news of the session's FULL history (hist_off / hist_val, not only the last l_hist).
+    `sessions`: session indices (None = all); row i of the result is session sessions[i].
+
+    Two stages (`generator`): for a `model` whose news vectors depend on the user (NPA: user_dependent_news and the hook
+    score_impressions) no table exists to rank.  `generator` -- any model recommend() accepts on its own -- then lists `pool`
+    news per session over ITS table (k <= pool <= 1024, default min(1024, max(8 k, 128)); exclusions and the pad row apply
+    there), `model` scores exactly those through score_impressions(store, hist, rows, sess, user_index[sess], relu=False),
+    and the k best of its scores are returned in the order above with the scores of `model`.  A place the generator could
+    not fill is encoded as the pad row and its score thrown away, so no list length is read on the host.  The selection
+    among at most 1024 scores per session is two device sorts, not a kernel of its own.  behaviors.user_index is required.
+
+    One process, one device: rank-sharded recommendation is out of scope.  A scorer without topk / prepare_csr, a model
+    whose news vectors depend on the user (NPA) without `generator`, and CAUM (no candidate-independent user vector, no
+    score_impressions) raise NotImplementedError."""
+    k = int(k)
+    if k > TOPK_DEEP_MAX_K:
+        raise ValueError(f"recommend(): k = {k} is above the longest list of the top-k kernels, {TOPK_DEEP_MAX_K}")
+    if generator is None:
+        if pool is not None:
+            raise ValueError("recommend(): `pool` is the list length of a `generator`; there is none")
+        parts = _recommending_model_parts(model, behaviors, k)
+        n = len(behaviors) if sessions is None else len(sessions)
+        dev = behaviors.hist_off.device
+        rows = torch.empty((n, k), dtype=torch.int32, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        for lo, _, _, r, s in _table_topk_batches(model, parts, store, behaviors, l_hist, k, sessions, batch, exclude_history):
+            rows[lo:lo + batch], scores[lo:lo + batch] = r, s
+        hip.check_status(dev)
+        return rows, scores
+    if not getattr(model, "user_dependent_news", False) or getattr(model, "score_impressions", None) is None:
+        raise NotImplementedError(f"recommend(generator=...): {type(model).__name__} has no score_impressions over news vectors "
+                                  "that depend on the user; a model that ranks the table is called without a generator")
+    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
+    if not k <= pool <= TOPK_DEEP_MAX_K:
+        raise ValueError(f"recommend(): pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
+    parts = _recommending_model_parts(generator, behaviors, pool)
+    uidx = getattr(behaviors, "user_index", None)
+    if uidx is None:
+        raise ValueError(f"recommend(): {type(model).__name__} needs the user index of every session (sessions without "
+                         "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    n = len(behaviors) if sessions is None else len(sessions)
+    dev = behaviors.hist_off.device
+    uidx = uidx.to(dev)
+    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    spare = store.pad_row if store.pad_row >= 0 else 0  # what stands in for a place the generator left empty
+    for lo, sess, hist, cand, _ in _table_topk_batches(generator, parts, store, behaviors, l_hist, pool, sessions, batch,
+                                                       exclude_history):
+        b = sess.numel()
+        csess = torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(pool)
+        crows = torch.where(cand >= 0, cand, torch.full_like(cand, spare)).reshape(-1)
+        r = model.score_impressions(store, hist, crows, csess, uidx[sess], relu=False)
+        rows[lo:lo + batch], scores[lo:lo + batch] = _rerank(cand, r.reshape(b, pool), k)
     hip.check_status(dev)
     return rows, scores
 

@@ -531,8 +531,10 @@ def score_csr_mlp(P, cand_rows, cand_sess, u, w1, b1, w2, b2, relu: bool = True)
     return r
 
 
-def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, k: int, excl_off, excl_rows, pad_row: int):
-    """The call every top-k entry point shares behind its own leading arguments `head` -> (rows:(B,k) int32, scores:(B,k))."""
+def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, k: int, excl_off, excl_rows, pad_row: int,
+          ws_query: str = "xnrs_topk_workspace_bytes"):
+    """The call every top-k entry point shares behind its own leading arguments `head` -> (rows:(B,k) int32, scores:(B,k)).
+    `entry` and `ws_query` name the entry point and its workspace query (xnrs_topk* or xnrs_topk_deep*)."""
     dev = table.device
     if (excl_off is None) != (excl_rows is None):
         raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
@@ -546,36 +548,43 @@ def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int,
     rows = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
     scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
     l = hip.lib()
-    nbytes = l.xnrs_topk_workspace_bytes(B, table.shape[0], proj_width, k)
+    nbytes = getattr(l, ws_query)(B, table.shape[0], proj_width, k)
     ws = hip.workspace(dev, nbytes)
     hip.check(getattr(l, entry)(*head, hip.ptr(excl_off), hip.ptr(excl_rows), int(pad_row), k,
                                 hip.ptr(rows), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
     return rows, scores
 
 
-def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
-    """Per user the k rows of `table` with the highest u . table[row] (include/xnrs_hip.h: xnrs_topk) -> (rows, scores)."""
+def _topk_dot(entry, ws_query, table, u, k, excl_off, excl_rows, pad_row):
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
     B = u.shape[0]
-    return _topk("xnrs_topk", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, k, excl_off, excl_rows, pad_row)
+    return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, k, excl_off, excl_rows, pad_row, ws_query)
 
 
-def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
-    """As topk_dot with the score u W[0] table[row] + bias (xnrs_topk_bilinear)."""
+def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """Per user the k rows of `table` with the highest u . table[row] (include/xnrs_hip.h: xnrs_topk) -> (rows, scores)."""
+    return _topk_dot("xnrs_topk", "xnrs_topk_workspace_bytes", table, u, k, excl_off, excl_rows, pad_row)
+
+
+def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_row):
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
     w = hip.dev_f32(w, "bilinear weight")
     b = None if b is None else hip.dev_f32(b, "bilinear bias")
     B = u.shape[0]
-    return _topk("xnrs_topk_bilinear", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E, k,
-                 excl_off, excl_rows, pad_row)
+    return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E, k,
+                 excl_off, excl_rows, pad_row, ws_query)
 
 
-def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
-    """As topk_dot with the score w2 . tanh(W1u u + b1 + P[row]) + b2, P = mlp_news_proj(table) (xnrs_topk_mlp)."""
+def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """As topk_dot with the score u W[0] table[row] + bias (xnrs_topk_bilinear)."""
+    return _topk_bilinear("xnrs_topk_bilinear", "xnrs_topk_workspace_bytes", table, u, w, b, k, excl_off, excl_rows, pad_row)
+
+
+def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row):
     P = hip.dev_f32(P, "projected news table")
     E = w1.shape[1] // 2
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -583,8 +592,32 @@ def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_ro
     if P.dim() != 2 or P.shape[1] != H:
         raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
     B = u.shape[0]
-    return _topk("xnrs_topk_mlp", P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2),
-                                      hip.ptr(b2)), B, H, k, excl_off, excl_rows, pad_row)
+    return _topk(entry, P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2), hip.ptr(b2)), B, H, k,
+                 excl_off, excl_rows, pad_row, ws_query)
+
+
+def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """As topk_dot with the score w2 . tanh(W1u u + b1 + P[row]) + b2, P = mlp_news_proj(table) (xnrs_topk_mlp)."""
+    return _topk_mlp("xnrs_topk_mlp", "xnrs_topk_workspace_bytes", P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row)
+
+
+_DEEP_WS = "xnrs_topk_deep_workspace_bytes"
+
+
+def topk_deep_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """topk_dot for 1 <= k <= 1024 (include/xnrs_hip.h: xnrs_topk_deep): the same order and the same score bits, so the first
+    128 places are those of topk_dot and topk_deep_dot(k)[:, :j] is topk_deep_dot(j)."""
+    return _topk_dot("xnrs_topk_deep", _DEEP_WS, table, u, k, excl_off, excl_rows, pad_row)
+
+
+def topk_deep_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """topk_bilinear for 1 <= k <= 1024 (xnrs_topk_deep_bilinear)."""
+    return _topk_bilinear("xnrs_topk_deep_bilinear", _DEEP_WS, table, u, w, b, k, excl_off, excl_rows, pad_row)
+
+
+def topk_deep_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    """topk_mlp for 1 <= k <= 1024 (xnrs_topk_deep_mlp)."""
+    return _topk_mlp("xnrs_topk_deep_mlp", _DEEP_WS, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row)
 
 
 def _csr_check(what: str, off, rows, B: int, dev):
