@@ -740,6 +740,60 @@ int32_t xnrs_rank_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, cons
                       const int64_t *excl_off, const int32_t *excl_rows, int32_t pad_row, int32_t *ranks, float *scores,
                       void *ws, size_t ws_bytes, void *stream);
 
+/* ---- a per-user row window for the two sweeps (time-aware recommendation and evaluation; csrc/topk.hip) --------------------
+ * xnrs_topk_deep*_win and xnrs_rank*_win take the argument lists of xnrs_topk_deep* / xnrs_rank* with two int32 device arrays
+ * of length B, win_lo and win_hi, behind excl_rows: user b sees the table rows [win_lo[b], win_hi[b]) only.  With the table
+ * ordered by publication time that is "the news that existed at the session's time and was still fresh".
+ * THE RESULT OF A WINDOWED CALL EQUALS THE PARENT'S RESULT WITH EVERY ROW OUTSIDE THE USER'S WINDOW APPENDED TO THE USER'S
+ * EXCLUSION LIST -- rows, ranks and score bits.  Everything else of the parents' contract holds word for word: order, fillers,
+ * the exclusion CSR, pad_row, the NaN / +-inf / +-0 rules, the arithmetic (a window changes which scores are looked at, never
+ * a score's bits), refusals on the host before any launch that write nothing, no host synchronisation, hipGraph-capturable, no
+ * allocation, no float atomics, results crossing launches at kernel boundaries only, and: a user's result does not depend
+ * on B, on the user's position in the batch, on the OTHER users' windows or on the slicing, and is the same on every run.
+ *   Eligible : row n is eligible for user b when it is eligible for the parent (inside [0, n_rows), not pad_row, not on b's
+ *              exclusion list, score not NaN) and win_lo[b] <= n < win_hi[b].
+ *   Bounds   : clamped to [0, n_rows] on the device; compared, never dereferenced.  win_lo[b] >= win_hi[b]: no row is eligible
+ *              -- fillers only, rank 0 for a scored target.
+ *   NULL     : both pointers NULL: the call IS the parent call, bit for bit (the same launches over the same slices).  Exactly
+ *              one NULL: XNRS_EINVAL.
+ *   top-k    : 1 <= k <= XNRS_TOPK_DEEP_MAX_K; k <= XNRS_TOPK_MAX_K runs the two launches of xnrs_topk* with their bits, so
+ *              there is no separate shallow entry.  prefix: win(k)[:, :j] == win(j).
+ *   rank     : as with the exclusion list the window removes competitors, not the query: A TARGET OUTSIDE ITS USER'S WINDOW IS
+ *              STILL SCORED AND RANKED among the eligible rows.  For a target that is eligible, ranks[e] < k exactly when
+ *              xnrs_topk_deep*_win with the same arguments lists it, at position ranks[e] with the bits of scores[e].
+ *   Work     : rows outside the windows are not scored.  A workgroup reduces the windows of its (up to 128) users to the chunk
+ *              range of their union on the device (128-row chunks) and the xnrs_topk_slices(B, n_rows) slices of the grid
+ *              split that range evenly instead of the whole table; a chunk of the union that no window of the tile touches
+ *              is skipped.  The cost of a tile therefore follows the UNION of its users' windows: sessions sorted by time
+ *              give narrow unions, shuffled sessions with narrow windows still sweep nearly the whole table per tile.
+ *   Floor    : the first sweep of the deep inner-product forms (k > XNRS_TOPK_MAX_K) sees the same windows and the same
+ *              slices, so a full slice list still proves that many eligible rows of the user; a user whose window holds fewer
+ *              than k rows, or touches too few slices, gets no floor and is swept from the filler.
+ * ws: the parents' xnrs_topk_deep_workspace_bytes / xnrs_rank_workspace_bytes; the windows need none. */
+int32_t xnrs_topk_deep_win(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const int64_t *excl_off,
+                           const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row, int32_t k,
+                           int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_topk_deep_bilinear_win(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const float *w,
+                                    const float *bias, const int64_t *excl_off, const int32_t *excl_rows, const int32_t *win_lo,
+                                    const int32_t *win_hi, int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws,
+                                    size_t ws_bytes, void *stream);
+int32_t xnrs_topk_deep_mlp_win(const float *P, int64_t n_rows, int32_t E, int32_t H, const float *u, int64_t B, const float *w1,
+                               const float *b1, const float *w2, const float *b2, const int64_t *excl_off,
+                               const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row,
+                               int32_t k, int32_t *rows, float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_rank_win(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const int64_t *tgt_off,
+                      const int32_t *tgt_rows, const int64_t *excl_off, const int32_t *excl_rows, const int32_t *win_lo,
+                      const int32_t *win_hi, int32_t pad_row, int32_t *ranks, float *scores, void *ws, size_t ws_bytes,
+                      void *stream);
+int32_t xnrs_rank_bilinear_win(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const float *w,
+                               const float *bias, const int64_t *tgt_off, const int32_t *tgt_rows, const int64_t *excl_off,
+                               const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row,
+                               int32_t *ranks, float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_rank_mlp_win(const float *P, int64_t n_rows, int32_t E, int32_t H, const float *u, int64_t B, const float *w1,
+                          const float *b1, const float *w2, const float *b2, const int64_t *tgt_off, const int32_t *tgt_rows,
+                          const int64_t *excl_off, const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi,
+                          int32_t pad_row, int32_t *ranks, float *scores, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

@@ -22,6 +22,10 @@
 // Either way the score of a (user, row) pair depends on nothing but that pair, so a user's result does not depend on B, on the
 // user's position in the batch or on the slicing, and is the same bits on every run.
 //
+// Row windows (xnrs_topk_deep*_win, xnrs_rank*_win): user b sees the rows [win_lo[b], win_hi[b]) only -- the result of the call
+// with every other row on b's exclusion list.  Both sweeps take their windows and their chunk range from tk_tile_range: a
+// workgroup walks the union of its users' windows, split evenly over the slices, instead of a fixed share of the table.
+//
 // Order: key = (order-preserving score bits << 32) | ~row, so "higher score first, equal scores (-0 == +0) lower row first" is
 // one unsigned compare.  A NaN score is never selected; -inf is a legal score.  Missing entries (fewer than k eligible rows)
 // are fillers -- row -1, score -inf -- whose key lies below every real key.  The ranking is by the RAW score: no ReLU (the
@@ -134,9 +138,83 @@ struct TkOperands {
   const float *table, *u, *w2, *bias;  // table:(n_rows, W), u:(B, W); w2:(W) in the MLP form
   const int64_t* excl_off;
   const int32_t* excl_rows;
+  const int32_t *win_lo, *win_hi;  // xnrs_*_win: per user the row window [win_lo[b], win_hi[b]); both NULL: the whole table
   int64_t n_rows, B, chunks_per_slice;
   int W, pad_row, vec_t, vec_u;
 };
+
+// Row windows (xnrs_*_win).  A lane keeps the windows of its two users -- uw + l32 and uw + 32 + l32, the users of its score
+// elements -- in registers, clamped to [0, n_rows], an empty one (lo >= hi, or no such user) as [0, 0); a bound is compared,
+// never dereferenced.  Without windows every lane holds [0, n_rows): the window is the test for the table's end as well.
+struct TkWin {
+  int32_t lo[2], hi[2];
+  int gaps;  // the tile's windows have no row in common: chunks between them may hold no window at all (tk_chunk_live)
+  // Which of the lane's 32 score elements of user block ub lie inside the user's window: bit rb * 16 + j for element (rb, j),
+  // the bit order of `pend`.  The element lies o = 32 rb + 8 (j / 4) + j % 4 rows behind the lane's first row of the chunk,
+  // `first`; o grows with the bit index, so the elements with o < x are the lowest 4 (x / 8) + min(x % 8, 4) bits.
+  __device__ __forceinline__ static uint32_t below(int64_t x) {
+    const int c = x <= 0 ? 0 : x >= 64 ? 32 : 4 * ((int)x >> 3) + (((int)x & 7) < 4 ? ((int)x & 7) : 4);
+    return c >= 32 ? ~0u : (1u << c) - 1u;
+  }
+  __device__ __forceinline__ uint32_t inside(int ub, int64_t first) const { return below(hi[ub] - first) & ~below(lo[ub] - first); }
+};
+
+// The chunks [c_lo, c_hi) of the sweep that workgroup (tile blockIdx.x, slice blockIdx.y) walks, and the lane's windows.
+// Without windows: the fixed share chunks_per_slice of the whole table.  With windows: the tile's users reduce their windows
+// to the chunk range of their union (integer min / max in LDS, rng[4]: found on the device, no host synchronisation), and
+// the gridDim.y slices split THAT range evenly -- slice s takes [n s / S, n (s + 1) / S) of its n chunks, so that no slice is
+// idle while another holds two chunks more; with n < S some slices are empty (they write fillers / an empty list).  All
+// 256 threads call it (two workgroup barriers).  A user's result does not depend on the split: the slices are disjoint and
+// cover every chunk that holds a row of a window of the tile.
+__device__ __forceinline__ void tk_tile_range(const TkOperands& a, int64_t u0, int nu, int* rng, TkWin& w, int64_t& c_lo, int64_t& c_hi) {
+  const int tid = threadIdx.x, wave = tid >> 6, l32 = tid & 31, uw = (wave & 1) * 64;
+  if (!a.win_lo) {
+    w.lo[0] = w.lo[1] = 0;
+    w.hi[0] = w.hi[1] = (int32_t)a.n_rows;
+    w.gaps = 0;
+    const int64_t chunks = (a.n_rows + TK_TILE - 1) / TK_TILE;
+    c_lo = (int64_t)blockIdx.y * a.chunks_per_slice;
+    c_hi = c_lo + a.chunks_per_slice < chunks ? c_lo + a.chunks_per_slice : chunks;
+    return;
+  }
+  if (tid == 0) {
+    rng[0] = rng[3] = 0x7fffffff;  // the least lo / TK_TILE, the least hi
+    rng[1] = rng[2] = 0;           // the greatest ceil(hi / TK_TILE), the greatest lo
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ub = 0; ub < 2; ++ub) {
+    const int ul = uw + ub * 32 + l32;
+    int32_t lo = 0, hi = 0;
+    if (ul < nu) {
+      lo = a.win_lo[u0 + ul];
+      hi = a.win_hi[u0 + ul];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > a.n_rows ? (int32_t)a.n_rows : hi;
+      if (lo >= hi) lo = hi = 0;
+    }
+    w.lo[ub] = lo;
+    w.hi[ub] = hi;
+    if (wave < 2 && hi > lo) {  // (waves 0 and 1 hold every user of the tile once)
+      atomicMin(&rng[0], lo / TK_TILE);
+      atomicMax(&rng[1], (int)(((int64_t)hi + TK_TILE - 1) / TK_TILE));
+      atomicMax(&rng[2], lo);
+      atomicMin(&rng[3], hi);
+    }
+  }
+  __syncthreads();
+  const int64_t t_lo = rng[0], n = rng[1] > rng[0] ? rng[1] - t_lo : 0, S = gridDim.y;  // n == 0: every window of the tile is empty
+  c_lo = t_lo + n * blockIdx.y / S;
+  c_hi = t_lo + n * (blockIdx.y + 1) / S;
+  w.gaps = rng[2] >= rng[3];  // (a row common to all windows: their union is one range, every chunk of it holds a window)
+}
+
+// whether chunk [r0, r0 + 128) holds a row of a window of the tile: the tile's windows may be disjoint, and the chunks of
+// their union that lie between them are not scored.  Uniform over the workgroup (one barrier); called when w.gaps only.
+__device__ __forceinline__ bool tk_chunk_live(const TkWin& w, int64_t r0) {
+  const int64_t r1 = r0 + TK_TILE;
+  return __syncthreads_or((w.lo[0] < r1 && w.hi[0] > r0) || (w.lo[1] < r1 && w.hi[1] > r0)) != 0;
+}
 struct TopkArgs : TkOperands {
   int k;
   uint64_t* part;
@@ -440,11 +518,15 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
   __shared__ uint64_t buf[TK_TILE * TK_CB], thr[TK_TILE];
   __shared__ TkHalfT<KCAP> halves[4][2];
   __shared__ int cnt[TK_TILE];
+  __shared__ int rng[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
   const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;  // the wave's 64 x 64 part of the score tile
   const int64_t u0 = (int64_t)blockIdx.x * TK_TILE;
   const int nu = a.B - u0 < TK_TILE ? (int)(a.B - u0) : TK_TILE;
   const int k = a.k;
+  TkWin win;
+  int64_t c_lo, c_hi;
+  tk_tile_range(a, u0, nu, rng, win, c_lo, c_hi);
   uint64_t* lists = a.part + ((int64_t)blockIdx.y * a.B + u0) * k;
   if constexpr (KCAP > XNRS_TOPK_MAX_K) {
     if (tid < TK_TILE) halves[tid & 3][0].nreal[tid >> 2] = 0;  // (the lists start empty, and are not filled)
@@ -460,11 +542,9 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
   }
   __syncthreads();
   const float bias = a.bias ? a.bias[0] : 0.f;
-  const int64_t chunks = (a.n_rows + TK_TILE - 1) / TK_TILE;
-  const int64_t c_lo = (int64_t)blockIdx.y * a.chunks_per_slice;
-  const int64_t c_hi = c_lo + a.chunks_per_slice < chunks ? c_lo + a.chunks_per_slice : chunks;
   for (int64_t c = c_lo; c < c_hi; ++c) {
     const int64_t r0 = c * TK_TILE;
+    if (win.gaps && !tk_chunk_live(win, r0)) continue;
     f32x16 acc[2][2];
     tk_score_tile<MLP, false>(a, r0, nullptr, u0, At, Bt, w2s, acc);
     // ---- selection: append what beats the threshold, merge full buffers, go round again while a buffer overflowed
@@ -482,6 +562,10 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
           if (ul < nu && s >= tS) pend |= 1ull << (ub * 32 + rb * 16 + j);  // (false for a NaN)
         }
     }
+    // only what lies inside the user's window -- and so inside the table -- is a candidate: a user whose window is elsewhere
+    // keeps its threshold at the filler, and would otherwise walk all 64 scores of the lane through the loop below
+    const int64_t first = r0 + rw + half * 4;
+    pend &= (uint64_t)win.inside(0, first) | ((uint64_t)win.inside(1, first) << 32);
     for (;;) {
       int overflow = 0;
       for (uint64_t todo = pend; todo; todo &= todo - 1) {
@@ -493,7 +577,7 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
         const int64_t row = r0 + rw + ((b >> 4) & 1) * 32 + ((b & 15) >> 2) * 8 + half * 4 + (b & 3);
         const uint64_t key = tk_key(s, (uint32_t)row);
         bool keep = false;
-        if (row < a.n_rows && row != a.pad_row && key > thr[ul]) {
+        if (row != a.pad_row && key > thr[ul]) {  // (`pend` holds rows inside the table and the user's window only)
           const int slot = atomicAdd(&cnt[ul], 1);
           if (slot < TK_CB) buf[ul * TK_CB + slot] = key;
           else keep = true;
@@ -699,6 +783,7 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void rank_sweep_kernel(RankArgs a
   __shared__ float w2s[TK_KT];
   __shared__ uint32_t excl[4 * TK_TILE];      // bit r % 32 of excl[(r / 32) * 128 + user]: row r of the chunk is excluded
   __shared__ int32_t slot[RK_SLOTS * TK_TILE];  // slot[i * 128 + user]: the slice's count for target i of the user
+  __shared__ int rng[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
   const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;
   const int64_t u0 = (int64_t)blockIdx.x * TK_TILE;
@@ -713,11 +798,12 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void rank_sweep_kernel(RankArgs a
   }
   const float bias = a.bias ? a.bias[0] : 0.f;
   const float nan = __builtin_nanf("");
-  const int64_t chunks = (a.n_rows + TK_TILE - 1) / TK_TILE;
-  const int64_t c_lo = (int64_t)blockIdx.y * a.chunks_per_slice;
-  const int64_t c_hi = c_lo + a.chunks_per_slice < chunks ? c_lo + a.chunks_per_slice : chunks;
+  TkWin win;
+  int64_t c_lo, c_hi;
+  tk_tile_range(a, u0, nu, rng, win, c_lo, c_hi);
   for (int64_t c = c_lo; c < c_hi; ++c) {
     const int64_t r0 = c * TK_TILE;
+    if (win.gaps && !tk_chunk_live(win, r0)) continue;  // (a target outside its window is ranked all the same: rank_target_kernel scored it)
     if (a.excl_off) {
       __syncthreads();  // (the bitmap of the chunk before has been read)
       for (int i = tid; i < 4 * TK_TILE; i += 256) excl[i] = 0;
@@ -737,6 +823,7 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void rank_sweep_kernel(RankArgs a
 #pragma unroll
     for (int ub = 0; ub < 2; ++ub) {
       const int ul = uw + ub * 32 + l32;
+      const uint32_t in = win.inside(ub, r0 + rw + half * 4);  // (inside the window: inside the table as well)
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
         const uint32_t word = a.excl_off ? excl[((rw >> 5) + rb) * TK_TILE + ul] : 0u;
@@ -744,7 +831,7 @@ __global__ __launch_bounds__(256, MLP ? 1 : 2) void rank_sweep_kernel(RankArgs a
         for (int j = 0; j < 16; ++j) {
           const int bit = (j >> 2) * 8 + half * 4 + (j & 3);
           const int64_t row = r0 + rw + rb * 32 + bit;
-          const bool ok = row < a.n_rows && row != a.pad_row && !((word >> bit) & 1u);
+          const bool ok = ((in >> (rb * 16 + j)) & 1u) && row != a.pad_row && !((word >> bit) & 1u);
           acc[rb][ub][j] = ok ? acc[rb][ub][j] + bias : nan;
         }
       }
@@ -804,6 +891,7 @@ struct TopkCall {
   size_t ws_bytes;
   int32_t proj_width;
   bool deep;  // xnrs_topk_deep*: k up to XNRS_TOPK_DEEP_MAX_K
+  const int32_t *win_lo = nullptr, *win_hi = nullptr;  // xnrs_topk_deep*_win: both or neither
 };
 
 // the projected user side [B, proj_width] | k > XNRS_TOPK_MAX_K: the floor keys [B] | the partial lists [slices, B, k] of 64-bit keys
@@ -818,6 +906,7 @@ int32_t tk_check(const TopkCall& c, const float* u, bool* run) {
   *run = false;
   const int32_t max_k = c.deep ? XNRS_TOPK_DEEP_MAX_K : XNRS_TOPK_MAX_K;
   if (c.k < 1 || c.k > max_k || c.W <= 0 || c.B < 0 || c.n_rows < 0 || c.n_rows > 0x7fffffffLL) return XNRS_EINVAL;
+  if (!c.win_lo != !c.win_hi) return XNRS_EINVAL;
   if (c.B == 0) return XNRS_OK;
   if (!c.rows || !c.scores || !u || (c.n_rows > 0 && !c.table) || (c.excl_off && !c.excl_rows)) return XNRS_EINVAL;
   const size_t need = tk_workspace_bytes(c.B, c.n_rows, c.proj_width, c.k, max_k);
@@ -844,6 +933,8 @@ hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const 
   a.bias = bias;
   a.excl_off = c.excl_off;
   a.excl_rows = c.excl_rows;
+  a.win_lo = c.win_lo;
+  a.win_hi = c.win_hi;
   a.n_rows = c.n_rows;
   a.B = c.B;
   a.chunks_per_slice = cps;
@@ -931,11 +1022,13 @@ struct RankCall {
   void* ws;
   size_t ws_bytes;
   int32_t proj_width;
+  const int32_t *win_lo = nullptr, *win_hi = nullptr;  // xnrs_rank*_win: both or neither
 };
 
 int32_t rk_check(const RankCall& c, const float* u, bool* run) {
   *run = false;
   if (c.W <= 0 || c.B < 0 || c.n_rows < 0 || c.n_rows > 0x7fffffffLL) return XNRS_EINVAL;
+  if (!c.win_lo != !c.win_hi) return XNRS_EINVAL;
   if (c.B == 0) return XNRS_OK;
   if (!c.ranks || !c.scores || !c.tgt_off || !c.tgt_rows || !u || (c.n_rows > 0 && !c.table) || (c.excl_off && !c.excl_rows))
     return XNRS_EINVAL;
@@ -954,6 +1047,8 @@ hipError_t rk_launch(const RankCall& c, const float* up, const float* w2, const 
   a.bias = bias;
   a.excl_off = c.excl_off;
   a.excl_rows = c.excl_rows;
+  a.win_lo = c.win_lo;
+  a.win_hi = c.win_hi;
   a.n_rows = c.n_rows;
   a.B = c.B;
   a.chunks_per_slice = tk_chunks_per_slice(c.B, c.n_rows);
@@ -975,6 +1070,40 @@ hipError_t rk_launch(const RankCall& c, const float* up, const float* w2, const 
   if (w2) hipLaunchKernelGGL(rank_sweep_kernel<true>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(rank_sweep_kernel<false>, grid, dim3(256), 0, stream, a);
   return hipGetLastError();
+}
+
+// the bodies of xnrs_rank / _bilinear / _mlp and of their _win twins
+int32_t rk_dot(const RankCall& c, const float* u, hipStream_t stream) {
+  bool run;
+  XNRS_TRY_RC(rk_check(c, u, &run));
+  if (run) XNRS_TRY(rk_launch(c, u, nullptr, nullptr, stream));
+  return XNRS_OK;
+}
+
+int32_t rk_bilinear(const RankCall& c, const float* u, const float* w, const float* bias, hipStream_t stream) {
+  const int32_t E = c.W;
+  bool run;
+  XNRS_TRY_RC(rk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w) return XNRS_EINVAL;
+  float* v = static_cast<float*>(c.ws);
+  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, c.B, E, E, stream));  // v_b = W[0]^T u_b, as xnrs_topk_bilinear
+  XNRS_TRY(rk_launch(c, v, nullptr, bias, stream));
+  return XNRS_OK;
+}
+
+int32_t rk_mlp(const RankCall& c, int32_t E, const float* u, const float* w1, const float* b1, const float* w2, const float* b2,
+               hipStream_t stream) {
+  const int32_t H = c.W;
+  if (E <= 0) return XNRS_EINVAL;
+  bool run;
+  XNRS_TRY_RC(rk_check(c, u, &run));
+  if (!run) return XNRS_OK;
+  if (!w1 || !w2) return XNRS_EINVAL;
+  float* q = static_cast<float*>(c.ws);
+  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, c.B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_topk_mlp
+  XNRS_TRY(rk_launch(c, q, w2, b2, stream));
+  return XNRS_OK;
 }
 
 }  // namespace
@@ -1048,44 +1177,72 @@ size_t xnrs_rank_workspace_bytes(int64_t B, int32_t proj_width) {
 int32_t xnrs_rank(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* tgt_off,
                   const int32_t* tgt_rows, const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t* ranks,
                   float* scores, void* ws, size_t ws_bytes, void* stream) {
-  const RankCall c{table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, 0};
-  bool run;
-  XNRS_TRY_RC(rk_check(c, u, &run));
-  if (run) XNRS_TRY(rk_launch(c, u, nullptr, nullptr, (hipStream_t)stream));
-  return XNRS_OK;
+  return rk_dot({table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, 0}, u,
+                (hipStream_t)stream);
 }
 
 int32_t xnrs_rank_bilinear(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
                            const float* bias, const int64_t* tgt_off, const int32_t* tgt_rows, const int64_t* excl_off,
                            const int32_t* excl_rows, int32_t pad_row, int32_t* ranks, float* scores, void* ws, size_t ws_bytes,
-                           void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const RankCall c{table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, E};
-  bool run;
-  XNRS_TRY_RC(rk_check(c, u, &run));
-  if (!run) return XNRS_OK;
-  if (!w) return XNRS_EINVAL;
-  float* v = static_cast<float*>(ws);
-  XNRS_TRY(sc_gemm(u, E, w, E, 1, nullptr, v, E, B, E, E, stream));  // v_b = W[0]^T u_b, as xnrs_topk_bilinear
-  XNRS_TRY(rk_launch(c, v, nullptr, bias, stream));
-  return XNRS_OK;
+                           void* stream) {
+  return rk_bilinear({table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, E}, u, w,
+                     bias, (hipStream_t)stream);
 }
 
 int32_t xnrs_rank_mlp(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
                       const float* b1, const float* w2, const float* b2, const int64_t* tgt_off, const int32_t* tgt_rows,
                       const int64_t* excl_off, const int32_t* excl_rows, int32_t pad_row, int32_t* ranks, float* scores,
-                      void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (E <= 0) return XNRS_EINVAL;
-  const RankCall c{P, n_rows, H, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, H};
-  bool run;
-  XNRS_TRY_RC(rk_check(c, u, &run));
-  if (!run) return XNRS_OK;
-  if (!w1 || !w2) return XNRS_EINVAL;
-  float* q = static_cast<float*>(ws);
-  XNRS_TRY(sc_gemm(u, E, w1, 2 * (int64_t)E, 0, b1, q, H, B, H, E, stream));  // q_b = W1u u_b + b1, as xnrs_topk_mlp
-  XNRS_TRY(rk_launch(c, q, w2, b2, stream));
-  return XNRS_OK;
+                      void* ws, size_t ws_bytes, void* stream) {
+  return rk_mlp({P, n_rows, H, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, H}, E, u, w1, b1,
+                w2, b2, (hipStream_t)stream);
+}
+
+// ---- the row-window entry points: the argument lists of their parents with win_lo, win_hi behind excl_rows
+int32_t xnrs_topk_deep_win(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* excl_off,
+                           const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi, int32_t pad_row, int32_t k,
+                           int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return tk_dot({table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, 0, true, win_lo, win_hi}, u,
+                (hipStream_t)stream);
+}
+
+int32_t xnrs_topk_deep_bilinear_win(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
+                                    const float* bias, const int64_t* excl_off, const int32_t* excl_rows, const int32_t* win_lo,
+                                    const int32_t* win_hi, int32_t pad_row, int32_t k, int32_t* rows, float* scores, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  return tk_bilinear({table, n_rows, E, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, E, true, win_lo, win_hi}, u,
+                     w, bias, (hipStream_t)stream);
+}
+
+int32_t xnrs_topk_deep_mlp_win(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
+                               const float* b1, const float* w2, const float* b2, const int64_t* excl_off,
+                               const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi, int32_t pad_row, int32_t k,
+                               int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return tk_mlp({P, n_rows, H, B, excl_off, excl_rows, pad_row, k, rows, scores, ws, ws_bytes, H, true, win_lo, win_hi}, E, u, w1,
+                b1, w2, b2, (hipStream_t)stream);
+}
+
+int32_t xnrs_rank_win(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* tgt_off,
+                      const int32_t* tgt_rows, const int64_t* excl_off, const int32_t* excl_rows, const int32_t* win_lo,
+                      const int32_t* win_hi, int32_t pad_row, int32_t* ranks, float* scores, void* ws, size_t ws_bytes,
+                      void* stream) {
+  return rk_dot({table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, 0, win_lo, win_hi},
+                u, (hipStream_t)stream);
+}
+
+int32_t xnrs_rank_bilinear_win(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
+                               const float* bias, const int64_t* tgt_off, const int32_t* tgt_rows, const int64_t* excl_off,
+                               const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi, int32_t pad_row,
+                               int32_t* ranks, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return rk_bilinear({table, n_rows, E, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, E, win_lo,
+                      win_hi}, u, w, bias, (hipStream_t)stream);
+}
+
+int32_t xnrs_rank_mlp_win(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
+                          const float* b1, const float* w2, const float* b2, const int64_t* tgt_off, const int32_t* tgt_rows,
+                          const int64_t* excl_off, const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi,
+                          int32_t pad_row, int32_t* ranks, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  return rk_mlp({P, n_rows, H, B, tgt_off, excl_off, tgt_rows, excl_rows, pad_row, ranks, scores, ws, ws_bytes, H, win_lo, win_hi},
+                E, u, w1, b1, w2, b2, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -372,6 +372,10 @@ class Behaviors:
         b = cls(hist, pos, neg, [str(s.get("main_theme", "")) for s in sessions])
         if sessions and all("user_index" in s for s in sessions):  # dataset.py:139-144,157 (NPA's user table)
             b.user_index = torch.tensor([int(s["user_index"]) for s in sessions], dtype=torch.int64)
+        # the time of the impression (the behaviour log's `time` column, xnrs/data/mind.py:108), kept when every session
+        # carries an integer one: evaluation.row_windows turns it into the rows of a time-ordered table the session may see
+        if sessions and all(isinstance(s.get("time"), int) and not isinstance(s["time"], bool) for s in sessions):
+            b.time = torch.tensor([s["time"] for s in sessions], dtype=torch.int64)
         return b
 
     def __len__(self):
@@ -383,6 +387,8 @@ class Behaviors:
             setattr(b, k, getattr(self, k).to(device))
         if hasattr(self, "user_index"):
             b.user_index = self.user_index.to(device)
+        if hasattr(self, "time"):
+            b.time = self.time.to(device)
         b.themes = self.themes
         return b
 

@@ -199,9 +199,57 @@ def _history_csr(behaviors: Behaviors, sess: torch.Tensor, first):
 TOPK_MAX_K, TOPK_DEEP_MAX_K = hip._CONSTANTS["TOPK_MAX_K"], hip._CONSTANTS["TOPK_DEEP_MAX_K"]  # include/xnrs_hip.h
 
 
-def _recommending_model_parts(model, behaviors: Behaviors, k: int):
+def _takes_windows(fn) -> bool:
+    """Whether a scorer's topk_deep / rank accepts the row windows as the keywords win_lo, win_hi."""
+    import inspect
+    try:
+        params = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    return ("win_lo" in params and "win_hi" in params) or any(p.kind is p.VAR_KEYWORD for p in params.values())
+
+
+def _session_windows(windows, behaviors: Behaviors, dev, who: str):
+    """`windows` = (lo, hi), integer tensors with one row bound per session of `behaviors` (indexed by session id, like
+    user_index) -> the pair as int32 on `dev`; None stays None."""
+    if windows is None:
+        return None
+    try:
+        lo, hi = windows
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: windows is a pair (lo, hi) of integer tensors, one entry per session") from None
+    out = []
+    for t in (lo, hi):
+        t = torch.as_tensor(t)
+        if t.dim() != 1 or t.numel() != len(behaviors) or t.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8,
+                                                                          torch.uint8):
+            raise ValueError(f"{who}: windows holds two integer tensors of length len(behaviors) = {len(behaviors)}, indexed by "
+                             f"session id; got {tuple(t.shape)} {t.dtype}")
+        out.append(t.to(device=dev, dtype=torch.int32).contiguous())
+    return tuple(out)
+
+
+def row_windows(row_time: torch.Tensor, session_time: torch.Tensor, horizon=None):
+    """The rows of a time-ordered news table a session at time t may see -> (lo, hi) int32 on row_time's device, the
+    `windows` of recommend / rank_clicked / evaluate_full_ranking: hi = the first row with row_time > t (published after
+    the impression), lo = the first row with row_time >= t - horizon (older than the horizon; 0 when `horizon` is None).
+    row_time:(n_rows,) must be non-decreasing over the table's rows -- a row_time that decreases anywhere raises ValueError
+    (one check, one host read, per call: build the windows once, outside any batch loop); the caller orders the table."""
+    row_time = torch.as_tensor(row_time)
+    if row_time.dim() != 1:
+        raise ValueError(f"row_windows(): row_time is 1-D, one time per table row; got {tuple(row_time.shape)}")
+    if row_time.numel() > 1 and bool((row_time[1:] < row_time[:-1]).any()):
+        raise ValueError("row_windows(): row_time decreases somewhere; a row window needs the table ordered by time")
+    row_time = row_time.contiguous()
+    t = torch.as_tensor(session_time).to(device=row_time.device, dtype=row_time.dtype).reshape(-1)
+    hi = torch.searchsorted(row_time, t, right=True)
+    lo = torch.zeros_like(hi) if horizon is None else torch.searchsorted(row_time, t - horizon, right=False)
+    return lo.to(torch.int32), hi.to(torch.int32)
+
+
+def _recommending_model_parts(model, behaviors: Behaviors, k: int, windowed: bool = False):
     """(prepare_csr, the scorer's top-k call for this k, user index or None) of a model that can rank the table on its own, or
-    the refusal -- before anything is encoded."""
+    the refusal -- before anything is encoded.  windowed: the call carries row windows, which go through topk_deep."""
     scorer = getattr(model, "rec_model", None)
     prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, "topk", None)
     if prepare is None or topk is None:
@@ -211,11 +259,14 @@ def _recommending_model_parts(model, behaviors: Behaviors, k: int):
         raise NotImplementedError(f"recommend(): the news vectors of {type(model).__name__} depend on the user, so no table of "
                                   "news vectors exists to rank; give it a candidate generator -- recommend(model, ..., "
                                   "generator=a model that ranks the table, pool=...) -- and it re-ranks the generator's list")
-    if k > TOPK_MAX_K:
+    if k > TOPK_MAX_K or windowed:
         topk = getattr(scorer, "topk_deep", None)
-        if topk is None:
+        if topk is None and not windowed:
             raise NotImplementedError(f"recommend(): the scorer {type(scorer).__name__} has no topk_deep, so it lists at most "
                                       f"k = {TOPK_MAX_K} news per session, not {k}")
+        if windowed and (topk is None or not _takes_windows(topk)):
+            raise NotImplementedError(f"recommend(windows=...): the topk_deep of the scorer {type(scorer).__name__} takes no "
+                                      "row windows (win_lo, win_hi)")
     uidx = None
     if getattr(model, "uses_user_index", False):
         uidx = getattr(behaviors, "user_index", None)
@@ -226,8 +277,9 @@ def _recommending_model_parts(model, behaviors: Behaviors, k: int):
 
 
 def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions, batch: int,
-                        exclude_history: bool):
-    """The table of `model` encoded once, then per batch of sessions (lo, sess, hist rows, top-k rows, top-k scores)."""
+                        exclude_history: bool, windows=None):
+    """The table of `model` encoded once, then per batch of sessions (lo, sess, hist rows, top-k rows, top-k scores).
+    windows: (lo, hi) int32 per session id on the device, gathered with the batch's sessions, or None."""
     prepare, topk, uidx = parts
     vecs, hm = encode_news_table(model, store)
     table = prepare(vecs)
@@ -244,7 +296,11 @@ def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_
         m = hm[hist.long()]
         u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
         excl = _history_csr(behaviors, sess, lo if every else None) if exclude_history else (None, None)
-        yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row))
+        if windows is None:
+            yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row))
+        else:
+            yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row,
+                                                win_lo=windows[0][sess], win_hi=windows[1][sess]))
 
 
 def _rerank(rows: torch.Tensor, r: torch.Tensor, k: int):
@@ -263,7 +319,7 @@ def _rerank(rows: torch.Tensor, r: torch.Tensor, k: int):
 
 @torch.no_grad()
 def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions=None, batch: int = 4096,
-              exclude_history: bool = True, generator=None, pool=None):
+              exclude_history: bool = True, generator=None, pool=None, windows=None):
     """For every session the k news of the WHOLE table its user scores highest -> (rows:(n,k) int32, scores:(n,k) fp32) on the
     device, best first (include/xnrs_hip.h: xnrs_topk -- higher raw score first, equal scores lower row first, no ReLU; with
     fewer than k eligible news the tail is row -1 / score -inf).  k <= 128 runs the scorer's topk, 129 <= k <= 1024 its
@@ -283,6 +339,12 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
     not fill is encoded as the pad row and its score thrown away, so no list length is read on the host.  The selection
     among at most 1024 scores per session is two device sorts, not a kernel of its own.  behaviors.user_index is required.
 
+    `windows` = (lo, hi), integer tensors indexed by session id (see row_windows): session i sees the table rows
+    [lo[i], hi[i]) only -- with a table ordered by publication time, the news that existed at the session's time and was still
+    fresh.  The result is that of per-session exclusion lists holding every other row, without the lists and without scoring
+    those rows (xnrs_topk_deep_win; every k goes through the scorer's topk_deep, the same bits).  With a `generator` the
+    windows apply to the generator's list, the only place rows are chosen.  None: the scorer is called exactly as before.
+
     One process, one device: rank-sharded recommendation is out of scope.  A scorer without topk / prepare_csr, a model
     whose news vectors depend on the user (NPA) without `generator`, and CAUM (no candidate-independent user vector, no
     score_impressions) raise NotImplementedError."""
@@ -292,12 +354,14 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
     if generator is None:
         if pool is not None:
             raise ValueError("recommend(): `pool` is the list length of a `generator`; there is none")
-        parts = _recommending_model_parts(model, behaviors, k)
+        parts = _recommending_model_parts(model, behaviors, k, windows is not None)
         n = len(behaviors) if sessions is None else len(sessions)
         dev = behaviors.hist_off.device
+        windows = _session_windows(windows, behaviors, dev, "recommend()")
         rows = torch.empty((n, k), dtype=torch.int32, device=dev)
         scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        for lo, _, _, r, s in _table_topk_batches(model, parts, store, behaviors, l_hist, k, sessions, batch, exclude_history):
+        for lo, _, _, r, s in _table_topk_batches(model, parts, store, behaviors, l_hist, k, sessions, batch, exclude_history,
+                                                  windows):
             rows[lo:lo + batch], scores[lo:lo + batch] = r, s
         hip.check_status(dev)
         return rows, scores
@@ -307,7 +371,7 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
     pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
     if not k <= pool <= TOPK_DEEP_MAX_K:
         raise ValueError(f"recommend(): pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
-    parts = _recommending_model_parts(generator, behaviors, pool)
+    parts = _recommending_model_parts(generator, behaviors, pool, windows is not None)
     uidx = getattr(behaviors, "user_index", None)
     if uidx is None:
         raise ValueError(f"recommend(): {type(model).__name__} needs the user index of every session (sessions without "
@@ -315,11 +379,12 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
     n = len(behaviors) if sessions is None else len(sessions)
     dev = behaviors.hist_off.device
     uidx = uidx.to(dev)
+    windows = _session_windows(windows, behaviors, dev, "recommend()")
     rows = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     spare = store.pad_row if store.pad_row >= 0 else 0  # what stands in for a place the generator left empty
     for lo, sess, hist, cand, _ in _table_topk_batches(generator, parts, store, behaviors, l_hist, pool, sessions, batch,
-                                                       exclude_history):
+                                                       exclude_history, windows):
         b = sess.numel()
         csess = torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(pool)
         crows = torch.where(cand >= 0, cand, torch.full_like(cand, spare)).reshape(-1)
@@ -329,9 +394,9 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
     return rows, scores
 
 
-def _ranking_model_parts(model, behaviors: Behaviors, who: str):
+def _ranking_model_parts(model, behaviors: Behaviors, who: str, windowed: bool = False):
     """(prepare_csr, rank, user index or None) of a model whose clicked news can be ranked within the table, or the refusal
-    -- before anything is encoded."""
+    -- before anything is encoded.  windowed: the call carries row windows."""
     scorer = getattr(model, "rec_model", None)
     prepare, rank = getattr(scorer, "prepare_csr", None), getattr(scorer, "rank", None)
     if prepare is None or rank is None:
@@ -340,6 +405,8 @@ def _ranking_model_parts(model, behaviors: Behaviors, who: str):
     if getattr(model, "user_dependent_news", False):
         raise NotImplementedError(f"{who}: the news vectors of {type(model).__name__} depend on the user, so no table of "
                                   "news vectors exists to rank")
+    if windowed and not _takes_windows(rank):
+        raise NotImplementedError(f"{who}: the rank of the scorer {type(scorer).__name__} takes no row windows (win_lo, win_hi)")
     uidx = None
     if getattr(model, "uses_user_index", False):
         uidx = getattr(behaviors, "user_index", None)
@@ -351,7 +418,7 @@ def _ranking_model_parts(model, behaviors: Behaviors, who: str):
 
 @torch.no_grad()
 def rank_clicked(model, store: NewsStore, behaviors: Behaviors, l_hist: int, sessions=None, batch: int = 4096,
-                 exclude_history: bool = True):
+                 exclude_history: bool = True, windows=None):
     """Where every clicked news ranks among ALL news of the table for its session's user -> (query_session int64, query_row
     int32, rank int32, score fp32) on the device, one entry per (session, clicked news) in session order (pos_off / pos_val;
     a session without a click gives no query).
@@ -365,8 +432,10 @@ def rank_clicked(model, store: NewsStore, behaviors: Behaviors, l_hist: int, ses
     Once per call the news table is encoded (encode_news_table) and handed to the scorer (prepare_csr); per batch of sessions
     the user tower runs as in recommend() and the scorer's rank(table, u, ...) sweeps the table without a (sessions, n_rows)
     score matrix.  `sessions`: session indices (None = all; a range of step 1 is taken as a slice, without gathering).
-    Refusals as recommend()."""
-    prepare, rank_fn, uidx = _ranking_model_parts(model, behaviors, "rank_clicked()")
+    `windows` = (lo, hi) indexed by session id, as recommend(): only the rows [lo[i], hi[i]) compete with session i's clicked
+    news (xnrs_rank_win); a clicked news outside its session's window is ranked all the same.  Refusals as recommend()."""
+    prepare, rank_fn, uidx = _ranking_model_parts(model, behaviors, "rank_clicked()", windows is not None)
+    windows = _session_windows(windows, behaviors, behaviors.hist_off.device, "rank_clicked()")
     vecs, hm = encode_news_table(model, store)
     table = prepare(vecs)
     batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
@@ -397,10 +466,14 @@ def rank_clicked(model, store: NewsStore, behaviors: Behaviors, l_hist: int, ses
         at = None if first is None else first + lo
         excl = _history_csr(behaviors, sess, at) if exclude_history else (None, None)
         tgt = _session_csr(pos_off, pos_val, sess, at)
+        win = {}
+        if windows is not None:  # the batch's sessions: a slice of a contiguous run, a gather otherwise
+            win = {"win_lo": windows[0][sess] if at is None else windows[0][at:at + sess.numel()],
+                   "win_hi": windows[1][sess] if at is None else windows[1][at:at + sess.numel()]}
         if first is not None:
-            rank_fn(table, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row, out=(ranks, scores))
+            rank_fn(table, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row, out=(ranks, scores), **win)
         else:
-            parts.append((tgt[1],) + tuple(rank_fn(table, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row)))
+            parts.append((tgt[1],) + tuple(rank_fn(table, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row, **win)))
     hip.check_status(dev)
     if first is not None:
         a, b = (int(v) for v in pos_off[[first, first + sessions.numel()]].tolist())
@@ -434,7 +507,7 @@ def full_ranking_metrics(sums: torch.Tensor, ks) -> Dict[str, float]:
 
 @torch.no_grad()
 def evaluate_full_ranking(model, store: NewsStore, behaviors: Behaviors, l_hist: int, ks=(5, 10, 100), sessions=None,
-                          batch: int = 4096, exclude_history: bool = True, distributed: bool = False) -> Dict[str, float]:
+                          batch: int = 4096, exclude_history: bool = True, distributed: bool = False, windows=None) -> Dict[str, float]:
     """Full-corpus ranking metrics of the clicked news (rank_clicked): hit@k (= recall@k: one relevant news per query),
     ndcg@k (1 / log2(2 + rank) when rank < k), mrr (1 / (1 + rank)), mean_rank (0-based) and n_queries, averaged in fp64
     over the queries with rank >= 0.
@@ -442,8 +515,8 @@ def evaluate_full_ranking(model, store: NewsStore, behaviors: Behaviors, l_hist:
     `distributed=True` (opt-in, never automatic: every rank of the default process group must then make this call) shards
     the sessions over the ranks (distributed.shard_range); every rank encodes the whole table, and ONE fp64 all-reduce adds
     the sums and the count, so every rank returns the same dict, equal to the single-process one up to the order of that
-    final sum."""
-    _ranking_model_parts(model, behaviors, "evaluate_full_ranking()")
+    final sum.  `windows` as rank_clicked(): indexed by session id, so they are sharded with the sessions."""
+    _ranking_model_parts(model, behaviors, "evaluate_full_ranking()", windows is not None)
     ks = tuple(int(k) for k in ks)
     on = False
     if distributed:
@@ -456,7 +529,7 @@ def evaluate_full_ranking(model, store: NewsStore, behaviors: Behaviors, l_hist:
             sessions = range(lo, hi)
         else:
             sessions = sessions[lo:hi]
-    _, _, ranks, _ = rank_clicked(model, store, behaviors, l_hist, sessions, batch, exclude_history)
+    _, _, ranks, _ = rank_clicked(model, store, behaviors, l_hist, sessions, batch, exclude_history, windows)
     sums = full_ranking_sums(ranks, ks)
     if on:
         import torch.distributed as dist

@@ -226,16 +226,21 @@ class DotScoring(nn.Module):
         from ..evaluation import score_csr
         return score_csr(table, rows, sess, ops.l2_normalize_rows(u) if self.normalize else u, relu=relu)
 
-    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None,
+             win_hi=None):
+        if win_lo is not None or win_hi is not None:  # a row window: the deep entry point, the same bits
+            return self.topk_deep(table, u, k, excl_off, excl_rows, pad_row, win_lo=win_lo, win_hi=win_hi)
         return ops.topk_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, k, excl_off, excl_rows, pad_row)
 
-    def topk_deep(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
-        return ops.topk_deep_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, k, excl_off, excl_rows, pad_row)
+    def topk_deep(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1,
+                  win_lo=None, win_hi=None):
+        return ops.topk_deep_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, k, excl_off, excl_rows, pad_row,
+                                 win_lo, win_hi)
 
     def rank(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
-             out=None):
+             out=None, win_lo=None, win_hi=None):
         return ops.rank_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, tgt_off, tgt_rows, excl_off, excl_rows,
-                            pad_row, out)
+                            pad_row, out, win_lo, win_hi)
 
 
 class BilinScoring(nn.Module):
@@ -258,19 +263,24 @@ class BilinScoring(nn.Module):
         u = ops.l2_normalize_rows(u) if self.normalize else u
         return ops.score_csr_bilinear(table, rows, sess, u, self.bilin.weight, self.bilin.bias, relu=relu)
 
-    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None,
+             win_hi=None):
+        if win_lo is not None or win_hi is not None:  # a row window: the deep entry point, the same bits
+            return self.topk_deep(table, u, k, excl_off, excl_rows, pad_row, win_lo=win_lo, win_hi=win_hi)
         u = ops.l2_normalize_rows(u) if self.normalize else u
         return ops.topk_bilinear(table, u, self.bilin.weight, self.bilin.bias, k, excl_off, excl_rows, pad_row)
 
-    def topk_deep(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    def topk_deep(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1,
+                  win_lo=None, win_hi=None):
         u = ops.l2_normalize_rows(u) if self.normalize else u
-        return ops.topk_deep_bilinear(table, u, self.bilin.weight, self.bilin.bias, k, excl_off, excl_rows, pad_row)
+        return ops.topk_deep_bilinear(table, u, self.bilin.weight, self.bilin.bias, k, excl_off, excl_rows, pad_row, win_lo,
+                                      win_hi)
 
     def rank(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
-             out=None):
+             out=None, win_lo=None, win_hi=None):
         u = ops.l2_normalize_rows(u) if self.normalize else u
         return ops.rank_bilinear(table, u, self.bilin.weight, self.bilin.bias, tgt_off, tgt_rows, excl_off, excl_rows, pad_row,
-                                 out)
+                                 out, win_lo, win_hi)
 
 
 def _is_tanh(activation) -> bool:
@@ -302,18 +312,22 @@ class FCScoring(nn.Module):
     def score_csr(self, table: torch.Tensor, rows: torch.Tensor, sess: torch.Tensor, u: torch.Tensor, relu: bool = True):
         return ops.score_csr_mlp(table, rows, sess, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, relu=relu)
 
-    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    def topk(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None,
+             win_hi=None):
+        if win_lo is not None or win_hi is not None:  # a row window: the deep entry point, the same bits
+            return self.topk_deep(table, u, k, excl_off, excl_rows, pad_row, win_lo=win_lo, win_hi=win_hi)
         return ops.topk_mlp(table, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, k, excl_off, excl_rows,
                             pad_row)
 
-    def topk_deep(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+    def topk_deep(self, table: torch.Tensor, u: torch.Tensor, k: int, excl_off=None, excl_rows=None, pad_row: int = -1,
+                  win_lo=None, win_hi=None):
         return ops.topk_deep_mlp(table, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, k, excl_off,
-                                 excl_rows, pad_row)
+                                 excl_rows, pad_row, win_lo, win_hi)
 
     def rank(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
-             out=None):
+             out=None, win_lo=None, win_hi=None):
         return ops.rank_mlp(table, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, tgt_off, tgt_rows,
-                            excl_off, excl_rows, pad_row, out)
+                            excl_off, excl_rows, pad_row, out, win_lo, win_hi)
 
 
 # ------------------------------------------------------------------------------------------- bi-encoder shell

@@ -531,11 +531,32 @@ def score_csr_mlp(P, cand_rows, cand_sess, u, w1, b1, w2, b2, relu: bool = True)
     return r
 
 
+def _windows(win_lo, win_hi, B: int, dev) -> tuple:
+    """The row-window arguments of an xnrs_*_win entry point: () without windows, else the two pointers.  win_lo / win_hi:
+    (B,) int32, contiguous, on the table's device, given together; anything else is refused before the call."""
+    if win_lo is None and win_hi is None:
+        return ()
+    if win_lo is None or win_hi is None:
+        raise ValueError("windows: win_lo and win_hi are given together or not at all")
+    for t, what in ((win_lo, "win_lo"), (win_hi, "win_hi")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"windows: {what} is a ({B},) int32 tensor, one row bound per user; got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} "
+                             f"{getattr(t, 'dtype', '')}")
+        if t.device != dev or not t.is_contiguous():
+            raise hip.XnrsHipError(f"windows: {what} must be a contiguous tensor on {dev}")
+    return hip.ptr(win_lo), hip.ptr(win_hi)
+
+
 def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, k: int, excl_off, excl_rows, pad_row: int,
-          ws_query: str = "xnrs_topk_workspace_bytes"):
+          ws_query: str = "xnrs_topk_workspace_bytes", win_lo=None, win_hi=None):
     """The call every top-k entry point shares behind its own leading arguments `head` -> (rows:(B,k) int32, scores:(B,k)).
-    `entry` and `ws_query` name the entry point and its workspace query (xnrs_topk* or xnrs_topk_deep*)."""
+    `entry` and `ws_query` name the entry point and its workspace query (xnrs_topk* or xnrs_topk_deep*); with row windows
+    the call goes to `entry`_win (xnrs_topk_deep*_win)."""
     dev = table.device
+    win = _windows(win_lo, win_hi, B, dev)
+    if win:
+        entry += "_win"
     if (excl_off is None) != (excl_rows is None):
         raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
     if excl_off is not None:
@@ -550,17 +571,18 @@ def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int,
     l = hip.lib()
     nbytes = getattr(l, ws_query)(B, table.shape[0], proj_width, k)
     ws = hip.workspace(dev, nbytes)
-    hip.check(getattr(l, entry)(*head, hip.ptr(excl_off), hip.ptr(excl_rows), int(pad_row), k,
+    hip.check(getattr(l, entry)(*head, hip.ptr(excl_off), hip.ptr(excl_rows), *win, int(pad_row), k,
                                 hip.ptr(rows), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
     return rows, scores
 
 
-def _topk_dot(entry, ws_query, table, u, k, excl_off, excl_rows, pad_row):
+def _topk_dot(entry, ws_query, table, u, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None):
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
     B = u.shape[0]
-    return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, k, excl_off, excl_rows, pad_row, ws_query)
+    return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, k, excl_off, excl_rows, pad_row, ws_query,
+                 win_lo, win_hi)
 
 
 def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
@@ -568,7 +590,7 @@ def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1)
     return _topk_dot("xnrs_topk", "xnrs_topk_workspace_bytes", table, u, k, excl_off, excl_rows, pad_row)
 
 
-def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_row):
+def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None):
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -576,7 +598,7 @@ def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_
     b = None if b is None else hip.dev_f32(b, "bilinear bias")
     B = u.shape[0]
     return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E, k,
-                 excl_off, excl_rows, pad_row, ws_query)
+                 excl_off, excl_rows, pad_row, ws_query, win_lo, win_hi)
 
 
 def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
@@ -584,7 +606,7 @@ def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row
     return _topk_bilinear("xnrs_topk_bilinear", "xnrs_topk_workspace_bytes", table, u, w, b, k, excl_off, excl_rows, pad_row)
 
 
-def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row):
+def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None):
     P = hip.dev_f32(P, "projected news table")
     E = w1.shape[1] // 2
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -593,7 +615,7 @@ def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad
         raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
     B = u.shape[0]
     return _topk(entry, P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2), hip.ptr(b2)), B, H, k,
-                 excl_off, excl_rows, pad_row, ws_query)
+                 excl_off, excl_rows, pad_row, ws_query, win_lo, win_hi)
 
 
 def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
@@ -604,20 +626,22 @@ def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_ro
 _DEEP_WS = "xnrs_topk_deep_workspace_bytes"
 
 
-def topk_deep_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
+def topk_deep_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
     """topk_dot for 1 <= k <= 1024 (include/xnrs_hip.h: xnrs_topk_deep): the same order and the same score bits, so the first
-    128 places are those of topk_dot and topk_deep_dot(k)[:, :j] is topk_deep_dot(j)."""
-    return _topk_dot("xnrs_topk_deep", _DEEP_WS, table, u, k, excl_off, excl_rows, pad_row)
+    128 places are those of topk_dot and topk_deep_dot(k)[:, :j] is topk_deep_dot(j).
+    win_lo, win_hi: (B,) int32 row windows (xnrs_topk_deep_win): user b sees the rows [win_lo[b], win_hi[b]) only -- the result
+    of the call with every other row on the user's exclusion list, without the list and without scoring those rows."""
+    return _topk_dot("xnrs_topk_deep", _DEEP_WS, table, u, k, excl_off, excl_rows, pad_row, win_lo, win_hi)
 
 
-def topk_deep_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
-    """topk_bilinear for 1 <= k <= 1024 (xnrs_topk_deep_bilinear)."""
-    return _topk_bilinear("xnrs_topk_deep_bilinear", _DEEP_WS, table, u, w, b, k, excl_off, excl_rows, pad_row)
+def topk_deep_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
+    """topk_bilinear for 1 <= k <= 1024 (xnrs_topk_deep_bilinear; with row windows xnrs_topk_deep_bilinear_win)."""
+    return _topk_bilinear("xnrs_topk_deep_bilinear", _DEEP_WS, table, u, w, b, k, excl_off, excl_rows, pad_row, win_lo, win_hi)
 
 
-def topk_deep_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
-    """topk_mlp for 1 <= k <= 1024 (xnrs_topk_deep_mlp)."""
-    return _topk_mlp("xnrs_topk_deep_mlp", _DEEP_WS, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row)
+def topk_deep_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
+    """topk_mlp for 1 <= k <= 1024 (xnrs_topk_deep_mlp; with row windows xnrs_topk_deep_mlp_win)."""
+    return _topk_mlp("xnrs_topk_deep_mlp", _DEEP_WS, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row, win_lo, win_hi)
 
 
 def _csr_check(what: str, off, rows, B: int, dev):
@@ -629,11 +653,15 @@ def _csr_check(what: str, off, rows, B: int, dev):
 
 
 def _rank(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, tgt_off, tgt_rows, excl_off, excl_rows,
-          pad_row: int, out):
+          pad_row: int, out, win_lo=None, win_hi=None):
     """The call every rank entry point shares behind its own leading arguments `head` -> (ranks int32, scores fp32), both
     indexed like tgt_rows.  The call writes the positions [tgt_off[0], tgt_off[B]) only: fresh outputs start at -1 / NaN
-    everywhere else, the tensors of `out` = (ranks, scores) keep what they held."""
+    everywhere else, the tensors of `out` = (ranks, scores) keep what they held.  With row windows the call goes to
+    `entry`_win."""
     dev = table.device
+    win = _windows(win_lo, win_hi, B, dev)
+    if win:
+        entry += "_win"
     if (excl_off is None) != (excl_rows is None):
         raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
     _csr_check("targets", tgt_off, tgt_rows, B, dev)
@@ -651,24 +679,27 @@ def _rank(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int,
     l = hip.lib()
     nbytes = l.xnrs_rank_workspace_bytes(B, proj_width)
     ws = hip.workspace(dev, nbytes)
-    hip.check(getattr(l, entry)(*head, hip.ptr(tgt_off), hip.ptr(tgt_rows), hip.ptr(excl_off), hip.ptr(excl_rows), int(pad_row),
-                                hip.ptr(ranks), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
+    hip.check(getattr(l, entry)(*head, hip.ptr(tgt_off), hip.ptr(tgt_rows), hip.ptr(excl_off), hip.ptr(excl_rows), *win,
+                                int(pad_row), hip.ptr(ranks), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
     return ranks, scores
 
 
-def rank_dot(table, u, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None):
+def rank_dot(table, u, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None, win_lo=None, win_hi=None):
     """For every (user, target row) of the CSR tgt_off / tgt_rows: how many eligible rows of `table` come before the target
-    in the order of topk_dot, and the target's score (include/xnrs_hip.h: xnrs_rank) -> (ranks, scores)."""
+    in the order of topk_dot, and the target's score (include/xnrs_hip.h: xnrs_rank) -> (ranks, scores).
+    win_lo, win_hi: (B,) int32 row windows (xnrs_rank_win): only the rows [win_lo[b], win_hi[b]) compete; a target outside its
+    user's window is ranked all the same."""
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
     B = u.shape[0]
     return _rank("xnrs_rank", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, tgt_off, tgt_rows, excl_off, excl_rows,
-                 pad_row, out)
+                 pad_row, out, win_lo, win_hi)
 
 
-def rank_bilinear(table, u, w, b, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None):
-    """As rank_dot with the score u W[0] table[row] + bias (xnrs_rank_bilinear)."""
+def rank_bilinear(table, u, w, b, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None, win_lo=None,
+                  win_hi=None):
+    """As rank_dot with the score u W[0] table[row] + bias (xnrs_rank_bilinear; with row windows xnrs_rank_bilinear_win)."""
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -676,11 +707,13 @@ def rank_bilinear(table, u, w, b, tgt_off, tgt_rows, excl_off=None, excl_rows=No
     b = None if b is None else hip.dev_f32(b, "bilinear bias")
     B = u.shape[0]
     return _rank("xnrs_rank_bilinear", table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E,
-                 tgt_off, tgt_rows, excl_off, excl_rows, pad_row, out)
+                 tgt_off, tgt_rows, excl_off, excl_rows, pad_row, out, win_lo, win_hi)
 
 
-def rank_mlp(P, u, w1, b1, w2, b2, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None):
-    """As rank_dot with the score w2 . tanh(W1u u + b1 + P[row]) + b2, P = mlp_news_proj(table) (xnrs_rank_mlp)."""
+def rank_mlp(P, u, w1, b1, w2, b2, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, out=None, win_lo=None,
+             win_hi=None):
+    """As rank_dot with the score w2 . tanh(W1u u + b1 + P[row]) + b2, P = mlp_news_proj(table) (xnrs_rank_mlp; with row
+    windows xnrs_rank_mlp_win)."""
     P = hip.dev_f32(P, "projected news table")
     E = w1.shape[1] // 2
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -689,7 +722,8 @@ def rank_mlp(P, u, w1, b1, w2, b2, tgt_off, tgt_rows, excl_off=None, excl_rows=N
         raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
     B = u.shape[0]
     return _rank("xnrs_rank_mlp", P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2),
-                                      hip.ptr(b2)), B, H, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, out)
+                                      hip.ptr(b2)), B, H, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, out,
+                 win_lo, win_hi)
 
 
 # ------------------------------------------------------------------------------------------------
