@@ -367,8 +367,8 @@ int32_t xnrs_seq_encoder_bwd_rows(const float *x, const float *m, const int32_t 
                                   const xnrs_head_grads *g_head, const xnrs_row_lists *rows, void *ws, size_t ws_bytes,
                                   void *stream);
 
-/* autograd of nn.Linear (xnrs_linear_fwd): dx = dy.W (nullable), dw = dy^T.x, db = colsum(dy) (nullable).
- * gather_ids as in the forward (then dx must be NULL).
+/* autograd of nn.Linear (xnrs_linear_fwd): dx = dy.W, dw = dy^T.x, db = colsum(dy), each nullable (db alone: a
+ * stand-alone column sum; with dw: summed by the product's own launch).  gather_ids as in the forward (then dx must be NULL).
  * M == 0, here and in the two xnrs_embedding_linear_bwd* below: every output that was asked for is written as zeros and
  * nothing else is touched; x / ids / dy and the workspace may be NULL. */
 size_t xnrs_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K);

@@ -126,6 +126,17 @@ MERGE_DW = os.environ.get("XNRS_MERGE_DW", "1") != "0"
 SKIP_UNUSED_DW = os.environ.get("XNRS_SKIP_UNUSED_DW", "1") != "0"
 
 
+def _engine_wants(fn) -> bool:
+    """torch._C._will_engine_execute_node(fn), asked per node.  Under torch.autograd.grad(..., inputs=[leaves]) the engine
+    answers False for the AccumulateGrad node of a leaf that is not among the inputs and RAISES for one that is (a captured
+    leaf is not executed, its gradient is handed back: "A leaf node was passed ... not supported"): that leaf is wanted.  Any
+    other refusal is answered the same way, on the safe side: the gradient is computed."""
+    try:
+        return bool(torch._C._will_engine_execute_node(fn))
+    except RuntimeError:
+        return True
+
+
 def _wanted_inputs(ctx, is_tensor, first):
     """[will the engine use the gradient of forward input i in THIS backward pass?] for the inputs from `first` on.
     is_tensor: per forward input, whether a tensor was passed -- ctx.next_functions holds one edge per TENSOR input, in order
@@ -143,9 +154,9 @@ def _wanted_inputs(ctx, is_tensor, first):
             fn = nf[e][0] if t else None
             e += 1 if t else 0
             if i >= first:
-                out.append(fn is not None and bool(torch._C._will_engine_execute_node(fn)))
+                out.append(fn is not None and _engine_wants(fn))
         return out
-    except (RuntimeError, AttributeError, IndexError):  # (an engine without the query: compute everything)
+    except (AttributeError, IndexError):  # (an engine without the query: compute everything)
         return [True] * count
 
 
