@@ -3,7 +3,10 @@
 entirely on the device: resident news table -> device batch assembly -> forward_ids (id gather fused into the first
 GEMM) -> relu/MSE + lambda * fused InfoNCE -> hand-written HIP backward -> Adam -> device evaluation.
 
-    python examples/train_synthetic.py [--model NRMS|standard] [--steps 300] [--batch 64] [--bf16x3]
+    python examples/train_synthetic.py [--model NRMS|standard] [--steps 300] [--batch 64] [--bf16x3] [--full-table-loss]
+
+--full-table-loss (off by default) trains with losses.full_table_loss instead: every clicked news of a session against ALL
+news of the table encoded in that step, the objective evaluate_full_ranking measures.
 
 Synthetic click world (xnrs_amd.synth.click_world): news carry a topic direction in their tokens, a user clicks news of
 its own topic -- so the ranking metrics have to rise if the whole stack (forward, gradients, optimiser, evaluation) is
@@ -19,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from xnrs_amd import evaluation, hip, synth  # noqa: E402
 from xnrs_amd.data import DeviceBatcher  # noqa: E402
-from xnrs_amd.losses import contrastive_loss  # noqa: E402
+from xnrs_amd.losses import contrastive_loss, full_table_loss  # noqa: E402
 from xnrs_amd.models import make_model  # noqa: E402
 
 
@@ -34,6 +37,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--hist", type=int, default=8)
     ap.add_argument("--bf16x3", action="store_true", help="forward GEMMs + dX products on the bf16 matrix cores (fp32-grade)")
+    ap.add_argument("--full-table-loss", action="store_true",
+                    help="train with the softmax ranking loss over the whole news table (losses.full_table_loss)")
     args = ap.parse_args()
     dev = "cuda:0"
     if args.bf16x3:
@@ -53,11 +58,14 @@ def main():
     t0 = time.perf_counter()
     for step in range(args.steps):
         sess = torch.randint(0, len(beh), (args.batch,), device=dev)
-        hist, cand, targets = batcher.train_batch(sess, n_neg=4, seed=step)
         opt.zero_grad()
-        r, u, _ = model.forward_ids(store.x, store.m, hist, cand, return_embeddings=True)
-        loss = torch.nn.functional.mse_loss(torch.relu(r), targets) + \
-            0.1 * contrastive_loss(u.squeeze(1), beh.theme_labels[sess], 0.08)
+        if args.full_table_loss:
+            loss = full_table_loss(model, store, beh, sess, args.hist)
+        else:
+            hist, cand, targets = batcher.train_batch(sess, n_neg=4, seed=step)
+            r, u, _ = model.forward_ids(store.x, store.m, hist, cand, return_embeddings=True)
+            loss = torch.nn.functional.mse_loss(torch.relu(r), targets) + \
+                0.1 * contrastive_loss(u.squeeze(1), beh.theme_labels[sess], 0.08)
         loss.backward()
         opt.step()
         if step % 50 == 0 or step == args.steps - 1:

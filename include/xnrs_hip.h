@@ -794,6 +794,60 @@ int32_t xnrs_rank_mlp_win(const float *P, int64_t n_rows, int32_t E, int32_t H, 
                           const int64_t *excl_off, const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi,
                           int32_t pad_row, int32_t *ranks, float *scores, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- the full-table softmax ranking loss: the training side of the two sweeps (csrc/topk.hip) ------------------------------
+ * The reference's ranking_loss(p, n) = -log(e^p / (e^p + sum e^n)) (xnrs/utils.py:117-131) with EVERY eligible news of the
+ * table as a negative, forward and backward, again without a (B, n_rows) score matrix.  The operands are those of
+ * xnrs_rank_win: table:(n_rows,E), the user side up:(B,E) as the score reads it (u, or v = u W[0] of the bilinear scorer),
+ * bias: one float on the device or NULL, the target CSR tgt_off / tgt_rows (one query per entry), the exclusion CSR (NULL:
+ * none), win_lo / win_hi (both or neither; exactly one: XNRS_EINVAL) and pad_row.  Scores s_bn = <table[n], up[b]> (+ bias)
+ * are formed by the score tile of xnrs_topk* / xnrs_rank* and by nothing else.
+ *   Negatives of user b: the rows eligible for xnrs_rank*_win (inside the table, not pad_row, not on b's exclusion list,
+ *              inside b's window) minus EVERY target row of b: another positive of the same session is not a negative.
+ *   Forward  : lse[b] = log sum_{n in negatives} exp(s_bn), max-stabilised (no overflow for finite scores), -inf when the
+ *              user has no negatives.  For query e = (b, t): scores[e] = the raw score, the bits xnrs_rank writes;
+ *              loss[e] = logaddexp(s_bt, lse[b]) - s_bt = ranking_loss(p = s_bt, n = all negatives).
+ *   No answer: the rank -1 queries of xnrs_rank (t outside the table, t == pad_row): scores[e] = NaN, loss[e] = 0, no
+ *              gradient.  As with rank, a target on its own exclusion list or outside its window is still a query.
+ *   No negatives: loss = 0 exactly and every gradient of the user 0; no NaN.
+ *   Backward : g[e] the upstream gradient per query, p_e = exp(s_bt - logaddexp(s_bt, lse[b])), c_b = sum_{e of b} g_e (1 - p_e):
+ *              d s_bt = -g_e (1 - p_e); d s_bn = c_b exp(s_bn - lse[b]) per negative; d_up[b] = sum_n d s_bn table[n];
+ *              d_table[n] = sum_b d s_bn up[b].  Duplicate targets are separate queries and both contribute.  d_up:(B,E) and
+ *              d_table:(n_rows,E) are OVERWRITTEN (zero rows where nothing flows); either may be NULL, and a NULL gradient's
+ *              sweep is not launched.  scores and lse are what the forward call over the same operands wrote.
+ *   Precondition: table and up are finite; the results for non-finite inputs are unspecified.
+ * Launches: forward 3 (target scores; the sweep -- user tiles x xnrs_topk_slices(B, n_rows), per (user, 128-row chunk) a
+ * partial (max, sum exp(s - max)); the combine, one thread per user).  d_up 2 (the sweep recomputes the score tile and feeds
+ * d s through LDS into a second fp32 MFMA product with the table chunk, 128 users x 256 features per pass; a reduce sums
+ * the slice partials in slice order and adds the target terms).  d_table 1 or 2 (the transposed sweep over row chunks, and
+ * over user groups when the table has fewer than 256 chunks; then a reduce in group order).
+ * Determinism: lse, loss and scores of a user do not depend on B, on the user's position in the batch, on the other users'
+ * windows or on the slicing and are the same bits on every run: chunk partials are folded in ascending chunk order, the
+ * in-chunk tree is fixed by the row's place in its chunk, and a chunk without a negative leaves the running value's bits
+ * untouched -- so A WINDOWED CALL EQUALS, BIT FOR BIT, THE CALL WITH EVERY OUT-OF-WINDOW ROW ON THE EXCLUSION LIST, and both
+ * window pointers NULL is the call without them.  d_up and d_table are the same bits on every run of the same call; their
+ * summation order follows the slicing, so they MAY differ in the last bits between batch sizes and batch positions.
+ * No float atomics, results cross launches at kernel boundaries only, no host synchronisation, no allocation, hipGraph-
+ * capturable.  XNRS_EINVAL and XNRS_EWORKSPACE are found on the host before any launch and write nothing.  B == 0: XNRS_OK,
+ * nothing written; an empty target span writes lse alone; n_rows == 0: lse = -inf, every query NaN / 0.  n_rows <= 2^31 - 1,
+ * any E >= 1 (E % 4 != 0 or an unaligned base takes scalar loads).
+ * ws: xnrs_table_loss_workspace_bytes(B, n_rows, E, want_d_table), one size for both calls, a pure host call, never a
+ * (B, n_rows) array: the larger of
+ *   forward : 8 ceil(n_rows / 128) B bytes                                            (1/64 of the score matrix)
+ *   backward: 4 S B E + (want_d_table and G > 1 ? 4 G n_rows E : 0) bytes, S = the slices of the d_up sweep = min(chunks,
+ *             ceil(256 / user tiles)) and G = the user groups of the d_table sweep = min(user tiles, ceil(256 / chunks)),
+ *             both rounded to even shares: the partials are bounded by 256 workgroups x 128 x E floats (+ one tile row),
+ * each region rounded up to 256 B. */
+size_t xnrs_table_loss_workspace_bytes(int64_t B, int64_t n_rows, int32_t E, int32_t want_d_table);
+int32_t xnrs_table_loss_fwd(const float *table, int64_t n_rows, int32_t E, const float *up, const float *bias, int64_t B,
+                            const int64_t *tgt_off, const int32_t *tgt_rows, const int64_t *excl_off, const int32_t *excl_rows,
+                            const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row, float *scores, float *loss,
+                            float *lse, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_table_loss_bwd(const float *table, int64_t n_rows, int32_t E, const float *up, const float *bias, int64_t B,
+                            const int64_t *tgt_off, const int32_t *tgt_rows, const int64_t *excl_off, const int32_t *excl_rows,
+                            const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row, const float *scores,
+                            const float *lse, const float *g, float *d_up, float *d_table, void *ws, size_t ws_bytes,
+                            void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

@@ -746,6 +746,45 @@ def dot_scoring(u, c, normalize):
     return _DotScoring.apply(u, c, normalize)
 
 
+class _TableLoss(torch.autograd.Function):
+    """ops.table_loss: the full-table softmax ranking loss (xnrs_table_loss_fwd / _bwd).  The backward recomputes the scores;
+    what is saved is per query and per user only."""
+
+    @staticmethod
+    def forward(ctx, table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias):
+        from . import ops
+        table = hip.dev_f32(table, "news vectors")
+        up_shape = tuple(up.shape)
+        up = hip.dev_f32(up, "user vectors").reshape(-1, table.shape[-1])
+        with torch.no_grad():
+            loss, scores, lse = ops.table_loss_forward(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi,
+                                                       bias)
+        ctx.save_for_backward(table, up, scores, lse)
+        ctx.rest = (tgt_off, tgt_rows, excl_off, excl_rows, int(pad_row), win_lo, win_hi, None if bias is None else bias.detach())
+        ctx.up_shape = up_shape
+        ctx.is_tensor = [isinstance(t, torch.Tensor) for t in (table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo,
+                                                               win_hi, bias)]
+        ctx.mark_non_differentiable(scores, lse)
+        return loss, scores, lse
+
+    @staticmethod
+    def backward(ctx, g, _g_scores, _g_lse):
+        from . import ops
+        table, up, scores, lse = ctx.saved_tensors
+        tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias = ctx.rest
+        wanted = _wanted_inputs(ctx, ctx.is_tensor, 0)  # (torch.autograd.grad(inputs=[u]) alone: the table's sweep is not run)
+        d_up, d_table = ops.table_loss_backward(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias,
+                                                scores, lse, g, want_d_up=ctx.needs_input_grad[1] and wanted[1],
+                                                want_d_table=ctx.needs_input_grad[0] and wanted[0])
+        if d_up is not None:
+            d_up = d_up.reshape(ctx.up_shape)
+        return d_table, d_up, None, None, None, None, None, None, None, None
+
+
+def table_loss(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias):
+    return _TableLoss.apply(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias)
+
+
 class _BilinScoring(torch.autograd.Function):
     """BilinScoring (scoring.py:41-66): backward G_b = sum_n g_bn c^_bn, dW[0] = U^^T G, du^_b = W[0] G_b, dc^_bn = g_bn v_b,
     dbias = sum g (then through the normalisation when it is on)."""

@@ -1,6 +1,8 @@
 """Loss kernels next to the hot path: the in-batch InfoNCE "theme" contrastive loss of
 ContrastiveRankingTrainer._compute_contrastive_loss (xnrs/training.py:433-472) as ONE fused HIP forward +
-ONE fused backward instead of a Python loop over the batch rows."""
+ONE fused backward instead of a Python loop over the batch rows; and the full-table softmax ranking loss -- the reference's
+ranking_loss (xnrs/utils.py:117-131) with every eligible news of the table as a negative -- over the sweep of
+recommend() / rank_clicked(), without a (sessions, n_rows) score matrix (table_ranking_loss, full_table_loss)."""
 from __future__ import annotations
 
 import torch
@@ -41,3 +43,99 @@ def contrastive_loss(embeddings: torch.Tensor, labels: torch.Tensor, temperature
     if embeddings.dim() > 2:
         embeddings = embeddings.reshape(embeddings.size(0), -1)
     return _InfoNCE.apply(embeddings, labels, temperature)
+
+
+def _table_loss_scorer(scorer, who: str):
+    fn = getattr(scorer, "table_loss", None)
+    if fn is None:
+        raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no full-table loss over a news table "
+                                  "(table_loss); training it with a plain dot product would train another model")
+    return fn
+
+
+def reduce_table_loss(loss: torch.Tensor, scores: torch.Tensor, reduction: str) -> torch.Tensor:
+    """'none': the loss per query; 'sum'; 'mean': the sum over the number of queries that have an answer (scores not NaN),
+    counted on the device, 0 when there are none."""
+    if reduction == "none":
+        return loss
+    if reduction == "sum":
+        return loss.sum()
+    if reduction == "mean":
+        n = (~torch.isnan(scores)).sum()
+        return loss.sum() / n.clamp(min=1).to(loss.dtype)
+    raise ValueError(f"reduction {reduction!r}: 'mean', 'sum' or 'none'")
+
+
+def table_ranking_loss(scorer, table: torch.Tensor, u: torch.Tensor, tgt_off: torch.Tensor, tgt_rows: torch.Tensor,
+                       excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None,
+                       reduction: str = "mean") -> torch.Tensor:
+    """ranking_loss(p, n) = -log(e^p / (e^p + sum e^n)) of every (user, target row) of the CSR tgt_off / tgt_rows with ALL
+    eligible rows of `table` as the negatives n (include/xnrs_hip.h: xnrs_table_loss_fwd): the rows rank() counts -- not
+    pad_row, not on the user's exclusion list, inside the user's window -- minus every target of the user.  `scorer`: a
+    DotScoring or BilinScoring (scorer.table_loss); differentiable in `table`, `u` and the scorer's weight.  A query without
+    an answer (a target outside the table, the pad row) and a user without negatives contribute 0."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"reduction {reduction!r}: 'mean', 'sum' or 'none'")
+    fn = _table_loss_scorer(scorer, "table_ranking_loss()")
+    loss, scores, _ = fn(table, u, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo=win_lo, win_hi=win_hi)
+    return reduce_table_loss(loss, scores, reduction)
+
+
+def full_table_loss(model, store_or_table, behaviors, sessions, l_hist: int, exclude_history: bool = True, windows=None,
+                    reduction: str = "mean", store=None) -> torch.Tensor:
+    """The full-table ranking loss of one batch of sessions, on the path of recommend() / rank_clicked() with autograd on:
+    the sessions' last `l_hist` history rows are gathered from the table of news vectors, model.encode_user gives the user
+    vectors, every clicked news of a session (pos_off / pos_val) is a query, the session's FULL history is excluded
+    (`exclude_history`) and `windows` = (lo, hi) indexed by session id restrict the negatives as in rank_clicked().
+
+    store_or_table: a NewsStore -- the table is encoded here, under autograd, so the news encoder trains too -- or a pair
+    (vecs:(n_rows,E), hm:(n_rows,1)) as encode_news_table returns it, together with `store` (its pad row): a detached pair
+    trains the user tower (and the scorer) only.  reduction 'mean' divides by the number of clicks that have an answer.
+    A scorer without table_loss (FCScoring), a model whose news vectors depend on the user (NPA) and CAUM raise
+    NotImplementedError before anything is encoded."""
+    from . import evaluation as EV
+    who = "full_table_loss()"
+    if getattr(model, "user_dependent_news", False):
+        raise NotImplementedError(f"{who}: the news vectors of {type(model).__name__} depend on the user, so no table of "
+                                  "news vectors exists to rank")
+    scorer = getattr(model, "rec_model", None)
+    _table_loss_scorer(scorer, who)
+    if getattr(scorer, "normalize", False):
+        raise NotImplementedError(f"{who}: {type(scorer).__name__}(normalize=True) has no full-table loss")
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"reduction {reduction!r}: 'mean', 'sum' or 'none'")
+    uidx = None
+    if getattr(model, "uses_user_index", False):
+        uidx = getattr(behaviors, "user_index", None)
+        if uidx is None:
+            raise ValueError(f"{who}: {type(model).__name__} needs the user index of every session (sessions without "
+                             "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    if isinstance(store_or_table, (tuple, list)):
+        vecs, hm = store_or_table
+        if store is None:
+            raise ValueError(f"{who}: a pre-encoded table comes with store= (its pad row and the history batcher's)")
+    else:
+        store = store_or_table
+        ids = torch.arange(store.n_rows, dtype=torch.int32, device=store.x.device).reshape(1, -1)
+        y, m = model.encode_news_ids(store, ids)  # (encode_news_table without its no_grad)
+        vecs, hm = y[0], m[0]
+    dev = vecs.device
+    windows = EV._session_windows(windows, behaviors, dev, who)
+    sess = torch.as_tensor(sessions, dtype=torch.int64, device=dev)
+    hist = EV.DeviceBatcher(behaviors, l_hist, store.pad_row).eval_batch(sess)[0]
+    h = _gather_rows(vecs, hist)
+    m = hm[hist.long()]
+    u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx.to(dev)[sess])
+    excl = EV._history_csr(behaviors, sess, None) if exclude_history else (None, None)
+    tgt = EV._session_csr(behaviors.pos_off, behaviors.pos_val, sess, None)
+    win = (None, None) if windows is None else (windows[0][sess].contiguous(), windows[1][sess].contiguous())
+    return table_ranking_loss(scorer, vecs, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row, win[0], win[1], reduction)
+
+
+def _gather_rows(vecs: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+    """vecs[hist]: through the project's row gather when the table carries a gradient (its backward scatters on the HIP
+    path), a plain index otherwise."""
+    if vecs.requires_grad and torch.is_grad_enabled():
+        from . import ops
+        return ops.embedding_rows(hist.reshape(-1), vecs).reshape(tuple(hist.shape) + (vecs.shape[1],))
+    return vecs[hist.long()]

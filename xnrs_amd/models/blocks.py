@@ -242,6 +242,15 @@ class DotScoring(nn.Module):
         return ops.rank_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, tgt_off, tgt_rows, excl_off, excl_rows,
                             pad_row, out, win_lo, win_hi)
 
+    def table_loss(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
+                   win_lo=None, win_hi=None):
+        """The softmax ranking loss of every target against all eligible rows of the table (ops.table_loss) -> (loss, scores,
+        lse), differentiable in `table` and `u`."""
+        if self.normalize:
+            raise NotImplementedError("DotScoring.table_loss with normalize=True: the full-table loss implements the raw inner "
+                                      "product only")
+        return ops.table_loss(table, u, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi)
+
 
 class BilinScoring(nn.Module):
     """Reference: scoring.py:41-66.  nn.Bilinear(E, E, 1, bias) registered as `bilin`; u:(B,1,E), c:(B,N,E) -> (B,N,1) =
@@ -281,6 +290,17 @@ class BilinScoring(nn.Module):
         u = ops.l2_normalize_rows(u) if self.normalize else u
         return ops.rank_bilinear(table, u, self.bilin.weight, self.bilin.bias, tgt_off, tgt_rows, excl_off, excl_rows, pad_row,
                                  out, win_lo, win_hi)
+
+    def table_loss(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
+                   win_lo=None, win_hi=None):
+        """As DotScoring.table_loss with the score u W[0] table[row] + bias: v = u W[0] through ops.linear, so that autograd
+        reaches W and u; the bias is passed for the score bits and gets no gradient (it cancels in the loss)."""
+        if self.normalize:
+            raise NotImplementedError("BilinScoring.table_loss with normalize=True: the full-table loss implements the raw "
+                                      "bilinear form only")
+        E = self.bilin.weight.shape[-1]
+        v = ops.linear(u.reshape(-1, E), self.bilin.weight[0].t())  # v_b = W[0]^T u_b
+        return ops.table_loss(table, v, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias=self.bilin.bias)
 
 
 def _is_tanh(activation) -> bool:

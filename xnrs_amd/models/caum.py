@@ -80,6 +80,7 @@ class CAUMScoring(DotScoring):
     score_csr = None
     topk = None
     rank = None
+    table_loss = None
 
 
 class CAUMNewsEncoder(nn.Module):

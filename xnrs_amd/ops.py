@@ -726,6 +726,93 @@ def rank_mlp(P, u, w1, b1, w2, b2, tgt_off, tgt_rows, excl_off=None, excl_rows=N
                  win_lo, win_hi)
 
 
+def _table_loss_check(table, up, tgt_off, tgt_rows, excl_off, excl_rows):
+    """What can be refused before anything touches the device: the table's shape and the CSRs' dtypes and lengths."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError(f"news vectors: a (n_rows, E) table, got {tuple(getattr(table, 'shape', ()))}")
+    E = table.shape[1]
+    if not isinstance(up, torch.Tensor) or up.numel() % E:
+        raise RuntimeError(f"user vectors: (B, {E}) or (B, 1, {E}), got {tuple(getattr(up, 'shape', ()))}")
+    B = up.numel() // E
+    if (excl_off is None) != (excl_rows is None):
+        raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
+    _csr_check("targets", tgt_off, tgt_rows, B, table.device)
+    if excl_off is not None:
+        _csr_check("exclusions", excl_off, excl_rows, B, table.device)
+
+
+def _table_loss_args(table, up, tgt_off, tgt_rows, excl_off, excl_rows, win_lo, win_hi, bias):
+    """The checked operands of xnrs_table_loss_fwd / _bwd: (table, up, bias, B, the pointer tuple of both calls)."""
+    _table_loss_check(table, up, tgt_off, tgt_rows, excl_off, excl_rows)
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    up = hip.dev_f32(up, "user vectors").reshape(-1, E)
+    bias = None if bias is None else hip.dev_f32(bias, "score bias").reshape(-1)[:1]
+    B, dev = up.shape[0], table.device
+    win = _windows(win_lo, win_hi, B, dev) or (None, None)
+    if (excl_off is None) != (excl_rows is None):
+        raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
+    _csr_check("targets", tgt_off, tgt_rows, B, dev)
+    if excl_off is not None:
+        _csr_check("exclusions", excl_off, excl_rows, B, dev)
+    if excl_rows is not None and excl_rows.numel() == 0:  # (an empty tensor has no address: no exclusions at all)
+        excl_off = excl_rows = None
+    # (no target at all: the offsets are all equal and the rows are never read, but the entry point wants an address)
+    rows = tgt_rows if tgt_rows.numel() else torch.zeros((1,), dtype=torch.int32, device=dev)
+    head = (hip.ptr(table), n_rows, E, hip.ptr(up), hip.ptr(bias), B, hip.ptr(tgt_off), hip.ptr(rows), hip.ptr(excl_off),
+            hip.ptr(excl_rows), *win)
+    return table, up, bias, B, (head, rows)
+
+
+def table_loss_forward(table, up, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None,
+                       bias=None):
+    """xnrs_table_loss_fwd -> (loss:(T,), scores:(T,), lse:(B,)); positions outside [tgt_off[0], tgt_off[B]) hold 0 / NaN."""
+    table, up, bias, B, head = _table_loss_args(table, up, tgt_off, tgt_rows, excl_off, excl_rows, win_lo, win_hi, bias)
+    dev, T = table.device, tgt_rows.numel()
+    loss = torch.zeros((T,), dtype=torch.float32, device=dev)
+    scores = torch.full((T,), float("nan"), dtype=torch.float32, device=dev)
+    lse = torch.empty((B,), dtype=torch.float32, device=dev)
+    l = hip.lib()
+    nbytes = l.xnrs_table_loss_workspace_bytes(B, table.shape[0], table.shape[1], 0)
+    ws = hip.workspace(dev, nbytes)
+    hip.check(l.xnrs_table_loss_fwd(*head[0], int(pad_row), hip.ptr(scores), hip.ptr(loss), hip.ptr(lse), hip.ptr(ws), nbytes,
+                                    hip.stream_ptr(dev)), "xnrs_table_loss_fwd")
+    return loss, scores, lse
+
+
+def table_loss_backward(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias, scores, lse, g,
+                        want_d_up: bool = True, want_d_table: bool = True):
+    """xnrs_table_loss_bwd -> (d_up or None, d_table or None): a gradient that is not wanted is not computed."""
+    table, up, bias, B, head = _table_loss_args(table, up, tgt_off, tgt_rows, excl_off, excl_rows, win_lo, win_hi, bias)
+    dev = table.device
+    g = hip.dev_f32(g, "upstream gradient").reshape(-1)
+    if g.numel() != tgt_rows.numel() or scores.numel() != tgt_rows.numel() or lse.numel() != B:
+        raise RuntimeError(f"table loss backward: g and scores have one entry per target row ({tgt_rows.numel()}), lse one per "
+                           f"user ({B}); got {g.numel()}, {scores.numel()}, {lse.numel()}")
+    d_up = torch.empty_like(up) if want_d_up else None
+    d_table = torch.empty_like(table) if want_d_table else None
+    if not (want_d_up or want_d_table):
+        return None, None
+    l = hip.lib()
+    nbytes = l.xnrs_table_loss_workspace_bytes(B, table.shape[0], table.shape[1], int(want_d_table))
+    ws = hip.workspace(dev, nbytes)
+    hip.check(l.xnrs_table_loss_bwd(*head[0], int(pad_row), hip.ptr(scores), hip.ptr(lse), hip.ptr(g), hip.ptr(d_up), hip.ptr(d_table),
+                                    hip.ptr(ws), nbytes, hip.stream_ptr(dev)), "xnrs_table_loss_bwd")
+    return d_up, d_table
+
+
+def table_loss(table, up, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None, bias=None):
+    """The softmax ranking loss of every (user, target row) of the CSR tgt_off / tgt_rows against ALL eligible rows of `table`
+    (include/xnrs_hip.h: xnrs_table_loss_fwd) -> (loss:(T,), scores:(T,), lse:(B,)), T = tgt_rows.numel().  The negatives of
+    a user are the rows rank_dot counts, minus every target of the user; loss = logaddexp(score, lse) - score, 0 for a query
+    without an answer (score NaN) and for a user without negatives (lse -inf).  Differentiable in `table` and `up` (a
+    gradient that nobody asks for is not computed); `scores` and `lse` carry no gradient, and neither does `bias`, which
+    cancels in the loss."""
+    from . import autograd
+    _table_loss_check(table, up, tgt_off, tgt_rows, excl_off, excl_rows)
+    return autograd.table_loss(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias)
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
