@@ -18,6 +18,12 @@
  *     backward entry points may fork weight-gradient launches onto a library-owned stream and join
  *     them back by events inside the call (one stream + 32 events per device, created at the first
  *     eager backward; XNRS_BWD_SIDE_STREAM=0: never).
+ *   - alignment: an operand pointer (inputs, weights, outputs, gradients) needs the 4 bytes of its element type and no
+ *     more (2 for bf16 rows); the launchers look at every address and take scalar loads and stores, or the unfused route,
+ *     where an operand is not on a 16-byte boundary -- slower, the same results (tests/test_hip_pointer_alignment.py).
+ *     A WORKSPACE is different: every `ws` and `saved` pointer, and every pointer derived from one with a *_offset query
+ *     (xnrs_row_lists::qkv_shared), must be 256-byte aligned.  The library carves these buffers into regions aligned
+ *     relative to their base and its 16-byte vector kernels rely on that; the base itself is not checked.
  *   - process-global state (documented at its entry points, nothing else exists): the forward-GEMM
  *     arithmetic mode (xnrs_set_gemm_mode), the development knobs (xnrs_reload_knobs), the optional
  *     launch timer (xnrs_profile_*), the status word (xnrs_set_status_word) and that side stream.  Encode / score calls on different streams may run from different

@@ -86,7 +86,10 @@ Plan make_plan(int64_t n_seq, int L, int D, int A, int E, bool att, bool additiv
 
 bool device_counts_ok(const float* x, int D, int A, const xnrs_mha_params* att, const xnrs_additive_params* pool) {
   if (!knobs().gemm_buf || gemm_mode() != 0 || D % 4 != 0 || D < 4 || (A > 0 && A % 4 != 0)) return false;
-  if (!aligned16(x) || (pool && !aligned16(pool->w1))) return false;
+  // (w1_folded: the fc1 weight such a product reads instead of w1 when the call folds -- fc1_pair.  Asked about whether or not
+  // THIS call folds: a pair that is given but unused and sits off a 16-byte boundary costs the route, never a result -- the
+  // predicate stays a function of the operands alone, as its callers in both directions and the Python mirror have it)
+  if (!aligned16(x) || (pool && !(aligned16(pool->w1) && aligned16(pool->w1_folded)))) return false;
   if (att && !(aligned16(att->wq) && aligned16(att->wk) && aligned16(att->wv) && aligned16(att->wo))) return false;
   return (int64_t)D * D * 4 <= (1ll << 30) && (int64_t)A * D * 4 <= (1ll << 30);
 }
@@ -155,11 +158,12 @@ int32_t fc1_pair(bool fold, const xnrs_mha_params* att, const xnrs_additive_para
 }
 
 // the fused row dots ride on the raw-buffer-load forward kernel: 16-byte aligned operands
+// (w1 and the caller's w1_folded both, whichever the call will multiply by: see device_counts_ok)
 bool fc1_rowdot_ok(const float* x, bool att, const xnrs_additive_params* pool, int D) {
   // (rows of any count / any gather: beyond the 1-GB descriptor window or with row ids the launcher takes the
   // pointer-gather variant of the same kernel)
   return knobs().fc1_rowdot && knobs().gemm_buf && gemm_mode() == 0 && pool && pool->w2 && D % 4 == 0 && D >= 4 &&
-         aligned16(pool->w1) && (att || aligned16(x)) && (int64_t)pool->hidden * D * 4 <= (1ll << 30);
+         aligned16(pool->w1) && aligned16(pool->w1_folded) && (att || aligned16(x)) && (int64_t)pool->hidden * D * 4 <= (1ll << 30);
 }
 inline int n_epart(int A) { return (A + 31) / 32; }  // partial fc2 dots per row: one per 32 hidden columns
 
@@ -373,6 +377,9 @@ bool news_fused_route(const SeqEncode& r, const Plan& p, int A, bool fold, NewsF
   if (r.x16) {  // bf16 table: the kernel runs pass by pass on the widened rows and the gathered mask rows (run_one_launch)
     f->x = at(r.ws, p.off_x32); f->ids = nullptr; f->mask = at(r.ws, p.off_m32);
   }
+  // (fold with the caller's folded pair: prepare_weights hands the kernel THAT w1 -- its alignment is asked about here, before
+  // the route is taken, not by the launch)
+  if (fold && r.pool->w1_folded && !aligned16(r.pool->w1_folded)) return false;
   return p.off_nf != 0 && news_fused_ready(*f);
 }
 
@@ -1128,6 +1135,9 @@ int32_t xnrs_text_encoder_fwd_compact(const float* x, const float* m, const int3
   // the device row counts ride on the fp32 forward kernel with the fc2 dot in its epilogue (what the padded and the
   // host-compacted paths run too: the three stay bitwise equal)
   if (gemm_mode() != 0 || !fc1_rowdot_ok(x, att != nullptr, pool, D)) return XNRS_EUNSUPPORTED;
+  // ... and so do the projections: a product that reads its row count on the device has no scalar-load instantiation, its
+  // launch would fail on rows or a projection weight off a 16-byte boundary (the padded entry point serves those)
+  if (att && !(aligned16(x) && aligned16(att->wq) && aligned16(att->wk) && aligned16(att->wv))) return XNRS_EUNSUPPORTED;
   const CompactPlan p = make_compact_plan(n_news, S, D, A, E, att != nullptr, head != nullptr, chunk);
   if (!ws || ws_bytes < p.total) return XNRS_EWORKSPACE;
   float *kv = at(ws, p.off_kv), *qc = at(ws, p.off_q), *oc = at(ws, p.off_o), *tc = at(ws, p.off_t);

@@ -839,9 +839,10 @@ struct MhaPick {
 };
 static MhaPick mha_pick(const MhaCoreArgs& a) {
   MhaPick p{};
-  p.vec = (a.d_k % 4 == 0) && (a.ld % 4 == 0) && (a.ldo % 4 == 0) &&
-          ((reinterpret_cast<uintptr_t>(a.q) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.k) & 15) == 0) &&
-          ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
+  // every operand the vector instantiations touch 16 bytes at a time: the q, k and v rows (their (sequence, head) block starts
+  // at seq * seq_stride + head * head_stride) and the out rows
+  p.vec = (a.d_k % 4 == 0) && (a.ld % 4 == 0) && (a.ldo % 4 == 0) && (a.seq_stride % 4 == 0) && (a.head_stride % 4 == 0) &&
+          aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.out);
   p.KT = (a.S + 15) / 16;
   // knobs().mha_headwave / mha_lds: development knobs for A/B runs
   p.fast = p.vec && a.S <= 64 && a.d_k <= 64 && ((int64_t)a.S * a.ld < (1ll << 31)) && knobs().mha_headwave;

@@ -744,6 +744,7 @@ bool news_fused_ready(const NewsFusedArgs& a) {
   if (!news_fused_plan(a.S, a.D, a.n_heads, a.A, &p, npw) || a.d_k * a.n_heads != a.D) return false;
   if (!aligned16(a.x) || !aligned16(a.wq) || !aligned16(a.wk) || !aligned16(a.wv) || !aligned16(a.wo) || !aligned16(a.w1) || !a.img || !aligned16(a.img))
     return false;
+  if (!aligned16(a.p) || a.ldp % 4 != 0) return false;  // the pooled vectors leave as 16-byte stores (the caller's y without a head and a fold)
   if (a.fold && (!a.o_scratch || !a.asum || !aligned16(a.o_scratch))) return false;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return false;

@@ -262,6 +262,8 @@ def stream_ptr(device) -> C.c_void_p:
 
 
 _workspaces = {}
+#: what include/xnrs_hip.h asks of every `ws` / `saved` pointer (bytes)
+WORKSPACE_ALIGN = 256
 
 
 def workspace(device, nbytes: int) -> Optional[torch.Tensor]:
@@ -274,6 +276,10 @@ def workspace(device, nbytes: int) -> Optional[torch.Tensor]:
         buf = None
         _workspaces.pop(key, None)
         buf = torch.empty(int(nbytes * 1.05) + 256, dtype=torch.uint8, device=device)
+        # include/xnrs_hip.h, Conventions: the library carves a workspace into regions aligned RELATIVE to its base, and its
+        # 16-byte vector kernels rely on them (a fresh allocation of torch's caching allocator starts on 512 bytes)
+        if buf.data_ptr() % WORKSPACE_ALIGN:
+            raise XnrsHipError(f"workspace at {buf.data_ptr():#x} is not {WORKSPACE_ALIGN}-byte aligned")
         _workspaces[key] = buf
     return buf
 

@@ -129,7 +129,7 @@ class TextEncoder(_Tower):
         b, n, s, d = x.shape
         xf, mf = self._drop(x.reshape(b * n, s, d)), m.reshape(b * n, s, 1)
         encode = self._encoder_fn()
-        if encode is ops.text_encoder_unpadded and ops.COMPACT_ON_DEVICE and ops.compact_supported(s, d, self.att, self.pooler) \
+        if encode is ops.text_encoder_unpadded and ops.COMPACT_ON_DEVICE and ops.compact_supported(s, d, self.att, self.pooler, xf) \
                 and not (self.att is not None and self.att.training and self.att.dropout.p > 0):
             # the device-compacted padding-free encoder drops empty news by itself: no host-side list, no sync
             y, hm = encode(xf, mf, self)

@@ -336,10 +336,18 @@ def text_encoder_forward_compact(x: torch.Tensor, m: torch.Tensor, att, pooler, 
     return y, hm
 
 
-def compact_supported(S: int, D: int, att, pooler) -> bool:
-    """Mirror of the C entry point's preconditions that can be decided on the host without touching the data."""
+def compact_supported(S: int, D: int, att, pooler, x: Optional[torch.Tensor] = None) -> bool:
+    """Mirror of the C entry point's preconditions that can be decided on the host without touching the data.  x (optional):
+    the fp32 rows the call will be given -- the entry point's products read their row counts on the device and have no
+    scalar-load form, so it refuses rows, fc1 or Q/K/V weights off a 16-byte boundary (parameters viewed out of one flat
+    buffer); the caller then takes the host-compacted path, which serves them."""
     from .models.components import layers
     if not isinstance(pooler, layers.AdditiveAttention) or hip.get_gemm_mode() != 0 or D % 4 != 0 or S > 512:
+        return False
+    operands = [pooler.fc1.weight] + ([att.q_linear.weight, att.k_linear.weight, att.v_linear.weight] if att is not None else [])
+    if isinstance(x, torch.Tensor) and x.dtype == torch.float32:
+        operands.append(x)
+    if any(t.is_cuda and t.data_ptr() % 16 != 0 for t in operands):
         return False
     if os.environ.get("XNRS_FC1_ROWDOT", "1") == "0" or os.environ.get("XNRS_GEMM_BUF", "1") == "0":
         return False
@@ -977,7 +985,7 @@ def text_encoder_unpadded(x, m, enc, ids=None):
     supported = S <= 64 and D % 4 == 0 and (att is None or (dk <= 64 and dk % 4 == 0))
     if _needs_grad(x, enc) or p > 0.0 or not supported:
         return text_encoder(x, m, enc, ids=ids)
-    if COMPACT_ON_DEVICE and compact_supported(S, D, att, pooler):
+    if COMPACT_ON_DEVICE and compact_supported(S, D, att, pooler, x):
         # row lists built on the device: no host sync, capturable; all-masked news cost nothing (so skip_empty's host-side
         # compaction is not needed on top).  A device without room for its scratch falls back to the host-compacted path
         # (the same results) instead of failing: hip.release_workspaces() returns the scratch when eval and train alternate
