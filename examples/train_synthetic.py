@@ -3,10 +3,13 @@
 entirely on the device: resident news table -> device batch assembly -> forward_ids (id gather fused into the first
 GEMM) -> relu/MSE + lambda * fused InfoNCE -> hand-written HIP backward -> Adam -> device evaluation.
 
-    python examples/train_synthetic.py [--model NRMS|standard] [--steps 300] [--batch 64] [--bf16x3] [--full-table-loss]
+    python examples/train_synthetic.py [--model NRMS|standard] [--steps 300] [--batch 64] [--bf16x3]
+                                      [--full-table-loss | --mined-negatives M]
 
 --full-table-loss (off by default) trains with losses.full_table_loss instead: every clicked news of a session against ALL
 news of the table encoded in that step, the objective evaluate_full_ranking measures.
+--mined-negatives M (mutually exclusive with it) trains with losses.mined_negatives_loss: the same clicks against the M news
+of that table the session's user scores highest in that step (topk_deep mines them, the listed loss reads their rows in place).
 
 Synthetic click world (xnrs_amd.synth.click_world): news carry a topic direction in their tokens, a user clicks news of
 its own topic -- so the ranking metrics have to rise if the whole stack (forward, gradients, optimiser, evaluation) is
@@ -22,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from xnrs_amd import evaluation, hip, synth  # noqa: E402
 from xnrs_amd.data import DeviceBatcher  # noqa: E402
-from xnrs_amd.losses import contrastive_loss, full_table_loss  # noqa: E402
+from xnrs_amd.losses import contrastive_loss, full_table_loss, mined_negatives_loss  # noqa: E402
 from xnrs_amd.models import make_model  # noqa: E402
 
 
@@ -37,8 +40,12 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--hist", type=int, default=8)
     ap.add_argument("--bf16x3", action="store_true", help="forward GEMMs + dX products on the bf16 matrix cores (fp32-grade)")
-    ap.add_argument("--full-table-loss", action="store_true",
-                    help="train with the softmax ranking loss over the whole news table (losses.full_table_loss)")
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument("--full-table-loss", action="store_true",
+                       help="train with the softmax ranking loss over the whole news table (losses.full_table_loss)")
+    which.add_argument("--mined-negatives", type=int, default=0, metavar="M",
+                       help="train with the ranking loss over the M hardest negatives of each session, mined per step "
+                            "(losses.mined_negatives_loss, 1 <= M <= 1024)")
     args = ap.parse_args()
     dev = "cuda:0"
     if args.bf16x3:
@@ -61,6 +68,8 @@ def main():
         opt.zero_grad()
         if args.full_table_loss:
             loss = full_table_loss(model, store, beh, sess, args.hist)
+        elif args.mined_negatives:
+            loss = mined_negatives_loss(model, store, beh, sess, args.hist, n_negatives=args.mined_negatives)
         else:
             hist, cand, targets = batcher.train_batch(sess, n_neg=4, seed=step)
             r, u, _ = model.forward_ids(store.x, store.m, hist, cand, return_embeddings=True)

@@ -854,6 +854,68 @@ int32_t xnrs_table_loss_bwd(const float *table, int64_t n_rows, int32_t E, const
                             const float *lse, const float *g, float *d_up, float *d_table, void *ws, size_t ws_bytes,
                             void *stream);
 
+/* ---- the softmax ranking loss over per-user row LISTS: training against mined negatives (csrc/list_loss.hip) -----------------
+ * The same ranking_loss(p, n) with the L rows a caller LISTS per user as the negatives -- the lists xnrs_topk_deep returns
+ * (the m hardest negatives), sampled rows, stale lists -- forward and backward, without a (B, L, E) copy of the listed rows.
+ * The operands are the user side of xnrs_table_loss_*: table:(n_rows,E), up:(B,E) as the score reads it (u, or v = u W[0] of
+ * the bilinear scorer), bias: one float on the device or NULL, the target CSR tgt_off / tgt_rows (one query per entry; T =
+ * the entries of tgt_rows, T >= tgt_off[B]) and pad_row; plus neg_rows:(B,L) int32, row-major.  Scores s = <table[r], up[b]>
+ * (+ bias).
+ *   Negatives of user b: every slot j whose row neg_rows[b][j] is inside [0, n_rows), is not pad_row and equals no target row
+ *              of b (a user's own click is never their negative, as in the table loss).  Every other slot is EMPTY: the -1
+ *              fillers of xnrs_topk_deep, ids outside the table, the pad row, a target; such a row is compared, never
+ *              dereferenced.  neg_scores[b][j] = the score of a negative, NaN for an empty slot.  A ROW LISTED TWICE BY ONE
+ *              USER COUNTS TWICE: this is the reference's loss over a gathered list, and it differs here from the table
+ *              loss, where a row is a negative once.
+ *   Forward  : lse[b] = log sum_{filled slots} exp(s_bj), max-stabilised, -inf when the user has no negatives.  For query
+ *              e = (b, t): scores[e] = the raw score, loss[e] = logaddexp(s_bt, lse[b]) - s_bt.  Entries of scores / loss
+ *              outside [tgt_off[0], tgt_off[B]) are not written.
+ *   No answer: t outside the table or t == pad_row: scores[e] = NaN, loss[e] = 0, no gradient.
+ *   No negatives: loss = 0 exactly and every gradient of the user 0; no NaN.  L == 0: every user is one.
+ *   Backward : the formulas of the table loss above with "negative" = a filled slot: g[e] the upstream gradient per query,
+ *              c_b = sum_{e of b} g_e (1 - p_e); d s_bt = -g_e (1 - p_e); d s_bj = c_b exp(s_bj - lse[b]) per filled slot;
+ *              d_up[b] = sum over b's slots and queries of d s * table[row]; d_table[n] = sum over every slot and query
+ *              whose row is n of d s * up[b].  d_up:(B,E) and d_table:(n_rows,E) are OVERWRITTEN (rows that nothing lists
+ *              are exactly zero); either may be NULL, and then its launches are skipped.  scores, lse and neg_scores are
+ *              what the forward call over the same operands wrote.
+ *   order    : (B L + T) int32, NULL iff d_table is NULL (one without the other: XNRS_EINVAL): a permutation of the entries
+ *              -- slot (b, j) is entry b L + j, query e is entry B L + e -- sorted ascending by row, ties in ascending
+ *              entry index, with every entry that has no row to give a gradient to (an empty slot, a query without an
+ *              answer: NaN in neg_scores / scores) behind all others.  A query of a user WITHOUT NEGATIVES has a score and
+ *              is sorted by its row like any other; it adds exactly 0 to that row.  The caller builds it (a stable sort of the row keys; xnrs_amd/ops.py: list_loss_backward); the
+ *              kernel walks the runs of equal rows in its first B L + tgt_off[B] positions.  A value outside [0, B L + T) is
+ *              skipped and never dereferenced.  An order that is NOT grouped by row gives unspecified gradients for the
+ *              rows concerned and nothing worse: no access outside the operands.
+ *   Precondition: table and up are finite; B (L + 1) <= 2^31 - 1 and n_rows <= 2^31 - 1 (else XNRS_EINVAL).
+ * Launches: forward 1 (a workgroup of four waves per user: a wave gathers four listed rows at a time against the user
+ * vector in LDS, then the workgroup folds max and sum exp over the slots and scores the user's queries).  d_up 1 (the same
+ * walk, d s * table[row] summed per wave in slot order, the four waves in wave order).  d_table 4 (c_b per user; the zero
+ * fill; the walk: the sorted positions are cut into G <= 8192 equal spans, a wave takes its span 64 positions at
+ * a time, decodes them with a lane per position and adds d s * up[b] in sorted order -- a run of equal rows inside a span is stored at
+ * once, the first and the last run of a span go to the workspace; the join adds the parts of a run that crosses span
+ * bounds in ascending span order).  A row that every user lists is summed by as many waves as its run touches spans.
+ * Determinism: scores, neg_scores, lse, loss and d_up of a user are the same bits on every run and depend neither on B
+ * nor on the user's position in the batch: one workgroup owns the user and every reduction tree is fixed by the slot
+ * position.  d_table is the same bits on every run of the same call; its summation order follows the sorted order and the
+ * span cut, so it MAY differ in the last bits between batches.  The 16-byte and the scalar load forms add the same elements
+ * in the same order: the alignment of an operand does not change a bit.  No float atomics, results cross launches at
+ * kernel boundaries only, no host synchronisation, no allocation, hipGraph-capturable.  XNRS_EINVAL (L < 0, E < 1, a NULL
+ * required pointer, order and d_table not NULL together) and XNRS_EWORKSPACE are found on the host before any launch and
+ * write nothing.  B == 0: XNRS_OK, nothing written.  Any E >= 1, any operand alignment its element type allows (E % 4 != 0
+ * or a base off the 16-byte boundary takes scalar loads).
+ * ws: xnrs_list_loss_workspace_bytes(B, L, T, E, want_d_table), a pure host call: 0 for the forward and for d_up alone (ws
+ * may then be NULL); with d_table 4 B + 8 G E + 8 G bytes, G = min(8192, ceil(B (L + 1) / 64)), each region rounded up to
+ * 256 B -- 1/32 of the (B, L, E) copy or less.  (T does not enter: the spans are cut on the device.) */
+size_t xnrs_list_loss_workspace_bytes(int64_t B, int32_t L, int64_t T, int32_t E, int32_t want_d_table);
+int32_t xnrs_list_loss_fwd(const float *table, int64_t n_rows, int32_t E, const float *up, const float *bias, int64_t B,
+                           const int64_t *tgt_off, const int32_t *tgt_rows, const int32_t *neg_rows, int32_t L,
+                           int32_t pad_row, float *scores, float *loss, float *lse, float *neg_scores, void *ws,
+                           size_t ws_bytes, void *stream);
+int32_t xnrs_list_loss_bwd(const float *table, int64_t n_rows, int32_t E, const float *up, const float *bias, int64_t B,
+                           const int64_t *tgt_off, const int32_t *tgt_rows, const int32_t *neg_rows, int32_t L,
+                           int32_t pad_row, const float *scores, const float *lse, const float *neg_scores, const float *g,
+                           const int32_t *order, float *d_up, float *d_table, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

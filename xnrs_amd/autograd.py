@@ -785,6 +785,43 @@ def table_loss(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_l
     return _TableLoss.apply(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias)
 
 
+class _ListLoss(torch.autograd.Function):
+    """ops.list_loss: the softmax ranking loss over per-user row lists (xnrs_list_loss_fwd / _bwd).  What is saved beside the
+    operands is per query, per user and per slot -- the slot scores, never the listed rows."""
+
+    @staticmethod
+    def forward(ctx, table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias):
+        from . import ops
+        table = hip.dev_f32(table, "news vectors")
+        up_shape = tuple(up.shape)
+        up = hip.dev_f32(up, "user vectors").reshape(-1, table.shape[-1])
+        with torch.no_grad():
+            loss, scores, lse, neg_scores = ops.list_loss_forward(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)
+        ctx.save_for_backward(table, up, scores, lse, neg_scores)
+        ctx.rest = (tgt_off, tgt_rows, neg_rows, int(pad_row), None if bias is None else bias.detach())
+        ctx.up_shape = up_shape
+        ctx.is_tensor = [isinstance(t, torch.Tensor) for t in (table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)]
+        ctx.mark_non_differentiable(scores, lse, neg_scores)
+        return loss, scores, lse, neg_scores
+
+    @staticmethod
+    def backward(ctx, g, _g_scores, _g_lse, _g_neg):
+        from . import ops
+        table, up, scores, lse, neg_scores = ctx.saved_tensors
+        tgt_off, tgt_rows, neg_rows, pad_row, bias = ctx.rest
+        wanted = _wanted_inputs(ctx, ctx.is_tensor, 0)  # (torch.autograd.grad(inputs=[u]) alone: the table's launches are not run)
+        d_up, d_table = ops.list_loss_backward(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias, scores, lse, neg_scores, g,
+                                               want_d_up=ctx.needs_input_grad[1] and wanted[1],
+                                               want_d_table=ctx.needs_input_grad[0] and wanted[0])
+        if d_up is not None:
+            d_up = d_up.reshape(ctx.up_shape)
+        return d_table, d_up, None, None, None, None, None
+
+
+def list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias):
+    return _ListLoss.apply(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)
+
+
 class _BilinScoring(torch.autograd.Function):
     """BilinScoring (scoring.py:41-66): backward G_b = sum_n g_bn c^_bn, dW[0] = U^^T G, du^_b = W[0] G_b, dc^_bn = g_bn v_b,
     dbias = sum g (then through the normalisation when it is on)."""

@@ -1,0 +1,582 @@
+// The softmax ranking loss over per-user row LISTS (xnrs_list_loss_fwd / _bwd, include/xnrs_hip.h): the reference's
+// ranking_loss(p, n) with the m negatives a caller lists per user (mined by xnrs_topk_deep, sampled, stale) instead of the
+// whole table, forward and backward, without a (B, L, E) copy of the listed rows.
+//
+// The work is a row gather with no reuse across users (every user lists other rows), so it is VALU work, not MFMA:
+//   forward : one workgroup of 4 waves per user.  A wave takes 4 slots at a time, gathers the 4 table rows (16-byte loads
+//             per lane where the operands allow it) against the user vector in LDS and reduces each dot product with a
+//             butterfly; the scores go to neg_scores, then the workgroup folds max and sum exp over the L slots and the
+//             waves score the user's queries.
+//   d_up    : the same walk; a wave adds ds * table[row] for its slots in ascending slot order, the four wave partials
+//             are added in wave order through LDS.
+//   d_table : `order` lists the entries (slots, then queries) grouped by row.  The sorted positions are cut into G equal
+//             spans, one wave per span (G <= LL_SPANS, the cut is computed on the device from the position count).  A wave
+//             takes its span in pieces of 64 positions and decodes a piece with one lane per position (entry -> row, user, ds), then
+//             walks it: it adds ds * up[user] in order and stores the sum whenever the row changes.  A run of equal rows
+//             that lies inside a span is stored straight into d_table; the first and the last run of a span may continue
+//             in the neighbours, so they go to the workspace (one head and one tail row per span), and a second launch
+//             adds the pieces of every such run in ascending span order.  However long a run is -- a popular news listed
+//             by every user of the batch -- it is cut at the span bounds and summed by as many waves as it touches.
+// Every sum has one fixed order (slot position, wave index, sorted position, span index): no float atomics, the same
+// bits on every run; scores, lse, loss and d_up of a user depend on nothing but that user's operands.
+// The scalar-load forms (E % 4 != 0 or a base off the 16-byte boundary) give a lane the SAME elements in the same order
+// as the 16-byte forms, so both produce the same bits.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "host.h"
+
+namespace xnrs {
+
+namespace {
+
+constexpr int LL_THREADS = 256;     // 4 waves per workgroup
+constexpr int LL_WAVES = LL_THREADS / 64;
+constexpr int LL_UNROLL = 4;        // slots / positions a wave has in flight
+constexpr int LL_UP_LDS = 4096;     // floats of a user vector kept in LDS (longer ones are read from global memory)
+constexpr int LL_PIECE = 64;        // sorted positions a wave decodes at once, one per lane
+constexpr int LL_SPANS = 8192;      // most spans (waves) of the d_table walk
+constexpr int LL_NO_RUN = -2;       // tail_row of a span that is one run (or empty); -1 is the "row" of entries without a gradient
+
+struct ListArgs {
+  const float* table;
+  const float* up;
+  const float* bias;
+  int64_t n_rows;
+  int E;
+  int64_t B;
+  const int64_t* tgt_off;
+  const int32_t* tgt_rows;
+  const int32_t* neg_rows;
+  int L;
+  int pad_row;
+  float* scores;      // (T)
+  float* lse;         // (B)
+  float* neg_scores;  // (B, L)
+};
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+
+// the four floats [i, i + 4) of a row of E floats; beyond E: 0.  VEC: one 16-byte load (E % 4 == 0, aligned base)
+template <bool VEC>
+__device__ __forceinline__ float4 load4(const float* __restrict__ p, int i, int E) {
+  if constexpr (VEC) {
+    return *reinterpret_cast<const float4*>(p + i);
+  } else {
+    float4 v;
+    v.x = i < E ? p[i] : 0.f;
+    v.y = i + 1 < E ? p[i + 1] : 0.f;
+    v.z = i + 2 < E ? p[i + 2] : 0.f;
+    v.w = i + 3 < E ? p[i + 3] : 0.f;
+    return v;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float* __restrict__ p, int i, int E, float4 v) {
+  if constexpr (VEC) {
+    *reinterpret_cast<float4*>(p + i) = v;
+  } else {
+    if (i < E) p[i] = v.x;
+    if (i + 1 < E) p[i + 1] = v.y;
+    if (i + 2 < E) p[i + 2] = v.z;
+    if (i + 3 < E) p[i + 3] = v.w;
+  }
+}
+__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
+  acc = fmaf(a.x, b.x, acc);
+  acc = fmaf(a.y, b.y, acc);
+  acc = fmaf(a.z, b.z, acc);
+  return fmaf(a.w, b.w, acc);
+}
+__device__ __forceinline__ void axpy4(float4& acc, float s, float4 x) {
+  acc.x = fmaf(s, x.x, acc.x);
+  acc.y = fmaf(s, x.y, acc.y);
+  acc.z = fmaf(s, x.z, acc.z);
+  acc.w = fmaf(s, x.w, acc.w);
+}
+
+// is row r one of the n rows at t?  (all lanes of the wave call it with the same arguments)
+__device__ __forceinline__ bool wave_listed(const int32_t* __restrict__ t, int64_t n, int r, int lane) {
+  bool hit = false;
+  for (int64_t k = lane; k < n; k += 64) hit |= t[k] == r;
+  return __any(hit);
+}
+
+// logaddexp(s, l) - s for finite s and finite l
+__device__ __forceinline__ float loss_of(float s, float l) {
+  const float d = l - s;
+  return d <= 0.f ? log1pf(expf(d)) : d + log1pf(expf(-d));
+}
+// 1 - p = sigmoid(l - s), p = exp(s - logaddexp(s, l))
+__device__ __forceinline__ float one_minus_p(float s, float l) {
+  const float d = s - l;
+  if (d >= 0.f) {
+    const float t = expf(-d);
+    return t / (1.f + t);
+  }
+  return 1.f / (1.f + expf(d));
+}
+// c_b = sum_{e of b} g_e (1 - p_e) in query order; 0 for a user without negatives
+__device__ __forceinline__ float user_coef(const ListArgs& a, const float* __restrict__ g, int64_t b) {
+  const float l = a.lse[b];
+  if (!(l > -INFINITY)) return 0.f;
+  float c = 0.f;
+  for (int64_t e = a.tgt_off[b]; e < a.tgt_off[b + 1]; ++e) {
+    const float s = a.scores[e];
+    if (s == s) c += g[e] * one_minus_p(s, l);
+  }
+  return c;
+}
+
+// the user vector of the workgroup: in LDS up to LL_UP_LDS floats, else where it lies
+template <bool VEC>
+__device__ __forceinline__ float4 up4(const float* __restrict__ s_up, const float* __restrict__ g_up, int i, int E) {
+  if (E <= LL_UP_LDS) return load4<VEC>(s_up, i, E);
+  return load4<VEC>(g_up, i, E);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- forward
+template <bool VEC>
+__global__ __launch_bounds__(LL_THREADS) void ll_fwd_kernel(ListArgs a, float* __restrict__ loss) {
+  __shared__ __attribute__((aligned(16))) float s_up[LL_UP_LDS];
+  __shared__ float s_red[LL_WAVES];
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int E = a.E, L = a.L;
+  const float* __restrict__ gu = a.up + b * E;
+  if (E <= LL_UP_LDS)
+    for (int i = tid; i < E; i += LL_THREADS) s_up[i] = gu[i];
+  __syncthreads();
+  const float bias = a.bias ? a.bias[0] : 0.f;
+  const int64_t t0 = a.tgt_off[b], t1 = a.tgt_off[b + 1];
+  const int32_t* __restrict__ rows = a.neg_rows + b * (int64_t)L;
+  float* ns = a.neg_scores + b * (int64_t)L;  // (written here and read back behind the barrier)
+
+  // the slots: wave w takes the groups of LL_UNROLL slots w, w + LL_WAVES, ...
+  for (int j0 = wave * LL_UNROLL; j0 < L; j0 += LL_WAVES * LL_UNROLL) {
+    int r[LL_UNROLL];
+    bool ok[LL_UNROLL];
+    float acc[LL_UNROLL];
+#pragma unroll
+    for (int q = 0; q < LL_UNROLL; ++q) {
+      const int j = j0 + q;
+      r[q] = j < L ? rows[j] : -1;
+      ok[q] = r[q] >= 0 && r[q] < a.n_rows && r[q] != a.pad_row;
+      if (ok[q]) ok[q] = !wave_listed(a.tgt_rows + t0, t1 - t0, r[q], lane);
+      acc[q] = 0.f;
+    }
+    for (int i = lane * 4; i < E; i += 256) {
+      const float4 u = up4<VEC>(s_up, gu, i, E);
+      float4 x[LL_UNROLL];
+#pragma unroll
+      for (int q = 0; q < LL_UNROLL; ++q)
+        x[q] = ok[q] ? load4<VEC>(a.table + (int64_t)r[q] * E, i, E) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int q = 0; q < LL_UNROLL; ++q) acc[q] = dot4(x[q], u, acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < LL_UNROLL; ++q) {
+      const float s = wave_sum(acc[q]) + bias;
+      if (lane == 0 && j0 + q < L) ns[j0 + q] = ok[q] ? s : NAN;
+    }
+  }
+  __syncthreads();  // (the slot scores of the workgroup are visible to all its threads)
+
+  // lse over the filled slots: thread t folds the slots t, t + 256, ... in ascending order, then the fixed tree
+  float m = -INFINITY;
+  for (int j = tid; j < L; j += LL_THREADS) {
+    const float s = ns[j];
+    if (s == s) m = fmaxf(m, s);
+  }
+  m = wave_max(m);
+  if (lane == 0) s_red[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  __syncthreads();
+  float sum = 0.f;
+  if (m > -INFINITY)
+    for (int j = tid; j < L; j += LL_THREADS) {
+      const float s = ns[j];
+      if (s == s) sum += expf(s - m);
+    }
+  sum = wave_sum(sum);
+  if (lane == 0) s_red[wave] = sum;
+  __syncthreads();
+  sum = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+  const float lse = m > -INFINITY ? m + logf(sum) : -INFINITY;
+  if (tid == 0) a.lse[b] = lse;
+
+  // the queries of the user: one wave per query
+  for (int64_t e = t0 + wave; e < t1; e += LL_WAVES) {
+    const int t = a.tgt_rows[e];
+    const bool ok = t >= 0 && t < a.n_rows && t != a.pad_row;
+    float acc = 0.f;
+    if (ok)
+      for (int i = lane * 4; i < E; i += 256) acc = dot4(load4<VEC>(a.table + (int64_t)t * E, i, E), up4<VEC>(s_up, gu, i, E), acc);
+    const float s = wave_sum(acc) + bias;
+    if (lane == 0) {
+      a.scores[e] = ok ? s : NAN;
+      loss[e] = ok && lse > -INFINITY ? loss_of(s, lse) : 0.f;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ d_up
+template <bool VEC>
+__global__ __launch_bounds__(LL_THREADS) void ll_dup_kernel(ListArgs a, const float* __restrict__ g, float* __restrict__ d_up) {
+  __shared__ __attribute__((aligned(16))) float s_part[LL_WAVES][256];
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int E = a.E, L = a.L;
+  const float lse = a.lse[b];
+  const float c = user_coef(a, g, b);  // (every thread the same sum in the same order)
+  const int64_t t0 = a.tgt_off[b], t1 = a.tgt_off[b + 1];
+  const int32_t* __restrict__ rows = a.neg_rows + b * (int64_t)L;
+  const float* __restrict__ ns = a.neg_scores + b * (int64_t)L;
+  for (int i0 = 0; i0 < E; i0 += 256) {  // 256 features per pass, four per lane
+    const int i = i0 + lane * 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c != 0.f)
+      for (int j0 = wave * LL_UNROLL; j0 < L; j0 += LL_WAVES * LL_UNROLL) {
+        float ds[LL_UNROLL];
+        float4 x[LL_UNROLL];
+#pragma unroll
+        for (int q = 0; q < LL_UNROLL; ++q) {
+          const int j = j0 + q;
+          const float s = j < L ? ns[j] : NAN;
+          const int r = j < L ? rows[j] : -1;
+          const bool ok = s == s && r >= 0 && r < a.n_rows;
+          ds[q] = ok ? c * expf(s - lse) : 0.f;
+          x[q] = ok && i < E ? load4<VEC>(a.table + (int64_t)r * E, i, E) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int q = 0; q < LL_UNROLL; ++q) axpy4(acc, ds[q], x[q]);
+      }
+    if (lse > -INFINITY)
+      for (int64_t e = t0 + wave; e < t1; e += LL_WAVES) {
+        const float s = a.scores[e];
+        const int t = a.tgt_rows[e];
+        if (s == s && t >= 0 && t < a.n_rows && i < E)
+          axpy4(acc, -g[e] * one_minus_p(s, lse), load4<VEC>(a.table + (int64_t)t * E, i, E));
+      }
+    *reinterpret_cast<float4*>(&s_part[wave][lane * 4]) = acc;
+    __syncthreads();
+    if (wave == 0 && i < E) {
+      float4 r = *reinterpret_cast<const float4*>(&s_part[0][lane * 4]);
+#pragma unroll
+      for (int w = 1; w < LL_WAVES; ++w) {
+        const float4 p = *reinterpret_cast<const float4*>(&s_part[w][lane * 4]);
+        r.x += p.x;
+        r.y += p.y;
+        r.z += p.z;
+        r.w += p.w;
+      }
+      store4<VEC>(d_up + b * E, i, E, r);
+    }
+    __syncthreads();
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- d_table
+__global__ __launch_bounds__(LL_THREADS) void ll_coef_kernel(ListArgs a, const float* __restrict__ g, float* __restrict__ coef) {
+  const int64_t b = (int64_t)blockIdx.x * LL_THREADS + threadIdx.x;
+  if (b < a.B) coef[b] = user_coef(a, g, b);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(LL_THREADS) void ll_zero_kernel(float* __restrict__ p, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * LL_THREADS;
+  if constexpr (VEC) {
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
+    for (int64_t i = (int64_t)blockIdx.x * LL_THREADS + threadIdx.x; i < n / 4; i += stride) p4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * LL_THREADS + threadIdx.x; i < n; i += stride) p[i] = 0.f;
+  }
+}
+
+struct WalkArgs {
+  ListArgs a;
+  const float* g;
+  const int32_t* order;
+  const float* coef;  // (B)
+  float* d_table;
+  float* head;        // (G, E): the sum of the first run of every span
+  float* tail;        // (G, E): the sum of its last run, when that is another one
+  int32_t* head_row;  // (G): the row of the first run; -1: none
+  int32_t* tail_row;  // (G): the row of the last run; LL_NO_RUN: the span is one run (or empty)
+  int G;
+};
+
+// the positions that can carry a gradient: every slot and the queries up to tgt_off[B]
+__device__ __forceinline__ int64_t walk_positions(const ListArgs& a) { return a.B * (int64_t)a.L + a.tgt_off[a.B]; }
+// positions per span: an even share, the same for every span (a span is walked in pieces of LL_PIECE positions from its
+// first one; it need not be a whole number of them, so no span stays empty while another holds two pieces)
+__device__ __forceinline__ int64_t walk_span(int64_t M, int G) { return (M + G - 1) / G; }
+
+template <bool VEC>
+__global__ __launch_bounds__(LL_THREADS) void ll_walk_kernel(WalkArgs w) {
+  const ListArgs& a = w.a;
+  const int lane = threadIdx.x & 63;
+  const int span_id = blockIdx.x * LL_WAVES + (threadIdx.x >> 6);
+  if (span_id >= w.G) return;
+  const int E = a.E;
+  const int64_t slots = a.B * (int64_t)a.L;
+  const int64_t q0 = a.tgt_off[0], q1 = a.tgt_off[a.B];
+  const int64_t M = walk_positions(a), span = walk_span(M, w.G);
+  const int64_t lo = span_id * span, hi = lo + span < M ? lo + span : M;
+  float* __restrict__ head = w.head + (int64_t)span_id * E;
+  float* __restrict__ tail = w.tail + (int64_t)span_id * E;
+
+  int first_row = -1, last_row = LL_NO_RUN;
+  for (int i0 = 0; i0 < E; i0 += 256) {  // 256 features per pass, four per lane
+    const int i = i0 + lane * 4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int cur = -1;          // the row of the running sum; -1: entries without a gradient
+    bool started = false;  // cur is the row of a position of the span
+    bool first = true;     // the running sum is the first run of the span
+    first_row = -1;
+    last_row = LL_NO_RUN;
+    for (int64_t p0 = lo; p0 < hi; p0 += LL_PIECE) {
+      // decode: lane k holds position p0 + k
+      int row = -1, user = 0;
+      float ds = 0.f;
+      const int64_t p = p0 + lane;
+      if (p < hi) {
+        const int64_t v = w.order[p];
+        if (v >= 0 && v < slots) {
+          const float s = a.neg_scores[v];
+          const int r = a.neg_rows[v];
+          if (s == s && r >= 0 && r < a.n_rows) {
+            user = (int)(v / a.L);
+            row = r;
+            ds = w.coef[user] * expf(s - a.lse[user]);
+          }
+        } else if (v >= slots + q0 && v < slots + q1) {
+          const int64_t e = v - slots;
+          const float s = a.scores[e];
+          const int r = a.tgt_rows[e];
+          if (s == s && r >= 0 && r < a.n_rows) {
+            int64_t l = 0, h = a.B;  // the user of query e: the last b with tgt_off[b] <= e
+            while (h - l > 1) {
+              const int64_t mid = (l + h) >> 1;
+              if (a.tgt_off[mid] <= e) l = mid; else h = mid;
+            }
+            // (a user without negatives passes no gradient, but its query is sorted by its row like any other and lies
+            // INSIDE the run of that row: it stays an entry of the run with ds = 0, or it would cut the run in two)
+            const float lse = a.lse[l];
+            user = (int)l;
+            row = r;
+            ds = lse > -INFINITY ? -w.g[e] * one_minus_p(s, lse) : 0.f;
+          }
+        }
+      }
+      const int n = (int)(hi - p0 < LL_PIECE ? hi - p0 : LL_PIECE);
+      for (int k0 = 0; k0 < n; k0 += LL_UNROLL) {
+        int rk[LL_UNROLL];
+        float dk[LL_UNROLL];
+        float4 x[LL_UNROLL];
+#pragma unroll
+        for (int q = 0; q < LL_UNROLL; ++q) {  // (lanes past n decoded to row -1, ds 0, user 0)
+          const int k = (k0 + q) & 63;
+          rk[q] = __shfl(row, k);
+          dk[q] = __shfl(ds, k);
+          const int uk = __shfl(user, k);
+          x[q] = rk[q] >= 0 && i < E ? load4<VEC>(a.up + (int64_t)uk * E, i, E) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int q = 0; q < LL_UNROLL; ++q) {
+          if (k0 + q >= n) break;
+          if (!started) {
+            cur = rk[q];
+            started = true;
+          } else if (rk[q] != cur) {  // the run ends: store its sum
+            if (first) {
+              if (i < E) store4<VEC>(head, i, E, acc);
+              first_row = cur;
+              first = false;
+            } else if (cur >= 0 && i < E) {
+              store4<VEC>(w.d_table + (int64_t)cur * E, i, E, acc);
+            }
+            acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            cur = rk[q];
+          }
+          axpy4(acc, dk[q], x[q]);
+        }
+      }
+    }
+    if (first) {
+      if (i < E) store4<VEC>(head, i, E, acc);
+      first_row = cur;
+    } else {
+      if (i < E) store4<VEC>(tail, i, E, acc);
+      last_row = cur;
+    }
+  }
+  if (lane == 0) {
+    w.head_row[span_id] = first_row;
+    w.tail_row[span_id] = last_row;
+  }
+}
+
+// One wave per span: the first and the last run of the span, when they BEGIN in it, are summed over the spans they continue
+// in, in ascending span order, and stored.  (A first run that continues the span before belongs to the wave of the span it
+// began in.)
+template <bool VEC>
+__global__ __launch_bounds__(LL_THREADS) void ll_join_kernel(WalkArgs w) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * LL_WAVES + (threadIdx.x >> 6);
+  if (s >= w.G) return;
+  const int E = w.a.E;
+  const int hr = w.head_row[s], tr = w.tail_row[s];
+  // the last row of the span before: the head run continues it when the rows are equal
+  int prev = -1;
+  if (s > 0) prev = w.tail_row[s - 1] != LL_NO_RUN ? w.tail_row[s - 1] : w.head_row[s - 1];
+  // candidates: the head run when it begins here, the tail run (it always begins here)
+  for (int which = 0; which < 2; ++which) {
+    const int row = which == 0 ? hr : tr;
+    if (row < 0 || row >= w.a.n_rows) continue;
+    if (which == 0 && s > 0 && prev == row) continue;      // begun in an earlier span: that span's wave sums it
+    const bool reaches_end = which == 1 || tr == LL_NO_RUN;  // a head run with a tail behind it ends inside the span
+    const float* __restrict__ src = (which == 0 ? w.head : w.tail) + (int64_t)s * E;
+    for (int i = lane * 4; i < E; i += 256) {
+      float4 acc = load4<VEC>(src, i, E);
+      if (reaches_end)
+        for (int q = s + 1; q < w.G && w.head_row[q] == row; ++q) {
+          const float4 p = load4<VEC>(w.head + (int64_t)q * E, i, E);
+          acc.x += p.x;
+          acc.y += p.y;
+          acc.z += p.z;
+          acc.w += p.w;
+          if (w.tail_row[q] != LL_NO_RUN) break;  // the run ended inside span q
+        }
+      store4<VEC>(w.d_table + (int64_t)row * E, i, E, acc);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host
+int ll_spans(int64_t B, int L) {
+  const int64_t pieces = (B * ((int64_t)L + 1) + LL_PIECE - 1) / LL_PIECE;
+  return (int)(pieces < 1 ? 1 : pieces > LL_SPANS ? LL_SPANS : pieces);
+}
+
+struct WalkRegions {
+  size_t coef, head, tail, head_row, tail_row, total;
+};
+WalkRegions ll_carve(int64_t B, int L, int E, bool want_d_table) {
+  Carver c;
+  WalkRegions r{};
+  const int G = ll_spans(B, L);
+  r.coef = c.take_if(want_d_table, (size_t)B * F32);
+  r.head = c.take_if(want_d_table, (size_t)G * E * F32);
+  r.tail = c.take_if(want_d_table, (size_t)G * E * F32);
+  r.head_row = c.take_if(want_d_table, (size_t)G * sizeof(int32_t));
+  r.tail_row = c.take_if(want_d_table, (size_t)G * sizeof(int32_t));
+  r.total = c.total();
+  return r;
+}
+
+bool ll_shape_ok(int64_t B, int L, int64_t n_rows, int E) {
+  return B >= 0 && L >= 0 && n_rows >= 0 && n_rows <= INT32_MAX && E >= 1 && B <= INT32_MAX &&
+         B * ((int64_t)L + 1) <= (int64_t)INT32_MAX;
+}
+
+}  // namespace
+
+}  // namespace xnrs
+
+using namespace xnrs;
+
+extern "C" {
+
+size_t xnrs_list_loss_workspace_bytes(int64_t B, int32_t L, int64_t T, int32_t E, int32_t want_d_table) {
+  (void)T;  // (the spans of the d_table walk are cut on the device; their number follows B and L alone)
+  if (B < 0 || L < 0 || E < 1) return 0;
+  return ll_carve(B, L, E, want_d_table != 0).total;
+}
+
+int32_t xnrs_list_loss_fwd(const float* table, int64_t n_rows, int32_t E, const float* up, const float* bias, int64_t B,
+                           const int64_t* tgt_off, const int32_t* tgt_rows, const int32_t* neg_rows, int32_t L, int32_t pad_row,
+                           float* scores, float* loss, float* lse, float* neg_scores, void* ws, size_t ws_bytes, void* stream) {
+  (void)ws;
+  (void)ws_bytes;  // (the forward needs no workspace)
+  if (!ll_shape_ok(B, L, n_rows, E)) return XNRS_EINVAL;
+  if (B == 0) return XNRS_OK;
+  if (!up || !tgt_off || !tgt_rows || !scores || !loss || !lse || (n_rows > 0 && !table) || (L > 0 && (!neg_rows || !neg_scores)))
+    return XNRS_EINVAL;
+  const ListArgs a{table, up, bias, n_rows, E, B, tgt_off, tgt_rows, neg_rows, L, pad_row, scores, lse, neg_scores};
+  const bool vec = E % 4 == 0 && aligned16(table) && aligned16(up);
+  if (vec)
+    ll_fwd_kernel<true><<<dim3((unsigned)B), LL_THREADS, 0, (hipStream_t)stream>>>(a, loss);
+  else
+    ll_fwd_kernel<false><<<dim3((unsigned)B), LL_THREADS, 0, (hipStream_t)stream>>>(a, loss);
+  return hip_rc(hipGetLastError());
+}
+
+int32_t xnrs_list_loss_bwd(const float* table, int64_t n_rows, int32_t E, const float* up, const float* bias, int64_t B,
+                           const int64_t* tgt_off, const int32_t* tgt_rows, const int32_t* neg_rows, int32_t L, int32_t pad_row,
+                           const float* scores, const float* lse, const float* neg_scores, const float* g, const int32_t* order,
+                           float* d_up, float* d_table, void* ws, size_t ws_bytes, void* stream) {
+  if (!ll_shape_ok(B, L, n_rows, E)) return XNRS_EINVAL;
+  if ((order == nullptr) != (d_table == nullptr)) return XNRS_EINVAL;
+  if (B == 0) return XNRS_OK;
+  if (!up || !tgt_off || !tgt_rows || !scores || !lse || !g || (n_rows > 0 && !table) || (L > 0 && (!neg_rows || !neg_scores)))
+    return XNRS_EINVAL;
+  const WalkRegions r = ll_carve(B, L, E, d_table != nullptr);
+  if (r.total > 0 && (!ws || ws_bytes < r.total)) return XNRS_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const ListArgs a{table, up, bias, n_rows, E, B, tgt_off, tgt_rows, neg_rows, L, pad_row, const_cast<float*>(scores),
+                   const_cast<float*>(lse), const_cast<float*>(neg_scores)};
+  if (d_up) {
+    const bool vec = E % 4 == 0 && aligned16(table) && aligned16(d_up);
+    if (vec)
+      ll_dup_kernel<true><<<dim3((unsigned)B), LL_THREADS, 0, st>>>(a, g, d_up);
+    else
+      ll_dup_kernel<false><<<dim3((unsigned)B), LL_THREADS, 0, st>>>(a, g, d_up);
+    XNRS_TRY(hipGetLastError());
+  }
+  if (d_table && n_rows > 0) {
+    const int G = ll_spans(B, L);
+    const WalkArgs w{a, g, order, at<float>(ws, r.coef), d_table, at<float>(ws, r.head), at<float>(ws, r.tail),
+                     at<int32_t>(ws, r.head_row), at<int32_t>(ws, r.tail_row), G};
+    ll_coef_kernel<<<dim3((unsigned)((B + LL_THREADS - 1) / LL_THREADS)), LL_THREADS, 0, st>>>(a, g, at<float>(ws, r.coef));
+    XNRS_TRY(hipGetLastError());
+    const int64_t n = n_rows * (int64_t)E;
+    const bool zvec = n % 4 == 0 && aligned16(d_table);
+    const int64_t zitems = zvec ? n / 4 : n;
+    const unsigned zgrid = (unsigned)std::min<int64_t>((zitems + LL_THREADS - 1) / LL_THREADS, 8192);
+    if (zvec)
+      ll_zero_kernel<true><<<dim3(zgrid ? zgrid : 1), LL_THREADS, 0, st>>>(d_table, n);
+    else
+      ll_zero_kernel<false><<<dim3(zgrid ? zgrid : 1), LL_THREADS, 0, st>>>(d_table, n);
+    XNRS_TRY(hipGetLastError());
+    // (head / tail rows of the workspace are 256-byte aligned and E % 4 == 0 keeps every row of them on 16 bytes)
+    const bool vec = E % 4 == 0 && aligned16(up) && aligned16(d_table) && aligned16(ws);
+    const unsigned grid = (unsigned)((G + LL_WAVES - 1) / LL_WAVES);
+    if (vec) {
+      ll_walk_kernel<true><<<dim3(grid), LL_THREADS, 0, st>>>(w);
+      XNRS_TRY(hipGetLastError());
+      ll_join_kernel<true><<<dim3(grid), LL_THREADS, 0, st>>>(w);
+    } else {
+      ll_walk_kernel<false><<<dim3(grid), LL_THREADS, 0, st>>>(w);
+      XNRS_TRY(hipGetLastError());
+      ll_join_kernel<false><<<dim3(grid), LL_THREADS, 0, st>>>(w);
+    }
+    XNRS_TRY(hipGetLastError());
+  }
+  return XNRS_OK;
+}
+
+}  // extern "C"

@@ -2,7 +2,9 @@
 ContrastiveRankingTrainer._compute_contrastive_loss (xnrs/training.py:433-472) as ONE fused HIP forward +
 ONE fused backward instead of a Python loop over the batch rows; and the full-table softmax ranking loss -- the reference's
 ranking_loss (xnrs/utils.py:117-131) with every eligible news of the table as a negative -- over the sweep of
-recommend() / rank_clicked(), without a (sessions, n_rows) score matrix (table_ranking_loss, full_table_loss)."""
+recommend() / rank_clicked(), without a (sessions, n_rows) score matrix (table_ranking_loss, full_table_loss); and the same
+loss over per-session row lists, the hardest negatives mined by topk_deep per step or any list the caller brings, without a
+copy of the listed rows (listed_ranking_loss, mined_negatives_loss)."""
 from __future__ import annotations
 
 import torch
@@ -81,27 +83,16 @@ def table_ranking_loss(scorer, table: torch.Tensor, u: torch.Tensor, tgt_off: to
     return reduce_table_loss(loss, scores, reduction)
 
 
-def full_table_loss(model, store_or_table, behaviors, sessions, l_hist: int, exclude_history: bool = True, windows=None,
-                    reduction: str = "mean", store=None) -> torch.Tensor:
-    """The full-table ranking loss of one batch of sessions, on the path of recommend() / rank_clicked() with autograd on:
-    the sessions' last `l_hist` history rows are gathered from the table of news vectors, model.encode_user gives the user
-    vectors, every clicked news of a session (pos_off / pos_val) is a query, the session's FULL history is excluded
-    (`exclude_history`) and `windows` = (lo, hi) indexed by session id restrict the negatives as in rank_clicked().
-
-    store_or_table: a NewsStore -- the table is encoded here, under autograd, so the news encoder trains too -- or a pair
-    (vecs:(n_rows,E), hm:(n_rows,1)) as encode_news_table returns it, together with `store` (its pad row): a detached pair
-    trains the user tower (and the scorer) only.  reduction 'mean' divides by the number of clicks that have an answer.
-    A scorer without table_loss (FCScoring), a model whose news vectors depend on the user (NPA) and CAUM raise
-    NotImplementedError before anything is encoded."""
-    from . import evaluation as EV
-    who = "full_table_loss()"
+def _refuse_before_encoding(model, behaviors, reduction: str, who: str, scorer_of, loss_name: str):
+    """What full_table_loss() and mined_negatives_loss() refuse before anything is encoded -> (scorer, user index or None).
+    scorer_of(scorer, who) raises for a scorer without the loss; loss_name words the normalize=True refusal."""
     if getattr(model, "user_dependent_news", False):
         raise NotImplementedError(f"{who}: the news vectors of {type(model).__name__} depend on the user, so no table of "
                                   "news vectors exists to rank")
     scorer = getattr(model, "rec_model", None)
-    _table_loss_scorer(scorer, who)
+    scorer_of(scorer, who)
     if getattr(scorer, "normalize", False):
-        raise NotImplementedError(f"{who}: {type(scorer).__name__}(normalize=True) has no full-table loss")
+        raise NotImplementedError(f"{who}: {type(scorer).__name__}(normalize=True) has no {loss_name}")
     if reduction not in ("mean", "sum", "none"):
         raise ValueError(f"reduction {reduction!r}: 'mean', 'sum' or 'none'")
     uidx = None
@@ -110,6 +101,16 @@ def full_table_loss(model, store_or_table, behaviors, sessions, l_hist: int, exc
         if uidx is None:
             raise ValueError(f"{who}: {type(model).__name__} needs the user index of every session (sessions without "
                              "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    return scorer, uidx
+
+
+def _encode_sessions(model, store_or_table, behaviors, sessions, l_hist: int, exclude_history: bool, windows, store, uidx,
+                     who: str):
+    """The shared path of both losses from the table to the user vectors, with autograd on -> (vecs, u, hist_csr, tgt_csr,
+    (win_lo, win_hi), pad_row): the table is encoded (a NewsStore) or taken as given (a pair with store=), the sessions' last
+    `l_hist` history rows are gathered from it, model.encode_user gives u; hist_csr is the exclusion CSR of the sessions'
+    FULL histories ((None, None) without `exclude_history`), tgt_csr their clicked rows, the windows those of the sessions."""
+    from . import evaluation as EV
     if isinstance(store_or_table, (tuple, list)):
         vecs, hm = store_or_table
         if store is None:
@@ -129,7 +130,118 @@ def full_table_loss(model, store_or_table, behaviors, sessions, l_hist: int, exc
     excl = EV._history_csr(behaviors, sess, None) if exclude_history else (None, None)
     tgt = EV._session_csr(behaviors.pos_off, behaviors.pos_val, sess, None)
     win = (None, None) if windows is None else (windows[0][sess].contiguous(), windows[1][sess].contiguous())
-    return table_ranking_loss(scorer, vecs, u, tgt[0], tgt[1], excl[0], excl[1], store.pad_row, win[0], win[1], reduction)
+    return vecs, u, excl, tgt, win, store.pad_row
+
+
+def full_table_loss(model, store_or_table, behaviors, sessions, l_hist: int, exclude_history: bool = True, windows=None,
+                    reduction: str = "mean", store=None) -> torch.Tensor:
+    """The full-table ranking loss of one batch of sessions, on the path of recommend() / rank_clicked() with autograd on:
+    the sessions' last `l_hist` history rows are gathered from the table of news vectors, model.encode_user gives the user
+    vectors, every clicked news of a session (pos_off / pos_val) is a query, the session's FULL history is excluded
+    (`exclude_history`) and `windows` = (lo, hi) indexed by session id restrict the negatives as in rank_clicked().
+
+    store_or_table: a NewsStore -- the table is encoded here, under autograd, so the news encoder trains too -- or a pair
+    (vecs:(n_rows,E), hm:(n_rows,1)) as encode_news_table returns it, together with `store` (its pad row): a detached pair
+    trains the user tower (and the scorer) only.  reduction 'mean' divides by the number of clicks that have an answer.
+    A scorer without table_loss (FCScoring), a model whose news vectors depend on the user (NPA) and CAUM raise
+    NotImplementedError before anything is encoded."""
+    who = "full_table_loss()"
+    scorer, uidx = _refuse_before_encoding(model, behaviors, reduction, who, _table_loss_scorer, "full-table loss")
+    vecs, u, excl, tgt, win, pad_row = _encode_sessions(model, store_or_table, behaviors, sessions, l_hist, exclude_history,
+                                                        windows, store, uidx, who)
+    return table_ranking_loss(scorer, vecs, u, tgt[0], tgt[1], excl[0], excl[1], pad_row, win[0], win[1], reduction)
+
+
+def _list_loss_scorer(scorer, who: str):
+    fn = getattr(scorer, "list_loss", None)
+    if fn is None:
+        raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no ranking loss over listed rows of a news "
+                                  "table (list_loss); training it with a plain dot product would train another model")
+    return fn
+
+
+def listed_ranking_loss(scorer, table: torch.Tensor, u: torch.Tensor, tgt_off: torch.Tensor, tgt_rows: torch.Tensor,
+                        neg_rows: torch.Tensor, pad_row: int = -1, reduction: str = "mean") -> torch.Tensor:
+    """ranking_loss(p, n) of every (user, target row) of the CSR tgt_off / tgt_rows with the rows the user LISTS in
+    neg_rows:(B, L) int32 as the negatives n (include/xnrs_hip.h: xnrs_list_loss_fwd): a slot counts when its row is inside
+    the table, not pad_row and no target of the user; -1 fillers and everything else are empty slots; a row listed twice
+    counts twice.  `scorer`: a DotScoring or BilinScoring (scorer.list_loss); differentiable in `table`, `u` and the scorer's
+    weight, without a copy of the listed rows.  Reduction as table_ranking_loss."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"reduction {reduction!r}: 'mean', 'sum' or 'none'")
+    fn = _list_loss_scorer(scorer, "listed_ranking_loss()")
+    loss, scores = fn(table, u, tgt_off, tgt_rows, neg_rows, pad_row)[:2]
+    return reduce_table_loss(loss, scores, reduction)
+
+
+def merged_exclusions(hist_csr, tgt_csr):
+    """Per session its history list followed by its clicked rows, as one exclusion CSR (off int64, rows int32): what the
+    mining step may not return.  hist_csr: (off, rows) or (None, None); both CSRs start at offset 0.  Device arithmetic
+    only; the lists stay unsorted and may hold duplicates, which the exclusion lists of xnrs_topk* allow."""
+    to, tr = tgt_csr
+    ho, hr = hist_csr
+    if ho is None:
+        return to, tr
+    nh, nt = hr.numel(), tr.numel()
+    dev = tr.device
+    rows = torch.empty((nh + nt,), dtype=torch.int32, device=dev)
+    # history entry k of session b moves behind the clicks of the sessions before b, click k behind the histories up to b
+    shift_h = torch.repeat_interleave(to[:-1], ho[1:] - ho[:-1], output_size=nh)
+    shift_t = torch.repeat_interleave(ho[1:], to[1:] - to[:-1], output_size=nt)
+    rows[torch.arange(nh, device=dev) + shift_h] = hr.to(torch.int32)
+    rows[torch.arange(nt, device=dev) + shift_t] = tr.to(torch.int32)
+    return ho + to, rows
+
+
+def _check_neg_rows(neg_rows, n_sessions: int, who: str):
+    if not isinstance(neg_rows, torch.Tensor) or neg_rows.dtype != torch.int32 or neg_rows.dim() != 2 \
+            or neg_rows.shape[0] != n_sessions:
+        raise ValueError(f"{who}: neg_rows is a ({n_sessions}, L) int32 tensor, one list of table rows per session; got "
+                         f"{tuple(getattr(neg_rows, 'shape', ()))} {getattr(neg_rows, 'dtype', type(neg_rows))}")
+
+
+def mine_and_rank(scorer, vecs, u, hist_csr, tgt_csr, pad_row: int, n_negatives: int, win=(None, None), reduction: str = "mean",
+                  neg_rows=None, return_negatives: bool = False):
+    """The part of mined_negatives_loss() behind the user vectors: without `neg_rows` the scorer's topk_deep lists, under
+    no_grad and on detached operands, the n_negatives rows each user scores highest outside the merged exclusions (history
+    and clicks) and inside the window; then the listed loss over those rows, under autograd."""
+    if neg_rows is None:
+        excl = merged_exclusions(hist_csr, tgt_csr)
+        with torch.no_grad():
+            kw = {} if win[0] is None else dict(win_lo=win[0], win_hi=win[1])
+            neg_rows = scorer.topk_deep(vecs.detach(), u.detach(), int(n_negatives), excl[0], excl[1], pad_row, **kw)[0]
+    loss = listed_ranking_loss(scorer, vecs, u, tgt_csr[0], tgt_csr[1], neg_rows, pad_row, reduction)
+    return (loss, neg_rows) if return_negatives else loss
+
+
+def mined_negatives_loss(model, store_or_table, behaviors, sessions, l_hist: int, n_negatives: int = 128,
+                         exclude_history: bool = True, windows=None, reduction: str = "mean", store=None, neg_rows=None,
+                         return_negatives: bool = False):
+    """The ranking loss of one batch of sessions against the `n_negatives` HARDEST negatives of each -- the news of the whole
+    table the session's user scores highest, mined per step -- instead of against the whole table: the path of
+    full_table_loss() up to the user vectors (same arguments, same refusals, raised before anything is encoded), then
+    scorer.topk_deep under no_grad over the detached table and user vectors, excluding the pad row, the session's clicked
+    rows and (`exclude_history`) its full history, inside the session's window (`windows`); then the scorer's list_loss over
+    the mined rows under autograd (xnrs_list_loss_fwd / _bwd: no copy of the listed rows).  The lists have the prefix
+    property of topk_deep, so the loss does not decrease with n_negatives and meets full_table_loss() when every eligible
+    row is listed.  1 <= n_negatives <= 1024, else ValueError.
+
+    neg_rows: a (len(sessions), L) int32 tensor of table rows on the table's device skips the mining: stale lists reused
+    over several steps, random sampled negatives.  A slot whose row is outside the table, the pad row or a click of its
+    session is ignored (-1 is the filler).  return_negatives=True returns (loss, rows) with the lists that were used."""
+    who = "mined_negatives_loss()"
+    scorer, uidx = _refuse_before_encoding(model, behaviors, reduction, who, _list_loss_scorer, "ranking loss over listed rows")
+    n_sessions = int(torch.as_tensor(sessions).numel())
+    if neg_rows is not None:
+        _check_neg_rows(neg_rows, n_sessions, who)
+    else:
+        if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or not 1 <= int(n_negatives) <= 1024:
+            raise ValueError(f"{who}: n_negatives = {n_negatives!r}: an integer in [1, 1024], the list lengths of topk_deep")
+        if getattr(scorer, "topk_deep", None) is None:
+            raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no topk_deep to mine negatives with")
+    vecs, u, excl, tgt, win, pad_row = _encode_sessions(model, store_or_table, behaviors, sessions, l_hist, exclude_history,
+                                                        windows, store, uidx, who)
+    return mine_and_rank(scorer, vecs, u, excl, tgt, pad_row, n_negatives, win, reduction, neg_rows, return_negatives)
 
 
 def _gather_rows(vecs: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:

@@ -251,6 +251,14 @@ class DotScoring(nn.Module):
                                       "product only")
         return ops.table_loss(table, u, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi)
 
+    def list_loss(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, neg_rows, pad_row: int = -1):
+        """The softmax ranking loss of every target against the rows its user lists in neg_rows:(B, L) (ops.list_loss) ->
+        (loss, scores, lse, neg_scores), differentiable in `table` and `u`."""
+        if self.normalize:
+            raise NotImplementedError("DotScoring.list_loss with normalize=True: the listed loss implements the raw inner "
+                                      "product only")
+        return ops.list_loss(table, u, tgt_off, tgt_rows, neg_rows, pad_row)
+
 
 class BilinScoring(nn.Module):
     """Reference: scoring.py:41-66.  nn.Bilinear(E, E, 1, bias) registered as `bilin`; u:(B,1,E), c:(B,N,E) -> (B,N,1) =
@@ -301,6 +309,16 @@ class BilinScoring(nn.Module):
         E = self.bilin.weight.shape[-1]
         v = ops.linear(u.reshape(-1, E), self.bilin.weight[0].t())  # v_b = W[0]^T u_b
         return ops.table_loss(table, v, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias=self.bilin.bias)
+
+    def list_loss(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, neg_rows, pad_row: int = -1):
+        """As DotScoring.list_loss with the score u W[0] table[row] + bias: v = u W[0] through ops.linear, as in table_loss,
+        so that autograd reaches W and u; the bias is passed for the score bits and gets no gradient."""
+        if self.normalize:
+            raise NotImplementedError("BilinScoring.list_loss with normalize=True: the listed loss implements the raw "
+                                      "bilinear form only")
+        E = self.bilin.weight.shape[-1]
+        v = ops.linear(u.reshape(-1, E), self.bilin.weight[0].t())  # v_b = W[0]^T u_b
+        return ops.list_loss(table, v, tgt_off, tgt_rows, neg_rows, pad_row, bias=self.bilin.bias)
 
 
 def _is_tanh(activation) -> bool:

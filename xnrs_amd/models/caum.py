@@ -81,6 +81,7 @@ class CAUMScoring(DotScoring):
     topk = None
     rank = None
     table_loss = None
+    list_loss = None
 
 
 class CAUMNewsEncoder(nn.Module):

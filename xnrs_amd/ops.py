@@ -821,6 +821,101 @@ def table_loss(table, up, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_
     return autograd.table_loss(table, up, tgt_off, tgt_rows, excl_off, excl_rows, pad_row, win_lo, win_hi, bias)
 
 
+def _list_loss_check(table, up, tgt_off, tgt_rows, neg_rows):
+    """What can be refused before anything touches the device: the table's shape, the target CSR and the lists."""
+    _table_loss_check(table, up, tgt_off, tgt_rows, None, None)
+    B = up.numel() // table.shape[1]
+    if not isinstance(neg_rows, torch.Tensor) or neg_rows.dtype != torch.int32 or neg_rows.dim() != 2 or neg_rows.shape[0] != B:
+        raise RuntimeError(f"negative lists: a ({B}, L) int32 tensor, one list of rows per user; got "
+                           f"{tuple(getattr(neg_rows, 'shape', ()))} {getattr(neg_rows, 'dtype', type(neg_rows))}")
+    if neg_rows.device != table.device or not neg_rows.is_contiguous():
+        raise hip.XnrsHipError(f"negative lists must be a contiguous tensor on {table.device}")
+
+
+def _list_loss_args(table, up, tgt_off, tgt_rows, neg_rows, bias):
+    """The checked operands of xnrs_list_loss_fwd / _bwd -> (table, up, B, L, head, keep): head holds the leading arguments of
+    both calls as raw addresses; keep holds the tensors behind those addresses that exist only here (the stand-in for an empty
+    tgt_rows, the fp32 bias) and must stay referenced by the caller until the call has been enqueued."""
+    _list_loss_check(table, up, tgt_off, tgt_rows, neg_rows)
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    up = hip.dev_f32(up, "user vectors").reshape(-1, E)
+    bias = None if bias is None else hip.dev_f32(bias, "score bias").reshape(-1)[:1]
+    B, L, dev = up.shape[0], neg_rows.shape[1], table.device
+    # (no target at all: the offsets are all equal and the rows are never read, but the entry point wants an address)
+    rows = tgt_rows if tgt_rows.numel() else torch.zeros((1,), dtype=torch.int32, device=dev)
+    head = (hip.ptr(table), n_rows, E, hip.ptr(up), hip.ptr(bias), B, hip.ptr(tgt_off), hip.ptr(rows), hip.ptr(neg_rows), L)
+    return table, up, B, L, head, (rows, bias)
+
+
+def list_loss_forward(table, up, tgt_off, tgt_rows, neg_rows, pad_row: int = -1, bias=None):
+    """xnrs_list_loss_fwd -> (loss:(T,), scores:(T,), lse:(B,), neg_scores:(B,L)); positions of loss / scores outside
+    [tgt_off[0], tgt_off[B]) hold 0 / NaN."""
+    table, up, B, L, head, keep = _list_loss_args(table, up, tgt_off, tgt_rows, neg_rows, bias)
+    dev, T = table.device, tgt_rows.numel()
+    loss = torch.zeros((T,), dtype=torch.float32, device=dev)
+    scores = torch.full((T,), float("nan"), dtype=torch.float32, device=dev)
+    lse = torch.empty((B,), dtype=torch.float32, device=dev)
+    neg_scores = torch.empty((B, L), dtype=torch.float32, device=dev)
+    l = hip.lib()
+    nbytes = l.xnrs_list_loss_workspace_bytes(B, L, T, table.shape[1], 0)
+    ws = hip.workspace(dev, nbytes)
+    # (no target at all: nothing per query is written, but the entry point wants addresses)
+    out = (scores, loss) if T else (torch.empty((1,), dtype=torch.float32, device=dev),) * 2
+    hip.check(l.xnrs_list_loss_fwd(*head, int(pad_row), hip.ptr(out[0]), hip.ptr(out[1]), hip.ptr(lse), hip.ptr(neg_scores),
+                                   hip.ptr(ws), nbytes, hip.stream_ptr(dev)), "xnrs_list_loss_fwd")
+    del keep  # (held until here)
+    return loss, scores, lse, neg_scores
+
+
+def list_loss_order(n_rows: int, tgt_rows, neg_rows, scores, neg_scores):
+    """The `order` operand of xnrs_list_loss_bwd, built on the device without a host read: the B L slots, then the T queries,
+    stably sorted by row, the entries that carry no gradient (NaN in neg_scores / scores) behind all others."""
+    key = torch.cat((torch.where(torch.isnan(neg_scores.reshape(-1)), n_rows, neg_rows.reshape(-1)),
+                     torch.where(torch.isnan(scores.reshape(-1)), n_rows, tgt_rows.reshape(-1))))
+    return torch.sort(key, stable=True).indices.to(torch.int32)
+
+
+def list_loss_backward(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias, scores, lse, neg_scores, g, want_d_up: bool = True,
+                       want_d_table: bool = True):
+    """xnrs_list_loss_bwd -> (d_up or None, d_table or None): a gradient that is not wanted is not computed (and without
+    d_table no order is sorted)."""
+    table, up, B, L, head, keep = _list_loss_args(table, up, tgt_off, tgt_rows, neg_rows, bias)
+    dev, T = table.device, tgt_rows.numel()
+    g = hip.dev_f32(g, "upstream gradient").reshape(-1)
+    if g.numel() != T or scores.numel() != T or lse.numel() != B or tuple(neg_scores.shape) != (B, L):
+        raise RuntimeError(f"list loss backward: g and scores have one entry per target row ({T}), lse one per user ({B}), "
+                           f"neg_scores one per slot ({B}, {L}); got {g.numel()}, {scores.numel()}, {lse.numel()}, "
+                           f"{tuple(neg_scores.shape)}")
+    if not (want_d_up or want_d_table):
+        return None, None
+    d_up = torch.empty_like(up) if want_d_up else None
+    d_table = torch.empty_like(table) if want_d_table else None
+    order = list_loss_order(table.shape[0], tgt_rows, neg_rows, scores, neg_scores) if want_d_table else None
+    l = hip.lib()
+    nbytes = l.xnrs_list_loss_workspace_bytes(B, L, T, table.shape[1], int(want_d_table))
+    ws = hip.workspace(dev, nbytes)
+    per_query = (scores, g) if T else (torch.empty((1,), dtype=torch.float32, device=dev),) * 2  # (as in the forward)
+    hip.check(l.xnrs_list_loss_bwd(*head, int(pad_row), hip.ptr(per_query[0]), hip.ptr(lse), hip.ptr(neg_scores),
+                                   hip.ptr(per_query[1]), hip.ptr(order), hip.ptr(d_up), hip.ptr(d_table), hip.ptr(ws), nbytes, hip.stream_ptr(dev)),
+              "xnrs_list_loss_bwd")
+    del keep  # (held until here)
+    return d_up, d_table
+
+
+def list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row: int = -1, bias=None):
+    """The softmax ranking loss of every (user, target row) of the CSR tgt_off / tgt_rows against the rows the user LISTS in
+    neg_rows:(B, L) int32 (include/xnrs_hip.h: xnrs_list_loss_fwd) -> (loss:(T,), scores:(T,), lse:(B,), neg_scores:(B,L)).
+    A slot is a negative when its row is inside the table, not pad_row and no target of the user; every other slot (the -1
+    fillers of topk_deep, foreign ids, the pad row, a target) is empty and NaN in neg_scores; a row listed twice counts
+    twice.  loss = logaddexp(score, lse) - score, 0 for a query without an answer (score NaN) and for a user without
+    negatives (lse -inf).  Differentiable in `table` and `up` (a gradient that nobody asks for is not computed); scores, lse
+    and neg_scores carry no gradient, and neither does `bias`, which cancels in the loss."""
+    from . import autograd
+    _list_loss_check(table, up, tgt_off, tgt_rows, neg_rows)
+    return autograd.list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
