@@ -710,7 +710,7 @@ int32_t xnrs_topk_deep_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H,
                            const int32_t *excl_rows, int32_t pad_row, int32_t k, int32_t *rows, float *scores, void *ws,
                            size_t ws_bytes, void *stream);
 
-/* ---- where given rows rank within the whole table per user (full-corpus evaluation; csrc/topk.hip) ------------------------
+/* ---- where given rows rank within the whole table per user (full-corpus evaluation; csrc/rank.hip) ------------------------
  * The sweep of xnrs_topk* that counts instead of selects, again without a (B, n_rows) score matrix.  table / P, u, the
  * weights, the exclusion CSR and pad_row mean what they mean for xnrs_topk*: the same tensors serve both calls.
  * Queries: tgt_off:(B+1) int64 and tgt_rows: int32 form a CSR of target rows over the users, the offsets ABSOLUTE into
@@ -746,7 +746,7 @@ int32_t xnrs_rank_mlp(const float *P, int64_t n_rows, int32_t E, int32_t H, cons
                       const int64_t *excl_off, const int32_t *excl_rows, int32_t pad_row, int32_t *ranks, float *scores,
                       void *ws, size_t ws_bytes, void *stream);
 
-/* ---- a per-user row window for the two sweeps (time-aware recommendation and evaluation; csrc/topk.hip) --------------------
+/* ---- a per-user row window for the two sweeps (time-aware recommendation and evaluation; csrc/sweep.h) ---------------------
  * xnrs_topk_deep*_win and xnrs_rank*_win take the argument lists of xnrs_topk_deep* / xnrs_rank* with two int32 device arrays
  * of length B, win_lo and win_hi, behind excl_rows: user b sees the table rows [win_lo[b], win_hi[b]) only.  With the table
  * ordered by publication time that is "the news that existed at the session's time and was still fresh".
@@ -800,7 +800,7 @@ int32_t xnrs_rank_mlp_win(const float *P, int64_t n_rows, int32_t E, int32_t H, 
                           const int64_t *excl_off, const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi,
                           int32_t pad_row, int32_t *ranks, float *scores, void *ws, size_t ws_bytes, void *stream);
 
-/* ---- the full-table softmax ranking loss: the training side of the two sweeps (csrc/topk.hip) ------------------------------
+/* ---- the full-table softmax ranking loss: the training side of the two sweeps (csrc/table_loss.hip) ------------------------
  * The reference's ranking_loss(p, n) = -log(e^p / (e^p + sum e^n)) (xnrs/utils.py:117-131) with EVERY eligible news of the
  * table as a negative, forward and backward, again without a (B, n_rows) score matrix.  The operands are those of
  * xnrs_rank_win: table:(n_rows,E), the user side up:(B,E) as the score reads it (u, or v = u W[0] of the bilinear scorer),

@@ -38,7 +38,7 @@ its predicate tests -> where an ABI caller can reach it ("ws" = a region of the 
   news_fused_ready (news_fused.hip:745)    x, wq, wk, wv, wo, w1 (prep kernel f32x4), img, o_scratch (ws), p (f32x4 store)
       | all but p  ->  ADDED p, ldp (p is the caller's y without a head and with XNRS_FOLD_OUT=0); and news_fused_route asked
       about pool->w1 while prepare_weights hands the kernel pool->w1_folded  ->  ADDED: such a call FAILED (launch refused).
-  tk_vec_ok (topk.hip)                     table / P, up rows through tk_load / tl_load | both, each on its own | top-k, rank,
+  tk_vec_ok (sweep.h: sweep_operands)      table / P, up rows through tk_load (sweep.h) / tl_load (table_loss.hip) | both, each on its own | top-k, rank,
       table loss.  Outputs, w, w1, bias: 4 bytes at a time.
   gru.hip:327                              w_hh, h0 (load_k4) | both, Hd % 4 | xnrs_gru_fwd*; the backward reads ws only
   batch.hip:235 / 291 / 369                table / x and out rows | both, row width | xnrs_gather_rows, _dropout_rows, *_bf16

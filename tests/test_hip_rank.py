@@ -1,5 +1,5 @@
 """GPU: where given rows rank within a whole news table per user (include/xnrs_hip.h: xnrs_rank / _bilinear / _mlp,
-csrc/topk.hip) and evaluation.rank_clicked / evaluate_full_ranking on top of it.
+csrc/rank.hip) and evaluation.rank_clicked / evaluate_full_ranking on top of it.
 
 1. exact-integer operands: every fp32 product and sum is exact in any order, so ranks AND scores must equal the NumPy reference
    of the contract (tests/rank_ref.py) bit for bit -- integer scores tie massively, which pins the tie rule;

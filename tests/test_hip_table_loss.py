@@ -1,4 +1,4 @@
-"""GPU: the full-table softmax ranking loss (include/xnrs_hip.h: xnrs_table_loss_fwd / _bwd, csrc/topk.hip) through
+"""GPU: the full-table softmax ranking loss (include/xnrs_hip.h: xnrs_table_loss_fwd / _bwd, csrc/table_loss.hip) through
 ops.table_loss and the raw entry points.
 
 1. parity of loss, d_up and d_table with the fp64 reference of the definition (tests/table_loss_ref.py) at the project's bar,

@@ -1,5 +1,5 @@
 """GPU: per-user row windows for the top-k and the rank sweep (include/xnrs_hip.h: xnrs_topk_deep*_win / xnrs_rank*_win,
-csrc/topk.hip) and evaluation.recommend / rank_clicked / evaluate_full_ranking on top of them.
+csrc/sweep.h, topk.hip, rank.hip) and evaluation.recommend / rank_clicked / evaluate_full_ranking on top of them.
 
 The specification is one sentence: the windowed result equals the parent's result with every row outside the user's window
 appended to the user's exclusion list.  So every exact case draws integer operands (entries in [-3, 3], |score| < 2^24: every
@@ -12,7 +12,7 @@ function, so again the same bits.  No tolerance anywhere in this file.
 and the prefix property; 5. the MLP and a real-valued case against the parent; 6. NULL windows are the parent call; 7. rank;
 8. batch invariance; 9. refusals; 10. hipGraph; 11. end to end.
 
-Two arithmetic mutations of csrc/topk.hip were built and run against this file (neither is committed):
+Two arithmetic mutations of csrc/topk.hip and csrc/sweep.h were built and run against this file (neither is committed):
  (a) the upper window bound dropped from the candidate mask of topk_partial_kernel (rows at and behind win_hi, up to the
      table's end, pass): 38 of
      the 57 cases fail -- test_one_chunk for every window that ends inside the table (edges inside, lo == hi, lo < 0, the

@@ -129,7 +129,7 @@ inline GemmArgs gemm_kmajor_ab(const float* At, int64_t lda, const float* B, int
   return g;
 }
 
-// the dense projections of the scorers (scorers.hip, topk.hip)
+// the dense projections of the scorers (scorers.hip, sweep.h)
 // C[M, N] = A[M, K] . op(W) (+ bias): W row-major [N][K] at pitch ldw (w_kn = 0: nn.Linear layout) or [K][N] at pitch ldw
 // (w_kn = 1); one launch, no split-K
 inline hipError_t sc_gemm(const float* A, int64_t lda, const float* W, int64_t ldw, int w_kn, const float* bias, float* C, int64_t ldc,
