@@ -46,6 +46,8 @@ def main():
     which.add_argument("--mined-negatives", type=int, default=0, metavar="M",
                        help="train with the ranking loss over the M hardest negatives of each session, mined per step "
                             "(losses.mined_negatives_loss, 1 <= M <= 1024)")
+    ap.add_argument("--explain", action="store_true",
+                    help="after training: recommend() three news for session 0 and explain_recommendations() for them")
     args = ap.parse_args()
     dev = "cuda:0"
     if args.bf16x3:
@@ -86,6 +88,14 @@ def main():
     print("after: ", {k: round(v, 4) for k, v in after.items()})
     print(f"{args.steps} steps of {args.batch} impressions in {dt:.2f} s = {args.steps * args.batch / dt:.0f} impressions/s (tiny model: launch-bound)")
     assert after["auc"] > before["auc"] + 0.1, "the model did not learn"
+    if args.explain:
+        # what does session 0 get, and which news of its history speak for each of those rows?
+        from xnrs_amd.explain import explain_recommendations
+        rows, scores = evaluation.recommend(model, store, beh, args.hist, k=3, sessions=[0])
+        out = explain_recommendations(model, store, beh, args.hist, 0, rows[0], n_steps=50)
+        for j, row in enumerate(rows[0].tolist()):
+            print(f"session 0 <- row {row} (score {scores[0, j].item():.3f}): attribution per history news",
+                  [round(v, 3) for v in out["news_attribution"][j].tolist()])
 
 
 if __name__ == "__main__":

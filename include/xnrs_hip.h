@@ -433,6 +433,25 @@ int32_t xnrs_gather_rows_bf16(const uint16_t *table, const int32_t *ids, float *
 int32_t xnrs_dropout_rows_bf16(const uint16_t *table, const int32_t *ids, float *out, int64_t n, int64_t row_elems,
                                float p, uint64_t seed, const uint64_t *seed_dev, void *stream);
 
+/* ---- integrated gradients with ONE Q|K|V projection (explain.py:152-173) ----
+ * The scaled tokens of interpolation step i are a_i x, and an attention tower reads its tokens through the Q|K|V
+ * projection alone: QKV_i = a_i P + b with P = x [Wq; Wk; Wv]^T, and sum_i d s_i / d (a_i x) = (sum_i dQKV_i) [Wq; Wk; Wv].
+ * Two streaming kernels turn the one product into the n images and the n gradient images into the operand of one product.
+ *
+ * xnrs_ig_expand: p:(rows, W), bias:(W) or NULL (= 0), alphas:(n) fp32 ON THE DEVICE -> out:(n * rows, W),
+ *   out[i * rows + r][c] = fmaf(alphas[i], p[r][c], bias[c])      (one fused multiply-add, nothing else)
+ * xnrs_ig_reduce: g:(n * rows, W) -> out:(rows, W).  Per element s = g[0] + g[1] + ... + g[n-1], ONE fp32 chain in
+ *   ascending i; out = scale * s (accumulate == 0) or out = out + scale * s (accumulate == 1), the product and every sum
+ *   rounded on their own (no contraction).  No atomics; the bits do not depend on the launch geometry.
+ * Both: one launch, no allocation, no host sync, capturable; int64 offsets (n * rows * W may pass 2^31).  16-byte accesses
+ * when W % 4 == 0 and p / g and out are 16-byte aligned (bias: any fp32 address), scalar accesses otherwise -- the same bits.
+ * n < 0, rows < 0, W <= 0, accumulate outside {0, 1}: XNRS_EINVAL.  n == 0 or rows == 0: XNRS_OK, nothing written.
+ * NULL p / alphas / g / out: XNRS_EINVAL.  Errors are found before any launch. */
+int32_t xnrs_ig_expand(const float *p, const float *bias, const float *alphas, int64_t n, int64_t rows, int32_t W,
+                       float *out, void *stream);
+int32_t xnrs_ig_reduce(const float *g, int64_t n, int64_t rows, int32_t W, float scale, float *out, int32_t accumulate,
+                       void *stream);
+
 /* ---- device-side batch assembly and evaluation -----------------------
  * Click histories / positives / negatives live on the device as CSR arrays of ROWS into the resident news
  * table ([n_rows,S,D] + mask; `pad_row` = the empty slot: all-zero tokens and mask, dataset.py:82-85).

@@ -520,6 +520,107 @@ def _device_lists(l, cfg, m, ids, dev):
     return live, live_src, kv, kv_src, counts
 
 
+class _SeqEncodeFromQkv(torch.autograd.Function):
+    """y = head(pool(att core(qkv))): an attention tower's training forward that READS a given Q|K|V image ((n_seq * L, 3D),
+    xnrs_row_lists::qkv_shared) and projects nothing; the image is the one differentiable input.  The backward leaves
+    dQ|dK|dV in the gradient it returns (XNRS_DQKV_DEFER) and stops before the projection products: no input gradient, no
+    parameter gradient -- the parameters are not even inputs of the node (integrated gradients with one projection,
+    explain.py).  No row lists: every row of the returned image is written, the rows of an all-masked
+    sequence as zeros.  Neither pass writes the image or the saved blob, so one forward serves any number of backward passes
+    (retain_graph=True); nothing is registered in _QKV_IMAGES and no _Pair is formed."""
+
+    @staticmethod
+    def forward(ctx, cfg: _Cfg, qkv, m, params):
+        qkv = hip.dev_f32(qkv, "Q|K|V image")
+        dev = qkv.device
+        n, L, D = cfg.n_seq, cfg.L, cfg.D
+        if tuple(qkv.shape) != (n * L, 3 * D):
+            raise hip.XnrsHipError(f"Q|K|V image {tuple(qkv.shape)}: expected {(n * L, 3 * D)}")
+        if qkv.data_ptr() % hip.WORKSPACE_ALIGN:
+            raise hip.XnrsHipError(f"Q|K|V image at {qkv.data_ptr():#x} is not {hip.WORKSPACE_ALIGN}-byte aligned")
+        params = list(params)
+        ap, pp, hp, keep = _param_structs(cfg, params)
+        Eo = cfg.E if cfg.has_head else D
+        y = torch.empty((n, Eo), dtype=torch.float32, device=dev)
+        hm = torch.empty((n,), dtype=torch.float32, device=dev)
+        l = hip.lib()
+        ctx.fold_pair = _train_fold(l, cfg, params, ap, pp, dev)
+        if ctx.fold_pair is not None:
+            pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
+        nsaved = l.xnrs_seq_encoder_saved_bytes(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head))
+        saved = torch.empty(max(nsaved, 1), dtype=torch.uint8, device=dev)
+        lists = hip.RowLists(None, None, 0, None, None, 0, qkv.data_ptr(), None, None, hip.DQKV_OWN)
+        # x: the entry points want a non-NULL input; with a given image nothing reads it (project() returns at once, every
+        # later stage of an attention tower reads the image or what follows it, and the deferring backward stops before the
+        # projection products) -- the image's own address stands in, which is at least as large as the tokens would be
+        hip.check(l.xnrs_seq_encoder_fwd_train_rows(hip.ptr(qkv), hip.ptr(m), None, n, L, D, hip.ref(ap), cfg.pool_kind, hip.ref(pp),
+                                                    hip.ref(hp), hip.ptr(y), None, hip.ptr(hm), hip.ptr(saved), nsaved,
+                                                    hip.ref(lists), hip.stream_ptr(dev)), "xnrs_seq_encoder_fwd_train_rows")
+        ctx.fold = l.xnrs_train_fold_enabled()  # the saved blob is laid out by this decision (include/xnrs_hip.h)
+        ctx.cfg, ctx.nsaved = cfg, nsaved
+        ctx.param_none = [p is None for p in params]
+        ctx.save_for_backward(qkv, m, saved, *[p for p in params if p is not None])
+        ctx.mark_non_differentiable(hm)
+        ctx.set_materialize_grads(False)
+        return y, hm
+
+    @staticmethod
+    def backward(ctx, dy, _dhm):
+        if dy is None:
+            return None, None, None, None
+        cfg = ctx.cfg
+        qkv, m, saved, *ptensors = ctx.saved_tensors
+        it = iter(ptensors)
+        params = [None if isnone else next(it) for isnone in ctx.param_none]
+        dev = qkv.device
+        n, L, D = cfg.n_seq, cfg.L, cfg.D
+        Eo = cfg.E if cfg.has_head else D
+        ap, pp, hp, keep = _param_structs(cfg, params)
+        if ctx.fold_pair is not None:  # the pair the forward was given (the saved blob holds no copy then)
+            pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
+        dy = hip.dev_f32(dy, "grad output")
+        l = hip.lib()
+        if l.xnrs_train_fold_enabled() != ctx.fold:
+            raise hip.XnrsHipError("XNRS_FOLD_TRAIN changed between a training forward and its backward: the saved "
+                                   "activations were laid out for the other setting (reload the knobs outside a step)")
+        nws = l.xnrs_seq_encoder_bwd_workspace_bytes(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head))
+        ws = hip.workspace(dev, nws)
+        image = _f32_out((n * L, 3 * D), dev)
+        # no row lists: dead_seq_mode 0, the attention backward writes EVERY row of the image (the reduce sums every row)
+        lists = hip.RowLists(None, None, 0, None, None, 0, qkv.data_ptr(), None, image.data_ptr(), hip.DQKV_DEFER)
+        hip.check(l.xnrs_seq_encoder_bwd_rows(hip.ptr(qkv), hip.ptr(m), None, n, L, D, hip.ref(ap), cfg.pool_kind, hip.ref(pp),
+                                              hip.ref(hp), hip.ptr(saved), ctx.nsaved, hip.ptr(dy), None, None, None, None,
+                                              hip.ref(lists), hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_seq_encoder_bwd_rows")
+        return None, image, None, None
+
+
+def text_encoder_from_qkv(qkv, x, m, enc, dropout_p, seed):
+    """ops.text_encoder_from_qkv: (y:(n_seq, E'), hm:(n_seq,)) of an attention TextEncoder from its Q|K|V image."""
+    from . import ops
+    L, D = x.shape[-2], x.shape[-1]  # x: the tokens the image was projected from -- for their shape; they are not read
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * D or qkv.shape[0] % L:
+        raise hip.XnrsHipError(f"Q|K|V image {tuple(qkv.shape)} does not hold sequences of {L} rows of 3 * {D}")
+    n = qkv.shape[0] // L
+    if m is None:
+        raise hip.XnrsHipError("text_encoder_from_qkv needs the token mask")
+    m2 = ops._mask2d(m, n, L, "encoder mask")
+    att, pooler, head = enc.att, enc.pooler, getattr(enc, "head", None)
+    pool_kind = _pool_kind(pooler)
+    params: List[Optional[torch.Tensor]] = _att_tensors(att)
+    A, E, has_head = 0, D, False
+    if pool_kind == hip.POOL_ADDITIVE:
+        params += _pool_tensors(pooler)
+        A = pooler.fc1.out_features
+    if head is not None:
+        params += _head_tensors(head)
+        has_head, E = True, head[0].out_features
+    cfg = _Cfg(n, L, D, att.h, att.scaled, pool_kind, A, has_head, E, False, dropout_p, seed, False)
+    if head is not None:
+        cfg.head_act = hip.head_activation(head[1])
+    # the parameters travel as a tuple: they are no inputs of the node, so no backward pass is ever asked for their gradients
+    return _SeqEncodeFromQkv.apply(cfg, qkv, m2, tuple(params))
+
+
 #: A DETERMINISTIC encode (no attention dropout in play: no attention tower, or p = 0 / eval mode) called again with the very
 #: same tensors -- input, mask, ids and every parameter the same objects at the same version -- while the first call's graph
 #: is still alive returns the first call's OUTPUT TENSORS (same autograd node).  The reference's train step encodes the

@@ -1067,6 +1067,63 @@ def text_encoder(x, m, enc, ids=None, chunk: int = 0):
     return text_encoder_forward(x, m, att, pooler, head, ids=ids, chunk=chunk, dropout_p=p, seed=seed)
 
 
+def text_encoder_from_qkv(qkv: torch.Tensor, x: torch.Tensor, m: torch.Tensor, enc):
+    """TextEncoder core from a GIVEN Q|K|V image: qkv (n_seq * L, 3D) fp32 = tokens . [Wq; Wk; Wv]^T + [bq; bk; bv], rows of
+    sequence i at [i * L, (i + 1) * L); x (..., L, D): the tokens behind it -- read for their shape only, so the unscaled
+    (H, L, D) tokens of an explanation serve every step; m: the mask of all n_seq sequences.  -> (y:(n_seq, E'), hm:(n_seq,))
+    like text_encoder.  The image is the one differentiable input: its gradient is dQ|dK|dV, every row written; no parameter
+    gradient is computed and several backward passes over one forward are fine (integrated gradients with one projection:
+    explain.py).  Needs an attention stage."""
+    att = enc.att
+    if att is None:
+        raise hip.XnrsHipError("text_encoder_from_qkv: the encoder has no attention stage, so there is no Q|K|V image to start from")
+    _check_att(att)
+    p, seed = _att_dropout(att)
+    from . import autograd
+    return autograd.text_encoder_from_qkv(qkv, x, m, enc, p, seed)
+
+
+def ig_expand(p: torch.Tensor, bias: Optional[torch.Tensor], alphas: torch.Tensor) -> torch.Tensor:
+    """xnrs_ig_expand: p (rows, W), bias (W) or None, alphas (n) on the device -> (n * rows, W),
+    out[i * rows + r] = fma(alphas[i], p[r], bias)."""
+    p = hip.dev_f32(p, "ig_expand rows")
+    alphas = hip.dev_f32(alphas, "ig_expand alphas")
+    b = None if bias is None else hip.dev_f32(bias, "ig_expand bias")
+    rows, W = p.shape
+    n = alphas.numel()
+    out = torch.empty((n * rows, W), dtype=torch.float32, device=p.device)
+    hip.check(hip.lib().xnrs_ig_expand(hip.ptr(p), hip.ptr(b), hip.ptr(alphas), n, rows, W, hip.ptr(out), hip.stream_ptr(p.device)),
+              "xnrs_ig_expand")
+    return out
+
+
+def ig_reduce(g: torch.Tensor, n: int, scale: float, out: torch.Tensor, accumulate: bool) -> torch.Tensor:
+    """xnrs_ig_reduce: g (n * rows, W) -> out (rows, W) (=) or (+=) scale * (g[0] + ... + g[n-1]), the slices summed in
+    ascending order as one fp32 chain.  out: a contiguous fp32 device tensor, written in place."""
+    g = hip.dev_f32(g, "ig_reduce images")
+    rows, W = out.shape
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()) or g.shape != (n * rows, W):
+        raise hip.XnrsHipError(f"ig_reduce: images {tuple(g.shape)} / sum {tuple(out.shape)} for n = {n}")
+    hip.check(hip.lib().xnrs_ig_reduce(hip.ptr(g), n, rows, W, float(scale), hip.ptr(out), int(bool(accumulate)),
+                                       hip.stream_ptr(out.device)), "xnrs_ig_reduce")
+    return out
+
+
+def linear_input_grad(dy: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """dy . W as ONE product: the input gradient of nn.Linear alone (xnrs_linear_bwd with dx only).  dy (M, N), W (N, K) -> (M, K)."""
+    dy, w = hip.dev_f32(dy, "dy"), hip.dev_f32(weight, "linear weight")
+    M, N = dy.shape
+    K = w.shape[1]
+    dx = torch.empty((M, K), dtype=torch.float32, device=dy.device)
+    l = hip.lib()
+    nws = l.xnrs_linear_bwd_workspace_bytes(M, N, K)
+    ws = hip.workspace(dy.device, nws)
+    # (x: only the weight gradient reads it; the entry point wants it non-NULL, dy stands in)
+    hip.check(l.xnrs_linear_bwd(hip.ptr(dy), None, 0, hip.ptr(w), hip.ptr(dy), hip.ptr(dx), None, None, M, N, K, hip.ptr(ws), nws,
+                                hip.stream_ptr(dy.device)), "xnrs_linear_bwd")
+    return dx
+
+
 def text_encoder_unpadded(x, m, enc, ids=None):
     """Inference-only variant of text_encoder that skips the padding work (text_encoder_forward_unpadded).  Falls
     back to the padded kernels -- loudly impossible cases aside -- when attention dropout is active (train mode)."""
