@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
+from collections import namedtuple
 from typing import List, Optional
 
 import torch
@@ -40,6 +42,7 @@ class _Cfg:
         self.n_heads, self.scaled = n_heads, scaled
         self.pool_kind, self.A = pool_kind, A
         self.has_head, self.E, self.head_bias = has_head, E, head_bias
+        self.Eo = E if has_head else D  # the width of a pooled output row
         self.dropout_p, self.seed = dropout_p, seed
         self.want_a = want_a
         self.head_act = hip.ACT_RELU
@@ -74,6 +77,15 @@ def _param_structs(cfg: _Cfg, params: List[Optional[torch.Tensor]]):
     return ap, pp, hp, keep
 
 
+def _grad_structs(cfg: _Cfg, grads: List[Optional[torch.Tensor]]):
+    """The flat gradient list (the layout of the parameter list) as the C structs; None asks for no gradient."""
+    ptrs = [_addr(g) for g in grads]
+    i = 8 if cfg.n_heads > 0 else 0
+    j = i + 4 if cfg.pool_kind == hip.POOL_ADDITIVE else i
+    return (hip.MhaGrads(*ptrs[:i]) if i else None, hip.AdditiveGrads(*ptrs[i:j]) if j > i else None,
+            hip.HeadGrads(*ptrs[j:j + 4]) if cfg.has_head else None)
+
+
 #: forward and backward over the unmasked token rows only (exact; include/xnrs_hip.h: xnrs_seq_encoder_fwd_train_live /
 #: xnrs_seq_encoder_bwd_live).  Environment
 #: XNRS_BWD_LIVE_ROWS=0 turns it off; it is used when at most LIVE_ROWS_MAX_FRACTION of the rows are unmasked.
@@ -100,6 +112,28 @@ def _addr(t):
 
 def _f32_out(shape, dev):
     return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+class _Rows:
+    """The row lists of one encoder call (include/xnrs_hip.h: xnrs_row_lists): the unmasked token rows and the token rows of
+    the non-empty news, each with its table rows under ids, and their counts -- on the host (n_live, n_kv), or as capacities
+    with the counts on the device (counts).  No field set: no lists, the call runs dense."""
+    __slots__ = ("live", "live_src", "n_live", "kv", "kv_src", "n_kv", "counts")
+
+    def __init__(self, live=None, live_src=None, n_live=0, kv=None, kv_src=None, n_kv=0, counts=None):
+        self.live, self.live_src, self.n_live = live, live_src, n_live
+        self.kv, self.kv_src, self.n_kv, self.counts = kv, kv_src, n_kv, counts
+
+    def struct(self, qkv_shared, dqkv_image, dqkv_mode):
+        """-> the hip.RowLists of a call that reads the Q|K|V image at address qkv_shared (None: it projects) and defers or
+        merges its dQ|dK|dV in the tensor dqkv_image as dqkv_mode says; None when there is nothing to pass."""
+        if self.live is None and qkv_shared is None and dqkv_mode == hip.DQKV_OWN:
+            return None
+        return hip.RowLists(_addr(self.live), _addr(self.live_src), self.n_live, _addr(self.kv), _addr(self.kv_src), self.n_kv,
+                            qkv_shared, _addr(self.counts), _addr(dqkv_image), dqkv_mode)
+
+
+_NO_ROWS = _Rows()  # (never written to: every call without lists shares it)
 
 
 #: The reference's train step encodes the history twice (training.py:406 scores, :409 get_user_embeddings); with input
@@ -165,16 +199,31 @@ class _Pair:
     __slots__ = ("a", "b", "image", "task", "owner", "ran", "__weakref__")
 
     def __init__(self, a, b):
-        import weakref
         self.a, self.b = weakref.ref(a), weakref.ref(b)
         self.image = None   # the deferred dQ|dK|dV of the node that ran first
         self.task = -1      # ... and the backward pass (graph task id) it belongs to
         self.owner = 0      # ... and that node's id
         self.ran = {}       # node id -> graph task id of its last backward
 
-    def other(self, ctx):
-        a, b = self.a(), self.b()
-        return b if ctx is a else a
+    def decide(self, ctx, task, qkv_all, shape, dev):
+        """One dW product per projection for the two backwards over one Q|K|V image (see MERGE_DW above) -> (mode, image) of
+        node ctx in backward pass `task`.  qkv_all: ctx computes all six projection gradients and no input gradient.  MERGE:
+        the partner ran first in this pass and left its image.  DEFER: it is still to run, ctx leaves a new image of `shape`
+        and returns none of the six.  OWN otherwise."""
+        mode, image = hip.DQKV_OWN, None
+        if self.image is not None and self.task == task and self.owner != id(ctx) and qkv_all:
+            mode, image, self.image = hip.DQKV_MERGE, self.image, None
+            STATS["merged_dqkv_backwards"] += 1
+        else:
+            self.image = None  # (an image left by a pass whose second node never ran is dropped)
+            partner = self.b() if ctx is self.a() else self.a()
+            if (qkv_all and partner is not None and task != -1 and self.ran.get(id(partner)) != task
+                    and torch._C._will_engine_execute_node(partner)):
+                mode, image = hip.DQKV_DEFER, torch.empty(shape, dtype=torch.float32, device=dev)
+                self.image, self.task, self.owner = image, task, id(ctx)
+                STATS["deferred_dqkv_backwards"] += 1
+        self.ran[id(ctx)] = task
+        return mode, image
 
 
 def _ident(t):
@@ -191,6 +240,27 @@ def _where(dev):
 def _qkv_key(cfg, x, m, ids, params):
     return (_where(x.device), cfg.n_seq, cfg.L, cfg.D, cfg.n_heads, cfg.A, cfg.E, cfg.pool_kind, cfg.has_head, x.device.index, _ident(x), _ident(m),
             _ident(ids), tuple(_ident(p) for p in params[:6]))  # (_att_tensors order: wq, bq, wk, bk, wv, bv, wo, bo)
+
+
+#: a _QKV_IMAGES entry: the saved blob of a training forward (it holds the Q|K|V image) and that forward's autograd node, both
+#: by weak reference -- the entry dies with the forward's graph -- and its row lists
+_QkvImage = namedtuple("_QkvImage", "blob rows node")
+
+
+def _find_qkv_image(key):
+    """-> (blob, row lists, node or None) of the live forward under key, or three Nones; a dead entry is dropped."""
+    ent = _QKV_IMAGES.get(key) if key is not None else None
+    blob = ent.blob() if ent is not None else None
+    if blob is None:
+        _QKV_IMAGES.pop(key, None)
+        return None, None, None
+    return blob, ent.rows, ent.node()
+
+
+def _publish_qkv_image(key, blob, rows, node):
+    for k in [k for k, v in _QKV_IMAGES.items() if v.blob() is None]:
+        del _QKV_IMAGES[k]
+    _QKV_IMAGES[key] = _QkvImage(weakref.ref(blob), rows, weakref.ref(node))
 
 
 #: A tower's parameters are shared by every call of the tower (the news tower of a grad step is called for the candidates, the
@@ -214,7 +284,6 @@ class _ParamGroup:
 
 
 def _join_group(ctx, params):
-    import weakref
     if not SUM_SHARED_GRADS:
         return None
     key = tuple(None if p is None else id(p) for p in params)
@@ -232,7 +301,7 @@ def _join_group(ctx, params):
 def _sum_with_group(ctx, grads):
     """Keep this node's parameter gradients back if another node of its tower is still to run in this pass; otherwise add what
     the earlier nodes kept.  -> the list to return to autograd."""
-    g = getattr(ctx, "pgroup", None)
+    g = ctx.pgroup
     task = torch._C._current_graph_task_id()
     if g is None or task == -1:
         return grads
@@ -301,6 +370,55 @@ def _train_fold(l, cfg, params, ap, pp, dev):
     return w1f, b1f
 
 
+def _shape_args(cfg):
+    """What the library's size queries take."""
+    return cfg.n_seq, cfg.L, cfg.D, cfg.A, cfg.Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head)
+
+
+def _forward_prologue(ctx, l, cfg, params, dev):
+    """What a training forward of either encoder node prepares -> (ap, pp, hp, keep, saved): the parameter structs with the
+    fold pair in place and the blob for the saved activations; on ctx, what _backward_prologue reads."""
+    ap, pp, hp, keep = _param_structs(cfg, params)
+    ctx.fold_pair = _train_fold(l, cfg, params, ap, pp, dev)
+    if ctx.fold_pair is not None:  # (None: the call folds for itself)
+        pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
+    ctx.nsaved = l.xnrs_seq_encoder_saved_bytes(*_shape_args(cfg))
+    saved = torch.empty(max(ctx.nsaved, 1), dtype=torch.uint8, device=dev)
+    ctx.fold = l.xnrs_train_fold_enabled()  # the saved blob is laid out by this decision (include/xnrs_hip.h)
+    ctx.cfg = cfg
+    ctx.param_none = [p is None for p in params]
+    return ap, pp, hp, keep, saved
+
+
+def _backward_prologue(ctx, l, ptensors):
+    """... and its backward -> (params, ap, pp, hp, keep, nws): the parameter list as the forward took it (ptensors: the saved
+    ones, without the None entries), its structs with the forward's fold pair, and the size of the workspace -- which the
+    caller takes (hip.workspace) behind its own allocations, so that a growing workspace lands where it always did."""
+    cfg = ctx.cfg
+    it = iter(ptensors)
+    params = [None if isnone else next(it) for isnone in ctx.param_none]
+    ap, pp, hp, keep = _param_structs(cfg, params)
+    if ctx.fold_pair is not None:  # the pair the forward was given (the saved blob holds no copy then)
+        pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
+    if l.xnrs_train_fold_enabled() != ctx.fold:
+        raise hip.XnrsHipError("XNRS_FOLD_TRAIN changed between a training forward and its backward: the saved "
+                               "activations were laid out for the other setting (reload the knobs outside a step)")
+    return params, ap, pp, hp, keep, l.xnrs_seq_encoder_bwd_workspace_bytes(*_shape_args(cfg))
+
+
+def _build_rows(l, cfg, x, m, ids, params):
+    """The row lists of a training forward that found no earlier forward's to reuse."""
+    # Nothing that flows through a masked token row reaches the output or a gradient (its pooling weight is
+    # exp(e)*0), so the row-parallel products of an attention tower -- forward (query projection, output projection,
+    # fc1) and backward -- run over the unmasked rows only (xnrs_seq_encoder_fwd_train_live / _bwd_live).  Index
+    # bookkeeping with torch (one host sync for the count); skipped when few rows are masked.
+    if not (LIVE_ROWS and m is not None and cfg.pool_kind == hip.POOL_ADDITIVE and cfg.n_seq * cfg.L >= LIVE_ROWS_MIN):
+        return _NO_ROWS
+    if DEVICE_LISTS and _device_lists_ok(cfg, x, params):
+        return _device_lists(l, cfg, m, ids, x.device)
+    return _host_lists(cfg, m, ids, x.device)
+
+
 class _SeqEncode(torch.autograd.Function):
     """y = head(pool(att(x)))  (any stage optional) with saved activations for the HIP backward."""
 
@@ -309,80 +427,37 @@ class _SeqEncode(torch.autograd.Function):
         x = hip.dev_f32(x, "encoder input")
         dev = x.device
         n, L, D = cfg.n_seq, cfg.L, cfg.D
-        ap, pp, hp, keep = _param_structs(cfg, list(params))
         pooled = cfg.pool_kind != hip.POOL_NONE
-        Eo = cfg.E if cfg.has_head else D
-        y = torch.empty((n, Eo) if pooled else (n, L, D), dtype=torch.float32, device=dev)
+        y = torch.empty((n, cfg.Eo) if pooled else (n, L, D), dtype=torch.float32, device=dev)
         a = torch.empty((n, L), dtype=torch.float32, device=dev) if (cfg.want_a and cfg.pool_kind == hip.POOL_ADDITIVE) else None
         hm = torch.empty((n,), dtype=torch.float32, device=dev) if (pooled and m is not None) else None
         l = hip.lib()
-        ctx.fold_pair = _train_fold(l, cfg, params, ap, pp, dev)
-        if ctx.fold_pair is not None:
-            pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
-        nsaved = l.xnrs_seq_encoder_saved_bytes(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head))
-        saved = torch.empty(max(nsaved, 1), dtype=torch.uint8, device=dev)
-        # Nothing that flows through a masked token row reaches the output or a gradient (its pooling weight is
-        # exp(e)*0), so the row-parallel products of an attention tower -- forward (query projection, output projection,
-        # fc1) and backward -- run over the unmasked rows only (xnrs_seq_encoder_fwd_train_live / _bwd_live).  Index
-        # bookkeeping with torch (one host sync for the count); skipped when few rows are masked.
-        live = live_src = kv = kv_src = counts = None
-        n_live = n_kv = 0
-        shared = None  # (blob of an earlier forward over the same input and projection weights, its row lists, its node)
-        key = None
-        if SHARE_QKV and cfg.n_heads > 0:
-            key = _qkv_key(cfg, x, m, ids, params)
-            ent = _QKV_IMAGES.get(key)
-            if ent is not None:
-                blob = ent[0]()
-                if blob is None:
-                    del _QKV_IMAGES[key]
-                else:
-                    shared = (blob, ent[1], ent[2]())
-        want_lists = LIVE_ROWS and m is not None and cfg.pool_kind == hip.POOL_ADDITIVE and n * L >= LIVE_ROWS_MIN
-        if shared is not None:
-            live, live_src, n_live, kv, kv_src, n_kv, counts = shared[1]
-            STATS["shared_qkv_forwards"] += 1
-        elif want_lists and DEVICE_LISTS and _device_lists_ok(cfg, x, params):
-            live, live_src, kv, kv_src, counts = _device_lists(l, cfg, m, ids, dev)
-            n_live = n_kv = n * L  # capacities: the counts stay on the device
-            STATS["device_list_forwards"] += 1
-            STATS["live_row_forwards"] += 1
-            if KV_ROWS and cfg.n_heads > 0:
-                STATS["kv_row_forwards"] += 1
-            else:
-                kv = kv_src = None
-        elif want_lists:
-            live, live_src, n_live, kv, kv_src, n_kv = _host_lists(cfg, m, ids, dev)
+        ap, pp, hp, keep, saved = _forward_prologue(ctx, l, cfg, params, dev)
+        # blob of an earlier forward over the same input and projection weights, its row lists, its node
+        key = _qkv_key(cfg, x, m, ids, params) if SHARE_QKV and cfg.n_heads > 0 else None
+        blob, rows, first = _find_qkv_image(key)
         qkv_shared = None
-        if shared is not None:
-            qkv_shared = shared[0].data_ptr() + l.xnrs_seq_encoder_saved_qkv_offset(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind,
-                                                                                     int(cfg.has_head))
-        lists = None
-        if live is not None or qkv_shared is not None:
-            lists = hip.RowLists(_addr(live), _addr(live_src), n_live, _addr(kv), _addr(kv_src), n_kv, qkv_shared,
-                                 _addr(counts), None, hip.DQKV_OWN)
+        if blob is not None:
+            STATS["shared_qkv_forwards"] += 1
+            qkv_shared = blob.data_ptr() + l.xnrs_seq_encoder_saved_qkv_offset(*_shape_args(cfg))
+        else:
+            rows = _build_rows(l, cfg, x, m, ids, params)
+        lists = rows.struct(qkv_shared, None, hip.DQKV_OWN)
         hip.check(l.xnrs_seq_encoder_fwd_train_rows(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n, L, D, hip.ref(ap), cfg.pool_kind,
                                                     hip.ref(pp), hip.ref(hp), hip.ptr(y), hip.ptr(a), hip.ptr(hm), hip.ptr(saved),
-                                                    nsaved, hip.ref(lists), hip.stream_ptr(dev)),
+                                                    ctx.nsaved, hip.ref(lists), hip.stream_ptr(dev)),
                   "xnrs_seq_encoder_fwd_train_rows")
-        ctx.row_lists = (live, live_src, n_live, kv, kv_src, n_kv, counts)
-        ctx.qkv_shared = qkv_shared
-        ctx.qkv_owner = shared[0] if shared is not None else None  # keeps the other forward's blob alive until our backward
+        ctx.row_lists, ctx.qkv_shared = rows, qkv_shared
+        ctx.qkv_owner = blob  # keeps the other forward's blob alive until our backward
         ctx.pair = None
-        if shared is not None and shared[2] is not None and getattr(shared[2], "pair", None) is None:
-            ctx.pair = shared[2].pair = _Pair(shared[2], ctx)  # the two backwards share one dW product per projection
-        if key is not None and shared is None:
-            import weakref
-            for k in [k for k, v in _QKV_IMAGES.items() if v[0]() is None]:
-                del _QKV_IMAGES[k]
-            _QKV_IMAGES[key] = (weakref.ref(saved), ctx.row_lists, weakref.ref(ctx))
+        if first is not None and first.pair is None:
+            ctx.pair = first.pair = _Pair(first, ctx)  # the two backwards share one dW product per projection
+        if key is not None and blob is None:
+            _publish_qkv_image(key, saved, rows, ctx)
         ctx.pgroup = _join_group(ctx, params)
-        ctx.fold = l.xnrs_train_fold_enabled()  # the saved blob is laid out by this decision (include/xnrs_hip.h)
-        ctx.cfg = cfg
-        ctx.nsaved = nsaved
+        ctx.okey = None  # (_run: the key of this forward's _OUTPUTS entry)
         ctx.n_params = len(params)
         ctx.save_for_backward(x, m, ids, saved, *[p for p in params if p is not None])
-        ctx.param_none = [p is None for p in params]
         outs = [y, a if a is not None else y.new_empty(0), hm if hm is not None else y.new_empty(0)]
         ctx.mark_non_differentiable(outs[1], outs[2])
         ctx.set_materialize_grads(False)  # (the two side outputs never carry a gradient: no zero tensors are made for them)
@@ -390,73 +465,33 @@ class _SeqEncode(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _da, _dhm):
-        _OUTPUTS.pop(getattr(ctx, "okey", None), None)  # the graph is being consumed: its outputs are no longer shareable
+        _OUTPUTS.pop(ctx.okey, None)  # the graph is being consumed: its outputs are no longer shareable
         if dy is None:  # (nothing flows into the only differentiable output)
             return (None,) * (4 + ctx.n_params)
         cfg = ctx.cfg
         x, m, ids, saved, *ptensors = ctx.saved_tensors
-        it = iter(ptensors)
-        params = [None if isnone else next(it) for isnone in ctx.param_none]
         dev = x.device
         n, L, D = cfg.n_seq, cfg.L, cfg.D
-        Eo = cfg.E if cfg.has_head else D
-        ap, pp, hp, keep = _param_structs(cfg, params)
-        if getattr(ctx, "fold_pair", None) is not None:  # the pair the forward was given (the saved blob holds no copy then)
-            pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
-        dy = hip.dev_f32(dy, "grad output")
         need = ctx.needs_input_grad  # (cfg, x, m, ids, *params)
         want_dx = need[1]
         if want_dx and ids is not None:
             raise hip.XnrsHipError("no input gradient through an id-gathered news table")
+        l = hip.lib()
+        params, ap, pp, hp, keep, nws = _backward_prologue(ctx, l, ptensors)
+        dy = hip.dev_f32(dy, "grad output")
         dx = torch.empty((n, L, D), dtype=torch.float32, device=dev) if want_dx else None
         wanted = _wanted_inputs(ctx, [False, True, m is not None, ids is not None] + [p is not None for p in params], 4)
-        grads: List[Optional[torch.Tensor]] = []
-        for j, p in enumerate(params):
-            grads.append(torch.empty_like(p, dtype=torch.float32) if (p is not None and need[4 + j] and wanted[j]) else None)
-        i = 0
-        ga = gp = gh = None
-        if cfg.n_heads > 0:
-            ga = hip.MhaGrads(*[None if g is None else g.data_ptr() for g in grads[i:i + 8]])
-            i += 8
-        if cfg.pool_kind == hip.POOL_ADDITIVE:
-            gp = hip.AdditiveGrads(*[None if g is None else g.data_ptr() for g in grads[i:i + 4]])
-            i += 4
-        if cfg.has_head:
-            gh = hip.HeadGrads(*[None if g is None else g.data_ptr() for g in grads[i:i + 4]])
-            i += 4
-        l = hip.lib()
-        if l.xnrs_train_fold_enabled() != ctx.fold:
-            raise hip.XnrsHipError("XNRS_FOLD_TRAIN changed between a training forward and its backward: the saved "
-                                   "activations were laid out for the other setting (reload the knobs outside a step)")
-        nws = l.xnrs_seq_encoder_bwd_workspace_bytes(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head))
+        grads = [torch.empty_like(p, dtype=torch.float32) if (p is not None and need[4 + j] and wanted[j]) else None
+                 for j, p in enumerate(params)]
         ws = hip.workspace(dev, nws)
-        live, live_src, n_live, kv, kv_src, n_kv, counts = ctx.row_lists  # the row lists built by the forward
-        # one dW product per projection for the two backwards over one Q|K|V image (see MERGE_DW above)
         mode, image = hip.DQKV_OWN, None
-        pair = ctx.pair
-        if pair is not None:
-            task = torch._C._current_graph_task_id()
+        if ctx.pair is not None:
             qkv_all = MERGE_DW and not want_dx and all(g is not None for g in grads[:6])
-            if pair.image is not None and pair.task == task and pair.owner != id(ctx) and qkv_all:
-                mode, image, pair.image = hip.DQKV_MERGE, pair.image, None
-                STATS["merged_dqkv_backwards"] += 1
-            else:
-                pair.image = None  # (an image left by a pass whose second node never ran is dropped)
-                partner = pair.other(ctx)
-                if (qkv_all and partner is not None and task != -1 and pair.ran.get(id(partner)) != task
-                        and torch._C._will_engine_execute_node(partner)):
-                    mode, image = hip.DQKV_DEFER, torch.empty((n * L, 3 * D), dtype=torch.float32, device=dev)
-                    pair.image, pair.task, pair.owner = image, task, id(ctx)
-                    for j in range(6):
-                        grads[j] = None  # the merging node returns them (computed from the sum)
-                    STATS["deferred_dqkv_backwards"] += 1
-            pair.ran[id(ctx)] = task
-            if cfg.n_heads > 0:
-                ga = hip.MhaGrads(*[None if g is None else g.data_ptr() for g in grads[0:8]])
-        lists = None
-        if live is not None or ctx.qkv_shared is not None or mode != hip.DQKV_OWN:
-            lists = hip.RowLists(_addr(live), _addr(live_src), n_live, _addr(kv), _addr(kv_src), n_kv, ctx.qkv_shared,
-                                 _addr(counts), _addr(image), mode)
+            mode, image = ctx.pair.decide(ctx, torch._C._current_graph_task_id(), qkv_all, (n * L, 3 * D), dev)
+            if mode == hip.DQKV_DEFER:
+                grads[:6] = [None] * 6  # the merging node returns them (computed from the sum)
+        ga, gp, gh = _grad_structs(cfg, grads)
+        lists = ctx.row_lists.struct(ctx.qkv_shared, image, mode)  # the row lists built by the forward
         hip.check(l.xnrs_seq_encoder_bwd_rows(hip.ptr(x), hip.ptr(m), hip.ptr(ids), n, L, D, hip.ref(ap), cfg.pool_kind, hip.ref(pp),
                                               hip.ref(hp), hip.ptr(saved), ctx.nsaved, hip.ptr(dy), hip.ptr(dx), hip.ref(ga),
                                               hip.ref(gp), hip.ref(gh), hip.ref(lists), hip.ptr(ws), nws,
@@ -468,31 +503,28 @@ def _host_lists(cfg, m, ids, dev):
     """The row lists by torch bookkeeping: a nonzero and ONE host read for both counts (round 3's path; kept for shapes the
     device-counted kernels do not serve and behind XNRS_DEVICE_LISTS=0)."""
     n, L = cfg.n_seq, cfg.L
-    live = live_src = kv = kv_src = None
-    n_kv = 0
     lm = (m[ids.long()] if ids is not None else m).reshape(n, L).ne(0)
     news_live = lm.any(dim=1)
     n_live, n_news_live = (int(v) for v in torch.stack([lm.sum(), news_live.sum()]).tolist())
     if n_live > LIVE_ROWS_MAX_FRACTION * n * L:
-        return None, None, 0, None, None, 0
+        return _NO_ROWS
     rows_live = torch.nonzero_static(lm.reshape(-1), size=n_live).squeeze(1)
-    live = rows_live.to(torch.int32)
+    r = _Rows(rows_live.to(torch.int32), n_live=n_live)
     STATS["live_row_forwards"] += 1
-    src_news = ids.long() if ids is not None else None
     if ids is not None:
+        src_news = ids.long()
         seq = torch.div(rows_live, L, rounding_mode="floor")
-        live_src = (src_news[seq] * L + (rows_live - seq * L)).to(torch.int32)
+        r.live_src = (src_news[seq] * L + (rows_live - seq * L)).to(torch.int32)
     # the token rows of the non-empty news: K and V are projected (and their weight gradients summed) over
     # these only -- nobody reads the keys of a news without a live query (include/xnrs_hip.h: xnrs_row_lists)
     if KV_ROWS and cfg.n_heads > 0 and n_news_live < n:
         news_idx = torch.nonzero_static(news_live, size=n_news_live).squeeze(1)
         tok = torch.arange(L, device=dev)
-        kv = (news_idx[:, None] * L + tok[None, :]).reshape(-1).to(torch.int32)
-        n_kv = n_news_live * L
+        r.kv, r.n_kv = (news_idx[:, None] * L + tok[None, :]).reshape(-1).to(torch.int32), n_news_live * L
         STATS["kv_row_forwards"] += 1
         if ids is not None:
-            kv_src = (src_news[news_idx][:, None] * L + tok[None, :]).reshape(-1).to(torch.int32)
-    return live, live_src, n_live, kv, kv_src, n_kv
+            r.kv_src = (src_news[news_idx][:, None] * L + tok[None, :]).reshape(-1).to(torch.int32)
+    return r
 
 
 def _device_lists_ok(cfg, x, params) -> bool:
@@ -500,9 +532,7 @@ def _device_lists_ok(cfg, x, params) -> bool:
     encoder_fwd.hip checks again: fp32 GEMM mode, D and A multiples of 4, 16-byte aligned input and weights.)"""
     if hip.get_gemm_mode() != 0 or cfg.D % 4 != 0 or cfg.A % 4 != 0 or cfg.n_seq * cfg.L >= 2 ** 31:
         return False
-    if x.data_ptr() % 16 != 0:
-        return False
-    return all(p is None or p.data_ptr() % 16 == 0 for p in params)
+    return x.data_ptr() % 16 == 0 and all(p is None or p.data_ptr() % 16 == 0 for p in params)
 
 
 def _device_lists(l, cfg, m, ids, dev):
@@ -517,7 +547,13 @@ def _device_lists(l, cfg, m, ids, dev):
     hip.check(l.xnrs_build_row_lists(hip.ptr(m), hip.ptr(ids), n, L, hip.ptr(live), hip.ptr(live_src), hip.ptr(kv),
                                      hip.ptr(kv_src), hip.ptr(counts), hip.ptr(ws), nws, hip.stream_ptr(dev)),
               "xnrs_build_row_lists")
-    return live, live_src, kv, kv_src, counts
+    STATS["device_list_forwards"] += 1
+    STATS["live_row_forwards"] += 1
+    if KV_ROWS and cfg.n_heads > 0:
+        STATS["kv_row_forwards"] += 1
+    else:
+        kv = kv_src = None
+    return _Rows(live, live_src, cap, kv, kv_src, cap, counts)  # capacities: the counts stay on the device
 
 
 class _SeqEncodeFromQkv(torch.autograd.Function):
@@ -538,27 +574,17 @@ class _SeqEncodeFromQkv(torch.autograd.Function):
             raise hip.XnrsHipError(f"Q|K|V image {tuple(qkv.shape)}: expected {(n * L, 3 * D)}")
         if qkv.data_ptr() % hip.WORKSPACE_ALIGN:
             raise hip.XnrsHipError(f"Q|K|V image at {qkv.data_ptr():#x} is not {hip.WORKSPACE_ALIGN}-byte aligned")
-        params = list(params)
-        ap, pp, hp, keep = _param_structs(cfg, params)
-        Eo = cfg.E if cfg.has_head else D
-        y = torch.empty((n, Eo), dtype=torch.float32, device=dev)
+        y = torch.empty((n, cfg.Eo), dtype=torch.float32, device=dev)
         hm = torch.empty((n,), dtype=torch.float32, device=dev)
         l = hip.lib()
-        ctx.fold_pair = _train_fold(l, cfg, params, ap, pp, dev)
-        if ctx.fold_pair is not None:
-            pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
-        nsaved = l.xnrs_seq_encoder_saved_bytes(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head))
-        saved = torch.empty(max(nsaved, 1), dtype=torch.uint8, device=dev)
-        lists = hip.RowLists(None, None, 0, None, None, 0, qkv.data_ptr(), None, None, hip.DQKV_OWN)
+        ap, pp, hp, keep, saved = _forward_prologue(ctx, l, cfg, params, dev)
+        lists = _NO_ROWS.struct(qkv.data_ptr(), None, hip.DQKV_OWN)
         # x: the entry points want a non-NULL input; with a given image nothing reads it (project() returns at once, every
         # later stage of an attention tower reads the image or what follows it, and the deferring backward stops before the
         # projection products) -- the image's own address stands in, which is at least as large as the tokens would be
         hip.check(l.xnrs_seq_encoder_fwd_train_rows(hip.ptr(qkv), hip.ptr(m), None, n, L, D, hip.ref(ap), cfg.pool_kind, hip.ref(pp),
-                                                    hip.ref(hp), hip.ptr(y), None, hip.ptr(hm), hip.ptr(saved), nsaved,
+                                                    hip.ref(hp), hip.ptr(y), None, hip.ptr(hm), hip.ptr(saved), ctx.nsaved,
                                                     hip.ref(lists), hip.stream_ptr(dev)), "xnrs_seq_encoder_fwd_train_rows")
-        ctx.fold = l.xnrs_train_fold_enabled()  # the saved blob is laid out by this decision (include/xnrs_hip.h)
-        ctx.cfg, ctx.nsaved = cfg, nsaved
-        ctx.param_none = [p is None for p in params]
         ctx.save_for_backward(qkv, m, saved, *[p for p in params if p is not None])
         ctx.mark_non_differentiable(hm)
         ctx.set_materialize_grads(False)
@@ -570,28 +596,39 @@ class _SeqEncodeFromQkv(torch.autograd.Function):
             return None, None, None, None
         cfg = ctx.cfg
         qkv, m, saved, *ptensors = ctx.saved_tensors
-        it = iter(ptensors)
-        params = [None if isnone else next(it) for isnone in ctx.param_none]
         dev = qkv.device
         n, L, D = cfg.n_seq, cfg.L, cfg.D
-        Eo = cfg.E if cfg.has_head else D
-        ap, pp, hp, keep = _param_structs(cfg, params)
-        if ctx.fold_pair is not None:  # the pair the forward was given (the saved blob holds no copy then)
-            pp.w1_folded, pp.b1_folded = ctx.fold_pair[0].data_ptr(), ctx.fold_pair[1].data_ptr()
-        dy = hip.dev_f32(dy, "grad output")
         l = hip.lib()
-        if l.xnrs_train_fold_enabled() != ctx.fold:
-            raise hip.XnrsHipError("XNRS_FOLD_TRAIN changed between a training forward and its backward: the saved "
-                                   "activations were laid out for the other setting (reload the knobs outside a step)")
-        nws = l.xnrs_seq_encoder_bwd_workspace_bytes(n, L, D, cfg.A, Eo, cfg.n_heads, cfg.pool_kind, int(cfg.has_head))
+        params, ap, pp, hp, keep, nws = _backward_prologue(ctx, l, ptensors)
+        dy = hip.dev_f32(dy, "grad output")
         ws = hip.workspace(dev, nws)
         image = _f32_out((n * L, 3 * D), dev)
         # no row lists: dead_seq_mode 0, the attention backward writes EVERY row of the image (the reduce sums every row)
-        lists = hip.RowLists(None, None, 0, None, None, 0, qkv.data_ptr(), None, image.data_ptr(), hip.DQKV_DEFER)
+        lists = _NO_ROWS.struct(qkv.data_ptr(), image, hip.DQKV_DEFER)
         hip.check(l.xnrs_seq_encoder_bwd_rows(hip.ptr(qkv), hip.ptr(m), None, n, L, D, hip.ref(ap), cfg.pool_kind, hip.ref(pp),
                                               hip.ref(hp), hip.ptr(saved), ctx.nsaved, hip.ptr(dy), None, None, None, None,
                                               hip.ref(lists), hip.ptr(ws), nws, hip.stream_ptr(dev)), "xnrs_seq_encoder_bwd_rows")
         return None, image, None, None
+
+
+def _encoder_cfg(n, L, D, att, pooler, head, pool_kind, dropout_p, seed, want_a):
+    """-> (cfg, params) of a call of n sequences through the modules given (att and head may be None): the static description
+    and the flat parameter list (att 8 | pool 4 | head 4) that _param_structs splits again."""
+    params: List[Optional[torch.Tensor]] = []
+    n_heads, scaled, A, E, has_head = 0, True, 0, D, False
+    if att is not None:
+        params += _att_tensors(att)
+        n_heads, scaled = att.h, att.scaled
+    if pool_kind == hip.POOL_ADDITIVE:
+        params += _pool_tensors(pooler)
+        A = pooler.fc1.out_features
+    if head is not None:
+        params += _head_tensors(head)
+        has_head, E = True, head[0].out_features
+    cfg = _Cfg(n, L, D, n_heads, scaled, pool_kind, A, has_head, E, False, dropout_p, seed, want_a)
+    if head is not None:
+        cfg.head_act = hip.head_activation(head[1])
+    return cfg, params
 
 
 def text_encoder_from_qkv(qkv, x, m, enc, dropout_p, seed):
@@ -604,19 +641,8 @@ def text_encoder_from_qkv(qkv, x, m, enc, dropout_p, seed):
     if m is None:
         raise hip.XnrsHipError("text_encoder_from_qkv needs the token mask")
     m2 = ops._mask2d(m, n, L, "encoder mask")
-    att, pooler, head = enc.att, enc.pooler, getattr(enc, "head", None)
-    pool_kind = _pool_kind(pooler)
-    params: List[Optional[torch.Tensor]] = _att_tensors(att)
-    A, E, has_head = 0, D, False
-    if pool_kind == hip.POOL_ADDITIVE:
-        params += _pool_tensors(pooler)
-        A = pooler.fc1.out_features
-    if head is not None:
-        params += _head_tensors(head)
-        has_head, E = True, head[0].out_features
-    cfg = _Cfg(n, L, D, att.h, att.scaled, pool_kind, A, has_head, E, False, dropout_p, seed, False)
-    if head is not None:
-        cfg.head_act = hip.head_activation(head[1])
+    cfg, params = _encoder_cfg(n, L, D, enc.att, enc.pooler, getattr(enc, "head", None), _pool_kind(enc.pooler), dropout_p,
+                               seed, False)
     # the parameters travel as a tuple: they are no inputs of the node, so no backward pass is ever asked for their gradients
     return _SeqEncodeFromQkv.apply(cfg, qkv, m2, tuple(params))
 
@@ -646,10 +672,48 @@ def _alive(refs, objs):
     return all((r is None and o is None) or (r is not None and r() is _root(o)) for r, o in zip(refs, objs))
 
 
+#: an _OUTPUTS entry: the tick of its last use, the call's tensor arguments by weak reference (a claim needs the very same
+#: objects), the outputs (y, a, hm), y's version when they were made and the bytes of saved activations the entry pins
+_Output = namedtuple("_Output", "tick refs outs version nbytes")
+
+
+def _claim_output(okey, objs):
+    """One encoder call further: entries unclaimed for _OUTPUTS_HORIZON calls are dropped.  -> the outputs under okey (None:
+    this call shares nothing) if they still stand for a call with the tensors objs (else that entry is dropped), or None."""
+    global _TICK
+    _TICK += 1
+    for k in [k for k, v in _OUTPUTS.items() if _TICK - v.tick > _OUTPUTS_HORIZON]:
+        del _OUTPUTS[k]  # (never claimed: a forward in grad mode that nobody repeated)
+    hit = _OUTPUTS.get(okey) if okey is not None else None
+    if hit is None:
+        return None
+    y = hit.outs[0]
+    if _alive(hit.refs, objs) and y._version == hit.version and y.grad_fn is not None:
+        STATS["shared_output_forwards"] += 1
+        _OUTPUTS[okey] = hit._replace(tick=_TICK)
+        return hit.outs
+    del _OUTPUTS[okey]
+    return None
+
+
+def _publish_output(okey, objs, outs):
+    # the entry holds the outputs themselves (modules drop them: a view of y fed to torch.cat keeps nothing alive) and
+    # is dropped by the node's backward, or after _OUTPUTS_HORIZON further encoder calls
+    node = outs[0].grad_fn
+    refs = [None if o is None else weakref.ref(_root(o)) for o in objs]
+    _OUTPUTS[okey] = _Output(_TICK, refs, outs, outs[0]._version, node.nsaved)
+    node.okey = okey
+    pinned = sum(v.nbytes for v in _OUTPUTS.values())
+    for k in sorted(_OUTPUTS, key=lambda k: _OUTPUTS[k].tick):  # oldest first; the entry just made always stays
+        if pinned <= _OUTPUTS_MAX_BYTES or k == okey:
+            break
+        pinned -= _OUTPUTS[k].nbytes
+        del _OUTPUTS[k]
+
+
 def _run(x, m, ids, att, pooler, head, pool_kind, dropout_p, seed, want_a):
     from . import ops
-    import weakref
-    x_in, m_in, ids_in = x, m, ids
+    objs = [x, m, ids]
     x = hip.dev_f32(x, "encoder input")
     n_tab, L, D = x.shape
     m2 = ops._mask2d(m, n_tab, L, "encoder mask")
@@ -658,53 +722,20 @@ def _run(x, m, ids, att, pooler, head, pool_kind, dropout_p, seed, want_a):
         n = ids.numel()
     else:
         n = n_tab
-    params: List[Optional[torch.Tensor]] = []
-    n_heads, scaled, A, E, has_head, head_bias = 0, True, 0, D, False, False
-    if att is not None:
-        params += _att_tensors(att)
-        n_heads, scaled = att.h, att.scaled
-    if pool_kind == hip.POOL_ADDITIVE:
-        params += _pool_tensors(pooler)
-        A = pooler.fc1.out_features
-    if head is not None:
-        params += _head_tensors(head)
-        has_head, E = True, head[0].out_features
-    cfg = _Cfg(n, L, D, n_heads, scaled, pool_kind, A, has_head, E, head_bias, dropout_p, seed, want_a)
-    if head is not None:
-        cfg.head_act = hip.head_activation(head[1])
+    cfg, params = _encoder_cfg(n, L, D, att, pooler, head, pool_kind, dropout_p, seed, want_a)
     okey = None
-    global _TICK
-    _TICK += 1
-    for k in [k for k, v in _OUTPUTS.items() if _TICK - v[0] > _OUTPUTS_HORIZON]:
-        del _OUTPUTS[k]  # (never claimed: a forward in grad mode that nobody repeated)
-    if SHARE_OUTPUTS and (n_heads == 0 or dropout_p == 0.0) and torch.is_grad_enabled():
-        objs = [x_in, m_in, ids_in] + params
-        okey = (_where(x.device), n, L, D, n_heads, scaled, pool_kind, A, has_head, E, cfg.head_act, want_a, x.device.index, _ident(x), _ident(m2),
-                _ident(ids), tuple(_ident(p) for p in params))
-        hit = _OUTPUTS.get(okey)
-        if hit is not None:
-            _, refs, (y, a, hm), ver, _nb = hit
-            if _alive(refs, objs) and y._version == ver and y.grad_fn is not None:
-                STATS["shared_output_forwards"] += 1
-                hit[0] = _TICK
-                return y, a, hm
-            del _OUTPUTS[okey]
+    if SHARE_OUTPUTS and (cfg.n_heads == 0 or dropout_p == 0.0) and torch.is_grad_enabled():
+        objs += params
+        okey = (_where(x.device), n, L, D, cfg.n_heads, cfg.scaled, pool_kind, cfg.A, cfg.has_head, cfg.E, cfg.head_act, want_a,
+                x.device.index, _ident(x), _ident(m2), _ident(ids), tuple(_ident(p) for p in params))
+    outs = _claim_output(okey, objs)
+    if outs is not None:
+        return outs
     y, a, hm = _SeqEncode.apply(cfg, x, m2, ids, *params)
-    a = a if a.numel() else None
-    hm = hm if hm.numel() else None
+    outs = (y, a if a.numel() else None, hm if hm.numel() else None)
     if okey is not None and y.grad_fn is not None:
-        # the entry holds the outputs themselves (modules drop them: a view of y fed to torch.cat keeps nothing alive) and
-        # is dropped by the node's backward, or after _OUTPUTS_HORIZON further encoder calls
-        wr = lambda t: None if t is None else weakref.ref(t)  # noqa: E731
-        _OUTPUTS[okey] = [_TICK, [wr(_root(o)) for o in objs], (y, a, hm), y._version, int(getattr(y.grad_fn, "nsaved", 0))]
-        y.grad_fn.okey = okey
-        pinned = sum(v[4] for v in _OUTPUTS.values())
-        for k in sorted(_OUTPUTS, key=lambda k: _OUTPUTS[k][0]):  # oldest first; the entry just made always stays
-            if pinned <= _OUTPUTS_MAX_BYTES or k == okey:
-                break
-            pinned -= _OUTPUTS[k][4]
-            del _OUTPUTS[k]
-    return y, a, hm
+        _publish_output(okey, objs, outs)
+    return outs
 
 
 def _pool_kind(pooler):
