@@ -935,6 +935,63 @@ int32_t xnrs_list_loss_bwd(const float *table, int64_t n_rows, int32_t E, const 
                            int32_t pad_row, const float *scores, const float *lse, const float *neg_scores, const float *g,
                            const int32_t *order, float *d_up, float *d_table, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- diverse lists: MMR re-ranking and intra-list distance over the table's own vectors (csrc/diversity.hip) ---------------
+ * Beyond-accuracy measures of a recommended list, and the re-ranking that trades relevance for variety.  Both rest on ONE
+ * similarity of two rows a, b of table:(n_rows,E) fp32 (the encoded news vectors, not a scorer's prepared table):
+ *   inv[r]    = 1 / sqrt(sum_e x[r][e]^2), 0 when the sum is 0        (xnrs_row_inv_norms, once per encoded table)
+ *   cos(a, b) = (sum_e x[a][e] x[b][e]) * inv[a] * inv[b]
+ * one device function: a lane's fp32 fma chain over the elements [4 l, 4 l + 4) + 256 j in ascending j, a butterfly over the 64
+ * lanes, then the two products.  The order is a function of E alone -- not of B, P, k, the session's place in the batch or an
+ * operand's alignment (E % 4 != 0 or a table off the 16-byte boundary takes scalar loads of the same elements in the same
+ * order).  A zero row has inv = 0: its cosines are 0, never NaN.  table must be finite.
+ *
+ * xnrs_row_inv_norms: inv_out:(n_rows,) fp32; one wave per row, one read of the table, no copy of it.
+ *
+ * xnrs_mmr_rerank: greedy maximal marginal relevance over a candidate list per session, e.g. the rows and scores of
+ * xnrs_topk_deep*.  pool_rows:(B,P) int32, pool_scores:(B,P) fp32.  A place i is VALID when 0 <= pool_rows[b][i] < n_rows and
+ * its score is finite; every other place (the -1 fillers, ids outside the table, NaN, +-inf) is ignored, its row compared and
+ * never dereferenced.  A row listed at two places is two candidates.
+ *   relevance r_i : XNRS_MMR_REL_RAW: the score s_i; XNRS_MMR_REL_MINMAX: (s_i - s_min) / (s_max - s_min) over the session's
+ *                   valid places, 0 when s_max == s_min (s_max - s_min must be finite).
+ *   for t = 0 .. k-1: among the valid places not yet selected pick the largest obj_i = lam * r_i - (1 - lam) * m_i, m_i = the
+ *                   largest cos(row_i, row_j) over the places j selected so far, m_i = 0 at t = 0; the two products and the
+ *                   difference are each rounded to fp32 (at lam = 1 the objective is r_i exactly).  Equal objectives (==, so
+ *                   -0 and +0 tie) go to the lower place.
+ *   out_rows[b][t] = the row, out_scores[b][t] = the pool's score, ITS OWN BITS (never recomputed), out_pos[b][t] = the place
+ *                   (int32).  Once the valid places run out: -1 / -inf / -1.
+ * Hence: at lam = 1 a pool in the order of xnrs_topk_deep* comes back as its own first k places; mmr(k)[:, :j] == mmr(j);
+ * a session's outputs depend on nothing but its own pool -- not on B or its position in the batch -- and are the same bits on
+ * every run.  One launch, one workgroup per session with the session's state in LDS (relevance, m, the alive flags and the row
+ * selected last); the pool's rows are streamed again every step, about k P E 4 bytes per session.  No workspace, no float
+ * atomics, no host synchronisation, no allocation, hipGraph-capturable.
+ * Limits: 1 <= k <= P <= XNRS_TOPK_DEEP_MAX_K, 0 <= lam <= 1 (NaN refused), 1 <= E <= XNRS_DIVERSITY_MAX_E (the row in LDS),
+ * n_rows <= 2^31 - 1, rel_mode one of the two.  A violation returns XNRS_EINVAL on the host before any launch and writes
+ * nothing.  B == 0: XNRS_OK, nothing written.
+ *
+ * xnrs_list_diversity: rows:(B,k) int32 lists (of xnrs_topk*, xnrs_mmr_rerank, anything); a place is valid when its row is
+ * inside [0, n_rows).  Per session b:
+ *   out_n[b]       = the number of valid places n (int32)
+ *   out_ild[b]     = pair_sum / n_pairs, ONE fp32 division of the fp32 sum of 1 - cos(row_i, row_j) over the valid pairs i < j
+ *                    by n (n - 1) / 2; 0 when n < 2.  A row listed twice is two places (their distance is 1 - cos of the row
+ *                    with itself).  The order of the sum is a function of (k, E) alone.
+ *   with row_cat:(n_rows,) int32 not NULL (else out_ncat / out_diffcat are not written and may be NULL; n_cat is still checked):
+ *   out_ncat[b]    = the number of distinct categories among the valid places
+ *   out_diffcat[b] = the number of valid pairs i < j whose categories differ
+ *                    a category outside [0, n_cat) takes its place out of both counts.
+ * Limits: 1 <= k <= XNRS_TOPK_MAX_K, 0 <= n_cat <= XNRS_DIVERSITY_MAX_CATEGORIES (an LDS histogram, integer atomics), E as
+ * above; refusals, B == 0 and the launch properties as xnrs_mmr_rerank.  A session's outputs do not depend on the batch. */
+#define XNRS_MMR_REL_RAW 0
+#define XNRS_MMR_REL_MINMAX 1
+#define XNRS_DIVERSITY_MAX_E 4096
+#define XNRS_DIVERSITY_MAX_CATEGORIES 4096
+int32_t xnrs_row_inv_norms(const float *table, int64_t n_rows, int32_t E, float *inv_out, void *stream);
+int32_t xnrs_mmr_rerank(const float *table, const float *inv, int64_t n_rows, int32_t E, const int32_t *pool_rows,
+                        const float *pool_scores, int64_t B, int32_t P, int32_t k, float lam, int32_t rel_mode,
+                        int32_t *out_rows, float *out_scores, int32_t *out_pos, void *stream);
+int32_t xnrs_list_diversity(const float *table, const float *inv, int64_t n_rows, int32_t E, const int32_t *rows, int64_t B,
+                            int32_t k, const int32_t *row_cat, int32_t n_cat, float *out_ild, int32_t *out_n,
+                            int32_t *out_ncat, int32_t *out_diffcat, void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

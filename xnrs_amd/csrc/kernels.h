@@ -726,6 +726,17 @@ hipError_t launch_score_csr_bilinear(const float* vecs, const int32_t* rows, con
 hipError_t launch_score_csr_mlp(const float* P, const int32_t* rows, const int32_t* sess, const float* q, const float* w2,
                                 const float* b2, float* r, int64_t n, int H, int relu, hipStream_t stream);
 
+// ---------------------------------------------------------------- diverse lists (diversity.hip; include/xnrs_hip.h)
+// inv[r] = 1 / ||table[r]|| (0 for a zero row); greedy MMR over (B, P) candidate lists; intra-list distance and category
+// counts of (B, k) lists.  The callers have checked the limits (P <= 1024, k <= 128, E <= 4096, n_cat <= 4096).
+hipError_t launch_row_inv_norms(const float* table, int64_t n_rows, int E, float* inv, hipStream_t stream);
+hipError_t launch_mmr_rerank(const float* table, const float* inv, int64_t n_rows, int E, const int32_t* pool_rows,
+                             const float* pool_scores, int64_t B, int P, int k, float lam, int rel_mode, int32_t* out_rows,
+                             float* out_scores, int32_t* out_pos, hipStream_t stream);
+hipError_t launch_list_diversity(const float* table, const float* inv, int64_t n_rows, int E, const int32_t* rows, int64_t B, int k,
+                                 const int32_t* row_cat, int n_cat, float* out_ild, int32_t* out_n, int32_t* out_ncat,
+                                 int32_t* out_diffcat, hipStream_t stream);
+
 // ---------------------------------------------------------------- in-batch InfoNCE (training.py:433-472)
 // ws: (B*E + 4*B + 1) floats = normalised embeddings | 1/norm | num | den | L_i | 1/(count+1e-8); kept for the backward
 hipError_t launch_infonce_fwd(const float* x, const int64_t* lab, int64_t B, int E, float temperature, float* loss, float* ws,

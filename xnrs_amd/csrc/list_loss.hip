@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "host.h"
+#include "row_dot.h"
 
 namespace xnrs {
 
@@ -58,31 +59,12 @@ struct ListArgs {
   float* neg_scores;  // (B, L)
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
   return v;
 }
 
-// the four floats [i, i + 4) of a row of E floats; beyond E: 0.  VEC: one 16-byte load (E % 4 == 0, aligned base)
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float* __restrict__ p, int i, int E) {
-  if constexpr (VEC) {
-    return *reinterpret_cast<const float4*>(p + i);
-  } else {
-    float4 v;
-    v.x = i < E ? p[i] : 0.f;
-    v.y = i + 1 < E ? p[i + 1] : 0.f;
-    v.z = i + 2 < E ? p[i + 2] : 0.f;
-    v.w = i + 3 < E ? p[i + 3] : 0.f;
-    return v;
-  }
-}
 template <bool VEC>
 __device__ __forceinline__ void store4(float* __restrict__ p, int i, int E, float4 v) {
   if constexpr (VEC) {
@@ -93,12 +75,6 @@ __device__ __forceinline__ void store4(float* __restrict__ p, int i, int E, floa
     if (i + 2 < E) p[i + 2] = v.z;
     if (i + 3 < E) p[i + 3] = v.w;
   }
-}
-__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
-  acc = fmaf(a.x, b.x, acc);
-  acc = fmaf(a.y, b.y, acc);
-  acc = fmaf(a.z, b.z, acc);
-  return fmaf(a.w, b.w, acc);
 }
 __device__ __forceinline__ void axpy4(float4& acc, float s, float4 x) {
   acc.x = fmaf(s, x.x, acc.x);

@@ -277,11 +277,14 @@ def _recommending_model_parts(model, behaviors: Behaviors, k: int, windowed: boo
 
 
 def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions, batch: int,
-                        exclude_history: bool, windows=None):
+                        exclude_history: bool, windows=None, vecs_out=None):
     """The table of `model` encoded once, then per batch of sessions (lo, sess, hist rows, top-k rows, top-k scores).
-    windows: (lo, hi) int32 per session id on the device, gathered with the batch's sessions, or None."""
+    windows: (lo, hi) int32 per session id on the device, gathered with the batch's sessions, or None.  vecs_out: a list that
+    receives the encoded news vectors before the first batch (what a second stage over the same table reads), or None."""
     prepare, topk, uidx = parts
     vecs, hm = encode_news_table(model, store)
+    if vecs_out is not None:
+        vecs_out.append(vecs)
     table = prepare(vecs)
     batcher = DeviceBatcher(behaviors, l_hist, store.pad_row)
     dev = vecs.device
@@ -535,3 +538,194 @@ def evaluate_full_ranking(model, store: NewsStore, behaviors: Behaviors, l_hist:
         import torch.distributed as dist
         dist.all_reduce(sums, op=dist.ReduceOp.SUM)
     return full_ranking_metrics(sums, ks)
+
+
+# ---------------------------------------------------------------------------------------------- diverse recommendations
+DIVERSITY_MAX_K = TOPK_MAX_K  # the longest list of xnrs_list_diversity
+
+
+def _diverse_args(who: str, k: int, lam, pool, rel: str):
+    """(k, lam, pool) of an MMR call checked against include/xnrs_hip.h: xnrs_mmr_rerank, or the ValueError; lam None (no
+    re-ranking) passes with pool None."""
+    from .ops import MMR_REL
+    k = int(k)
+    if k < 1 or k > TOPK_DEEP_MAX_K:
+        raise ValueError(f"{who}: k = {k} must lie in [1, {TOPK_DEEP_MAX_K}], the longest list of the top-k kernels")
+    if lam is None:
+        if pool is not None:
+            raise ValueError(f"{who}: `pool` is the list MMR re-ranks; without `lam` nothing is re-ranked")
+        return k, None, None
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:  # (NaN too)
+        raise ValueError(f"{who}: lam = {lam} must lie in [0, 1] (1: relevance alone, 0: variety alone)")
+    if rel not in MMR_REL:
+        raise ValueError(f"{who}: rel is one of {sorted(MMR_REL)}, got {rel!r}")
+    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
+    if not k <= pool <= TOPK_DEEP_MAX_K:
+        raise ValueError(f"{who}: pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
+    return k, lam, pool
+
+
+def _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, sessions, batch, exclude_history, windows):
+    """Per batch of sessions (lo, sess, rows:(b,k), scores:(b,k), vecs, inv): the lists of recommend(k) (lam None) or the MMR
+    re-ranking of the scorer's `pool` best (xnrs_mmr_rerank over the encoded news vectors); inv = their inverse row norms."""
+    from . import ops
+    got, inv = [], None
+    for lo, sess, _, rows, scores in _table_topk_batches(model, parts, store, behaviors, l_hist, k if lam is None else pool,
+                                                         sessions, batch, exclude_history, windows, vecs_out=got):
+        if inv is None:
+            inv = ops.row_inv_norms(got[0])
+        if lam is not None:
+            rows, scores, _ = ops.mmr_rerank(got[0], inv, rows, scores, k, lam, rel)
+        yield lo, sess, rows, scores, got[0], inv
+
+
+@torch.no_grad()
+def recommend_diverse(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, lam: float, pool=None,
+                      rel: str = "minmax", sessions=None, batch: int = 4096, exclude_history: bool = True, windows=None):
+    """recommend() with variety: per session the scorer lists its `pool` best news of the whole table (topk / topk_deep, as
+    recommend(pool): exclusions, the pad row and `windows` apply there) and greedy MMR picks k of them -> (rows:(n,k) int32,
+    scores:(n,k) fp32) on the device in the order picked; the scores are the model's relevance scores of the picks, bit for
+    bit the pool's.  Step by step the pick is the candidate with the largest lam * relevance - (1 - lam) * (largest cosine to
+    a news picked so far), cosines between the ENCODED news vectors (not the scorer's prepared table), equal objectives to
+    the better-ranked candidate (include/xnrs_hip.h: xnrs_mmr_rerank).  rel "minmax" rescales a session's pool scores to
+    [0, 1] first, so one lam means the same for every session and scorer; "raw" takes the scores as they are.  lam = 1 returns
+    recommend(k) in rows and score bits.  pool: k <= pool <= 1024, default min(1024, max(8 k, 128)).  With fewer than k
+    eligible news the tail is row -1 / score -inf.
+
+    The table is encoded once.  Refusals are those of recommend(), raised before anything is encoded.  There is no `generator`
+    form: a model whose news vectors depend on the user (NPA) has no table vectors to compare."""
+    if lam is None:
+        raise ValueError("recommend_diverse(): lam in [0, 1] is required (recommend() lists by relevance alone)")
+    k, lam, pool = _diverse_args("recommend_diverse()", k, lam, pool, rel)
+    parts = _recommending_model_parts(model, behaviors, pool, windows is not None)
+    n = len(behaviors) if sessions is None else len(sessions)
+    dev = behaviors.hist_off.device
+    windows = _session_windows(windows, behaviors, dev, "recommend_diverse()")
+    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    for lo, _, r, s, _, _ in _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, sessions, batch,
+                                              exclude_history, windows):
+        rows[lo:lo + batch], scores[lo:lo + batch] = r, s
+    hip.check_status(dev)
+    return rows, scores
+
+
+def _diversity_check(rows: torch.Tensor, who: str):
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype != torch.int32:
+        raise ValueError(f"{who}: lists are a (n, k) int32 tensor, got {tuple(getattr(rows, 'shape', ()))} "
+                         f"{getattr(rows, 'dtype', type(rows))}")
+    if not 1 <= rows.shape[1] <= DIVERSITY_MAX_K:
+        raise ValueError(f"{who}: k = {rows.shape[1]} must lie in [1, {DIVERSITY_MAX_K}], the longest list of xnrs_list_diversity")
+
+
+def _diversity_sums(vecs, inv, rows, pad_row: int, row_category, n_categories: int, counts: torch.Tensor) -> torch.Tensor:
+    """fp64 sums over the lists rows:(b,k): [lists, lists with n >= 1, lists with n >= 2, ild, cat_ild, n_categories]; adds the
+    lists' rows to the exposure counts:(n_rows,) int64.  A pad-row entry is no place."""
+    from . import ops
+    if pad_row >= 0:
+        rows = torch.where(rows == pad_row, torch.full_like(rows, -1), rows)
+    ild, n, n_cat, diff_cat = ops.list_diversity(vecs, inv, rows, row_category, n_categories)
+    ok = (rows >= 0) & (rows < counts.numel())
+    counts += torch.bincount(rows[ok].long(), minlength=counts.numel())
+    n = n.double()
+    two = n >= 2
+    zero = torch.zeros((), dtype=torch.float64, device=rows.device)
+    out = [zero + rows.shape[0], (n >= 1).double().sum(), two.double().sum(), torch.where(two, ild.double(), zero).sum()]
+    if row_category is None:
+        out += [zero, zero]
+    else:
+        pairs = (n * (n - 1) / 2).clamp(min=1)
+        out += [torch.where(two, diff_cat.double() / pairs, zero).sum(), n_cat.double().sum()]
+    return torch.stack(out)
+
+
+def _diversity_dict(sums: torch.Tensor, counts: torch.Tensor, k: int, pad_row: int, with_categories: bool) -> Dict[str, float]:
+    """The dict of diversity_metrics out of the added _diversity_sums and the exposure counts (fp64, one host read)."""
+    c = counts.double()
+    if 0 <= pad_row < c.numel():
+        c = torch.cat((c[:pad_row], c[pad_row + 1:]))
+    n = c.numel()
+    total = c.sum()
+    asc = torch.sort(c).values
+    weighted = (torch.arange(1, n + 1, dtype=torch.float64, device=c.device) * asc).sum()
+    gini = torch.where(total > 0, 2 * weighted / (max(n, 1) * total.clamp(min=1)) - (n + 1) / max(n, 1), torch.zeros_like(total))
+    cover = (c > 0).double().sum() / max(n, 1)
+    v = torch.cat((sums, torch.stack((gini, cover, total)))).tolist()
+    out = {f"ild@{k}": v[3] / max(v[2], 1.0), f"catalog_coverage@{k}": v[7], f"gini@{k}": v[6], "n_lists": int(v[0]),
+           "n_listed": int(v[8])}
+    if with_categories:
+        out.update({f"cat_ild@{k}": v[4] / max(v[2], 1.0), f"n_categories@{k}": v[5] / max(v[1], 1.0)})
+    return out
+
+
+@torch.no_grad()
+def diversity_metrics(vecs: torch.Tensor, rows: torch.Tensor, n_rows: int, pad_row: int, row_category=None,
+                      n_categories: int = 0) -> Dict[str, float]:
+    """Beyond-accuracy measures of recommended lists from anywhere: rows:(n,k) int32 on the device (k <= 128; -1, an id outside
+    [0, n_rows) or pad_row: no place) over the first n_rows encoded news vectors `vecs`.
+      ild@k              the mean over the lists with two or more places of the intra-list distance, the mean of 1 - cos(news
+                         vectors) over the list's pairs (include/xnrs_hip.h: xnrs_list_diversity)
+      catalog_coverage@k the share of the non-pad rows that appear in any list
+      gini@k             the Gini coefficient of the exposure counts c over the non-pad rows, 2 sum_i i c_(i) / (n sum c) -
+                         (n + 1) / n over the ascending counts, i from 1: 0 for even exposure, (n - 1) / n when one news takes
+                         it all; 0 when nothing was listed
+      n_lists, n_listed  the lists given, the places they fill
+    and with row_category:(n_rows,) int32 (values in [0, n_categories); another value is a news without a category, which
+    counts in no pair and as no category):
+      cat_ild@k          the mean over the same lists of the share of pairs whose categories differ
+      n_categories@k     the mean over the lists with a place of the number of distinct categories.
+    Means, coverage and Gini are taken in fp64 on the device (bincount, sort): index bookkeeping, as full_ranking_metrics."""
+    _diversity_check(rows, "diversity_metrics()")
+    from . import ops
+    n_rows = int(n_rows)
+    vecs = hip.dev_f32(vecs, "news vectors")
+    if vecs.dim() != 2 or not 0 <= n_rows <= vecs.shape[0]:
+        raise ValueError(f"diversity_metrics(): n_rows = {n_rows} rows of a (rows, E) table of news vectors, got {tuple(vecs.shape)}")
+    vecs = vecs[:n_rows]
+    if row_category is not None:
+        row_category = row_category[:n_rows]
+    counts = torch.zeros((n_rows,), dtype=torch.int64, device=vecs.device)
+    sums = _diversity_sums(vecs, ops.row_inv_norms(vecs), rows.contiguous(), int(pad_row), row_category, n_categories, counts)
+    return _diversity_dict(sums, counts, rows.shape[1], int(pad_row), row_category is not None)
+
+
+@torch.no_grad()
+def evaluate_diversity(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, lam=None, pool=None,
+                       rel: str = "minmax", row_category=None, n_categories: int = 0, sessions=None, batch: int = 4096,
+                       exclude_history: bool = True, windows=None) -> Dict[str, float]:
+    """Diversity, exposure and accuracy of the model's lists in one place: the dict of diversity_metrics over the lists of
+    recommend(k) (lam None) or recommend_diverse(k, lam, pool, rel), plus hit@k and ndcg@k of the clicked news WITHIN the
+    returned list with the definitions of evaluate_full_ranking -- every (session, clicked news) is a query, hit = the list
+    holds it, ndcg = 1 / log2(2 + position), averaged in fp64 over n_queries (a clicked pad row is no query) -- so a sweep
+    over lam shows what variety costs.  (A clicked news of the session's history is never listed under exclude_history, while
+    evaluate_full_ranking ranks it all the same: the two agree where no click lies in its history.)
+
+    The sums are added batch by batch: beyond the exposure counts no more than one batch of lists is resident.  k <= 128 (the
+    lists go through xnrs_list_diversity); a larger k raises ValueError.  Refusals as recommend(), before anything is encoded."""
+    k, lam, pool = _diverse_args("evaluate_diversity()", k, lam, pool, rel)
+    if k > DIVERSITY_MAX_K:
+        raise ValueError(f"evaluate_diversity(): k = {k} is above the longest list of xnrs_list_diversity, {DIVERSITY_MAX_K}")
+    parts = _recommending_model_parts(model, behaviors, k if lam is None else pool, windows is not None)
+    dev = behaviors.hist_off.device
+    windows = _session_windows(windows, behaviors, dev, "evaluate_diversity()")
+    pad = int(store.pad_row)
+    counts = torch.zeros((store.n_rows,), dtype=torch.int64, device=dev)
+    sums = torch.zeros((6,), dtype=torch.float64, device=dev)
+    acc = torch.zeros((3,), dtype=torch.float64, device=dev)  # queries, hits, dcg
+    for _, sess, rows, _, vecs, inv in _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, sessions, batch,
+                                                         exclude_history, windows):
+        sums += _diversity_sums(vecs, inv, rows, pad, row_category, n_categories, counts)
+        off, clicked = _session_csr(behaviors.pos_off, behaviors.pos_val, sess, None)  # (gathered: offsets from 0)
+        q = torch.repeat_interleave(torch.arange(sess.numel(), device=dev), off[1:] - off[:-1])
+        asked = (clicked >= 0) & (clicked < store.n_rows) & (clicked != pad)
+        at = rows[q] == clicked.to(torch.int32)[:, None]
+        hit = at.any(dim=1) & asked
+        place = at.to(torch.int8).argmax(dim=1).double()
+        acc += torch.stack((asked.double().sum(), hit.double().sum(),
+                            torch.where(hit, 1.0 / torch.log2(2.0 + place), torch.zeros_like(place)).sum()))
+    hip.check_status(dev)
+    out = _diversity_dict(sums, counts, k, pad, row_category is not None)
+    nq, hits, dcg = acc.tolist()
+    out.update({f"hit@{k}": hits / max(nq, 1.0), f"ndcg@{k}": dcg / max(nq, 1.0), "n_queries": int(nq)})
+    return out

@@ -916,6 +916,84 @@ def list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row: int = -1, bias=No
     return autograd.list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)
 
 
+MMR_REL = {"raw": hip._CONSTANTS["MMR_REL_RAW"], "minmax": hip._CONSTANTS["MMR_REL_MINMAX"]}  # include/xnrs_hip.h
+
+
+def row_inv_norms(vecs: torch.Tensor):
+    """inv:(n_rows,) = 1 / ||vecs[r]||, 0 for a zero row (include/xnrs_hip.h: xnrs_row_inv_norms): once per encoded table, the
+    `inv` operand of mmr_rerank and list_diversity."""
+    vecs = hip.dev_f32(vecs, "news vectors")
+    if vecs.dim() != 2:
+        raise RuntimeError(f"news vectors: a (n_rows, E) table, got {tuple(vecs.shape)}")
+    n_rows, E = vecs.shape
+    inv = torch.empty((n_rows,), dtype=torch.float32, device=vecs.device)
+    hip.check(hip.lib().xnrs_row_inv_norms(hip.ptr(vecs), n_rows, E, hip.ptr(inv), hip.stream_ptr(vecs.device)), "xnrs_row_inv_norms")
+    return inv
+
+
+def _diversity_operands(vecs, inv, rows, what: str):
+    """The checked table, norms and (B, n) int32 lists of xnrs_mmr_rerank / xnrs_list_diversity."""
+    vecs = hip.dev_f32(vecs, "news vectors")
+    if vecs.dim() != 2:
+        raise RuntimeError(f"news vectors: a (n_rows, E) table, got {tuple(vecs.shape)}")
+    inv = hip.dev_f32(inv, "inverse row norms")
+    if inv.dim() != 1 or inv.numel() != vecs.shape[0]:
+        raise RuntimeError(f"inverse row norms: one per table row ({vecs.shape[0]},), got {tuple(inv.shape)} (row_inv_norms(vecs))")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2:
+        raise RuntimeError(f"{what}: a (B, n) int32 tensor, one list of rows per session; got "
+                           f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    if rows.device != vecs.device or inv.device != vecs.device or not rows.is_contiguous():
+        raise hip.XnrsHipError(f"{what} and the inverse row norms must be contiguous tensors on {vecs.device}")
+    return vecs, inv
+
+
+def mmr_rerank(vecs, inv, pool_rows, pool_scores, k: int, lam: float, rel: str = "minmax"):
+    """Greedy MMR over per-session candidate lists (include/xnrs_hip.h: xnrs_mmr_rerank) -> (rows:(B,k) int32, scores:(B,k)
+    fp32, pos:(B,k) int32): step by step the valid place of the pool with the largest lam * relevance - (1 - lam) * (largest
+    cosine to a place selected so far), equal objectives to the lower place; scores are the pool's own bits, pos the place in
+    the pool; -1 / -inf / -1 once the valid places run out.  pool_rows:(B,P) int32 (-1: empty), pool_scores:(B,P) fp32, e.g.
+    what topk_deep_* returned; inv = row_inv_norms(vecs); rel "minmax" (per-session min-max of the valid scores) or "raw"."""
+    vecs, inv = _diversity_operands(vecs, inv, pool_rows, "candidate lists")
+    if rel not in MMR_REL:
+        raise ValueError(f"mmr_rerank(): rel is one of {sorted(MMR_REL)}, got {rel!r}")
+    pool_scores = hip.dev_f32(pool_scores, "candidate scores")
+    if tuple(pool_scores.shape) != tuple(pool_rows.shape) or pool_scores.device != vecs.device:
+        raise RuntimeError(f"candidate scores {tuple(pool_scores.shape)} on {pool_scores.device} do not match the candidate lists "
+                           f"{tuple(pool_rows.shape)} on {vecs.device}")
+    (B, P), k, dev = pool_rows.shape, int(k), vecs.device
+    rows = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    hip.check(hip.lib().xnrs_mmr_rerank(hip.ptr(vecs), hip.ptr(inv), vecs.shape[0], vecs.shape[1], hip.ptr(pool_rows),
+                                        hip.ptr(pool_scores), B, P, k, float(lam), MMR_REL[rel], hip.ptr(rows), hip.ptr(scores),
+                                        hip.ptr(pos), hip.stream_ptr(dev)), "xnrs_mmr_rerank")
+    return rows, scores, pos
+
+
+def list_diversity(vecs, inv, rows, row_category=None, n_categories: int = 0):
+    """Per list of rows:(B,k) int32 (-1 or out of the table: no place) -> (ild:(B,) fp32, n:(B,) int32, n_cat:(B,) int32,
+    diff_cat:(B,) int32) (include/xnrs_hip.h: xnrs_list_diversity): the mean of 1 - cos over the pairs of valid places (0
+    below two), the valid places, and -- with row_category:(n_rows,) int32 and its n_categories -- the distinct categories and
+    the pairs of differing category (both None without row_category).  inv = row_inv_norms(vecs)."""
+    vecs, inv = _diversity_operands(vecs, inv, rows, "lists")
+    (B, k), dev = rows.shape, vecs.device
+    if row_category is not None:
+        if not isinstance(row_category, torch.Tensor) or row_category.dtype != torch.int32 or row_category.dim() != 1 \
+                or row_category.numel() != vecs.shape[0]:
+            raise RuntimeError(f"row categories: a ({vecs.shape[0]},) int32 tensor, one category per table row; got "
+                               f"{tuple(getattr(row_category, 'shape', ()))} {getattr(row_category, 'dtype', type(row_category))}")
+        if row_category.device != dev or not row_category.is_contiguous():
+            raise hip.XnrsHipError(f"row categories must be a contiguous tensor on {dev}")
+    ild = torch.empty((B,), dtype=torch.float32, device=dev)
+    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    n_cat = None if row_category is None else torch.empty((B,), dtype=torch.int32, device=dev)
+    diff_cat = None if row_category is None else torch.empty((B,), dtype=torch.int32, device=dev)
+    hip.check(hip.lib().xnrs_list_diversity(hip.ptr(vecs), hip.ptr(inv), vecs.shape[0], vecs.shape[1], hip.ptr(rows), B, k,
+                                            hip.ptr(row_category), int(n_categories), hip.ptr(ild), hip.ptr(n), hip.ptr(n_cat),
+                                            hip.ptr(diff_cat), hip.stream_ptr(dev)), "xnrs_list_diversity")
+    return ild, n, n_cat, diff_cat
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
