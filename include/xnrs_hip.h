@@ -992,6 +992,58 @@ int32_t xnrs_list_diversity(const float *table, const float *inv, int64_t n_rows
                             int32_t k, const int32_t *row_cat, int32_t n_cat, float *out_ild, int32_t *out_n,
                             int32_t *out_ncat, int32_t *out_diffcat, void *stream);
 
+/* ---- calibrated lists: re-ranking towards a target category mix, and the miscalibration of a list (csrc/calibration.hip) ---
+ * Does a user whose history is 70 % sports get a list in that proportion?  (Steck, "Calibrated Recommendations", RecSys
+ * 2018.)  Only the categories of the listed rows are read, never a news vector.
+ *   row_cat:(n_rows,) int32; a value outside [0, n_cat) is "no category".
+ *   target:(B,n_cat) fp32 weights; w_c COUNTS when it is finite and > 0, anything else is 0.  W = the fp32 sum of the counting
+ *   weights (it must stay finite), p_c = w_c / W (one fp32 division; a p_c that rounds to 0 is 0).  W == 0: the session has NO
+ *   TARGET.
+ *   KL(n, N) = sum over c with p_c > 0 of t_c(n_c, N),  t_c(n, N) = p_c * logf(p_c / ((1 - alpha) * (n / N) + alpha * p_c)),
+ *   n / N = 0 at N == 0; every operation rounded to fp32 on its own, logf of OCML (<= 1 ulp), 1 - alpha one fp32 subtraction.
+ *   0 <= KL <= -ln(alpha).  ORDER of every sum over categories (W, KL): thread t of 256 adds its terms c = t, t + 256, ... in
+ *   ascending c from 0, a butterfly (xor 32, 16, .., 1) adds the 64 chains of a wave, the four wave sums are added as
+ *   (w0 + w1) + (w2 + w3): a function of n_cat alone.  KL is ONE device function, shared by the two entry points below.
+ *
+ * xnrs_csr_category_counts: per list b of a CSR (off:(B+1) int64, rows int32 -- the shape of the exclusion CSR),
+ * counts_out[b][c] = the number of its rows of category c.  A row outside [0, n_rows), pad_row (-1: none) or a row without a
+ * category counts nowhere.  One workgroup per list, an LDS histogram with integer atomics, every output word written.
+ *
+ * xnrs_calibrated_rerank: pool_rows:(B,P) int32, pool_scores:(B,P) fp32, e.g. of xnrs_topk_deep*.  VALID places and the
+ * relevance r_i (rel_mode XNRS_MMR_REL_RAW / XNRS_MMR_REL_MINMAX) are those of xnrs_mmr_rerank; a row outside the table is
+ * never dereferenced, not in row_cat either; a row listed twice is two candidates.  State: the counts n_c of the categorised
+ * picks so far, N = sum n_c.
+ *   pen(c) for a candidate of category c = KL(n + e_c, N + 1), formed as (S1 - t_c(n_c, N + 1)) + t_c(n_c + 1, N + 1) with
+ *          S1 = KL(n, N + 1) summed once per step in the order above; a candidate without a category: pen = KL(n, N);
+ *          a session without a target: pen = 0 for every candidate.
+ *   for t = 0 .. k-1: among the valid places not yet picked take the largest obj_i = lam * r_i - (1 - lam) * pen(cat_i), the
+ *          two products and the difference each rounded to fp32 (at lam = 1 the objective is r_i exactly).  Equal objectives
+ *          (==) go to the lower place.
+ *   out_rows / out_scores (the pool's OWN BITS) / out_pos as xnrs_mmr_rerank; -1 / -inf / -1 once the valid places run out.
+ *   out_kl[b] = KL(n, N) of the final counts, 0 without a target: what xnrs_list_calibration says of out_rows, bit for bit.
+ * Hence: lam = 1, or no target at any lam, returns the first k valid places of a pool in the order of xnrs_topk_deep*;
+ * cal(k)[:, :j] == cal(j); a session's outputs depend on its own pool and target only -- not on B, its position in the batch
+ * or an operand's address (every load is of one element; there is no second code path) -- and are the same bits on every
+ * run.  One launch, one workgroup of four waves per session, the state in LDS; row_cat[pool_rows] is read once and nothing
+ * else of the table.  No workspace, no float atomics, no host synchronisation, no allocation, hipGraph-capturable.
+ *
+ * xnrs_list_calibration: rows:(B,k) int32 lists (of xnrs_topk*, xnrs_mmr_rerank, xnrs_calibrated_rerank, anything); a place
+ * is valid when its row is inside [0, n_rows).  out_counts[b][c] (nullable) = the valid places of category c, out_n[b] = N =
+ * their sum, out_kl[b] = KL(counts, N) (about -ln alpha at N == 0), 0 without a target.
+ *
+ * Limits: 1 <= k <= P <= XNRS_TOPK_DEEP_MAX_K (xnrs_list_calibration: 1 <= k <= XNRS_TOPK_DEEP_MAX_K), 1 <= n_cat <=
+ * XNRS_DIVERSITY_MAX_CATEGORIES, 0 <= lam <= 1, 0 < alpha < 1 (NaN refused for both), n_rows <= 2^31 - 1, rel_mode one of the
+ * two.  A violation returns XNRS_EINVAL on the host before any launch and writes nothing.  B == 0: XNRS_OK, nothing written. */
+int32_t xnrs_csr_category_counts(const int64_t *off, const int32_t *rows, int64_t B, const int32_t *row_cat, int64_t n_rows,
+                                 int32_t n_cat, int32_t pad_row, int32_t *counts_out, void *stream);
+int32_t xnrs_calibrated_rerank(const int32_t *pool_rows, const float *pool_scores, int64_t B, int32_t P, int32_t k,
+                               const int32_t *row_cat, int64_t n_rows, int32_t n_cat, const float *target, float lam,
+                               float alpha, int32_t rel_mode, int32_t *out_rows, float *out_scores, int32_t *out_pos,
+                               float *out_kl, void *stream);
+int32_t xnrs_list_calibration(const int32_t *rows, int64_t B, int32_t k, const int32_t *row_cat, int64_t n_rows, int32_t n_cat,
+                              const float *target, float alpha, float *out_kl, int32_t *out_n, int32_t *out_counts,
+                              void *stream);
+
 /* ---- layers.PersonalizedAttention (layers.py:72-102) and NPA's news encoder (npa.py:63-69) ------------------------------
  *   t_i = tanh(x_fc x_i)   e_i = q . t_i   s_i = exp(e_i) m_i   a_i = s_i / (sum_j s_j + 1e-8)   p = sum_i a_i x_i
  * (no max-stabilisation, the mask after the exp, an all-masked sequence pools to 0), then the optional head

@@ -737,6 +737,19 @@ hipError_t launch_list_diversity(const float* table, const float* inv, int64_t n
                                  const int32_t* row_cat, int n_cat, float* out_ild, int32_t* out_n, int32_t* out_ncat,
                                  int32_t* out_diffcat, hipStream_t stream);
 
+// ---------------------------------------------------------------- calibrated lists (calibration.hip; include/xnrs_hip.h)
+// category histograms of CSR lists; greedy re-ranking of (B, P) candidate lists towards a (B, n_cat) target mix; the
+// miscalibration of (B, k) lists.  The callers have checked the limits (k <= P <= 1024, n_cat <= 4096, lam, alpha).
+hipError_t launch_csr_category_counts(const int64_t* off, const int32_t* rows, int64_t B, const int32_t* row_cat, int64_t n_rows,
+                                      int n_cat, int pad_row, int32_t* counts_out, hipStream_t stream);
+hipError_t launch_calibrated_rerank(const int32_t* pool_rows, const float* pool_scores, int64_t B, int P, int k,
+                                    const int32_t* row_cat, int64_t n_rows, int n_cat, const float* target, float lam, float alpha,
+                                    int rel_mode, int32_t* out_rows, float* out_scores, int32_t* out_pos, float* out_kl,
+                                    hipStream_t stream);
+hipError_t launch_list_calibration(const int32_t* rows, int64_t B, int k, const int32_t* row_cat, int64_t n_rows, int n_cat,
+                                   const float* target, float alpha, float* out_kl, int32_t* out_n, int32_t* out_counts,
+                                   hipStream_t stream);
+
 // ---------------------------------------------------------------- in-batch InfoNCE (training.py:433-472)
 // ws: (B*E + 4*B + 1) floats = normalised embeddings | 1/norm | num | den | L_i | 1/(count+1e-8); kept for the backward
 hipError_t launch_infonce_fwd(const float* x, const int64_t* lab, int64_t B, int E, float temperature, float* loss, float* ws,

@@ -368,23 +368,42 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
             rows[lo:lo + batch], scores[lo:lo + batch] = r, s
         hip.check_status(dev)
         return rows, scores
+    pool, parts, uidx = _two_stage_parts(model, generator, behaviors, k, pool, windows is not None)
+    n = len(behaviors) if sessions is None else len(sessions)
+    dev = behaviors.hist_off.device
+    windows = _session_windows(windows, behaviors, dev, "recommend()")
+    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    for lo, _, cand, r in _two_stage_batches(model, generator, parts, uidx, store, behaviors, l_hist, pool, sessions, batch,
+                                             exclude_history, windows):
+        rows[lo:lo + batch], scores[lo:lo + batch] = _rerank(cand, r, k)
+    hip.check_status(dev)
+    return rows, scores
+
+
+def _two_stage_parts(model, generator, behaviors: Behaviors, k: int, pool, windowed: bool):
+    """(pool, the generator's _recommending_model_parts for it, user index) of recommend(generator=...), or the refusal --
+    before anything is encoded."""
     if not getattr(model, "user_dependent_news", False) or getattr(model, "score_impressions", None) is None:
         raise NotImplementedError(f"recommend(generator=...): {type(model).__name__} has no score_impressions over news vectors "
                                   "that depend on the user; a model that ranks the table is called without a generator")
     pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
     if not k <= pool <= TOPK_DEEP_MAX_K:
         raise ValueError(f"recommend(): pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
-    parts = _recommending_model_parts(generator, behaviors, pool, windows is not None)
+    parts = _recommending_model_parts(generator, behaviors, pool, windowed)
     uidx = getattr(behaviors, "user_index", None)
     if uidx is None:
         raise ValueError(f"recommend(): {type(model).__name__} needs the user index of every session (sessions without "
                          "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
-    n = len(behaviors) if sessions is None else len(sessions)
+    return pool, parts, uidx
+
+
+def _two_stage_batches(model, generator, parts, uidx, store: NewsStore, behaviors: Behaviors, l_hist: int, pool: int, sessions,
+                       batch: int, exclude_history: bool, windows):
+    """Per batch of sessions (lo, sess, cand:(b,pool) int32, r:(b,pool)): the generator's list over its table and the scores
+    `model` gives exactly those news (score_impressions, no ReLU); the score of an empty place (-1) means nothing."""
     dev = behaviors.hist_off.device
     uidx = uidx.to(dev)
-    windows = _session_windows(windows, behaviors, dev, "recommend()")
-    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     spare = store.pad_row if store.pad_row >= 0 else 0  # what stands in for a place the generator left empty
     for lo, sess, hist, cand, _ in _table_topk_batches(generator, parts, store, behaviors, l_hist, pool, sessions, batch,
                                                        exclude_history, windows):
@@ -392,9 +411,7 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
         csess = torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(pool)
         crows = torch.where(cand >= 0, cand, torch.full_like(cand, spare)).reshape(-1)
         r = model.score_impressions(store, hist, crows, csess, uidx[sess], relu=False)
-        rows[lo:lo + batch], scores[lo:lo + batch] = _rerank(cand, r.reshape(b, pool), k)
-    hip.check_status(dev)
-    return rows, scores
+        yield lo, sess, cand, r.reshape(b, pool)
 
 
 def _ranking_model_parts(model, behaviors: Behaviors, who: str, windowed: bool = False):
@@ -716,16 +733,235 @@ def evaluate_diversity(model, store: NewsStore, behaviors: Behaviors, l_hist: in
     for _, sess, rows, _, vecs, inv in _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, sessions, batch,
                                                          exclude_history, windows):
         sums += _diversity_sums(vecs, inv, rows, pad, row_category, n_categories, counts)
-        off, clicked = _session_csr(behaviors.pos_off, behaviors.pos_val, sess, None)  # (gathered: offsets from 0)
-        q = torch.repeat_interleave(torch.arange(sess.numel(), device=dev), off[1:] - off[:-1])
-        asked = (clicked >= 0) & (clicked < store.n_rows) & (clicked != pad)
-        at = rows[q] == clicked.to(torch.int32)[:, None]
-        hit = at.any(dim=1) & asked
-        place = at.to(torch.int8).argmax(dim=1).double()
-        acc += torch.stack((asked.double().sum(), hit.double().sum(),
-                            torch.where(hit, 1.0 / torch.log2(2.0 + place), torch.zeros_like(place)).sum()))
+        acc += _list_accuracy_sums(behaviors, sess, rows, store.n_rows, pad)
     hip.check_status(dev)
     out = _diversity_dict(sums, counts, k, pad, row_category is not None)
+    out.update(_list_accuracy_dict(acc, k))
+    return out
+
+
+def _list_accuracy_sums(behaviors: Behaviors, sess: torch.Tensor, rows: torch.Tensor, n_rows: int, pad: int) -> torch.Tensor:
+    """fp64 [queries, hits, dcg] of the clicked news of the sessions `sess` WITHIN their lists rows:(b,k): every (session,
+    clicked news) is a query (a clicked pad row or a row outside the table is none), hit = the list holds it, dcg = 1 / log2(2 +
+    position)."""
+    dev = rows.device
+    off, clicked = _session_csr(behaviors.pos_off, behaviors.pos_val, sess, None)  # (gathered: offsets from 0)
+    q = torch.repeat_interleave(torch.arange(sess.numel(), device=dev), off[1:] - off[:-1])
+    asked = (clicked >= 0) & (clicked < n_rows) & (clicked != pad)
+    at = rows[q] == clicked.to(torch.int32)[:, None]
+    hit = at.any(dim=1) & asked
+    place = at.to(torch.int8).argmax(dim=1).double()
+    return torch.stack((asked.double().sum(), hit.double().sum(),
+                        torch.where(hit, 1.0 / torch.log2(2.0 + place), torch.zeros_like(place)).sum()))
+
+
+def _list_accuracy_dict(acc: torch.Tensor, k: int) -> Dict[str, float]:
+    """hit@k, ndcg@k and n_queries out of the added _list_accuracy_sums (one host read)."""
     nq, hits, dcg = acc.tolist()
-    out.update({f"hit@{k}": hits / max(nq, 1.0), f"ndcg@{k}": dcg / max(nq, 1.0), "n_queries": int(nq)})
+    return {f"hit@{k}": hits / max(nq, 1.0), f"ndcg@{k}": dcg / max(nq, 1.0), "n_queries": int(nq)}
+
+
+# -------------------------------------------------------------------------------------------- calibrated recommendations
+CALIBRATION_MAX_CATEGORIES = hip._CONSTANTS["DIVERSITY_MAX_CATEGORIES"]  # include/xnrs_hip.h
+
+
+def _calibrated_args(who: str, behaviors, k: int, lam, pool, rel: str, alpha, row_category, n_categories, target, two_stage: bool):
+    """(k, lam, pool, alpha, n_categories) of a calibration call checked against include/xnrs_hip.h: xnrs_calibrated_rerank, or
+    the ValueError; lam None (no re-ranking) passes, with pool None unless a generator lists the pool.  target: "history", a
+    (n_categories,) tensor or -- behaviors given -- a (len(behaviors), n_categories) tensor."""
+    from .ops import MMR_REL
+    k = int(k)
+    if k < 1 or k > TOPK_DEEP_MAX_K:
+        raise ValueError(f"{who}: k = {k} must lie in [1, {TOPK_DEEP_MAX_K}], the longest list of the top-k kernels")
+    n_categories = int(n_categories)
+    if not 1 <= n_categories <= CALIBRATION_MAX_CATEGORIES:
+        raise ValueError(f"{who}: n_categories = {n_categories} must lie in [1, {CALIBRATION_MAX_CATEGORIES}]")
+    if not isinstance(row_category, torch.Tensor) or row_category.dim() != 1 or row_category.dtype != torch.int32:
+        raise ValueError(f"{who}: row_category is a (n_rows,) int32 tensor, one category per table row; got "
+                         f"{tuple(getattr(row_category, 'shape', ()))} {getattr(row_category, 'dtype', type(row_category))}")
+    alpha = float(alpha)
+    if not 0.0 < alpha < 1.0:  # (NaN too)
+        raise ValueError(f"{who}: alpha = {alpha} must lie in (0, 1): the share of the target mixed into the list's mix")
+    if isinstance(target, str):
+        if target != "history" or behaviors is None:
+            forms = "a tensor of weights" if behaviors is None else "'history' or a tensor of weights"
+            raise ValueError(f"{who}: target is {forms}, ({n_categories},) or one row per "
+                             f"{'list' if behaviors is None else 'session'}; got {target!r}")
+    else:
+        per = (len(behaviors), n_categories) if behaviors is not None else None
+        if not isinstance(target, torch.Tensor) or target.dim() not in (1, 2) or target.shape[-1] != n_categories \
+                or (target.dim() == 2 and per is not None and tuple(target.shape) != per) or not target.is_floating_point():
+            raise ValueError(f"{who}: target is a ({n_categories},) tensor of weights or one row per "
+                             f"{'session, ' + str(per) if per else 'list'}; got {tuple(getattr(target, 'shape', ()))} "
+                             f"{getattr(target, 'dtype', type(target))}")
+    if lam is None:
+        if pool is not None and not two_stage:
+            raise ValueError(f"{who}: `pool` is the list that is re-ranked; without `lam` nothing is re-ranked")
+        return k, None, pool, alpha, n_categories
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:  # (NaN too)
+        raise ValueError(f"{who}: lam = {lam} must lie in [0, 1] (1: relevance alone, 0: the category mix alone)")
+    if rel not in MMR_REL:
+        raise ValueError(f"{who}: rel is one of {sorted(MMR_REL)}, got {rel!r}")
+    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
+    if not k <= pool <= TOPK_DEEP_MAX_K:
+        raise ValueError(f"{who}: pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
+    return k, lam, pool, alpha, n_categories
+
+
+def _target_rows(target, n: int, index, dev) -> torch.Tensor:
+    """(n, C) fp32 target mix on `dev` out of a (C,) tensor (one mix for everybody) or a (m, C) tensor gathered by `index`
+    (None: as it lies)."""
+    t = target.to(device=dev, dtype=torch.float32)
+    if t.dim() == 1:
+        return t.expand(n, t.numel()).contiguous()
+    return (t if index is None else t[index]).contiguous()
+
+
+def _calibrated_batches(model, generator, parts, uidx, store, behaviors, l_hist, k, lam, pool, rel, alpha, row_category,
+                        n_categories, target, sessions, batch, exclude_history, windows):
+    """Per batch of sessions (lo, sess, rows:(b,k), scores:(b,k), target:(b,C)): the lists of recommend(k) (lam None) or the
+    calibrated re-ranking of the `pool` best -- the scorer's own (table form) or the generator's as `model` re-scored them
+    (two stages, in the order of recommend(pool))."""
+    from . import ops
+    every = sessions is None
+    if not isinstance(target, str):
+        target = target.to(device=behaviors.hist_off.device, dtype=torch.float32)
+    if generator is None:
+        source = ((lo, sess, r, s) for lo, sess, _, r, s in
+                  _table_topk_batches(model, parts, store, behaviors, l_hist, k if lam is None else pool, sessions, batch,
+                                      exclude_history, windows))
+    else:
+        source = ((lo, sess) + _rerank(cand, r, k if lam is None else pool) for lo, sess, cand, r in
+                  _two_stage_batches(model, generator, parts, uidx, store, behaviors, l_hist, pool, sessions, batch,
+                                     exclude_history, windows))
+    for lo, sess, rows, scores in source:
+        if isinstance(target, str):  # the mix of the session's FULL history, the one exclude_history excludes
+            off, val = _history_csr(behaviors, sess, lo if every else None)
+            tgt = ops.csr_category_counts(off.contiguous(), val, row_category, n_categories, store.pad_row).float()
+        else:
+            tgt = _target_rows(target, sess.numel(), sess, rows.device)
+        if lam is not None:
+            rows, scores, _, _ = ops.calibrated_rerank(rows.contiguous(), scores.contiguous(), k, lam, row_category, n_categories,
+                                                       tgt, alpha, rel)
+        yield lo, sess, rows, scores, tgt
+
+
+def _calibrated_parts(who, model, store, behaviors, k, lam, pool, rel, alpha, row_category, n_categories, target, windows, generator):
+    """Every refusal of a calibration call, before anything is encoded -> (k, lam, pool, alpha, n_categories, parts, uidx,
+    windows, row_category on the device)."""
+    k, lam, pool, alpha, n_categories = _calibrated_args(who, behaviors, k, lam, pool, rel, alpha, row_category, n_categories,
+                                                         target, generator is not None)
+    if generator is None:
+        parts, uidx = _recommending_model_parts(model, behaviors, k if lam is None else pool, windows is not None), None
+    else:
+        pool, parts, uidx = _two_stage_parts(model, generator, behaviors, k, pool, windows is not None)
+    dev = behaviors.hist_off.device
+    if row_category.numel() < store.n_rows:
+        raise ValueError(f"{who}: row_category holds {row_category.numel()} categories for a store of {store.n_rows} rows")
+    return k, lam, pool, alpha, n_categories, parts, uidx, _session_windows(windows, behaviors, dev, who), \
+        row_category.to(dev).contiguous()
+
+
+@torch.no_grad()
+def recommend_calibrated(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, lam: float, row_category,
+                         n_categories: int, target="history", alpha: float = 0.01, pool=None, rel: str = "minmax", sessions=None,
+                         batch: int = 4096, exclude_history: bool = True, windows=None, generator=None):
+    """recommend() steered towards a category mix (Steck, "Calibrated Recommendations", RecSys 2018): per session the scorer
+    lists its `pool` best news of the whole table (as recommend(pool): exclusions, the pad row and `windows` apply there) and a
+    greedy picks k of them -> (rows:(n,k) int32, scores:(n,k) fp32) on the device in the order picked; the scores are the
+    model's relevance scores of the picks, bit for bit the pool's.  Step by step the pick is the candidate with the largest
+    lam * relevance - (1 - lam) * KL(p || q~), p the session's target mix and q~ = (1 - alpha) * (category mix of the list with
+    the candidate added) + alpha * p; equal objectives go to the better-ranked candidate (include/xnrs_hip.h:
+    xnrs_calibrated_rerank).  row_category:(n_rows,) int32 with values in [0, n_categories) (another value: a news without a
+    category, which never changes the mix) -- e.g. store.category_index, whose 0 is the padding, with n_categories =
+    cfg.n_categories + 1.
+      target "history"   the category counts of the session's FULL history (hist_off / hist_val, the one exclude_history
+                         excludes; xnrs_csr_category_counts)
+      target (C,)        one mix for everybody, e.g. the catalogue's or an editor's
+      target (len(behaviors), C)  one row of weights per session, indexed by session id like `windows`
+    Weights need not be normalised; a session whose weights are all <= 0 has no target and gets recommend(k)'s list.  rel and
+    pool as recommend_diverse (default pool min(1024, max(8 k, 128))); lam = 1 returns recommend(k) in rows and score bits.
+
+    `generator`: the two-stage form of recommend() (NPA) -- the generator lists the pool, `model` re-scores it, and the
+    re-scored pool is calibrated; only categories are compared, so no table of news vectors is needed.  The table is encoded
+    once; no more than one batch of pools is resident.  Refusals are those of recommend(), raised before anything is encoded."""
+    if lam is None:
+        raise ValueError("recommend_calibrated(): lam in [0, 1] is required (recommend() lists by relevance alone)")
+    k, lam, pool, alpha, n_categories, parts, uidx, windows, row_category = _calibrated_parts(
+        "recommend_calibrated()", model, store, behaviors, k, lam, pool, rel, alpha, row_category, n_categories, target, windows,
+        generator)
+    n = len(behaviors) if sessions is None else len(sessions)
+    dev = behaviors.hist_off.device
+    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    for lo, _, r, s, _ in _calibrated_batches(model, generator, parts, uidx, store, behaviors, l_hist, k, lam, pool, rel, alpha,
+                                              row_category, n_categories, target, sessions, batch, exclude_history, windows):
+        rows[lo:lo + batch], scores[lo:lo + batch] = r, s
+    hip.check_status(dev)
+    return rows, scores
+
+
+def _calibration_sums(rows, row_category, n_categories: int, target: torch.Tensor, pad_row: int, alpha: float) -> torch.Tensor:
+    """fp64 [lists, lists with a target, sum of their KL] over the lists rows:(b,k) against target:(b,C).  A pad-row entry is no
+    place."""
+    from . import ops
+    if pad_row >= 0:
+        rows = torch.where(rows == pad_row, torch.full_like(rows, -1), rows)
+    kl, _, _ = ops.list_calibration(rows.contiguous(), row_category, n_categories, target, alpha)
+    has = ((target > 0) & torch.isfinite(target)).any(dim=1)
+    zero = torch.zeros((), dtype=torch.float64, device=rows.device)
+    return torch.stack((zero + rows.shape[0], has.double().sum(), torch.where(has, kl.double(), zero).sum()))
+
+
+def _calibration_dict(sums: torch.Tensor, k: int) -> Dict[str, float]:
+    n, n_cal, kl = sums.tolist()
+    return {f"calibration_kl@{k}": kl / max(n_cal, 1.0), "n_lists": int(n), "n_calibrated": int(n_cal)}
+
+
+@torch.no_grad()
+def calibration_metrics(rows: torch.Tensor, row_category, n_categories: int, target, pad_row: int, alpha: float = 0.01) -> Dict[str, float]:
+    """How far recommended lists from anywhere are from a target category mix: rows:(n,k) int32 on the device (k <= 1024; -1, an
+    id outside the table or pad_row: no place), row_category:(n_rows,) int32, target a (n_categories,) tensor of weights or one
+    row per list.
+      calibration_kl@k   the fp64 mean over the lists that have a target (a positive weight) of KL(p || q~), p the target mix,
+                         q~ = (1 - alpha) * (the mix of the list's places that have a category) + alpha * p
+                         (include/xnrs_hip.h: xnrs_list_calibration); 0 is a list in exactly the target's proportion, -ln alpha
+                         a list without one categorised place
+      n_lists, n_calibrated  the lists given, and those with a target."""
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype != torch.int32:
+        raise ValueError(f"calibration_metrics(): lists are a (n, k) int32 tensor, got {tuple(getattr(rows, 'shape', ()))} "
+                         f"{getattr(rows, 'dtype', type(rows))}")
+    k, _, _, alpha, n_categories = _calibrated_args("calibration_metrics()", None, rows.shape[1], None, None, "minmax", alpha,
+                                                    row_category, n_categories, target, False)
+    if target.dim() == 2 and target.shape[0] != rows.shape[0]:
+        raise ValueError(f"calibration_metrics(): target holds {target.shape[0]} rows of weights for {rows.shape[0]} lists")
+    tgt = _target_rows(target, rows.shape[0], None, rows.device)
+    return _calibration_dict(_calibration_sums(rows, row_category.to(rows.device).contiguous(), n_categories, tgt, int(pad_row), alpha), k)
+
+
+@torch.no_grad()
+def evaluate_calibration(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, lam=None, row_category=None,
+                         n_categories: int = 0, target="history", alpha: float = 0.01, pool=None, rel: str = "minmax",
+                         sessions=None, batch: int = 4096, exclude_history: bool = True, windows=None, generator=None) -> Dict[str, float]:
+    """Calibration and accuracy of the model's lists in one place: the dict of calibration_metrics over the lists of
+    recommend(k) (lam None) or recommend_calibrated(k, lam, ...) against the same target, plus hit@k, ndcg@k and n_queries of
+    the clicked news WITHIN the returned list with the definitions of evaluate_diversity -- so a sweep over lam shows what
+    calibration costs.  Keywords as recommend_calibrated; the sums are added batch by batch.  Refusals as recommend(), before
+    anything is encoded."""
+    k, lam, pool, alpha, n_categories, parts, uidx, windows, row_category = _calibrated_parts(
+        "evaluate_calibration()", model, store, behaviors, k, lam, pool, rel, alpha, row_category, n_categories, target, windows,
+        generator)
+    dev = behaviors.hist_off.device
+    pad = int(store.pad_row)
+    sums = torch.zeros((3,), dtype=torch.float64, device=dev)
+    acc = torch.zeros((3,), dtype=torch.float64, device=dev)  # queries, hits, dcg
+    for _, sess, rows, _, tgt in _calibrated_batches(model, generator, parts, uidx, store, behaviors, l_hist, k, lam, pool, rel,
+                                                     alpha, row_category, n_categories, target, sessions, batch, exclude_history,
+                                                     windows):
+        sums += _calibration_sums(rows, row_category, n_categories, tgt, pad, alpha)
+        acc += _list_accuracy_sums(behaviors, sess, rows, store.n_rows, pad)
+    hip.check_status(dev)
+    out = _calibration_dict(sums, k)
+    out.update(_list_accuracy_dict(acc, k))
     return out

@@ -994,6 +994,95 @@ def list_diversity(vecs, inv, rows, row_category=None, n_categories: int = 0):
     return ild, n, n_cat, diff_cat
 
 
+def _calibration_operands(rows, row_category, n_categories: int, target, what: str):
+    """The checked (B, n) int32 lists, (n_rows,) int32 categories and (B, n_categories) fp32 target mix of
+    xnrs_calibrated_rerank / xnrs_list_calibration -> the target as a contiguous fp32 tensor."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2:
+        raise RuntimeError(f"{what}: a (B, n) int32 tensor, one list of rows per session; got "
+                           f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    if not rows.is_cuda:
+        raise hip.XnrsHipError(f"{what}: tensor is on {rows.device}; xnrs_amd runs on a HIP device only (there is no CPU fallback)")
+    _row_categories(row_category, rows.device)
+    target = hip.dev_f32(target, "target mix")
+    if tuple(target.shape) != (rows.shape[0], int(n_categories)):
+        raise RuntimeError(f"target mix: ({rows.shape[0]}, {int(n_categories)}) weights, one row per session; got {tuple(target.shape)}")
+    if target.device != rows.device or not rows.is_contiguous():
+        raise hip.XnrsHipError(f"{what} and the target mix must be contiguous tensors on {rows.device}")
+    return target
+
+
+def _row_categories(row_category, dev):
+    if not isinstance(row_category, torch.Tensor) or row_category.dtype != torch.int32 or row_category.dim() != 1:
+        raise RuntimeError(f"row categories: a (n_rows,) int32 tensor, one category per table row; got "
+                           f"{tuple(getattr(row_category, 'shape', ()))} {getattr(row_category, 'dtype', type(row_category))}")
+    if row_category.device != dev or not row_category.is_contiguous():
+        raise hip.XnrsHipError(f"row categories must be a contiguous tensor on {dev}")
+
+
+def csr_category_counts(off, rows, row_category, n_categories: int, pad_row: int = -1):
+    """counts:(B, n_categories) int32, the category histogram of every list of the CSR off:(B+1) int64 / rows int32 (the shape
+    of an exclusion CSR, e.g. the histories) (include/xnrs_hip.h: xnrs_csr_category_counts).  A row outside the table, the pad
+    row or a row whose category lies outside [0, n_categories) counts nowhere."""
+    if not isinstance(off, torch.Tensor) or off.dtype != torch.int64 or off.dim() != 1 or off.numel() < 1:
+        raise RuntimeError(f"CSR offsets: a (B + 1,) int64 tensor, got {tuple(getattr(off, 'shape', ()))} {getattr(off, 'dtype', type(off))}")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1:
+        raise RuntimeError(f"CSR rows: a 1-D int32 tensor, got {tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    if not off.is_cuda:
+        raise hip.XnrsHipError(f"CSR offsets: tensor is on {off.device}; xnrs_amd runs on a HIP device only (there is no CPU fallback)")
+    dev = off.device
+    _row_categories(row_category, dev)
+    if rows.device != dev or not rows.is_contiguous() or not off.is_contiguous():
+        raise hip.XnrsHipError(f"the CSR must be contiguous tensors on {dev}")
+    B = off.numel() - 1
+    counts = torch.empty((B, max(int(n_categories), 0)), dtype=torch.int32, device=dev)
+    hip.check(hip.lib().xnrs_csr_category_counts(hip.ptr(off), hip.ptr(rows), B, hip.ptr(row_category), row_category.numel(),
+                                                 int(n_categories), int(pad_row), hip.ptr(counts), hip.stream_ptr(dev)),
+              "xnrs_csr_category_counts")
+    return counts
+
+
+def calibrated_rerank(pool_rows, pool_scores, k: int, lam: float, row_category, n_categories: int, target, alpha: float = 0.01,
+                      rel: str = "minmax"):
+    """Greedy calibrated re-ranking of per-session candidate lists (include/xnrs_hip.h: xnrs_calibrated_rerank) -> (rows:(B,k)
+    int32, scores:(B,k) fp32, pos:(B,k) int32, kl:(B,) fp32): step by step the valid place of the pool with the largest
+    lam * relevance - (1 - lam) * KL(target || mix of the list with that place added), equal objectives to the lower place;
+    scores are the pool's own bits, pos the place in the pool, -1 / -inf / -1 once the valid places run out; kl is the
+    miscalibration of the final list (0 for a session whose target has no positive weight).  pool_rows:(B,P) int32,
+    pool_scores:(B,P) fp32, e.g. what topk_deep_* returned; row_category:(n_rows,) int32, target:(B, n_categories) weights."""
+    target = _calibration_operands(pool_rows, row_category, n_categories, target, "candidate lists")
+    if rel not in MMR_REL:
+        raise ValueError(f"calibrated_rerank(): rel is one of {sorted(MMR_REL)}, got {rel!r}")
+    pool_scores = hip.dev_f32(pool_scores, "candidate scores")
+    if tuple(pool_scores.shape) != tuple(pool_rows.shape) or pool_scores.device != pool_rows.device:
+        raise RuntimeError(f"candidate scores {tuple(pool_scores.shape)} on {pool_scores.device} do not match the candidate lists "
+                           f"{tuple(pool_rows.shape)} on {pool_rows.device}")
+    (B, P), k, dev = pool_rows.shape, int(k), pool_rows.device
+    rows = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    kl = torch.empty((B,), dtype=torch.float32, device=dev)
+    hip.check(hip.lib().xnrs_calibrated_rerank(hip.ptr(pool_rows), hip.ptr(pool_scores), B, P, k, hip.ptr(row_category),
+                                               row_category.numel(), int(n_categories), hip.ptr(target), float(lam), float(alpha),
+                                               MMR_REL[rel], hip.ptr(rows), hip.ptr(scores), hip.ptr(pos), hip.ptr(kl),
+                                               hip.stream_ptr(dev)), "xnrs_calibrated_rerank")
+    return rows, scores, pos, kl
+
+
+def list_calibration(rows, row_category, n_categories: int, target, alpha: float = 0.01, want_counts: bool = False):
+    """Per list of rows:(B,k) int32 (-1 or out of the table: no place) -> (kl:(B,) fp32, n:(B,) int32, counts:(B, n_categories)
+    int32 or None) (include/xnrs_hip.h: xnrs_list_calibration): the KL divergence of the target mix from the list's smoothed
+    category mix (0 for a session without a target), the places that have a category, and their histogram."""
+    target = _calibration_operands(rows, row_category, n_categories, target, "lists")
+    (B, k), dev = rows.shape, rows.device
+    kl = torch.empty((B,), dtype=torch.float32, device=dev)
+    n = torch.empty((B,), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, int(n_categories)), dtype=torch.int32, device=dev) if want_counts else None
+    hip.check(hip.lib().xnrs_list_calibration(hip.ptr(rows), B, k, hip.ptr(row_category), row_category.numel(), int(n_categories),
+                                              hip.ptr(target), float(alpha), hip.ptr(kl), hip.ptr(n), hip.ptr(counts),
+                                              hip.stream_ptr(dev)), "xnrs_list_calibration")
+    return kl, n, counts
+
+
 # ------------------------------------------------------------------------------------------------
 # module-level dispatch: what the nn.Module mirrors call.  Handles train-mode attention dropout and
 # routes to the autograd path when gradients are required.
