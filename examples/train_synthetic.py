@@ -4,12 +4,14 @@ entirely on the device: resident news table -> device batch assembly -> forward_
 GEMM) -> relu/MSE + lambda * fused InfoNCE -> hand-written HIP backward -> Adam -> device evaluation.
 
     python examples/train_synthetic.py [--model NRMS|standard] [--steps 300] [--batch 64] [--bf16x3]
-                                      [--full-table-loss | --mined-negatives M]
+                                      [--full-table-loss | --mined-negatives M [--negatives-temperature T]]
 
 --full-table-loss (off by default) trains with losses.full_table_loss instead: every clicked news of a session against ALL
 news of the table encoded in that step, the objective evaluate_full_ranking measures.
 --mined-negatives M (mutually exclusive with it) trains with losses.mined_negatives_loss: the same clicks against the M news
 of that table the session's user scores highest in that step (topk_deep mines them, the listed loss reads their rows in place).
+--negatives-temperature T draws the M negatives instead, P(news first) ~ exp(score / T) without replacement (topk_sample, the
+step number as the seed): the hardest rows are where the false negatives live.
 
 Synthetic click world (xnrs_amd.synth.click_world): news carry a topic direction in their tokens, a user clicks news of
 its own topic -- so the ranking metrics have to rise if the whole stack (forward, gradients, optimiser, evaluation) is
@@ -46,9 +48,14 @@ def main():
     which.add_argument("--mined-negatives", type=int, default=0, metavar="M",
                        help="train with the ranking loss over the M hardest negatives of each session, mined per step "
                             "(losses.mined_negatives_loss, 1 <= M <= 1024)")
+    ap.add_argument("--negatives-temperature", type=float, default=None, metavar="T",
+                    help="with --mined-negatives: draw the M negatives with probability ~ exp(score / T) instead of taking the "
+                         "M hardest (losses.mined_negatives_loss(temperature=T, seed=step))")
     ap.add_argument("--explain", action="store_true",
                     help="after training: recommend() three news for session 0 and explain_recommendations() for them")
     args = ap.parse_args()
+    if args.negatives_temperature is not None and not args.mined_negatives:
+        ap.error("--negatives-temperature goes with --mined-negatives M")
     dev = "cuda:0"
     if args.bf16x3:
         hip.set_gemm_mode(hip.GEMM_BF16X3)
@@ -71,7 +78,8 @@ def main():
         if args.full_table_loss:
             loss = full_table_loss(model, store, beh, sess, args.hist)
         elif args.mined_negatives:
-            loss = mined_negatives_loss(model, store, beh, sess, args.hist, n_negatives=args.mined_negatives)
+            sampling = {} if args.negatives_temperature is None else dict(temperature=args.negatives_temperature, seed=step)
+            loss = mined_negatives_loss(model, store, beh, sess, args.hist, n_negatives=args.mined_negatives, **sampling)
         else:
             hist, cand, targets = batcher.train_batch(sess, n_neg=4, seed=step)
             r, u, _ = model.forward_ids(store.x, store.m, hist, cand, return_embeddings=True)

@@ -819,6 +819,50 @@ int32_t xnrs_rank_mlp_win(const float *P, int64_t n_rows, int32_t E, int32_t H, 
                           const int64_t *excl_off, const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi,
                           int32_t pad_row, int32_t *ranks, float *scores, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- sampled top-k: a list DRAWN from the scores instead of the k best (stochastic ranking; csrc/topk.hip) ------------------
+ * xnrs_topk_sample*_win take the argument lists of xnrs_topk_deep*_win with temperature, seed and user_keys behind k.  The
+ * list of user b is a sample WITHOUT replacement from the Plackett-Luce distribution over b's eligible rows: the first place
+ * is row n with probability proportional to exp(s_bn / temperature), the second is drawn the same way from the rest, and so
+ * on.  It is computed as Gumbel top-k -- the k largest of the perturbed keys
+ *     key_bn = fl(fl(s_bn * (1 / temperature)) + g_bn),    g_bn = -log(-log(1 - w)),  w = min((x + 1/2) 2^-32, 1 - 2^-24)
+ * (fp32; product and sum rounded separately), x the 32-bit word of the dropout stream of xnrs_dropout_rows for seed `seed`,
+ * row user_keys[b] and element n (one splitmix64 per (seed, user key), one murmur3 fmix32 per table row; csrc/kernels.h:
+ * drop_word, drop_gumbel).  The uniform keeps an fp32's relative precision towards 0, the tail the winners of a large table
+ * come from; there are 2^32 draws per (seed, user key), and g lies in [-2.8116, 22.874].  s_bn is the score of xnrs_topk*,
+ * formed by its score tile, bias included.
+ *   rows     : (B,k) int32, best perturbed key first; scores: (B,k) fp32 holds the PERTURBED KEYS, not the raw scores (score
+ *              the returned rows with xnrs_score_csr* where those are wanted).  Fillers: row -1, key -inf.
+ *   Order    : of the keys as xnrs_topk* orders scores: higher key first, equal keys lower row first.  A NaN score never
+ *              wins; a -inf score keeps the key -inf, behind every finite key and before the fillers; +inf stays +inf.
+ *   Pure     : key_bn depends on (seed, user_keys[b], n, s_bn, temperature) and nothing else -- not on B, on the user's position
+ *              in the batch, on the other users, on the windows, on the slicing, on k or on the run.  So a call repeats bit
+ *              for bit, sample(k)[:, :j] == sample(j), and a user called alone with its key gets the list it got in a batch.
+ *   user_keys: (B,) int64 on the device, any values (a session id); NULL: the user's index in the call, 0 .. B-1.  Two users
+ *              with one key and one score vector draw the same list.
+ *   Limits   : 1 <= k <= XNRS_TOPK_DEEP_MAX_K; temperature finite, > 0 and with a finite 1 / temperature, else XNRS_EINVAL
+ *              before any launch.  As temperature -> 0 the list tends to xnrs_topk_deep*_win's (once the gaps of s / temperature
+ *              exceed the range of g, 25.69, it IS that list); as it grows the list tends to a uniform draw.
+ * Everything else is the contract of xnrs_topk_deep*_win word for word: eligibility, the exclusion CSR, pad_row, the windows
+ * (both NULL: none; exactly one: XNRS_EINVAL), refusals on the host that write nothing, no host synchronisation,
+ * hipGraph-capturable, no allocation, no float atomics.  Launches: those of xnrs_topk_deep* with the sampled instantiations of
+ * the partial kernel (both sweeps of a k > XNRS_TOPK_MAX_K inner-product call draw the same noise); a score whose
+ * fl(fl(s / temperature) + 22.874) is below the user's current threshold is dropped without its draw.
+ * ws: xnrs_topk_deep_workspace_bytes(B, n_rows, proj_width, k). */
+int32_t xnrs_topk_sample_win(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const int64_t *excl_off,
+                             const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row,
+                             int32_t k, float temperature, uint64_t seed, const int64_t *user_keys, int32_t *rows,
+                             float *scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_topk_sample_bilinear_win(const float *table, int64_t n_rows, int32_t E, const float *u, int64_t B, const float *w,
+                                      const float *bias, const int64_t *excl_off, const int32_t *excl_rows,
+                                      const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row, int32_t k,
+                                      float temperature, uint64_t seed, const int64_t *user_keys, int32_t *rows, float *scores,
+                                      void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_topk_sample_mlp_win(const float *P, int64_t n_rows, int32_t E, int32_t H, const float *u, int64_t B,
+                                 const float *w1, const float *b1, const float *w2, const float *b2, const int64_t *excl_off,
+                                 const int32_t *excl_rows, const int32_t *win_lo, const int32_t *win_hi, int32_t pad_row,
+                                 int32_t k, float temperature, uint64_t seed, const int64_t *user_keys, int32_t *rows,
+                                 float *scores, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- the full-table softmax ranking loss: the training side of the two sweeps (csrc/table_loss.hip) ------------------------
  * The reference's ranking_loss(p, n) = -log(e^p / (e^p + sum e^n)) (xnrs/utils.py:117-131) with EVERY eligible news of the
  * table as a negative, forward and backward, again without a (B, n_rows) score matrix.  The operands are those of

@@ -482,6 +482,45 @@ struct DropRowsArgs {
 __device__ __forceinline__ float drop_uniform(const DropRowsArgs& a, int64_t row, uint32_t j) {
   return drop_uniform(a, row, 0, 0, 0, (int)j);
 }
+// The same stream, taken apart for a caller that keeps the 64-bit part of a pair in registers (topk.hip: the sampled top-k
+// holds one per user and spends one fmix32 per score): drop_pair is the splitmix64 of (seed, row), drop_word(z, j) the 32-bit
+// x of drop_uniform(DropRowsArgs, row, j) before its `>> 8`.
+__device__ __forceinline__ uint64_t drop_pair(uint64_t seed, int64_t row) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)row + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ uint32_t drop_word(uint32_t z_lo, uint32_t z_hi, uint32_t j) {
+  uint32_t x = z_lo ^ (j * 0x9E3779B9u);
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x ^ z_hi;
+}
+__device__ __forceinline__ uint32_t drop_word(const DropRowsArgs& a, int64_t row, uint32_t j) {
+  const uint64_t z = drop_pair(drop_seed(a), row);
+  return drop_word((uint32_t)z, (uint32_t)(z >> 32), j);
+}
+// A standard Gumbel draw from that word: g = -log(-log(1 - w)), w = (x + 1/2) 2^-32 in (0, 1).  The uniform is NOT the 24-bit
+// one of drop_uniform: towards 0 it keeps the relative precision of an fp32 (x = 0 gives 2^-33, and the winners of a large
+// table come from that tail: g grows as w falls); towards 1 it is clamped to 1 - 2^-24, the last fp32 below 1.  There are 2^32
+// draws per pair (seed, row).  g lies in [-2.8116 (x = 2^32 - 1), 22.874 (x = 0)]; DROP_GUMBEL_MAX is an upper bound of every
+// value this function returns (33 ln 2 = 22.87386; the library's two logarithms are a few ulp of 2e-6 off).
+constexpr float DROP_GUMBEL_MAX = 22.874f;
+__device__ __forceinline__ float drop_gumbel_uniform(uint32_t x) {
+  return fminf(((float)x + 0.5f) * 2.3283064365386963e-10f, 0.99999994f);  // 2^-32; 1 - 2^-24
+}
+__device__ __forceinline__ float drop_gumbel(uint32_t x) { return -logf(-log1pf(-drop_gumbel_uniform(x))); }
+// An upper bound of drop_gumbel(x) without a logarithm, from the exponent of w alone: -log(1 - w) >= w, so g <= -log(w)
+// <= e log(2) for w in [2^-e, 2^(1-e)), e = 1 .. 33.  The fp32 of log(2) lies above it; 1e-4 covers the product's rounding and
+// the few ulp (2e-6 each) of the two library logarithms in drop_gumbel.
+__device__ __forceinline__ float drop_gumbel_bound(uint32_t x) {
+  const int e = 127 - (int)((__float_as_uint(drop_gumbel_uniform(x)) >> 23) & 0xffu);
+  return fmaf((float)e, 0.69314718f, 1e-4f);
+}
 
 // ---------------------------------------------------------------- fused news encoder, S <= 32 tokens (news_fused.hip)
 // att -> additive pooler of TextEncoder.forward in ONE launch (news_encoding.py:48-54, layers.py:60-65,128-154)

@@ -21,6 +21,8 @@
 // evaluation's relu would tie every negative score).
 //
 // The score tile and the row windows of xnrs_topk_deep*_win: sweep.h.
+#include <cmath>
+
 #include "sweep.h"
 
 namespace xnrs {
@@ -68,6 +70,21 @@ struct TopkArgs : TkOperands {
   int k;
   uint64_t* part;
   const uint64_t* floor;  // xnrs_topk_deep*, k > XNRS_TOPK_MAX_K: per user a key below which nothing is wanted (topk_floor_kernel), or NULL
+};
+// xnrs_topk_sample*: the keys are score * inv_tau + g, g the standard Gumbel draw of the pair (seed, user key) at the table row
+// (kernels.h: drop_pair, drop_word, drop_gumbel); user_keys NULL: the user's index in the call
+struct TopkSampleArgs : TopkArgs {
+  float inv_tau;
+  uint64_t seed;
+  const int64_t* user_keys;
+};
+template <bool SAMPLE>
+struct TkArgsOf {
+  using type = TopkArgs;
+};
+template <>
+struct TkArgsOf<true> {
+  using type = TopkSampleArgs;
 };
 
 // One wave merges the candidate buffers of up to two users at once, one user per half-wave (32 lanes = TK_CB candidates, one
@@ -298,15 +315,28 @@ __device__ __forceinline__ void tk_merge_phase(const TopkArgs& a, int64_t u0, ui
 
 // (two workgroups per CU for the MFMA form; the MLP form's 64 tanhf per feature want more than 256 registers.  KCAP: the
 // longest list of the call -- XNRS_TOPK_MAX_K for xnrs_topk*; the 1024 of xnrs_topk_deep* stages 8 KB per half-wave, 135 KB of
-// LDS in all, and is alone on its CU)
-template <bool MLP, int KCAP = XNRS_TOPK_MAX_K>
-__global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void topk_partial_kernel(TopkArgs a) {
+// LDS in all, and is alone on its CU.
+// SAMPLE (xnrs_topk_sample*): the score becomes the perturbed key s * inv_tau + g before it meets the threshold, and nothing
+// behind that line knows: the lists, the merges, the floor and the merge kernel order perturbed keys as they order scores.
+// A lane holds the splitmix64 word of each of its two users in registers; a draw is one fmix32 and two logarithms.  The fp32
+// add is monotone, so a score p = s * inv_tau whose fl(p + b) lies below the user's threshold for an upper bound b of its
+// draw cannot become a candidate and needs no draw.  DROP_GUMBEL_MAX is the bound that costs nothing, and it only bites at a
+// cold temperature: a draw near 22.9 is one in 2^33, and in the unrolled loop over the lane's 64 scores a wave takes the
+// logarithms of an element whenever ONE of its 64 lanes needs them.  Measured (profiles/topk_sample_resource_usage.md), the
+// k <= 128 form is fastest with the draw where the score is formed, a flat cost per score; the long-list form, whose
+// thresholds start at the floor of the first sweep, tests the bound of the pair's own word instead (drop_gumbel_bound: the
+// fmix32 and the exponent of the uniform), puts what passes into `pend` as a score at the threshold, and takes the logarithms
+// in the candidate loop, where each lane walks its own few set bits (DRAW_LATE).  The keys are the same bits either way.  The
+// product and the sum are rounded separately (__fmul_rn, __fadd_rn: no contraction), so tests and key share the product's bits.)
+template <bool MLP, int KCAP = XNRS_TOPK_MAX_K, bool SAMPLE = false>
+__global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void topk_partial_kernel(typename TkArgsOf<SAMPLE>::type a) {
   __shared__ float At[TK_KT * TK_PITCH], Bt[TK_KT * TK_PITCH];  // table rows / users of one stage, feature-major
   __shared__ float w2s[TK_KT];
   __shared__ uint64_t buf[TK_TILE * TK_CB], thr[TK_TILE];
   __shared__ TkHalfT<KCAP> halves[4][2];
   __shared__ int cnt[TK_TILE];
   __shared__ int rng[4];
+  constexpr bool DRAW_LATE = SAMPLE && KCAP > XNRS_TOPK_MAX_K;  // the logarithms of a draw: in the candidate loop
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, half = lane >> 5;
   const int rw = (wave >> 1) * 64, uw = (wave & 1) * 64;  // (TkThread's coordinates, spelled out: profiles/sweep_split_resource_usage.md)
   const int64_t u0 = (int64_t)blockIdx.x * TK_TILE;
@@ -330,6 +360,17 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
   }
   __syncthreads();
   const float bias = a.bias ? a.bias[0] : 0.f;
+  uint32_t z_lo[2] = {0u, 0u}, z_hi[2] = {0u, 0u};  // SAMPLE: the 64-bit part of the draws of the lane's two users
+  if constexpr (SAMPLE) {
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub) {
+      const int ul = uw + ub * 32 + l32;
+      const int64_t key = ul >= nu ? 0 : a.user_keys ? a.user_keys[u0 + ul] : u0 + ul;
+      const uint64_t z = drop_pair(a.seed, key);
+      z_lo[ub] = (uint32_t)z;
+      z_hi[ub] = (uint32_t)(z >> 32);
+    }
+  }
   for (int64_t c = c_lo; c < c_hi; ++c) {
     const int64_t r0 = c * TK_TILE;
     if (win.gaps && !tk_chunk_live(win, r0)) continue;
@@ -345,9 +386,28 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
       for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-          const float s = acc[rb][ub][j] + bias;
-          acc[rb][ub][j] = s;
-          if (ul < nu && s >= tS) pend |= 1ull << (ub * 32 + rb * 16 + j);  // (false for a NaN)
+          float s = acc[rb][ub][j] + bias;
+          if constexpr (DRAW_LATE) {
+            const float p = __fmul_rn(s, a.inv_tau);
+            acc[rb][ub][j] = p;  // (the key is p + g: formed in the candidate loop, for what may reach the threshold)
+            bool may = ul < nu && __fadd_rn(p, DROP_GUMBEL_MAX) >= tS;  // (false for a NaN)
+            if (may) {
+              const uint32_t row = (uint32_t)(r0 + rw + rb * 32 + (j >> 2) * 8 + half * 4 + (j & 3));
+              may = __fadd_rn(p, drop_gumbel_bound(drop_word(z_lo[ub], z_hi[ub], row))) >= tS;
+            }
+            if (may) pend |= 1ull << (ub * 32 + rb * 16 + j);
+          } else {
+            if constexpr (SAMPLE) {
+              const float p = __fmul_rn(s, a.inv_tau);
+              s = p;  // (without a draw: p <= fl(p + DROP_GUMBEL_MAX) < tS, or a NaN -- not a candidate either way)
+              if (ul < nu && __fadd_rn(p, DROP_GUMBEL_MAX) >= tS) {  // (false for a NaN)
+                const uint32_t row = (uint32_t)(r0 + rw + rb * 32 + (j >> 2) * 8 + half * 4 + (j & 3));
+                s = __fadd_rn(p, drop_gumbel(drop_word(z_lo[ub], z_hi[ub], row)));
+              }
+            }
+            acc[rb][ub][j] = s;
+            if (ul < nu && s >= tS) pend |= 1ull << (ub * 32 + rb * 16 + j);  // (false for a NaN)
+          }
         }
     }
     // only what lies inside the user's window -- and so inside the table -- is a candidate: a user whose window is elsewhere
@@ -359,10 +419,11 @@ __global__ __launch_bounds__(256, MLP || KCAP > XNRS_TOPK_MAX_K ? 1 : 2) void to
       for (uint64_t todo = pend; todo; todo &= todo - 1) {
         const int b = __ffsll((unsigned long long)todo) - 1;
         // element b of the lane's 64 scores
-        const float s = (b & 32) ? ((b & 16) ? tk_pick16(acc[1][1], b) : tk_pick16(acc[0][1], b))
-                                 : ((b & 16) ? tk_pick16(acc[1][0], b) : tk_pick16(acc[0][0], b));
+        float s = (b & 32) ? ((b & 16) ? tk_pick16(acc[1][1], b) : tk_pick16(acc[0][1], b))
+                           : ((b & 16) ? tk_pick16(acc[1][0], b) : tk_pick16(acc[0][0], b));
         const int ul = uw + (b >> 5) * 32 + l32;
         const int64_t row = r0 + rw + ((b >> 4) & 1) * 32 + ((b & 15) >> 2) * 8 + half * 4 + (b & 3);
+        if constexpr (DRAW_LATE) s = __fadd_rn(s, drop_gumbel(drop_word((b & 32) ? z_lo[1] : z_lo[0], (b & 32) ? z_hi[1] : z_hi[0], (uint32_t)row)));
         const uint64_t key = tk_key(s, (uint32_t)row);
         bool keep = false;
         if (row != a.pad_row && key > thr[ul]) {  // (`pend` holds rows inside the table and the user's window only)
@@ -494,6 +555,11 @@ struct TopkCall : SweepCall {
   int32_t* rows;
   float* scores;
   bool deep;  // xnrs_topk_deep*: k up to XNRS_TOPK_DEEP_MAX_K
+  // xnrs_topk_sample*: the keys are score / temperature + Gumbel noise of (seed, user key, row); `scores` receives the keys
+  bool sample;
+  float temperature;
+  uint64_t seed;
+  const int64_t* user_keys;
 };
 
 // the projected user side [B, proj_width] | k > XNRS_TOPK_MAX_K: the floor keys [B] | the partial lists [slices, B, k] of 64-bit keys
@@ -506,6 +572,8 @@ size_t tk_workspace_bytes(int64_t B, int64_t n_rows, int32_t proj_width, int32_t
 int32_t tk_check(const TopkCall& c, const float* u, bool* run) {
   const int32_t max_k = c.deep ? XNRS_TOPK_DEEP_MAX_K : XNRS_TOPK_MAX_K;
   if (c.k < 1 || c.k > max_k) return XNRS_EINVAL;
+  // (!(x > 0) refuses a NaN; a temperature so small that its reciprocal overflows would turn a zero score into a NaN key)
+  if (c.sample && (!(c.temperature > 0.f) || !std::isfinite(c.temperature) || !std::isfinite(1.f / c.temperature))) return XNRS_EINVAL;
   XNRS_TRY_RC(sweep_check(c, u, run));
   if (*run && (!c.rows || !c.scores)) return XNRS_EINVAL;
   if (*run && (!c.ws || c.ws_bytes < tk_workspace_bytes(c.B, c.n_rows, c.proj_width, c.k, max_k))) return XNRS_EWORKSPACE;
@@ -520,11 +588,19 @@ int32_t tk_check(const TopkCall& c, const float* u, bool* run) {
 // there, so that about k rows of the whole table pass instead of about k (1 + ln(slice rows / k)) per slice.  The floor only
 // removes rows that cannot be among the k, so the result does not depend on it.  The MLP form sweeps once: its tanhf cost more
 // than its merges.  The first sweep's lists lie where the second sweep's will (they are dead by then).
-hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const float* bias, hipStream_t stream) {
+// SAMPLE (xnrs_topk_sample*): the same launches with the sampled instantiations of the partial kernel; both sweeps of a deep
+// call draw the same noise, so the floor is a floor of the perturbed keys.
+template <bool SAMPLE>
+hipError_t tk_launch_as(const TopkCall& c, const float* up, const float* w2, const float* bias, hipStream_t stream) {
   const int32_t slices = xnrs_topk_slices(c.B, c.n_rows);
-  TopkArgs a{};
+  typename TkArgsOf<SAMPLE>::type a{};
   sweep_operands(c, up, w2, bias, a);
   a.k = c.k;
+  if constexpr (SAMPLE) {
+    a.inv_tau = 1.f / c.temperature;
+    a.seed = c.seed;
+    a.user_keys = c.user_keys;
+  }
   const bool deep = c.k > XNRS_TOPK_MAX_K;
   Carver carve;
   carve.take((size_t)c.B * c.proj_width * F32);
@@ -536,7 +612,7 @@ hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const 
   const int kl = slices > 1 ? (c.k + slices - 2) / (slices - 1) : 0;
   if (deep && !w2 && kl >= 1 && kl <= XNRS_TOPK_MAX_K) {
     a.k = kl;
-    hipLaunchKernelGGL(topk_partial_kernel<false>, grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((topk_partial_kernel<false, XNRS_TOPK_MAX_K, SAMPLE>), grid, dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(topk_floor_kernel, dim3((unsigned)((c.B + 255) / 256)), dim3(256), 0, stream, a.part, slices, c.B, kl, c.k, floor);
@@ -545,10 +621,10 @@ hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const 
     a.k = c.k;
     a.floor = floor;
   }
-  if (deep && w2) hipLaunchKernelGGL((topk_partial_kernel<true, XNRS_TOPK_DEEP_MAX_K>), grid, dim3(256), 0, stream, a);
-  else if (deep) hipLaunchKernelGGL((topk_partial_kernel<false, XNRS_TOPK_DEEP_MAX_K>), grid, dim3(256), 0, stream, a);
-  else if (w2) hipLaunchKernelGGL(topk_partial_kernel<true>, grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(topk_partial_kernel<false>, grid, dim3(256), 0, stream, a);
+  if (deep && w2) hipLaunchKernelGGL((topk_partial_kernel<true, XNRS_TOPK_DEEP_MAX_K, SAMPLE>), grid, dim3(256), 0, stream, a);
+  else if (deep) hipLaunchKernelGGL((topk_partial_kernel<false, XNRS_TOPK_DEEP_MAX_K, SAMPLE>), grid, dim3(256), 0, stream, a);
+  else if (w2) hipLaunchKernelGGL((topk_partial_kernel<true, XNRS_TOPK_MAX_K, SAMPLE>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((topk_partial_kernel<false, XNRS_TOPK_MAX_K, SAMPLE>), grid, dim3(256), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 mgrid((unsigned)((c.B + 3) / 4));
@@ -556,13 +632,25 @@ hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const 
   else hipLaunchKernelGGL(topk_merge_kernel<XNRS_TOPK_MAX_K>, mgrid, dim3(256), 0, stream, a.part, slices, c.B, c.k, c.rows, c.scores);
   return hipGetLastError();
 }
+hipError_t tk_launch(const TopkCall& c, const float* up, const float* w2, const float* bias, hipStream_t stream) {
+  return c.sample ? tk_launch_as<true>(c, up, w2, bias, stream) : tk_launch_as<false>(c, up, w2, bias, stream);
+}
 
-// the one body of the nine entry points: W the table's width (E, or H of the MLP form); win_lo, win_hi NULL without windows
+// what xnrs_topk_sample* adds to a deep call
+struct TkNoise {
+  float temperature;
+  uint64_t seed;
+  const int64_t* user_keys;
+};
+
+// the one body of the twelve entry points: W the table's width (E, or H of the MLP form); win_lo, win_hi NULL without windows;
+// noise NULL but for xnrs_topk_sample*
 int32_t tk_run(bool deep, const Scorer& s, const float* table, int64_t n_rows, int32_t W, const float* u, int64_t B,
                const int64_t* excl_off, const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi, int32_t pad_row,
-               int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
+               int32_t k, int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream, const TkNoise* noise = nullptr) {
   const SweepCall sc(table, n_rows, W, B, excl_off, excl_rows, win_lo, win_hi, pad_row, ws, ws_bytes, s.form == Scorer::DOT ? 0 : W);
-  const TopkCall c{sc, k, rows, scores, deep};
+  TopkCall c{sc, k, rows, scores, deep};
+  if (noise) c.sample = true, c.temperature = noise->temperature, c.seed = noise->seed, c.user_keys = noise->user_keys;
   return sweep_scored<TopkCall>(c, s, u, tk_check, tk_launch, (hipStream_t)stream);
 }
 
@@ -630,6 +718,36 @@ int32_t xnrs_topk_deep_mlp_win(const float* P, int64_t n_rows, int32_t E, int32_
                                int32_t* rows, float* scores, void* ws, size_t ws_bytes, void* stream) {
   return tk_run(true, sc_mlp(E, w1, b1, w2, b2), P, n_rows, H, u, B, excl_off, excl_rows, win_lo, win_hi, pad_row, k, rows, scores, ws,
                 ws_bytes, stream);
+}
+
+// ---- xnrs_topk_sample*_win: the deep twins with the noise behind k
+int32_t xnrs_topk_sample_win(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const int64_t* excl_off,
+                             const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi, int32_t pad_row, int32_t k,
+                             float temperature, uint64_t seed, const int64_t* user_keys, int32_t* rows, float* scores, void* ws,
+                             size_t ws_bytes, void* stream) {
+  const TkNoise noise{temperature, seed, user_keys};
+  return tk_run(true, {}, table, n_rows, E, u, B, excl_off, excl_rows, win_lo, win_hi, pad_row, k, rows, scores, ws, ws_bytes, stream,
+                &noise);
+}
+
+int32_t xnrs_topk_sample_bilinear_win(const float* table, int64_t n_rows, int32_t E, const float* u, int64_t B, const float* w,
+                                      const float* bias, const int64_t* excl_off, const int32_t* excl_rows, const int32_t* win_lo,
+                                      const int32_t* win_hi, int32_t pad_row, int32_t k, float temperature, uint64_t seed,
+                                      const int64_t* user_keys, int32_t* rows, float* scores, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  const TkNoise noise{temperature, seed, user_keys};
+  return tk_run(true, sc_bilinear(w, bias), table, n_rows, E, u, B, excl_off, excl_rows, win_lo, win_hi, pad_row, k, rows, scores, ws,
+                ws_bytes, stream, &noise);
+}
+
+int32_t xnrs_topk_sample_mlp_win(const float* P, int64_t n_rows, int32_t E, int32_t H, const float* u, int64_t B, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, const int64_t* excl_off,
+                                 const int32_t* excl_rows, const int32_t* win_lo, const int32_t* win_hi, int32_t pad_row, int32_t k,
+                                 float temperature, uint64_t seed, const int64_t* user_keys, int32_t* rows, float* scores,
+                                 void* ws, size_t ws_bytes, void* stream) {
+  const TkNoise noise{temperature, seed, user_keys};
+  return tk_run(true, sc_mlp(E, w1, b1, w2, b2), P, n_rows, H, u, B, excl_off, excl_rows, win_lo, win_hi, pad_row, k, rows, scores, ws,
+                ws_bytes, stream, &noise);
 }
 
 // ---- xnrs_topk_deep*: their _win twins without windows

@@ -277,10 +277,12 @@ def _recommending_model_parts(model, behaviors: Behaviors, k: int, windowed: boo
 
 
 def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, sessions, batch: int,
-                        exclude_history: bool, windows=None, vecs_out=None):
+                        exclude_history: bool, windows=None, vecs_out=None, sample=None):
     """The table of `model` encoded once, then per batch of sessions (lo, sess, hist rows, top-k rows, top-k scores).
     windows: (lo, hi) int32 per session id on the device, gathered with the batch's sessions, or None.  vecs_out: a list that
-    receives the encoded news vectors before the first batch (what a second stage over the same table reads), or None."""
+    receives the encoded news vectors before the first batch (what a second stage over the same table reads), or None.
+    sample = (temperature, seed): parts holds the scorer's topk_sample, called with the session ids as the user keys, and a
+    batch is (lo, sess, hist rows, sampled rows, their raw scores, their perturbed keys)."""
     prepare, topk, uidx = parts
     vecs, hm = encode_news_table(model, store)
     if vecs_out is not None:
@@ -299,11 +301,24 @@ def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_
         m = hm[hist.long()]
         u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
         excl = _history_csr(behaviors, sess, lo if every else None) if exclude_history else (None, None)
-        if windows is None:
+        if sample is not None:
+            kw = {} if windows is None else dict(win_lo=windows[0][sess].contiguous(), win_hi=windows[1][sess].contiguous())
+            rows, keys = topk(table, u, k, sample[0], sample[1], sess.contiguous(), excl[0], excl[1], store.pad_row, **kw)
+            yield lo, sess, hist, rows, _raw_scores(model.rec_model, table, u, rows), keys
+        elif windows is None:
             yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row))
         else:
             yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row,
                                                 win_lo=windows[0][sess], win_hi=windows[1][sess]))
+
+
+def _raw_scores(scorer, table: torch.Tensor, u: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """The scorer's raw scores (score_csr, no ReLU) of the listed rows:(b, k) int32 of each user, -inf on the empty places (-1)."""
+    b, k = rows.shape
+    ok = rows >= 0
+    sess = torch.arange(b, device=rows.device, dtype=torch.int32).repeat_interleave(k)
+    r = scorer.score_csr(table, torch.where(ok, rows, torch.zeros_like(rows)).reshape(-1), sess, u, relu=False).reshape(b, k)
+    return torch.where(ok, r, torch.full_like(r, float("-inf")))
 
 
 def _rerank(rows: torch.Tensor, r: torch.Tensor, k: int):
@@ -379,6 +394,69 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
         rows[lo:lo + batch], scores[lo:lo + batch] = _rerank(cand, r, k)
     hip.check_status(dev)
     return rows, scores
+
+
+@torch.no_grad()
+def recommend_sampled(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int, temperature: float, seed: int,
+                      sessions=None, batch: int = 4096, exclude_history: bool = True, windows=None, return_keys: bool = False,
+                      generator=None):
+    """recommend() as a stochastic ranking policy: for every session a list of k news DRAWN from the whole table instead of
+    the k best -- a sample without replacement from the Plackett-Luce distribution P(news first) ~ exp(score / temperature),
+    continued over the rest (include/xnrs_hip.h: xnrs_topk_sample_win; Gumbel top-k inside the top-k sweep, no (sessions,
+    n_rows) matrix) -> (rows:(n,k) int32, scores:(n,k) fp32[, keys:(n,k) fp32]) on the device, in the order drawn.  One
+    temperature trades accuracy against exposure: towards 0 the lists tend to recommend()'s, a large one spreads exposure
+    over the catalogue (diversity_metrics measures coverage and the Gini of exposure of either).
+
+    The draw of a (session, news) pair is a pure function of (seed, SESSION ID, table row): a session's list does not depend
+    on `batch`, on which other sessions are asked for or on the run; vary `seed` to draw again.  Encoding, eligibility
+    (store.pad_row, `exclude_history`), `sessions` and `windows` are those of recommend().
+
+    `scores` are the model's RAW scores of the returned rows, from the scorer's score_csr(..., relu=False), -inf on the empty
+    places (-1) of a session with fewer than k eligible news.  They agree with recommend()'s scores of the same rows to
+    rounding, NOT bit for bit: score_csr sums a row's products in another order than the sweep's score tile.
+    return_keys=True adds the perturbed keys score / temperature + g the lists are ordered by.
+
+    Refused before anything is encoded: temperature not finite or <= 0 and k > 1024 (ValueError); a scorer without
+    topk_sample / prepare_csr / score_csr, a model whose news vectors depend on the user (NPA), CAUM, and `generator` --
+    sampling behind a candidate generator is not implemented (NotImplementedError)."""
+    import math
+    k = int(k)
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"recommend_sampled(): temperature = {temperature!r}: a finite number above 0")
+    if k > TOPK_DEEP_MAX_K:
+        raise ValueError(f"recommend_sampled(): k = {k} is above the longest list of the top-k kernels, {TOPK_DEEP_MAX_K}")
+    if generator is not None:
+        raise NotImplementedError("recommend_sampled(generator=...): sampling behind a candidate generator is not implemented")
+    scorer = getattr(model, "rec_model", None)
+    prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, "topk_sample", None)
+    if prepare is None or topk is None or getattr(scorer, "score_csr", None) is None:
+        raise NotImplementedError(f"recommend_sampled(): the scorer {type(scorer).__name__} has no sampled top-k path over a news "
+                                  "table (prepare_csr / topk_sample / score_csr)")
+    if getattr(model, "user_dependent_news", False):
+        raise NotImplementedError(f"recommend_sampled(): the news vectors of {type(model).__name__} depend on the user, so no "
+                                  "table of news vectors exists to sample from")
+    from .models.caum import CAUM
+    if isinstance(model, CAUM):
+        raise NotImplementedError("recommend_sampled(): CAUM has no candidate-independent user vector to rank a table with")
+    if windows is not None and not _takes_windows(topk):
+        raise NotImplementedError(f"recommend_sampled(windows=...): the topk_sample of the scorer {type(scorer).__name__} takes "
+                                  "no row windows (win_lo, win_hi)")
+    uidx = None
+    if getattr(model, "uses_user_index", False):
+        uidx = getattr(behaviors, "user_index", None)
+        if uidx is None:
+            raise ValueError(f"recommend_sampled(): {type(model).__name__} needs the user index of every session")
+    n = len(behaviors) if sessions is None else len(sessions)
+    dev = behaviors.hist_off.device
+    windows = _session_windows(windows, behaviors, dev, "recommend_sampled()")
+    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    keys = torch.empty((n, k), dtype=torch.float32, device=dev)
+    for lo, _, _, r, s, g in _table_topk_batches(model, (prepare, topk, uidx), store, behaviors, l_hist, k, sessions, batch,
+                                                 exclude_history, windows, sample=(float(temperature), int(seed))):
+        rows[lo:lo + batch], scores[lo:lo + batch], keys[lo:lo + batch] = r, s, g
+    hip.check_status(dev)
+    return (rows, scores, keys) if return_keys else (rows, scores)
 
 
 def _two_stage_parts(model, generator, behaviors: Behaviors, k: int, pool, windowed: bool):

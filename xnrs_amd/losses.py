@@ -200,23 +200,43 @@ def _check_neg_rows(neg_rows, n_sessions: int, who: str):
                          f"{tuple(getattr(neg_rows, 'shape', ()))} {getattr(neg_rows, 'dtype', type(neg_rows))}")
 
 
+def _check_sampling(temperature, seed, who: str):
+    """temperature / seed of a loss whose negatives are drawn: a finite temperature above 0 comes with an integer seed."""
+    import math
+    if temperature is None:
+        if seed is not None:
+            raise ValueError(f"{who}: seed = {seed!r} without a temperature: the hardest negatives are not drawn")
+        return
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"{who}: temperature = {temperature!r}: a finite number above 0, or None for the hardest negatives")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"{who}: seed = {seed!r}: drawn negatives need an integer seed; vary it per step")
+
+
 def mine_and_rank(scorer, vecs, u, hist_csr, tgt_csr, pad_row: int, n_negatives: int, win=(None, None), reduction: str = "mean",
-                  neg_rows=None, return_negatives: bool = False):
+                  neg_rows=None, return_negatives: bool = False, temperature=None, seed=None, user_keys=None):
     """The part of mined_negatives_loss() behind the user vectors: without `neg_rows` the scorer's topk_deep lists, under
     no_grad and on detached operands, the n_negatives rows each user scores highest outside the merged exclusions (history
-    and clicks) and inside the window; then the listed loss over those rows, under autograd."""
+    and clicks) and inside the window; then the listed loss over those rows, under autograd.  With a `temperature` the lists
+    are DRAWN instead (scorer.topk_sample: P(row first) ~ exp(score / temperature), without replacement) under the same
+    exclusions and windows, from `seed` and the (B,) int64 `user_keys` (None: the user's index)."""
     if neg_rows is None:
+        _check_sampling(temperature, seed, "mine_and_rank()")
         excl = merged_exclusions(hist_csr, tgt_csr)
         with torch.no_grad():
             kw = {} if win[0] is None else dict(win_lo=win[0], win_hi=win[1])
-            neg_rows = scorer.topk_deep(vecs.detach(), u.detach(), int(n_negatives), excl[0], excl[1], pad_row, **kw)[0]
+            if temperature is None:
+                neg_rows = scorer.topk_deep(vecs.detach(), u.detach(), int(n_negatives), excl[0], excl[1], pad_row, **kw)[0]
+            else:
+                neg_rows = scorer.topk_sample(vecs.detach(), u.detach(), int(n_negatives), float(temperature), seed, user_keys,
+                                              excl[0], excl[1], pad_row, **kw)[0]
     loss = listed_ranking_loss(scorer, vecs, u, tgt_csr[0], tgt_csr[1], neg_rows, pad_row, reduction)
     return (loss, neg_rows) if return_negatives else loss
 
 
 def mined_negatives_loss(model, store_or_table, behaviors, sessions, l_hist: int, n_negatives: int = 128,
                          exclude_history: bool = True, windows=None, reduction: str = "mean", store=None, neg_rows=None,
-                         return_negatives: bool = False):
+                         return_negatives: bool = False, temperature=None, seed=None):
     """The ranking loss of one batch of sessions against the `n_negatives` HARDEST negatives of each -- the news of the whole
     table the session's user scores highest, mined per step -- instead of against the whole table: the path of
     full_table_loss() up to the user vectors (same arguments, same refusals, raised before anything is encoded), then
@@ -228,19 +248,32 @@ def mined_negatives_loss(model, store_or_table, behaviors, sessions, l_hist: int
 
     neg_rows: a (len(sessions), L) int32 tensor of table rows on the table's device skips the mining: stale lists reused
     over several steps, random sampled negatives.  A slot whose row is outside the table, the pad row or a click of its
-    session is ignored (-1 is the filler).  return_negatives=True returns (loss, rows) with the lists that were used."""
+    session is ignored (-1 is the filler).  return_negatives=True returns (loss, rows) with the lists that were used.
+
+    temperature: the hardest rows are where the false negatives live; with a finite temperature > 0 the n_negatives rows are
+    DRAWN instead, without replacement, P(row first) ~ exp(score / temperature) (scorer.topk_sample: Gumbel top-k inside the
+    same sweep, the same exclusions and windows; the draws are keyed by the session ids).  `seed` (an integer) is then
+    required, and the caller varies it per step -- the same seed draws the same lists.  The listed loss behind the lists is
+    the same call.  temperature=None (the default) is the mining above, bit for bit."""
     who = "mined_negatives_loss()"
     scorer, uidx = _refuse_before_encoding(model, behaviors, reduction, who, _list_loss_scorer, "ranking loss over listed rows")
     n_sessions = int(torch.as_tensor(sessions).numel())
     if neg_rows is not None:
         _check_neg_rows(neg_rows, n_sessions, who)
     else:
+        _check_sampling(temperature, seed, who)
+        if temperature is not None and getattr(scorer, "topk_sample", None) is None:
+            raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no topk_sample to draw negatives with")
         if isinstance(n_negatives, bool) or int(n_negatives) != n_negatives or not 1 <= int(n_negatives) <= 1024:
             raise ValueError(f"{who}: n_negatives = {n_negatives!r}: an integer in [1, 1024], the list lengths of topk_deep")
         if getattr(scorer, "topk_deep", None) is None:
             raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no topk_deep to mine negatives with")
     vecs, u, excl, tgt, win, pad_row = _encode_sessions(model, store_or_table, behaviors, sessions, l_hist, exclude_history,
                                                         windows, store, uidx, who)
+    if neg_rows is None and temperature is not None:
+        keys = torch.as_tensor(sessions, dtype=torch.int64, device=vecs.device).reshape(-1).contiguous()
+        return mine_and_rank(scorer, vecs, u, excl, tgt, pad_row, n_negatives, win, reduction, None, return_negatives,
+                             temperature, seed, keys)
     return mine_and_rank(scorer, vecs, u, excl, tgt, pad_row, n_negatives, win, reduction, neg_rows, return_negatives)
 
 

@@ -237,6 +237,12 @@ class DotScoring(nn.Module):
         return ops.topk_deep_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, k, excl_off, excl_rows, pad_row,
                                  win_lo, win_hi)
 
+    def topk_sample(self, table: torch.Tensor, u: torch.Tensor, k: int, temperature: float, seed: int, user_keys=None,
+                    excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
+        """A list drawn from the scores of topk_deep (ops.topk_sample_dot) -> (rows, perturbed keys)."""
+        return ops.topk_sample_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, k, temperature, seed, user_keys,
+                                   excl_off, excl_rows, pad_row, win_lo, win_hi)
+
     def rank(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
              out=None, win_lo=None, win_hi=None):
         return ops.rank_dot(table, ops.l2_normalize_rows(u) if self.normalize else u, tgt_off, tgt_rows, excl_off, excl_rows,
@@ -292,6 +298,13 @@ class BilinScoring(nn.Module):
         u = ops.l2_normalize_rows(u) if self.normalize else u
         return ops.topk_deep_bilinear(table, u, self.bilin.weight, self.bilin.bias, k, excl_off, excl_rows, pad_row, win_lo,
                                       win_hi)
+
+    def topk_sample(self, table: torch.Tensor, u: torch.Tensor, k: int, temperature: float, seed: int, user_keys=None,
+                    excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
+        """A list drawn from the scores of topk_deep (ops.topk_sample_bilinear) -> (rows, perturbed keys)."""
+        u = ops.l2_normalize_rows(u) if self.normalize else u
+        return ops.topk_sample_bilinear(table, u, self.bilin.weight, self.bilin.bias, k, temperature, seed, user_keys, excl_off,
+                                        excl_rows, pad_row, win_lo, win_hi)
 
     def rank(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
              out=None, win_lo=None, win_hi=None):
@@ -361,6 +374,12 @@ class FCScoring(nn.Module):
                   win_lo=None, win_hi=None):
         return ops.topk_deep_mlp(table, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, k, excl_off,
                                  excl_rows, pad_row, win_lo, win_hi)
+
+    def topk_sample(self, table: torch.Tensor, u: torch.Tensor, k: int, temperature: float, seed: int, user_keys=None,
+                    excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
+        """A list drawn from the scores of topk_deep (ops.topk_sample_mlp) -> (rows, perturbed keys)."""
+        return ops.topk_sample_mlp(table, u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, k, temperature, seed,
+                                   user_keys, excl_off, excl_rows, pad_row, win_lo, win_hi)
 
     def rank(self, table: torch.Tensor, u: torch.Tensor, tgt_off, tgt_rows, excl_off=None, excl_rows=None, pad_row: int = -1,
              out=None, win_lo=None, win_hi=None):

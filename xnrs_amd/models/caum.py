@@ -79,6 +79,7 @@ class CAUMScoring(DotScoring):
     prepare_csr = None
     score_csr = None
     topk = None
+    topk_sample = None
     rank = None
     table_loss = None
     list_loss = None

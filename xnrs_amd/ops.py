@@ -557,13 +557,17 @@ def _windows(win_lo, win_hi, B: int, dev) -> tuple:
 
 
 def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int, k: int, excl_off, excl_rows, pad_row: int,
-          ws_query: str = "xnrs_topk_workspace_bytes", win_lo=None, win_hi=None):
+          ws_query: str = "xnrs_topk_workspace_bytes", win_lo=None, win_hi=None, noise=None):
     """The call every top-k entry point shares behind its own leading arguments `head` -> (rows:(B,k) int32, scores:(B,k)).
     `entry` and `ws_query` name the entry point and its workspace query (xnrs_topk* or xnrs_topk_deep*); with row windows
-    the call goes to `entry`_win (xnrs_topk_deep*_win)."""
+    the call goes to `entry`_win (xnrs_topk_deep*_win).  noise = (temperature, seed, user_keys): `entry` is one of
+    xnrs_topk_sample*_win, which take the three behind k and the windows as nullable pointers."""
     dev = table.device
     win = _windows(win_lo, win_hi, B, dev)
-    if win:
+    if noise is not None:
+        win = win or (None, None)
+        noise = _noise(*noise, B, dev)
+    elif win:
         entry += "_win"
     if (excl_off is None) != (excl_rows is None):
         raise RuntimeError("exclusions: excl_off and excl_rows are given together (a CSR over the users) or not at all")
@@ -579,18 +583,35 @@ def _topk(entry: str, table: torch.Tensor, head: tuple, B: int, proj_width: int,
     l = hip.lib()
     nbytes = getattr(l, ws_query)(B, table.shape[0], proj_width, k)
     ws = hip.workspace(dev, nbytes)
-    hip.check(getattr(l, entry)(*head, hip.ptr(excl_off), hip.ptr(excl_rows), *win, int(pad_row), k,
+    hip.check(getattr(l, entry)(*head, hip.ptr(excl_off), hip.ptr(excl_rows), *win, int(pad_row), k, *(noise or ()),
                                 hip.ptr(rows), hip.ptr(scores), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), entry)
     return rows, scores
 
 
-def _topk_dot(entry, ws_query, table, u, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None):
+def _noise(temperature, seed, user_keys, B: int, dev) -> tuple:
+    """The arguments temperature, seed, user_keys of an xnrs_topk_sample*_win entry point.  temperature: a finite float > 0;
+    seed: any integer, taken mod 2^64; user_keys: None (the user's index in the call) or a (B,) int64 tensor on the table's
+    device.  Anything else is refused before the call."""
+    import math
+    temperature = float(temperature)
+    if not (math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"topk_sample: temperature = {temperature!r}: a finite number above 0")
+    if user_keys is not None:
+        if not isinstance(user_keys, torch.Tensor) or user_keys.dtype != torch.int64 or user_keys.dim() != 1 or user_keys.numel() != B:
+            raise ValueError(f"topk_sample: user_keys is a ({B},) int64 tensor, one key per user; got "
+                             f"{tuple(getattr(user_keys, 'shape', ()))} {getattr(user_keys, 'dtype', type(user_keys))}")
+        if user_keys.device != dev or not user_keys.is_contiguous():
+            raise hip.XnrsHipError(f"topk_sample: user_keys must be a contiguous tensor on {dev}")
+    return temperature, int(seed) % (1 << 64), hip.ptr(user_keys)
+
+
+def _topk_dot(entry, ws_query, table, u, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None, noise=None):
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
     B = u.shape[0]
     return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B), B, 0, k, excl_off, excl_rows, pad_row, ws_query,
-                 win_lo, win_hi)
+                 win_lo, win_hi, noise)
 
 
 def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
@@ -598,7 +619,7 @@ def topk_dot(table, u, k: int, excl_off=None, excl_rows=None, pad_row: int = -1)
     return _topk_dot("xnrs_topk", "xnrs_topk_workspace_bytes", table, u, k, excl_off, excl_rows, pad_row)
 
 
-def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None):
+def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None, noise=None):
     table = hip.dev_f32(table, "news vectors")
     n_rows, E = table.shape
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -606,7 +627,7 @@ def _topk_bilinear(entry, ws_query, table, u, w, b, k, excl_off, excl_rows, pad_
     b = None if b is None else hip.dev_f32(b, "bilinear bias")
     B = u.shape[0]
     return _topk(entry, table, (hip.ptr(table), n_rows, E, hip.ptr(u), B, hip.ptr(w), hip.ptr(b)), B, E, k,
-                 excl_off, excl_rows, pad_row, ws_query, win_lo, win_hi)
+                 excl_off, excl_rows, pad_row, ws_query, win_lo, win_hi, noise)
 
 
 def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
@@ -614,7 +635,7 @@ def topk_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pad_row
     return _topk_bilinear("xnrs_topk_bilinear", "xnrs_topk_workspace_bytes", table, u, w, b, k, excl_off, excl_rows, pad_row)
 
 
-def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None):
+def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row, win_lo=None, win_hi=None, noise=None):
     P = hip.dev_f32(P, "projected news table")
     E = w1.shape[1] // 2
     u = hip.dev_f32(u, "user vectors").reshape(-1, E)
@@ -623,7 +644,7 @@ def _topk_mlp(entry, ws_query, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad
         raise RuntimeError(f"projected news table {tuple(P.shape)} does not match the hidden size {H}")
     B = u.shape[0]
     return _topk(entry, P, (hip.ptr(P), P.shape[0], E, H, hip.ptr(u), B, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2), hip.ptr(b2)), B, H, k,
-                 excl_off, excl_rows, pad_row, ws_query, win_lo, win_hi)
+                 excl_off, excl_rows, pad_row, ws_query, win_lo, win_hi, noise)
 
 
 def topk_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1):
@@ -650,6 +671,32 @@ def topk_deep_bilinear(table, u, w, b, k: int, excl_off=None, excl_rows=None, pa
 def topk_deep_mlp(P, u, w1, b1, w2, b2, k: int, excl_off=None, excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
     """topk_mlp for 1 <= k <= 1024 (xnrs_topk_deep_mlp; with row windows xnrs_topk_deep_mlp_win)."""
     return _topk_mlp("xnrs_topk_deep_mlp", _DEEP_WS, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row, win_lo, win_hi)
+
+
+def topk_sample_dot(table, u, k: int, temperature: float, seed: int, user_keys=None, excl_off=None, excl_rows=None,
+                    pad_row: int = -1, win_lo=None, win_hi=None):
+    """A list of k rows per user DRAWN from the scores of topk_deep_dot (include/xnrs_hip.h: xnrs_topk_sample_win): a sample
+    without replacement from the Plackett-Luce distribution P(row first) ~ exp(score / temperature), as Gumbel top-k -- the k
+    largest of score / temperature + g, g the Gumbel draw of (seed, user_keys[b], row) -> (rows:(B,k) int32, keys:(B,k) fp32),
+    best key first; `keys` are the PERTURBED keys, not the scores.  user_keys: (B,) int64 (None: 0 .. B-1); a user's list depends
+    on (seed, its key, its scores, temperature) alone, and topk_sample_dot(k)[:, :j] is topk_sample_dot(j).  Exclusions, pad
+    row and windows as topk_deep_dot; 1 <= k <= 1024."""
+    return _topk_dot("xnrs_topk_sample_win", _DEEP_WS, table, u, k, excl_off, excl_rows, pad_row, win_lo, win_hi,
+                     (temperature, seed, user_keys))
+
+
+def topk_sample_bilinear(table, u, w, b, k: int, temperature: float, seed: int, user_keys=None, excl_off=None, excl_rows=None,
+                         pad_row: int = -1, win_lo=None, win_hi=None):
+    """topk_sample_dot over the scores of topk_deep_bilinear (xnrs_topk_sample_bilinear_win)."""
+    return _topk_bilinear("xnrs_topk_sample_bilinear_win", _DEEP_WS, table, u, w, b, k, excl_off, excl_rows, pad_row, win_lo,
+                          win_hi, (temperature, seed, user_keys))
+
+
+def topk_sample_mlp(P, u, w1, b1, w2, b2, k: int, temperature: float, seed: int, user_keys=None, excl_off=None,
+                    excl_rows=None, pad_row: int = -1, win_lo=None, win_hi=None):
+    """topk_sample_dot over the scores of topk_deep_mlp (xnrs_topk_sample_mlp_win)."""
+    return _topk_mlp("xnrs_topk_sample_mlp_win", _DEEP_WS, P, u, w1, b1, w2, b2, k, excl_off, excl_rows, pad_row, win_lo, win_hi,
+                     (temperature, seed, user_keys))
 
 
 def _csr_check(what: str, off, rows, B: int, dev):
