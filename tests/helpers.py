@@ -190,3 +190,20 @@ def fc2_bias_extra_bar(rows, gw, scale, gmax):
     plus 1e-6 of the step's largest gradient, both relative to `scale`.  rows: token rows that went through the pooler;
     gw: max|d fc2.weight| of the reference; gmax: the largest reference gradient of the step."""
     return 4.0 * (rows ** 0.5) * 2.0 ** -23 * gw / scale + 1e-6 * gmax / scale
+
+
+def npa_and_nrms(dev):
+    """(a tiny NPA, a small NRMS over the same token shapes) in eval mode on `dev`, seeded: the two-stage pair of the
+    recommendation tests, NPA re-scoring what the NRMS lists."""
+    from tests.golden import npa_cases as NC
+    from xnrs_amd.models import make_model
+    from xnrs_amd.models.npa import make_npa
+
+    class Cfg(dict):
+        __getattr__ = dict.__getitem__
+
+    torch.manual_seed(4)
+    npa = make_npa(Cfg(NC.model_cfg(dict(NC.CASES["tiny"], D=32, n_users=50), "dot"))).to(dev).eval()
+    torch.manual_seed(11)
+    nrms = make_model(Cfg(synth.model_cfg(dict(model="NRMS", E=32, bias=True, h=4, D=32, H=8, S=6)))).to(dev).eval()
+    return npa, nrms

@@ -298,15 +298,8 @@ def test_recommend_deep_end_to_end(kind):
 
 # ------------------------------------------------------------------------------------------- 11. two stages
 def _npa_and_nrms():
-    from tests.golden import npa_cases as NC
-    from tests.test_hip_npa import Cfg
-    from xnrs_amd.models import make_model
-    from xnrs_amd.models.npa import make_npa
-    torch.manual_seed(4)
-    npa = make_npa(Cfg(NC.model_cfg(dict(NC.CASES["tiny"], D=32, n_users=50), "dot"))).to(DEV).eval()
-    torch.manual_seed(11)
-    nrms = make_model(Cfg(synth.model_cfg(dict(model="NRMS", E=32, bias=True, h=4, D=32, H=8, S=6)))).to(DEV).eval()
-    return npa, nrms
+    from tests.helpers import npa_and_nrms
+    return npa_and_nrms(DEV)
 
 
 def _npa_scores(npa, store, beh, l_hist, cand):

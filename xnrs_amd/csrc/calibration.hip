@@ -11,33 +11,30 @@
 //                is 0 at N == 0), again a block_sum2 -- beside it the same sum at N + 1, which the greedy needs
 // kl_term rounds every operation on its own (no contraction) and calls logf (OCML).  xnrs_list_calibration's out_kl and the
 // out_kl of xnrs_calibrated_rerank are both block_kl over LDS counts: the same bits for the same counts.
-//   rerank : one workgroup per session; LDS holds lam * r, the category and the alive byte of each of the P places, and p, the
-//            counts and the penalty of each of the n_cat categories.  A step: (1) every category's term at N + 1 goes to LDS
-//            while block_kl adds them to S1 and the terms at N to S0; (2) pen[c] = (S1 - term_c(n_c)) + term_c(n_c + 1), a
-//            place without a category takes S0; (3) argmax of lam r - (1 - lam) pen over the alive places (thread, wave
-//            butterfly, four waves through LDS; equal objectives to the lower place); (4) thread 0 counts the pick and writes
-//            it.  A session without a target skips (1) and (2): its penalty is 0.
+//   rerank : the greedy loop of greedy.h under the penalty KL(p || mix of the picks with the place added); LDS holds the
+//            category of each of the P places, and p, the counts and the penalty of each of the n_cat categories.  Before a
+//            step's argmax (1) every category's term at N + 1 goes to LDS while block_kl adds them to S1 and the terms at N to
+//            S0; (2) pen[c] = (S1 - term_c(n_c)) + term_c(n_c + 1), a place without a category takes S0; thread 0 counts the
+//            pick.  A session without a target skips (1) and (2): its penalty is 0.
 //   counts : one workgroup per list, an LDS histogram with integer atomics, every output word written.
 // Every load is of one element (4 bytes; the CSR offsets 8): an operand may sit at any address of its element type, and no
 // second code path exists.  No workspace, no float atomics, no host synchronisation; a session's bits depend on its own
 // operands alone.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 
+#include "greedy.h"
 #include "host.h"
 
 namespace xnrs {
 
 namespace {
 
-constexpr int CB_THREADS = 256;  // 4 waves per workgroup
-constexpr int CB_WAVES = CB_THREADS / 64;
-constexpr int CB_SCRATCH = 16;   // words in front of the dynamic LDS: two sums or an argmax per wave, the integer counters
-
-__host__ __device__ __forceinline__ int cb_pad4(int n) { return (n + 3) & ~3; }
+constexpr int CB_THREADS = GREEDY_THREADS;  // 4 waves per workgroup
+constexpr int CB_WAVES = GREEDY_WAVES;
+constexpr int CB_SCRATCH = GREEDY_SCRATCH;  // words in front of the dynamic LDS: two sums or an argmax per wave, the integer counters
 
 // (a, b) summed over the workgroup in the order of the header; red: 2 * CB_WAVES floats nobody else writes.  The barrier in
 // front keeps a second call from overwriting sums a slower wave has yet to read.
@@ -128,166 +125,93 @@ __global__ __launch_bounds__(CB_THREADS) void csr_counts_kernel(const int64_t* _
 
 // --------------------------------------------------------------------------------------------------------------- rerank
 struct CalArgs {
-  const int32_t* pool_rows;
-  const float* pool_scores;
-  int P, k;
+  GreedyArgs g;
   const int32_t* row_cat;
-  int64_t n_rows;
   int n_cat;
   const float* target;
-  float lam, alpha;
-  int rel_mode;
-  int32_t* out_rows;
-  float* out_scores;
-  int32_t* out_pos;
+  float alpha;
   float* out_kl;
 };
 
-// lam r - (1 - lam) pen, two products and one difference, each rounded (no contraction: at lam = 1 it is r exactly)
-__device__ __forceinline__ float cal_objective(float lam_r, float oml, float pen) {
-#pragma clang fp contract(off)
-  const float cost = oml * pen;
-  return lam_r - cost;
-}
 // (S1 - term_c(n_c)) + term_c(n_c + 1), each rounded
 __device__ __forceinline__ float cal_penalty(float s1, float now, float then) {
 #pragma clang fp contract(off)
   const float rest = s1 - now;
   return rest + then;
 }
-// does the candidate (v, i) come before (bv, bi)?  higher objective, then the lower place; (-inf, INT_MAX) is "none"
-__device__ __forceinline__ bool cal_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 // dynamic LDS of a session: the scratch words, then lam * r and the category (int32) per place, then p, the counts and the
 // penalty per category, then the alive bytes
 __host__ __device__ __forceinline__ size_t cal_lds_bytes(int P, int n_cat) {
-  return (size_t)CB_SCRATCH * 4 + (size_t)cb_pad4(P) * 8 + (size_t)cb_pad4(n_cat) * 12 + (size_t)cb_pad4(P);
+  return (size_t)CB_SCRATCH * 4 + (size_t)pad4(P) * 8 + (size_t)pad4(n_cat) * 12 + (size_t)pad4(P);
 }
 
-__global__ __launch_bounds__(CB_THREADS) void cal_kernel(CalArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  const int P = a.P, k = a.k, C = a.n_cat;
-  float* s_red = reinterpret_cast<float*>(s_raw);         // 2 * CB_WAVES sums (block_sum2), or minima and maxima
-  float* s_wv = s_red;                                     // the waves' argmax values ...
-  int* s_wi = reinterpret_cast<int*>(s_red + 2 * CB_WAVES);  // ... and places
-  float* s_lr = s_red + CB_SCRATCH;
-  int* s_cat = reinterpret_cast<int*>(s_lr + cb_pad4(P));
-  float* s_p = reinterpret_cast<float*>(s_cat + cb_pad4(P));
-  int* s_cnt = reinterpret_cast<int*>(s_p + cb_pad4(C));
-  float* s_pen = reinterpret_cast<float*>(s_cnt + cb_pad4(C));
-  unsigned char* s_alive = reinterpret_cast<unsigned char*>(s_pen + cb_pad4(C));
-  const int64_t b = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t* __restrict__ rows = a.pool_rows + b * (int64_t)P;
-  const float* __restrict__ scores = a.pool_scores + b * (int64_t)P;
+// the penalty of calibration (greedy.h): the miscalibration of the picks so far with place i added
+struct CalPolicy {
+  const int32_t* row_cat;
+  int C;
+  float alpha, oma;
+  float* s_red;
+  int* s_cat;
+  const float* s_p;
+  int* s_cnt;
+  float* s_pen;
+  bool has_target = false;
+  int N = 0;         // categorised picks so far (the same in every thread)
+  float pen0 = 0.f;  // the penalty of a place without a category
 
-  // the places: valid = a row of the table and a finite score; the category is read for a valid place only
-  float lo = INFINITY, hi = -INFINITY;
-  for (int i = tid; i < P; i += CB_THREADS) {
-    const int r = rows[i];
-    const float s = scores[i];
-    const bool ok = r >= 0 && r < a.n_rows && fabsf(s) < INFINITY;  // (NaN compares false)
+  // the category is read for a valid place only
+  __device__ __forceinline__ void stage(int i, int r, bool ok) {
     int c = -1;
     if (ok) {
-      c = a.row_cat[r];
+      c = row_cat[r];
       if (c < 0 || c >= C) c = -1;
     }
     s_cat[i] = c;
-    s_alive[i] = ok ? 1 : 0;
-    s_lr[i] = ok ? s : 0.f;  // (the score for now)
-    if (ok) {
-      lo = fminf(lo, s);
-      hi = fmaxf(hi, s);
-    }
   }
-  for (int c = tid; c < C; c += CB_THREADS) s_cnt[c] = 0;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, m));
-    hi = fmaxf(hi, __shfl_xor(hi, m));
-  }
-  if (lane == 0) {
-    s_red[wave] = lo;
-    s_red[CB_WAVES + wave] = hi;
-  }
-  __syncthreads();
-  lo = fminf(fminf(s_red[0], s_red[1]), fminf(s_red[2], s_red[3]));
-  hi = fmaxf(fmaxf(s_red[CB_WAVES], s_red[CB_WAVES + 1]), fmaxf(s_red[CB_WAVES + 2], s_red[CB_WAVES + 3]));
-  const float span = hi - lo;
-  for (int i = tid; i < P; i += CB_THREADS) {  // (a thread rewrites the places it wrote)
-    float r = s_lr[i];
-    if (a.rel_mode == XNRS_MMR_REL_MINMAX) r = span > 0.f ? (r - lo) / span : 0.f;
-    s_lr[i] = a.lam * r;
-  }
-  const float oml = 1.f - a.lam, alpha = a.alpha, oma = 1.f - a.alpha;
-  const bool has_target = stage_target(a.target + b * (int64_t)C, C, s_p, s_red);  // (its barriers cover the loops above)
-
-  int N = 0;  // categorised picks so far (the same in every thread)
-  int t = 0;
-  for (; t < k; ++t) {
-    float pen0 = 0.f;
+  __device__ __forceinline__ void prepare(int) {
     if (has_target) {
       float s1;
       pen0 = block_kl(s_p, s_cnt, C, N, oma, alpha, s_red, s_pen, &s1);  // s_pen[c] = term_c(n_c) at N + 1 for now
-      for (int c = tid; c < C; c += CB_THREADS)                          // (a thread rewrites the categories it wrote)
+      for (int c = threadIdx.x; c < C; c += CB_THREADS)                  // (a thread rewrites the categories it wrote)
         s_pen[c] = cal_penalty(s1, s_pen[c], kl_term(s_p[c], s_cnt[c] + 1, N + 1, oma, alpha));
     }
     __syncthreads();
-    // argmax of the objective over the alive places: ascending places per thread, so `>` keeps the lower of two equals
-    float bv = -INFINITY;
-    int bi = INT_MAX;
-    for (int i = tid; i < P; i += CB_THREADS)
-      if (s_alive[i]) {
-        const int c = s_cat[i];
-        const float pen = !has_target ? 0.f : (c >= 0 ? s_pen[c] : pen0);
-        const float v = cal_objective(s_lr[i], oml, pen);
-        if (cal_before(v, i, bv, bi)) {
-          bv = v;
-          bi = i;
-        }
-      }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float ov = __shfl_xor(bv, m);
-      const int oi = __shfl_xor(bi, m);
-      if (cal_before(ov, oi, bv, bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      s_wv[wave] = bv;
-      s_wi[wave] = bi;
-    }
-    __syncthreads();
-    bv = s_wv[0];
-    bi = s_wi[0];
-#pragma unroll
-    for (int w = 1; w < CB_WAVES; ++w)
-      if (cal_before(s_wv[w], s_wi[w], bv, bi)) {
-        bv = s_wv[w];
-        bi = s_wi[w];
-      }
-    if (bi == INT_MAX) break;  // no valid place is left (the same for every thread)
+  }
+  __device__ __forceinline__ float penalty(int i) const {
+    const int c = s_cat[i];
+    return !has_target ? 0.f : (c >= 0 ? s_pen[c] : pen0);
+  }
+  // the last pick is counted too: out_kl is over all of them
+  __device__ __forceinline__ void take(int bi, int, bool) {
     const int c = s_cat[bi];
-    if (tid == 0) {
-      a.out_rows[b * k + t] = rows[bi];
-      a.out_scores[b * k + t] = scores[bi];  // the pool's own bits
-      a.out_pos[b * k + t] = bi;
-      s_alive[bi] = 0;
-      if (c >= 0) s_cnt[c] += 1;
+    if (c >= 0) {
+      if (threadIdx.x == 0) s_cnt[c] += 1;
+      ++N;
     }
-    if (c >= 0) ++N;
-    __syncthreads();  // (the pick is counted before the next step's sums; s_wv is read before block_sum2 writes over it)
+    __syncthreads();  // (the pick is counted before the next step's sums; the argmax words are read before block_sum2 writes over them)
   }
-  for (int u = t + tid; u < k; u += CB_THREADS) {  // fillers behind the picks
-    a.out_rows[b * k + u] = -1;
-    a.out_scores[b * k + u] = -INFINITY;
-    a.out_pos[b * k + u] = -1;
-  }
+};
+
+__global__ __launch_bounds__(CB_THREADS) void cal_kernel(CalArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  const int P = a.g.P, C = a.n_cat;
+  float* s_red = reinterpret_cast<float*>(s_raw);  // the scratch words of the loop; [0, 2 * CB_WAVES) are block_sum2's too
+  float* s_lr = s_red + CB_SCRATCH;
+  int* s_cat = reinterpret_cast<int*>(s_lr + pad4(P));
+  float* s_p = reinterpret_cast<float*>(s_cat + pad4(P));
+  int* s_cnt = reinterpret_cast<int*>(s_p + pad4(C));
+  float* s_pen = reinterpret_cast<float*>(s_cnt + pad4(C));
+  unsigned char* s_alive = reinterpret_cast<unsigned char*>(s_pen + pad4(C));
+  const int64_t b = blockIdx.x;
+  CalPolicy pol{a.row_cat, C, a.alpha, 1.f - a.alpha, s_red, s_cat, s_p, s_cnt, s_pen};
+  for (int c = threadIdx.x; c < C; c += CB_THREADS) s_cnt[c] = 0;
+  greedy_stage(a.g, b, s_red, s_lr, s_alive, pol);
+  pol.has_target = stage_target(a.target + b * (int64_t)C, C, s_p, s_red);  // (its barriers cover the loops above)
+  greedy_loop(a.g, b, s_red, s_lr, s_alive, pol);
   float kl = 0.f;
-  if (has_target) kl = block_kl(s_p, s_cnt, C, N, oma, alpha, s_red, nullptr, nullptr);
-  if (tid == 0) a.out_kl[b] = kl;
+  if (pol.has_target) kl = block_kl(s_p, s_cnt, C, pol.N, pol.oma, pol.alpha, s_red, nullptr, nullptr);
+  if (threadIdx.x == 0) a.out_kl[b] = kl;
 }
 
 // ------------------------------------------------------------------------------------------------------ list calibration
@@ -305,7 +229,7 @@ struct ListCalArgs {
 };
 
 // dynamic LDS of a list: the scratch words, then p and the counts per category
-__host__ __device__ __forceinline__ size_t listcal_lds_bytes(int n_cat) { return (size_t)CB_SCRATCH * 4 + (size_t)cb_pad4(n_cat) * 8; }
+__host__ __device__ __forceinline__ size_t listcal_lds_bytes(int n_cat) { return (size_t)CB_SCRATCH * 4 + (size_t)pad4(n_cat) * 8; }
 
 __global__ __launch_bounds__(CB_THREADS) void listcal_kernel(ListCalArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -313,7 +237,7 @@ __global__ __launch_bounds__(CB_THREADS) void listcal_kernel(ListCalArgs a) {
   float* s_red = reinterpret_cast<float*>(s_raw);
   int* s_n = reinterpret_cast<int*>(s_red + 2 * CB_WAVES);
   float* s_p = s_red + CB_SCRATCH;
-  int* s_cnt = reinterpret_cast<int*>(s_p + cb_pad4(C));
+  int* s_cnt = reinterpret_cast<int*>(s_p + pad4(C));
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
   if (tid == 0) *s_n = 0;
@@ -357,7 +281,7 @@ hipError_t launch_calibrated_rerank(const int32_t* pool_rows, const float* pool_
                                     int rel_mode, int32_t* out_rows, float* out_scores, int32_t* out_pos, float* out_kl,
                                     hipStream_t stream) {
   if (B <= 0) return hipSuccess;
-  const CalArgs a{pool_rows, pool_scores, P, k, row_cat, n_rows, n_cat, target, lam, alpha, rel_mode, out_rows, out_scores, out_pos,
+  const CalArgs a{{pool_rows, pool_scores, P, k, n_rows, lam, rel_mode, out_rows, out_scores, out_pos}, row_cat, n_cat, target, alpha,
                   out_kl};
   cal_kernel<<<dim3((unsigned)B), CB_THREADS, cal_lds_bytes(P, n_cat), stream>>>(a);
   return hipGetLastError();

@@ -9,22 +9,21 @@
 // boundary) gives a lane the SAME elements in the same order as the 16-byte form: both produce the same bits.  The norms
 // are the same sum with a == b (the lane's chain and the butterfly: row_dot.h, shared with list_loss.hip).  This is a row
 // gather with no reuse across sessions, so it is VALU work, not MFMA.
-//   mmr  : one workgroup of 4 waves per session, the state of the session in LDS: lam * relevance, the largest cosine to a
-//          selected place, the reciprocal norm, the row and the alive flag of each of the P places, and the row selected
-//          last.  A step is an argmax of lam r_i - (1 - lam) m_i over the alive places (thread, wave butterfly, four waves
-//          through LDS; equal objectives go to the lower place) and one update of m_i over the alive places, DV_UNROLL rows
-//          in flight per wave, against the selected row in LDS.  The pool is streamed again every step (k P E 4 bytes per
-//          session, from L2 / Infinity Cache for the pools this is built for); nothing is staged.
+//   mmr  : the greedy loop of greedy.h under the penalty m_i, the largest cosine of place i to a selected place.  LDS holds
+//          m, the reciprocal norm and the row of each of the P places and the row selected last; a pick is one update of m_i
+//          over the alive places, DV_UNROLL rows in flight per wave, against the selected row in LDS.  The pool is streamed
+//          again every step (k P E 4 bytes per session, from L2 / Infinity Cache for the pools this is built for); nothing
+//          is staged.
 //   ild  : one workgroup per session; place i < k - 1 in turn is the row in LDS and the waves take the places j > i in
 //          groups.  Lane 0 of a wave adds its terms 1 - cos in the order (i, group, j); the four wave sums are added in
 //          wave order: the order is a function of (k, E).  Category counts go through an LDS histogram with integer atomics.
 // No workspace, no float atomics, no host synchronisation; a session's bits depend on nothing but its own operands.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 
+#include "greedy.h"
 #include "host.h"
 #include "row_dot.h"
 
@@ -32,11 +31,9 @@ namespace xnrs {
 
 namespace {
 
-constexpr int DV_THREADS = 256;  // 4 waves per workgroup
+constexpr int DV_THREADS = GREEDY_THREADS;  // 4 waves per workgroup
 constexpr int DV_WAVES = DV_THREADS / 64;
 constexpr int DV_UNROLL = 8;     // table rows a wave has in flight against the row in LDS
-
-__host__ __device__ __forceinline__ int pad4(int E) { return (E + 3) & ~3; }
 
 // the row in LDS of a workgroup: s_row[0, pad4(E)) = table[row][0, E), zeros behind (every thread of the workgroup calls it)
 __device__ __forceinline__ void stage_row(float* s_row, const float* __restrict__ table, int64_t row, int E) {
@@ -85,145 +82,44 @@ __global__ __launch_bounds__(DV_THREADS) void inv_norms_kernel(const float* __re
 
 // -------------------------------------------------------------------------------------------------------------------- mmr
 struct MmrArgs {
+  GreedyArgs g;
   const float* table;
   const float* inv;
-  int64_t n_rows;
   int E;
-  const int32_t* pool_rows;
-  const float* pool_scores;
-  int P, k;
-  float lam;
-  int rel_mode;
-  int32_t* out_rows;
-  float* out_scores;
-  int32_t* out_pos;
 };
 
-// lam r - (1 - lam) m, two products and one difference, each rounded (no contraction: at lam = 1 it is r exactly)
-__device__ __forceinline__ float mmr_objective(float lam_r, float oml, float m) {
-#pragma clang fp contract(off)
-  const float pen = oml * m;
-  return lam_r - pen;
-}
-// does the candidate (v, i) come before (bv, bi)?  higher objective, then the lower place; (-inf, INT_MAX) is "none"
-__device__ __forceinline__ bool mmr_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-// dynamic LDS of a session, in floats: the selected row, then lam * r, m, inv, row (int32) per place, then the alive bytes
-// (every LDS word of the kernel lies in the dynamic region, every region on 16 bytes)
-constexpr int MMR_SCRATCH = 16;  // floats in front: the waves' argmax values, minima, argmax places
+// dynamic LDS of a session, in floats: the scratch words of the loop, the selected row, then lam * r, m, inv, row (int32) per
+// place, then the alive bytes (every LDS word of the kernel lies in the dynamic region, every region on 16 bytes)
 __host__ __device__ __forceinline__ size_t mmr_lds_bytes(int P, int E) {
-  return (size_t)(MMR_SCRATCH + pad4(E)) * 4 + (size_t)pad4(P) * 16 + (size_t)pad4(P);
+  return (size_t)(GREEDY_SCRATCH + pad4(E)) * 4 + (size_t)pad4(P) * 16 + (size_t)pad4(P);
 }
 
+// the penalty of MMR (greedy.h): m_i, the largest cosine of place i to a selected place
 template <bool VEC>
-__global__ __launch_bounds__(DV_THREADS) void mmr_kernel(MmrArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  const int P = a.P, E = a.E, k = a.k;
-  float* s_wv = reinterpret_cast<float*>(s_raw);
-  float* s_lo = s_wv + DV_WAVES;
-  int* s_wi = reinterpret_cast<int*>(s_lo + DV_WAVES);
-  float* s_sel = s_wv + MMR_SCRATCH;
-  float* s_lr = s_sel + pad4(E);
-  float* s_m = s_lr + pad4(P);
-  float* s_inv = s_m + pad4(P);
-  int* s_row = reinterpret_cast<int*>(s_inv + pad4(P));
-  unsigned char* s_alive = reinterpret_cast<unsigned char*>(s_row + pad4(P));
-  const int64_t b = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t* __restrict__ rows = a.pool_rows + b * (int64_t)P;
-  const float* __restrict__ scores = a.pool_scores + b * (int64_t)P;
+struct MmrPolicy {
+  const float* table;
+  const float* inv;
+  int E, P;
+  float* s_sel;  // the row selected last
+  float* s_m;
+  float* s_inv;
+  int* s_row;
+  const unsigned char* s_alive;
 
-  // the places: valid = a row of the table and a finite score
-  float lo = INFINITY, hi = -INFINITY;
-  for (int i = tid; i < P; i += DV_THREADS) {
-    const int r = rows[i];
-    const float s = scores[i];
-    const bool ok = r >= 0 && r < a.n_rows && fabsf(s) < INFINITY;  // (NaN compares false)
+  __device__ __forceinline__ void stage(int i, int r, bool ok) {
     s_row[i] = ok ? r : -1;
-    s_alive[i] = ok ? 1 : 0;
-    s_lr[i] = ok ? s : 0.f;  // (the score for now)
     s_m[i] = 0.f;
-    s_inv[i] = ok ? a.inv[r] : 0.f;
-    if (ok) {
-      lo = fminf(lo, s);
-      hi = fmaxf(hi, s);
-    }
+    s_inv[i] = ok ? inv[r] : 0.f;
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, m));
-    hi = fmaxf(hi, __shfl_xor(hi, m));
-  }
-  if (lane == 0) {
-    s_lo[wave] = lo;
-    s_wv[wave] = hi;
-  }
-  __syncthreads();
-  lo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
-  hi = fmaxf(fmaxf(s_wv[0], s_wv[1]), fmaxf(s_wv[2], s_wv[3]));
-  const float span = hi - lo;
-  for (int i = tid; i < P; i += DV_THREADS) {  // (a thread rewrites the places it wrote)
-    float r = s_lr[i];
-    if (a.rel_mode == XNRS_MMR_REL_MINMAX) r = span > 0.f ? (r - lo) / span : 0.f;
-    s_lr[i] = a.lam * r;
-  }
-  const float oml = 1.f - a.lam;
-  __syncthreads();
-
-  for (int t = 0; t < k; ++t) {
-    // argmax of the objective over the alive places: ascending places per thread, so `>` keeps the lower of two equals
-    float bv = -INFINITY;
-    int bi = INT_MAX;
-    for (int i = tid; i < P; i += DV_THREADS)
-      if (s_alive[i]) {
-        const float v = mmr_objective(s_lr[i], oml, s_m[i]);
-        if (mmr_before(v, i, bv, bi)) {
-          bv = v;
-          bi = i;
-        }
-      }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float ov = __shfl_xor(bv, m);
-      const int oi = __shfl_xor(bi, m);
-      if (mmr_before(ov, oi, bv, bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      s_wv[wave] = bv;
-      s_wi[wave] = bi;
-    }
-    __syncthreads();
-    bv = s_wv[0];
-    bi = s_wi[0];
-#pragma unroll
-    for (int w = 1; w < DV_WAVES; ++w)
-      if (mmr_before(s_wv[w], s_wi[w], bv, bi)) {
-        bv = s_wv[w];
-        bi = s_wi[w];
-      }
-    if (bi == INT_MAX) {  // no valid place is left (the same for every thread): fillers behind the picks
-      for (int u = t + tid; u < k; u += DV_THREADS) {
-        a.out_rows[b * k + u] = -1;
-        a.out_scores[b * k + u] = -INFINITY;
-        a.out_pos[b * k + u] = -1;
-      }
-      return;
-    }
-    const int sel = s_row[bi];
+  __device__ __forceinline__ void prepare(int) {}
+  __device__ __forceinline__ float penalty(int i) const { return s_m[i]; }
+  // m_i of the alive places against the selected row: wave w takes the groups of DV_UNROLL places w, w + DV_WAVES, ...
+  __device__ __forceinline__ void take(int bi, int t, bool last) {
+    if (last) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float sel_inv = s_inv[bi];
-    if (tid == 0) {
-      a.out_rows[b * k + t] = sel;
-      a.out_scores[b * k + t] = scores[bi];  // the pool's own bits
-      a.out_pos[b * k + t] = bi;
-    }
-    if (t + 1 == k) return;
-    if (tid == 0) s_alive[bi] = 0;  // (the scan of this step lies behind the barrier above; so does every use of the row in LDS)
-    stage_row(s_sel, a.table, sel, E);
+    stage_row(s_sel, table, s_row[bi], E);  // (every use of the row before lies behind the barrier of the argmax)
     __syncthreads();
-    // m_i of the alive places against the selected row: wave w takes the groups of DV_UNROLL places w, w + DV_WAVES, ...
     for (int j0 = wave * DV_UNROLL; j0 < P; j0 += DV_WAVES * DV_UNROLL) {
       int r[DV_UNROLL];
       bool ok[DV_UNROLL];
@@ -238,15 +134,33 @@ __global__ __launch_bounds__(DV_THREADS) void mmr_kernel(MmrArgs a) {
         any |= ok[q];
       }
       if (!any) continue;
-      wave_cos<VEC>(a.table, E, r, ok, ir, s_sel, sel_inv, lane, c);
+      wave_cos<VEC>(table, E, r, ok, ir, s_sel, sel_inv, lane, c);
       if (lane == 0) {
+        float* m = s_m + j0;  // (one address for the group: written as s_m[j0 + q] it is computed again at every use)
 #pragma unroll
         for (int q = 0; q < DV_UNROLL; ++q)
-          if (ok[q]) s_m[j0 + q] = t == 0 ? c[q] : fmaxf(s_m[j0 + q], c[q]);
+          if (ok[q]) m[q] = t == 0 ? c[q] : fmaxf(m[q], c[q]);
       }
     }
     __syncthreads();
   }
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(DV_THREADS) void mmr_kernel(MmrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  const int P = a.g.P, E = a.E;
+  float* s_scratch = reinterpret_cast<float*>(s_raw);
+  float* s_sel = s_scratch + GREEDY_SCRATCH;
+  float* s_lr = s_sel + pad4(E);
+  float* s_m = s_lr + pad4(P);
+  float* s_inv = s_m + pad4(P);
+  int* s_row = reinterpret_cast<int*>(s_inv + pad4(P));
+  unsigned char* s_alive = reinterpret_cast<unsigned char*>(s_row + pad4(P));
+  MmrPolicy<VEC> pol{a.table, a.inv, E, P, s_sel, s_m, s_inv, s_row, s_alive};
+  greedy_stage(a.g, blockIdx.x, s_scratch, s_lr, s_alive, pol);
+  __syncthreads();
+  greedy_loop(a.g, blockIdx.x, s_scratch, s_lr, s_alive, pol);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- ild
@@ -368,7 +282,7 @@ hipError_t launch_mmr_rerank(const float* table, const float* inv, int64_t n_row
                              const float* pool_scores, int64_t B, int P, int k, float lam, int rel_mode, int32_t* out_rows,
                              float* out_scores, int32_t* out_pos, hipStream_t stream) {
   if (B <= 0) return hipSuccess;
-  const MmrArgs a{table, inv, n_rows, E, pool_rows, pool_scores, P, k, lam, rel_mode, out_rows, out_scores, out_pos};
+  const MmrArgs a{{pool_rows, pool_scores, P, k, n_rows, lam, rel_mode, out_rows, out_scores, out_pos}, table, inv, E};
   const size_t lds = mmr_lds_bytes(P, E);
   if (E % 4 == 0 && aligned16(table))
     mmr_kernel<true><<<dim3((unsigned)B), DV_THREADS, lds, stream>>>(a);

@@ -247,31 +247,34 @@ def row_windows(row_time: torch.Tensor, session_time: torch.Tensor, horizon=None
     return lo.to(torch.int32), hi.to(torch.int32)
 
 
-def _recommending_model_parts(model, behaviors: Behaviors, k: int, windowed: bool = False):
-    """(prepare_csr, the scorer's top-k call for this k, user index or None) of a model that can rank the table on its own, or
-    the refusal -- before anything is encoded.  windowed: the call carries row windows, which go through topk_deep."""
+def _recommending_model_parts(model, behaviors: Behaviors, k: int, windowed: bool = False, fn: str = "recommend",
+                              method: str = "topk"):
+    """(prepare_csr, the scorer's `method` call for this k, user index or None) of a model that can rank the table on its own,
+    or the refusal under the name `fn` of the public function called -- before anything is encoded.  method "topk" becomes topk_deep beyond k = 128;
+    windowed: the call carries row windows, which go through topk_deep too."""
     scorer = getattr(model, "rec_model", None)
-    prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, "topk", None)
+    prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, method, None)
     if prepare is None or topk is None:
-        raise NotImplementedError(f"recommend(): the scorer {type(scorer).__name__} has no top-k path over a news table "
-                                  "(prepare_csr / topk); ranking it with a plain dot product would recommend another model's news")
+        raise NotImplementedError(f"{fn}(): the scorer {type(scorer).__name__} has no {method} path over a news table "
+                                  f"(prepare_csr / {method}); ranking it with a plain dot product would recommend another "
+                                  "model's news")
     if getattr(model, "user_dependent_news", False):
-        raise NotImplementedError(f"recommend(): the news vectors of {type(model).__name__} depend on the user, so no table of "
-                                  "news vectors exists to rank; give it a candidate generator -- recommend(model, ..., "
-                                  "generator=a model that ranks the table, pool=...) -- and it re-ranks the generator's list")
-    if k > TOPK_MAX_K or windowed:
-        topk = getattr(scorer, "topk_deep", None)
+        raise NotImplementedError(f"{fn}(): the news vectors of {type(model).__name__} depend on the user, so no table of "
+                                  "news vectors exists to rank; recommend() re-ranks the list of a candidate generator for it "
+                                  "-- recommend(model, ..., generator=a model that ranks the table, pool=...)")
+    if method == "topk" and (k > TOPK_MAX_K or windowed):
+        method, topk = "topk_deep", getattr(scorer, "topk_deep", None)
         if topk is None and not windowed:
-            raise NotImplementedError(f"recommend(): the scorer {type(scorer).__name__} has no topk_deep, so it lists at most "
+            raise NotImplementedError(f"{fn}(): the scorer {type(scorer).__name__} has no topk_deep, so it lists at most "
                                       f"k = {TOPK_MAX_K} news per session, not {k}")
-        if windowed and (topk is None or not _takes_windows(topk)):
-            raise NotImplementedError(f"recommend(windows=...): the topk_deep of the scorer {type(scorer).__name__} takes no "
-                                      "row windows (win_lo, win_hi)")
+    if windowed and (topk is None or not _takes_windows(topk)):
+        raise NotImplementedError(f"{fn}(windows=...): the {method} of the scorer {type(scorer).__name__} takes no "
+                                  "row windows (win_lo, win_hi)")
     uidx = None
     if getattr(model, "uses_user_index", False):
         uidx = getattr(behaviors, "user_index", None)
         if uidx is None:
-            raise ValueError(f"recommend(): {type(model).__name__} needs the user index of every session (sessions without "
+            raise ValueError(f"{fn}(): {type(model).__name__} needs the user index of every session (sessions without "
                              "'user_index': Behaviors.from_sessions keeps it when every session carries it)")
     return prepare, topk, uidx
 
@@ -301,15 +304,12 @@ def _table_topk_batches(model, parts, store: NewsStore, behaviors: Behaviors, l_
         m = hm[hist.long()]
         u = model.encode_user(h, m) if uidx is None else model.encode_user(h, m, uidx[sess])
         excl = _history_csr(behaviors, sess, lo if every else None) if exclude_history else (None, None)
+        noise = () if sample is None else (sample[0], sample[1], sess.contiguous())
+        kw = {} if windows is None else dict(win_lo=windows[0][sess], win_hi=windows[1][sess])
+        out = tuple(topk(table, u, k, *noise, excl[0], excl[1], store.pad_row, **kw))
         if sample is not None:
-            kw = {} if windows is None else dict(win_lo=windows[0][sess].contiguous(), win_hi=windows[1][sess].contiguous())
-            rows, keys = topk(table, u, k, sample[0], sample[1], sess.contiguous(), excl[0], excl[1], store.pad_row, **kw)
-            yield lo, sess, hist, rows, _raw_scores(model.rec_model, table, u, rows), keys
-        elif windows is None:
-            yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row))
-        else:
-            yield (lo, sess, hist) + tuple(topk(table, u, k, excl[0], excl[1], store.pad_row,
-                                                win_lo=windows[0][sess], win_hi=windows[1][sess]))
+            out = (out[0], _raw_scores(model.rec_model, table, u, out[0]), out[1])
+        yield (lo, sess, hist) + out
 
 
 def _raw_scores(scorer, table: torch.Tensor, u: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
@@ -333,6 +333,44 @@ def _rerank(rows: torch.Tensor, r: torch.Tensor, k: int):
     ok = ok.gather(1, idx)
     return (torch.where(ok, rows.gather(1, idx), torch.full_like(idx, -1, dtype=torch.int32)),
             torch.where(ok, r.gather(1, idx), torch.full_like(score[:, :k], float("-inf"))))
+
+
+def _pool_arg(who: str, k: int, pool) -> int:
+    """The list length a re-ranker or a second stage picks k from: k <= pool <= 1024, by default min(1024, max(8 k, 128))."""
+    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
+    if not k <= pool <= TOPK_DEEP_MAX_K:
+        raise ValueError(f"{who}: pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
+    return pool
+
+
+def _pool_batches(model, generator, parts, uidx, store, behaviors, l_hist, n_list, pool, sessions, batch, exclude_history, windows,
+                  vecs_out=None):
+    """Per batch of sessions (lo, sess, rows:(b,n_list), scores:(b,n_list)), best first: the scorer's own list over its table
+    (generator None), or the generator's `pool` best as `model` re-scored them (two stages), in the order of recommend()."""
+    if generator is None:
+        for lo, sess, _, rows, scores in _table_topk_batches(model, parts, store, behaviors, l_hist, n_list, sessions, batch,
+                                                             exclude_history, windows, vecs_out=vecs_out):
+            yield lo, sess, rows, scores
+    else:
+        for lo, sess, cand, r in _two_stage_batches(model, generator, parts, uidx, store, behaviors, l_hist, pool, sessions, batch,
+                                                    exclude_history, windows):
+            yield (lo, sess) + _rerank(cand, r, n_list)
+
+
+def _fill_lists(behaviors: Behaviors, sessions, k: int, batch: int, dtypes, batches):
+    """One (n, k) tensor per dtype on the device, filled from `batches` = (lo, one (b, k) tensor per dtype) in turn; then the
+    status of the device is checked."""
+    n = len(behaviors) if sessions is None else len(sessions)
+    dev = behaviors.hist_off.device
+    outs = tuple(torch.empty((n, k), dtype=t, device=dev) for t in dtypes)
+    for lo, *got in batches:
+        for out, g in zip(outs, got):
+            out[lo:lo + batch] = g
+    hip.check_status(dev)
+    return outs
+
+
+_ROWS_SCORES = (torch.int32, torch.float32)
 
 
 @torch.no_grad()
@@ -372,28 +410,13 @@ def recommend(model, store: NewsStore, behaviors: Behaviors, l_hist: int, k: int
     if generator is None:
         if pool is not None:
             raise ValueError("recommend(): `pool` is the list length of a `generator`; there is none")
-        parts = _recommending_model_parts(model, behaviors, k, windows is not None)
-        n = len(behaviors) if sessions is None else len(sessions)
-        dev = behaviors.hist_off.device
-        windows = _session_windows(windows, behaviors, dev, "recommend()")
-        rows = torch.empty((n, k), dtype=torch.int32, device=dev)
-        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-        for lo, _, _, r, s in _table_topk_batches(model, parts, store, behaviors, l_hist, k, sessions, batch, exclude_history,
-                                                  windows):
-            rows[lo:lo + batch], scores[lo:lo + batch] = r, s
-        hip.check_status(dev)
-        return rows, scores
-    pool, parts, uidx = _two_stage_parts(model, generator, behaviors, k, pool, windows is not None)
-    n = len(behaviors) if sessions is None else len(sessions)
-    dev = behaviors.hist_off.device
-    windows = _session_windows(windows, behaviors, dev, "recommend()")
-    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    for lo, _, cand, r in _two_stage_batches(model, generator, parts, uidx, store, behaviors, l_hist, pool, sessions, batch,
-                                             exclude_history, windows):
-        rows[lo:lo + batch], scores[lo:lo + batch] = _rerank(cand, r, k)
-    hip.check_status(dev)
-    return rows, scores
+        parts, uidx = _recommending_model_parts(model, behaviors, k, windows is not None), None
+    else:
+        pool, parts, uidx = _two_stage_parts(model, generator, behaviors, k, pool, windows is not None)
+    windows = _session_windows(windows, behaviors, behaviors.hist_off.device, "recommend()")
+    return _fill_lists(behaviors, sessions, k, batch, _ROWS_SCORES,
+                       ((lo, r, s) for lo, _, r, s in _pool_batches(model, generator, parts, uidx, store, behaviors, l_hist, k, pool,
+                                                                   sessions, batch, exclude_history, windows)))
 
 
 @torch.no_grad()
@@ -428,35 +451,19 @@ def recommend_sampled(model, store: NewsStore, behaviors: Behaviors, l_hist: int
     if generator is not None:
         raise NotImplementedError("recommend_sampled(generator=...): sampling behind a candidate generator is not implemented")
     scorer = getattr(model, "rec_model", None)
-    prepare, topk = getattr(scorer, "prepare_csr", None), getattr(scorer, "topk_sample", None)
-    if prepare is None or topk is None or getattr(scorer, "score_csr", None) is None:
-        raise NotImplementedError(f"recommend_sampled(): the scorer {type(scorer).__name__} has no sampled top-k path over a news "
-                                  "table (prepare_csr / topk_sample / score_csr)")
-    if getattr(model, "user_dependent_news", False):
-        raise NotImplementedError(f"recommend_sampled(): the news vectors of {type(model).__name__} depend on the user, so no "
-                                  "table of news vectors exists to sample from")
+    if getattr(scorer, "score_csr", None) is None:
+        raise NotImplementedError(f"recommend_sampled(): the scorer {type(scorer).__name__} has no score_csr for the raw scores "
+                                  "of the sampled rows")
     from .models.caum import CAUM
     if isinstance(model, CAUM):
         raise NotImplementedError("recommend_sampled(): CAUM has no candidate-independent user vector to rank a table with")
-    if windows is not None and not _takes_windows(topk):
-        raise NotImplementedError(f"recommend_sampled(windows=...): the topk_sample of the scorer {type(scorer).__name__} takes "
-                                  "no row windows (win_lo, win_hi)")
-    uidx = None
-    if getattr(model, "uses_user_index", False):
-        uidx = getattr(behaviors, "user_index", None)
-        if uidx is None:
-            raise ValueError(f"recommend_sampled(): {type(model).__name__} needs the user index of every session")
-    n = len(behaviors) if sessions is None else len(sessions)
-    dev = behaviors.hist_off.device
-    windows = _session_windows(windows, behaviors, dev, "recommend_sampled()")
-    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    keys = torch.empty((n, k), dtype=torch.float32, device=dev)
-    for lo, _, _, r, s, g in _table_topk_batches(model, (prepare, topk, uidx), store, behaviors, l_hist, k, sessions, batch,
-                                                 exclude_history, windows, sample=(float(temperature), int(seed))):
-        rows[lo:lo + batch], scores[lo:lo + batch], keys[lo:lo + batch] = r, s, g
-    hip.check_status(dev)
-    return (rows, scores, keys) if return_keys else (rows, scores)
+    parts = _recommending_model_parts(model, behaviors, k, windows is not None, "recommend_sampled", "topk_sample")
+    windows = _session_windows(windows, behaviors, behaviors.hist_off.device, "recommend_sampled()")
+    out = _fill_lists(behaviors, sessions, k, batch, _ROWS_SCORES + (torch.float32,),
+                      ((lo, r, s, g) for lo, _, _, r, s, g in
+                       _table_topk_batches(model, parts, store, behaviors, l_hist, k, sessions, batch, exclude_history, windows,
+                                           sample=(float(temperature), int(seed)))))
+    return out if return_keys else out[:2]
 
 
 def _two_stage_parts(model, generator, behaviors: Behaviors, k: int, pool, windowed: bool):
@@ -465,9 +472,7 @@ def _two_stage_parts(model, generator, behaviors: Behaviors, k: int, pool, windo
     if not getattr(model, "user_dependent_news", False) or getattr(model, "score_impressions", None) is None:
         raise NotImplementedError(f"recommend(generator=...): {type(model).__name__} has no score_impressions over news vectors "
                                   "that depend on the user; a model that ranks the table is called without a generator")
-    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
-    if not k <= pool <= TOPK_DEEP_MAX_K:
-        raise ValueError(f"recommend(): pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
+    pool = _pool_arg("recommend()", k, pool)
     parts = _recommending_model_parts(generator, behaviors, pool, windowed)
     uidx = getattr(behaviors, "user_index", None)
     if uidx is None:
@@ -639,26 +644,24 @@ def evaluate_full_ranking(model, store: NewsStore, behaviors: Behaviors, l_hist:
 DIVERSITY_MAX_K = TOPK_MAX_K  # the longest list of xnrs_list_diversity
 
 
-def _diverse_args(who: str, k: int, lam, pool, rel: str):
-    """(k, lam, pool) of an MMR call checked against include/xnrs_hip.h: xnrs_mmr_rerank, or the ValueError; lam None (no
-    re-ranking) passes with pool None."""
+def _rerank_args(who: str, k: int, lam, pool, rel: str, other: str, keep_pool: bool = False):
+    """(k, lam, pool) of a re-ranking call checked against include/xnrs_hip.h: xnrs_mmr_rerank / xnrs_calibrated_rerank, or the
+    ValueError; lam None (no re-ranking) passes, with pool None unless a generator lists the pool (keep_pool).  other: what
+    lam = 0 ranks by alone."""
     from .ops import MMR_REL
     k = int(k)
     if k < 1 or k > TOPK_DEEP_MAX_K:
         raise ValueError(f"{who}: k = {k} must lie in [1, {TOPK_DEEP_MAX_K}], the longest list of the top-k kernels")
     if lam is None:
-        if pool is not None:
-            raise ValueError(f"{who}: `pool` is the list MMR re-ranks; without `lam` nothing is re-ranked")
-        return k, None, None
+        if pool is not None and not keep_pool:
+            raise ValueError(f"{who}: `pool` is the list that is re-ranked; without `lam` nothing is re-ranked")
+        return k, None, pool
     lam = float(lam)
     if not 0.0 <= lam <= 1.0:  # (NaN too)
-        raise ValueError(f"{who}: lam = {lam} must lie in [0, 1] (1: relevance alone, 0: variety alone)")
+        raise ValueError(f"{who}: lam = {lam} must lie in [0, 1] (1: relevance alone, 0: {other} alone)")
     if rel not in MMR_REL:
         raise ValueError(f"{who}: rel is one of {sorted(MMR_REL)}, got {rel!r}")
-    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
-    if not k <= pool <= TOPK_DEEP_MAX_K:
-        raise ValueError(f"{who}: pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
-    return k, lam, pool
+    return k, lam, _pool_arg(who, k, pool)
 
 
 def _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, sessions, batch, exclude_history, windows):
@@ -666,8 +669,8 @@ def _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, 
     re-ranking of the scorer's `pool` best (xnrs_mmr_rerank over the encoded news vectors); inv = their inverse row norms."""
     from . import ops
     got, inv = [], None
-    for lo, sess, _, rows, scores in _table_topk_batches(model, parts, store, behaviors, l_hist, k if lam is None else pool,
-                                                         sessions, batch, exclude_history, windows, vecs_out=got):
+    for lo, sess, rows, scores in _pool_batches(model, None, parts, None, store, behaviors, l_hist, k if lam is None else pool, pool,
+                                                sessions, batch, exclude_history, windows, vecs_out=got):
         if inv is None:
             inv = ops.row_inv_norms(got[0])
         if lam is not None:
@@ -692,18 +695,12 @@ def recommend_diverse(model, store: NewsStore, behaviors: Behaviors, l_hist: int
     form: a model whose news vectors depend on the user (NPA) has no table vectors to compare."""
     if lam is None:
         raise ValueError("recommend_diverse(): lam in [0, 1] is required (recommend() lists by relevance alone)")
-    k, lam, pool = _diverse_args("recommend_diverse()", k, lam, pool, rel)
+    k, lam, pool = _rerank_args("recommend_diverse()", k, lam, pool, rel, "variety")
     parts = _recommending_model_parts(model, behaviors, pool, windows is not None)
-    n = len(behaviors) if sessions is None else len(sessions)
-    dev = behaviors.hist_off.device
-    windows = _session_windows(windows, behaviors, dev, "recommend_diverse()")
-    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    for lo, _, r, s, _, _ in _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel, sessions, batch,
-                                              exclude_history, windows):
-        rows[lo:lo + batch], scores[lo:lo + batch] = r, s
-    hip.check_status(dev)
-    return rows, scores
+    windows = _session_windows(windows, behaviors, behaviors.hist_off.device, "recommend_diverse()")
+    return _fill_lists(behaviors, sessions, k, batch, _ROWS_SCORES,
+                       ((lo, r, s) for lo, _, r, s, _, _ in _diverse_batches(model, parts, store, behaviors, l_hist, k, lam, pool, rel,
+                                                                            sessions, batch, exclude_history, windows)))
 
 
 def _diversity_check(rows: torch.Tensor, who: str):
@@ -798,7 +795,7 @@ def evaluate_diversity(model, store: NewsStore, behaviors: Behaviors, l_hist: in
 
     The sums are added batch by batch: beyond the exposure counts no more than one batch of lists is resident.  k <= 128 (the
     lists go through xnrs_list_diversity); a larger k raises ValueError.  Refusals as recommend(), before anything is encoded."""
-    k, lam, pool = _diverse_args("evaluate_diversity()", k, lam, pool, rel)
+    k, lam, pool = _rerank_args("evaluate_diversity()", k, lam, pool, rel, "variety")
     if k > DIVERSITY_MAX_K:
         raise ValueError(f"evaluate_diversity(): k = {k} is above the longest list of xnrs_list_diversity, {DIVERSITY_MAX_K}")
     parts = _recommending_model_parts(model, behaviors, k if lam is None else pool, windows is not None)
@@ -847,10 +844,7 @@ def _calibrated_args(who: str, behaviors, k: int, lam, pool, rel: str, alpha, ro
     """(k, lam, pool, alpha, n_categories) of a calibration call checked against include/xnrs_hip.h: xnrs_calibrated_rerank, or
     the ValueError; lam None (no re-ranking) passes, with pool None unless a generator lists the pool.  target: "history", a
     (n_categories,) tensor or -- behaviors given -- a (len(behaviors), n_categories) tensor."""
-    from .ops import MMR_REL
-    k = int(k)
-    if k < 1 or k > TOPK_DEEP_MAX_K:
-        raise ValueError(f"{who}: k = {k} must lie in [1, {TOPK_DEEP_MAX_K}], the longest list of the top-k kernels")
+    k, lam, pool = _rerank_args(who, k, lam, pool, rel, "the category mix", two_stage)
     n_categories = int(n_categories)
     if not 1 <= n_categories <= CALIBRATION_MAX_CATEGORIES:
         raise ValueError(f"{who}: n_categories = {n_categories} must lie in [1, {CALIBRATION_MAX_CATEGORIES}]")
@@ -872,18 +866,6 @@ def _calibrated_args(who: str, behaviors, k: int, lam, pool, rel: str, alpha, ro
             raise ValueError(f"{who}: target is a ({n_categories},) tensor of weights or one row per "
                              f"{'session, ' + str(per) if per else 'list'}; got {tuple(getattr(target, 'shape', ()))} "
                              f"{getattr(target, 'dtype', type(target))}")
-    if lam is None:
-        if pool is not None and not two_stage:
-            raise ValueError(f"{who}: `pool` is the list that is re-ranked; without `lam` nothing is re-ranked")
-        return k, None, pool, alpha, n_categories
-    lam = float(lam)
-    if not 0.0 <= lam <= 1.0:  # (NaN too)
-        raise ValueError(f"{who}: lam = {lam} must lie in [0, 1] (1: relevance alone, 0: the category mix alone)")
-    if rel not in MMR_REL:
-        raise ValueError(f"{who}: rel is one of {sorted(MMR_REL)}, got {rel!r}")
-    pool = min(TOPK_DEEP_MAX_K, max(8 * k, TOPK_MAX_K)) if pool is None else int(pool)
-    if not k <= pool <= TOPK_DEEP_MAX_K:
-        raise ValueError(f"{who}: pool = {pool} must lie in [k, {TOPK_DEEP_MAX_K}], k = {k}")
     return k, lam, pool, alpha, n_categories
 
 
@@ -905,15 +887,8 @@ def _calibrated_batches(model, generator, parts, uidx, store, behaviors, l_hist,
     every = sessions is None
     if not isinstance(target, str):
         target = target.to(device=behaviors.hist_off.device, dtype=torch.float32)
-    if generator is None:
-        source = ((lo, sess, r, s) for lo, sess, _, r, s in
-                  _table_topk_batches(model, parts, store, behaviors, l_hist, k if lam is None else pool, sessions, batch,
-                                      exclude_history, windows))
-    else:
-        source = ((lo, sess) + _rerank(cand, r, k if lam is None else pool) for lo, sess, cand, r in
-                  _two_stage_batches(model, generator, parts, uidx, store, behaviors, l_hist, pool, sessions, batch,
-                                     exclude_history, windows))
-    for lo, sess, rows, scores in source:
+    for lo, sess, rows, scores in _pool_batches(model, generator, parts, uidx, store, behaviors, l_hist, k if lam is None else pool,
+                                                pool, sessions, batch, exclude_history, windows):
         if isinstance(target, str):  # the mix of the session's FULL history, the one exclude_history excludes
             off, val = _history_csr(behaviors, sess, lo if every else None)
             tgt = ops.csr_category_counts(off.contiguous(), val, row_category, n_categories, store.pad_row).float()
@@ -969,15 +944,10 @@ def recommend_calibrated(model, store: NewsStore, behaviors: Behaviors, l_hist: 
     k, lam, pool, alpha, n_categories, parts, uidx, windows, row_category = _calibrated_parts(
         "recommend_calibrated()", model, store, behaviors, k, lam, pool, rel, alpha, row_category, n_categories, target, windows,
         generator)
-    n = len(behaviors) if sessions is None else len(sessions)
-    dev = behaviors.hist_off.device
-    rows = torch.empty((n, k), dtype=torch.int32, device=dev)
-    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    for lo, _, r, s, _ in _calibrated_batches(model, generator, parts, uidx, store, behaviors, l_hist, k, lam, pool, rel, alpha,
-                                              row_category, n_categories, target, sessions, batch, exclude_history, windows):
-        rows[lo:lo + batch], scores[lo:lo + batch] = r, s
-    hip.check_status(dev)
-    return rows, scores
+    return _fill_lists(behaviors, sessions, k, batch, _ROWS_SCORES,
+                       ((lo, r, s) for lo, _, r, s, _ in
+                        _calibrated_batches(model, generator, parts, uidx, store, behaviors, l_hist, k, lam, pool, rel, alpha,
+                                            row_category, n_categories, target, sessions, batch, exclude_history, windows)))
 
 
 def _calibration_sums(rows, row_category, n_categories: int, target: torch.Tensor, pad_row: int, alpha: float) -> torch.Tensor:

@@ -978,17 +978,46 @@ def row_inv_norms(vecs: torch.Tensor):
     return inv
 
 
+def _lists(rows, what: str):
+    """The (B, n) int32 check of every list operand: candidate lists and recommended lists."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2:
+        raise RuntimeError(f"{what}: a (B, n) int32 tensor, one list of rows per session; got "
+                           f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+
+
+def _row_categories(row_category, dev):
+    if not isinstance(row_category, torch.Tensor) or row_category.dtype != torch.int32 or row_category.dim() != 1:
+        raise RuntimeError(f"row categories: a (n_rows,) int32 tensor, one category per table row; got "
+                           f"{tuple(getattr(row_category, 'shape', ()))} {getattr(row_category, 'dtype', type(row_category))}")
+    if row_category.device != dev or not row_category.is_contiguous():
+        raise hip.XnrsHipError(f"row categories must be a contiguous tensor on {dev}")
+
+
+def _pool_scores(who: str, pool_scores, pool_rows, rel: str):
+    """(the checked candidate scores of the checked candidate lists, the code of `rel`) of a re-ranker."""
+    if rel not in MMR_REL:
+        raise ValueError(f"{who}: rel is one of {sorted(MMR_REL)}, got {rel!r}")
+    pool_scores = hip.dev_f32(pool_scores, "candidate scores")
+    if tuple(pool_scores.shape) != tuple(pool_rows.shape) or pool_scores.device != pool_rows.device:
+        raise RuntimeError(f"candidate scores {tuple(pool_scores.shape)} on {pool_scores.device} do not match the candidate lists "
+                           f"{tuple(pool_rows.shape)} on {pool_rows.device}")
+    return pool_scores, MMR_REL[rel]
+
+
+def _picks(B: int, k: int, dev):
+    """The (rows, scores, pos) outputs of a re-ranker."""
+    return tuple(torch.empty((B, max(k, 0)), dtype=t, device=dev) for t in (torch.int32, torch.float32, torch.int32))
+
+
 def _diversity_operands(vecs, inv, rows, what: str):
-    """The checked table, norms and (B, n) int32 lists of xnrs_mmr_rerank / xnrs_list_diversity."""
+    """The checked table, norms and lists of xnrs_mmr_rerank / xnrs_list_diversity."""
     vecs = hip.dev_f32(vecs, "news vectors")
     if vecs.dim() != 2:
         raise RuntimeError(f"news vectors: a (n_rows, E) table, got {tuple(vecs.shape)}")
     inv = hip.dev_f32(inv, "inverse row norms")
     if inv.dim() != 1 or inv.numel() != vecs.shape[0]:
         raise RuntimeError(f"inverse row norms: one per table row ({vecs.shape[0]},), got {tuple(inv.shape)} (row_inv_norms(vecs))")
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2:
-        raise RuntimeError(f"{what}: a (B, n) int32 tensor, one list of rows per session; got "
-                           f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    _lists(rows, what)
     if rows.device != vecs.device or inv.device != vecs.device or not rows.is_contiguous():
         raise hip.XnrsHipError(f"{what} and the inverse row norms must be contiguous tensors on {vecs.device}")
     return vecs, inv
@@ -1001,18 +1030,11 @@ def mmr_rerank(vecs, inv, pool_rows, pool_scores, k: int, lam: float, rel: str =
     the pool; -1 / -inf / -1 once the valid places run out.  pool_rows:(B,P) int32 (-1: empty), pool_scores:(B,P) fp32, e.g.
     what topk_deep_* returned; inv = row_inv_norms(vecs); rel "minmax" (per-session min-max of the valid scores) or "raw"."""
     vecs, inv = _diversity_operands(vecs, inv, pool_rows, "candidate lists")
-    if rel not in MMR_REL:
-        raise ValueError(f"mmr_rerank(): rel is one of {sorted(MMR_REL)}, got {rel!r}")
-    pool_scores = hip.dev_f32(pool_scores, "candidate scores")
-    if tuple(pool_scores.shape) != tuple(pool_rows.shape) or pool_scores.device != vecs.device:
-        raise RuntimeError(f"candidate scores {tuple(pool_scores.shape)} on {pool_scores.device} do not match the candidate lists "
-                           f"{tuple(pool_rows.shape)} on {vecs.device}")
+    pool_scores, rel = _pool_scores("mmr_rerank()", pool_scores, pool_rows, rel)
     (B, P), k, dev = pool_rows.shape, int(k), vecs.device
-    rows = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    rows, scores, pos = _picks(B, k, dev)
     hip.check(hip.lib().xnrs_mmr_rerank(hip.ptr(vecs), hip.ptr(inv), vecs.shape[0], vecs.shape[1], hip.ptr(pool_rows),
-                                        hip.ptr(pool_scores), B, P, k, float(lam), MMR_REL[rel], hip.ptr(rows), hip.ptr(scores),
+                                        hip.ptr(pool_scores), B, P, k, float(lam), rel, hip.ptr(rows), hip.ptr(scores),
                                         hip.ptr(pos), hip.stream_ptr(dev)), "xnrs_mmr_rerank")
     return rows, scores, pos
 
@@ -1025,12 +1047,9 @@ def list_diversity(vecs, inv, rows, row_category=None, n_categories: int = 0):
     vecs, inv = _diversity_operands(vecs, inv, rows, "lists")
     (B, k), dev = rows.shape, vecs.device
     if row_category is not None:
-        if not isinstance(row_category, torch.Tensor) or row_category.dtype != torch.int32 or row_category.dim() != 1 \
-                or row_category.numel() != vecs.shape[0]:
-            raise RuntimeError(f"row categories: a ({vecs.shape[0]},) int32 tensor, one category per table row; got "
-                               f"{tuple(getattr(row_category, 'shape', ()))} {getattr(row_category, 'dtype', type(row_category))}")
-        if row_category.device != dev or not row_category.is_contiguous():
-            raise hip.XnrsHipError(f"row categories must be a contiguous tensor on {dev}")
+        _row_categories(row_category, dev)
+        if row_category.numel() != vecs.shape[0]:
+            raise RuntimeError(f"row categories: one per table row ({vecs.shape[0]},), got {tuple(row_category.shape)}")
     ild = torch.empty((B,), dtype=torch.float32, device=dev)
     n = torch.empty((B,), dtype=torch.int32, device=dev)
     n_cat = None if row_category is None else torch.empty((B,), dtype=torch.int32, device=dev)
@@ -1042,11 +1061,9 @@ def list_diversity(vecs, inv, rows, row_category=None, n_categories: int = 0):
 
 
 def _calibration_operands(rows, row_category, n_categories: int, target, what: str):
-    """The checked (B, n) int32 lists, (n_rows,) int32 categories and (B, n_categories) fp32 target mix of
-    xnrs_calibrated_rerank / xnrs_list_calibration -> the target as a contiguous fp32 tensor."""
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2:
-        raise RuntimeError(f"{what}: a (B, n) int32 tensor, one list of rows per session; got "
-                           f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    """The checked lists, (n_rows,) int32 categories and (B, n_categories) fp32 target mix of xnrs_calibrated_rerank /
+    xnrs_list_calibration -> the target as a contiguous fp32 tensor."""
+    _lists(rows, what)
     if not rows.is_cuda:
         raise hip.XnrsHipError(f"{what}: tensor is on {rows.device}; xnrs_amd runs on a HIP device only (there is no CPU fallback)")
     _row_categories(row_category, rows.device)
@@ -1056,14 +1073,6 @@ def _calibration_operands(rows, row_category, n_categories: int, target, what: s
     if target.device != rows.device or not rows.is_contiguous():
         raise hip.XnrsHipError(f"{what} and the target mix must be contiguous tensors on {rows.device}")
     return target
-
-
-def _row_categories(row_category, dev):
-    if not isinstance(row_category, torch.Tensor) or row_category.dtype != torch.int32 or row_category.dim() != 1:
-        raise RuntimeError(f"row categories: a (n_rows,) int32 tensor, one category per table row; got "
-                           f"{tuple(getattr(row_category, 'shape', ()))} {getattr(row_category, 'dtype', type(row_category))}")
-    if row_category.device != dev or not row_category.is_contiguous():
-        raise hip.XnrsHipError(f"row categories must be a contiguous tensor on {dev}")
 
 
 def csr_category_counts(off, rows, row_category, n_categories: int, pad_row: int = -1):
@@ -1097,20 +1106,13 @@ def calibrated_rerank(pool_rows, pool_scores, k: int, lam: float, row_category, 
     miscalibration of the final list (0 for a session whose target has no positive weight).  pool_rows:(B,P) int32,
     pool_scores:(B,P) fp32, e.g. what topk_deep_* returned; row_category:(n_rows,) int32, target:(B, n_categories) weights."""
     target = _calibration_operands(pool_rows, row_category, n_categories, target, "candidate lists")
-    if rel not in MMR_REL:
-        raise ValueError(f"calibrated_rerank(): rel is one of {sorted(MMR_REL)}, got {rel!r}")
-    pool_scores = hip.dev_f32(pool_scores, "candidate scores")
-    if tuple(pool_scores.shape) != tuple(pool_rows.shape) or pool_scores.device != pool_rows.device:
-        raise RuntimeError(f"candidate scores {tuple(pool_scores.shape)} on {pool_scores.device} do not match the candidate lists "
-                           f"{tuple(pool_rows.shape)} on {pool_rows.device}")
+    pool_scores, rel = _pool_scores("calibrated_rerank()", pool_scores, pool_rows, rel)
     (B, P), k, dev = pool_rows.shape, int(k), pool_rows.device
-    rows = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    pos = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    rows, scores, pos = _picks(B, k, dev)
     kl = torch.empty((B,), dtype=torch.float32, device=dev)
     hip.check(hip.lib().xnrs_calibrated_rerank(hip.ptr(pool_rows), hip.ptr(pool_scores), B, P, k, hip.ptr(row_category),
                                                row_category.numel(), int(n_categories), hip.ptr(target), float(lam), float(alpha),
-                                               MMR_REL[rel], hip.ptr(rows), hip.ptr(scores), hip.ptr(pos), hip.ptr(kl),
+                                               rel, hip.ptr(rows), hip.ptr(scores), hip.ptr(pos), hip.ptr(kl),
                                                hip.stream_ptr(dev)), "xnrs_calibrated_rerank")
     return rows, scores, pos, kl
 
