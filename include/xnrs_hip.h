@@ -979,6 +979,63 @@ int32_t xnrs_list_loss_bwd(const float *table, int64_t n_rows, int32_t E, const 
                            int32_t pad_row, const float *scores, const float *lse, const float *neg_scores, const float *g,
                            const int32_t *order, float *d_up, float *d_table, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- the soft-target loss over per-user row LISTS: distilling a re-ranker, graded labels (csrc/list_loss.hip) ---------------
+ * The listwise loss whose target is a DISTRIBUTION over the listed rows instead of one click: the cross-entropy between
+ * the per-slot weights a caller gives (the softmax of a teacher's scores: distillation; graded labels: ListNet) and the
+ * softmax of the user's own scores over the same slots.  Forward and backward, without a (B, L, E) copy of the listed rows.
+ * Operands: table:(n_rows,E), up:(B,E) as the score reads it, bias: one float on the device or NULL, pad_row -- as
+ * xnrs_list_loss_* -- plus rows:(B,L) int32 and weights:(B,L) fp32, both row-major.  There are no queries.
+ *   Filled slot: slot (b, j) is FILLED when 0 <= rows[b][j] < n_rows and the row is not pad_row.  Every other slot is EMPTY:
+ *              the -1 fillers of xnrs_topk_deep, ids outside the table, the pad row; its row is compared, never
+ *              dereferenced, its weight is ignored (it may be anything, NaN included), slot_scores holds NaN there.  A ROW
+ *              LISTED TWICE IS TWO SLOTS.  Unlike xnrs_list_loss_* nothing else empties a slot: a click is a row like any other.
+ *   Weights  : must be finite on the filled slots; they need not sum to 1 and may be 0 (or negative).
+ *   Forward  : s_bj = <table[row], up[b]> (+ bias), the dot chain of xnrs_list_loss_fwd; slot_scores[b][j] = s_bj.
+ *              lse[b] = log sum_{filled} exp(s_bj), max-stabilised, -inf when b has no filled slot.  With W_b = sum_{filled}
+ *              w_bj: loss[b] = sum_{filled} w_bj (lse[b] - s_bj), summed in THIS form term by term (never W_b lse - sum w s,
+ *              which cancels at large scores), in the fixed slot tree of the sum exp; a term's lse[b] - s_bj is evaluated as
+ *              (m - s_bj) + log sum exp(s - m), m the largest score, so the rounding of lse to the ulp of m does not enter;
+ *              and that log as log(c) + log1p(r / c), c the number of slots at the maximum and r the sum over the others, so a
+ *              sum of 1 + a little is not rounded to the ulp of 1 (the loss of a confident user IS that little).
+ *              With W_b = 1 it is the cross-entropy of the target distribution against softmax(s).
+ *   Zero cases: a user with no filled slot, or with all weights 0, has loss = 0 exactly and every gradient exactly 0; no NaN.
+ *              L == 0: every user is one.
+ *   Backward : g:(B) the upstream gradient per user, p_bj = exp(s_bj - lse[b]); d s_bj = g[b] (W_b p_bj - w_bj) per filled
+ *              slot; d_up[b] = sum_j d s_bj * table[row]; d_table[n] = sum over the slots whose row is n of d s_bj * up[b].
+ *              d_up:(B,E) and d_table:(n_rows,E) are OVERWRITTEN (rows that nothing lists are exactly zero); either may be
+ *              NULL, and then its launches are skipped.  lse and slot_scores are what the forward call over the same
+ *              operands wrote.  bias shifts every score of a user alike and gets no gradient.
+ *   order    : (B L) int32, NULL iff d_table is NULL (one without the other: XNRS_EINVAL): the slots -- slot (b, j) is entry
+ *              b L + j -- sorted ascending by row, ties in ascending entry index, the empty slots (NaN in slot_scores) behind
+ *              all others: the order of xnrs_list_loss_bwd with no queries (xnrs_amd/ops.py: list_xent_order).  A value
+ *              outside [0, B L) is skipped and never dereferenced.  An order that is NOT grouped by row gives unspecified
+ *              gradients for the rows concerned and nothing worse: no access outside the operands.
+ *   Precondition: table and up are finite; B L <= 2^31 - 1 and n_rows <= 2^31 - 1 (else XNRS_EINVAL).
+ * Launches: forward 1 (a workgroup of four waves per user: the gather walk of xnrs_list_loss_fwd, then max, sum exp and the
+ * weighted sum over the slots).  d_up 1 (W_b in the slot tree, then the same walk, d s * table[row] summed per wave in slot
+ * order, the four waves in wave order).  d_table 4 (W_b per user; the zero fill; the walk and the join of
+ * xnrs_list_loss_bwd -- the same two kernels, only the decode of a sorted position into (row, user, d s) differs).
+ * Determinism: loss, lse, slot_scores and d_up of a user are the same bits on every run and depend neither on B nor on the
+ * user's position in the batch: one workgroup owns the user and every reduction tree is fixed by the slot position.
+ * d_table is the same bits on every run of the same call; its summation order follows the sorted order and the span cut, so
+ * it MAY differ in the last bits between batches.  The 16-byte and the scalar load forms add the same elements in the same
+ * order: the alignment of an operand does not change a bit.  No float atomics, results cross launches at kernel boundaries
+ * only, no host synchronisation, no allocation, hipGraph-capturable.  XNRS_EINVAL (L < 0, E < 1, a NULL required pointer,
+ * order and d_table not NULL together) and XNRS_EWORKSPACE are found on the host before any launch and write nothing.
+ * B == 0: XNRS_OK, nothing written.  Any E >= 1, any operand alignment its element type allows (E % 4 != 0 or a base off the
+ * 16-byte boundary takes scalar loads).  The user vector sits in LDS up to 4096 floats and is read from global memory beyond.
+ * ws: xnrs_list_xent_workspace_bytes(B, L, E, want_d_table), a pure host call: 0 for the forward and for d_up alone (ws may
+ * then be NULL); with d_table 4 B + 8 G E + 8 G bytes, G = max(1, min(8192, ceil(B L / 64))), each of the five regions (W_b,
+ * head rows, tail rows, head row ids, tail row ids) rounded up to 256 B. */
+size_t xnrs_list_xent_workspace_bytes(int64_t B, int32_t L, int32_t E, int32_t want_d_table);
+int32_t xnrs_list_xent_fwd(const float *table, int64_t n_rows, int32_t E, const float *up, const float *bias, int64_t B,
+                           const int32_t *rows, const float *weights, int32_t L, int32_t pad_row, float *loss, float *lse,
+                           float *slot_scores, void *ws, size_t ws_bytes, void *stream);
+int32_t xnrs_list_xent_bwd(const float *table, int64_t n_rows, int32_t E, const float *up, const float *bias, int64_t B,
+                           const int32_t *rows, const float *weights, int32_t L, int32_t pad_row, const float *lse,
+                           const float *slot_scores, const float *g, const int32_t *order, float *d_up, float *d_table,
+                           void *ws, size_t ws_bytes, void *stream);
+
 /* ---- diverse lists: MMR re-ranking and intra-list distance over the table's own vectors (csrc/diversity.hip) ---------------
  * Beyond-accuracy measures of a recommended list, and the re-ranking that trades relevance for variety.  Both rest on ONE
  * similarity of two rows a, b of table:(n_rows,E) fp32 (the encoded news vectors, not a scorer's prepared table):

@@ -954,6 +954,44 @@ def list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias):
     return _ListLoss.apply(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)
 
 
+class _ListXent(torch.autograd.Function):
+    """ops.list_xent: the soft-target loss over per-user row lists (xnrs_list_xent_fwd / _bwd).  What is saved beside the
+    operands is per user and per slot -- lse and the slot scores, never the listed rows."""
+
+    @staticmethod
+    def forward(ctx, table, up, rows, weights, pad_row, bias):
+        from . import ops
+        table = hip.dev_f32(table, "news vectors")
+        up_shape = tuple(up.shape)
+        up = hip.dev_f32(up, "user vectors").reshape(-1, table.shape[-1])
+        weights = weights.detach()
+        with torch.no_grad():
+            loss, lse, slot_scores = ops.list_xent_forward(table, up, rows, weights, pad_row, bias)
+        ctx.save_for_backward(table, up, lse, slot_scores)
+        ctx.rest = (rows, weights, int(pad_row), None if bias is None else bias.detach())
+        ctx.up_shape = up_shape
+        ctx.is_tensor = [isinstance(t, torch.Tensor) for t in (table, up, rows, weights, pad_row, bias)]
+        ctx.mark_non_differentiable(lse, slot_scores)
+        return loss, lse, slot_scores
+
+    @staticmethod
+    def backward(ctx, g, _g_lse, _g_slots):
+        from . import ops
+        table, up, lse, slot_scores = ctx.saved_tensors
+        rows, weights, pad_row, bias = ctx.rest
+        wanted = _wanted_inputs(ctx, ctx.is_tensor, 0)  # (torch.autograd.grad(inputs=[u]) alone: the table's launches are not run)
+        d_up, d_table = ops.list_xent_backward(table, up, rows, weights, pad_row, bias, lse, slot_scores, g,
+                                               want_d_up=ctx.needs_input_grad[1] and wanted[1],
+                                               want_d_table=ctx.needs_input_grad[0] and wanted[0])
+        if d_up is not None:
+            d_up = d_up.reshape(ctx.up_shape)
+        return d_table, d_up, None, None, None, None
+
+
+def list_xent(table, up, rows, weights, pad_row, bias):
+    return _ListXent.apply(table, up, rows, weights, pad_row, bias)
+
+
 class _BilinScoring(torch.autograd.Function):
     """BilinScoring (scoring.py:41-66): backward G_b = sum_n g_bn c^_bn, dW[0] = U^^T G, du^_b = W[0] G_b, dc^_bn = g_bn v_b,
     dbias = sum g (then through the normalisation when it is on)."""

@@ -836,6 +836,30 @@ def _list_accuracy_dict(acc: torch.Tensor, k: int) -> Dict[str, float]:
     return {f"hit@{k}": hits / max(nq, 1.0), f"ndcg@{k}": dcg / max(nq, 1.0), "n_queries": int(nq)}
 
 
+LIST_RECALL_CHUNK = 1 << 24  # most elements of the (sessions, k, P) comparison that exist at once
+
+
+def list_recall(found_rows: torch.Tensor, wanted_rows: torch.Tensor) -> torch.Tensor:
+    """Per session the share of its wanted rows:(n, k) that its other list found_rows:(n, P) holds -> (n,) fp32 on the lists'
+    device.  Only rows >= 0 count (-1 is the filler of both lists); a session that wants nothing gets 0.  What a two-stage
+    list is judged by -- how much of the re-ranker's top k the candidate generator's pool of P contains (found = the
+    generator's pool, wanted = the re-ranker's list) -- and what losses.distillation_loss is there to raise.  Device
+    arithmetic, in chunks of sessions so that no comparison array beyond LIST_RECALL_CHUNK elements exists."""
+    if found_rows.dim() != 2 or wanted_rows.dim() != 2 or found_rows.shape[0] != wanted_rows.shape[0]:
+        raise ValueError(f"list_recall(): two lists per session, (n, P) and (n, k); got {tuple(found_rows.shape)} and "
+                         f"{tuple(wanted_rows.shape)}")
+    n, P = found_rows.shape
+    k = wanted_rows.shape[1]
+    out = torch.zeros((n,), dtype=torch.float32, device=wanted_rows.device)
+    step = max(1, LIST_RECALL_CHUNK // max(1, k * P))
+    for lo in range(0, n, step):
+        want, found = wanted_rows[lo:lo + step], found_rows[lo:lo + step]
+        asked = want >= 0
+        hit = (want[:, :, None] == found[:, None, :]).any(dim=2) & asked
+        out[lo:lo + step] = hit.sum(dim=1).float() / asked.sum(dim=1).clamp(min=1).float()
+    return out
+
+
 # -------------------------------------------------------------------------------------------- calibrated recommendations
 CALIBRATION_MAX_CATEGORIES = hip._CONSTANTS["DIVERSITY_MAX_CATEGORIES"]  # include/xnrs_hip.h
 

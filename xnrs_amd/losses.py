@@ -277,6 +277,153 @@ def mined_negatives_loss(model, store_or_table, behaviors, sessions, l_hist: int
     return mine_and_rank(scorer, vecs, u, excl, tgt, pad_row, n_negatives, win, reduction, neg_rows, return_negatives)
 
 
+def _list_xent_scorer(scorer, who: str):
+    fn = getattr(scorer, "list_xent", None)
+    if fn is None:
+        raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no soft-target loss over listed rows of a "
+                                  "news table (list_xent); training it with a plain dot product would train another model")
+    return fn
+
+
+def listed_soft_target_loss(scorer, table: torch.Tensor, u: torch.Tensor, rows: torch.Tensor, weights: torch.Tensor,
+                            pad_row: int = -1, reduction: str = "mean") -> torch.Tensor:
+    """The listwise loss against SOFT targets: per user the cross-entropy between the weights:(B, L) float32 a caller gives
+    the rows:(B, L) int32 the user lists and the softmax of the user's scores over the same slots (include/xnrs_hip.h:
+    xnrs_list_xent_fwd) -- sum over the filled slots of w (lse - s).  Teacher scores through a softmax give distillation,
+    graded labels ListNet.  A slot counts when its row is inside the table and not pad_row; -1 fillers and everything else
+    are empty slots whose weight is ignored; a row listed twice is two slots.  `scorer`: a DotScoring or BilinScoring
+    (scorer.list_xent); differentiable in `table`, `u` and the scorer's weight, without a copy of the listed rows.
+    reduction 'mean' divides by the number of users with a filled slot, counted on the device (at least 1); 'sum'; 'none':
+    the loss per user."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"reduction {reduction!r}: 'mean', 'sum' or 'none'")
+    fn = _list_xent_scorer(scorer, "listed_soft_target_loss()")
+    loss, lse = fn(table, u, rows, weights, pad_row)[:2]
+    return _reduce_per_user(loss, lse, reduction)
+
+
+def _reduce_per_user(loss: torch.Tensor, lse: torch.Tensor, reduction: str) -> torch.Tensor:
+    if reduction == "none":
+        return loss
+    if reduction == "sum":
+        return loss.sum()
+    return loss.sum() / torch.isfinite(lse).sum().clamp(min=1).to(loss.dtype)
+
+
+def _teacher_kind(teacher, who: str) -> str:
+    """'table': a teacher that ranks a table of news vectors with its own user vector; 'impressions': one whose news vectors
+    depend on the user and that scores listed impressions (NPA).  Anything else (CAUM) is refused."""
+    if getattr(teacher, "user_dependent_news", False):
+        if callable(getattr(teacher, "score_impressions", None)):
+            return "impressions"
+    else:
+        scorer = getattr(teacher, "rec_model", None)
+        if callable(getattr(scorer, "prepare_csr", None)) and callable(getattr(scorer, "score_csr", None)):
+            return "table"
+    raise NotImplementedError(f"{who}: the teacher {type(teacher).__name__} neither scores listed rows of a news table with a "
+                              "user vector of its own (prepare_csr / score_csr of a dot, bilinear or fc scorer) nor has "
+                              "score_impressions over news vectors that depend on the user")
+
+
+def _teacher_scores(teacher, kind: str, store, behaviors, sess, l_hist: int, rows: torch.Tensor, teacher_table, t_uidx):
+    """(B, L) raw scores the teacher gives the listed rows of each session, under no_grad; the score of an empty place (-1)
+    means nothing."""
+    from . import evaluation as EV
+    B, L = rows.shape
+    dev = rows.device
+    hist = EV.DeviceBatcher(behaviors, l_hist, store.pad_row).eval_batch(sess)[0]
+    csess = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(L)
+    spare = store.pad_row if store.pad_row >= 0 else 0  # what stands in for an empty place
+    crows = torch.where(rows >= 0, rows, torch.full_like(rows, spare)).reshape(-1)
+    if kind == "impressions":
+        return teacher.score_impressions(store, hist, crows, csess, t_uidx.to(dev)[sess], relu=False).reshape(B, L)
+    vecs, hm = EV.encode_news_table(teacher, store) if teacher_table is None else teacher_table
+    h, m = vecs[hist.long()], hm[hist.long()]
+    u = teacher.encode_user(h, m) if t_uidx is None else teacher.encode_user(h, m, t_uidx.to(dev)[sess])
+    scorer = teacher.rec_model
+    return scorer.score_csr(scorer.prepare_csr(vecs), crows, csess, u, relu=False).reshape(B, L)
+
+
+def soft_targets(teacher_scores: torch.Tensor, filled: torch.Tensor, temperature: float = 1.0):
+    """softmax(teacher_scores / temperature) over the filled slots -> (weights:(B, L) float32 with 0 in the empty slots and
+    all zeros for a session without a filled slot, entropy:(B,) of those weights); no NaN."""
+    z = (teacher_scores.float() / temperature).masked_fill(~filled, float("-inf"))
+    z = z - z.max(dim=1, keepdim=True).values.clamp(min=torch.finfo(torch.float32).min)  # (-inf - -inf never happens)
+    e = torch.where(filled, z.exp(), torch.zeros_like(z))
+    w = e / e.sum(dim=1, keepdim=True).clamp(min=torch.finfo(torch.float32).tiny)
+    entropy = -(w * torch.where(w > 0, w.log(), torch.zeros_like(w))).sum(dim=1)
+    return w.contiguous(), entropy
+
+
+def distillation_loss(student, teacher, store_or_table, behaviors, sessions, l_hist: int, pool: int = 128,
+                      temperature: float = 1.0, exclude_history: bool = True, windows=None, reduction: str = "mean", store=None,
+                      rows=None, teacher_table=None, return_lists: bool = False):
+    """Distil a re-ranker into its candidate generator: per session KL(teacher || student) between the two models' softmax
+    distributions over the `pool` rows the STUDENT lists for the session, so that the student's pool comes to hold what the
+    teacher would put on top.  The path is that of mined_negatives_loss() up to the user vectors (same arguments, the
+    student's refusals raised before anything is encoded); then
+
+      the pool    : without `rows`, the student's topk_deep(pool) under no_grad over the detached table and user vectors,
+                    excluding the pad row and (`exclude_history`) the session's full history, inside its window (`windows`).
+                    The session's clicks are NOT excluded: they are what both models should rank high.  1 <= pool <= 1024.
+      the teacher : scores exactly those rows under no_grad.  A teacher that ranks a table (a dot, bilinear or fc scorer:
+                    prepare_csr / score_csr) encodes its own user vector from the same history batch and scores the rows of
+                    ITS table -- encoded here, or given as teacher_table=(vecs, hm) as encode_news_table returns it: a
+                    teacher is normally frozen, so encode its table ONCE and pass it to every step.  A teacher whose news
+                    vectors depend on the user (NPA: user_dependent_news and score_impressions) scores the rows as the second
+                    stage of recommend(generator=...) does; it needs a NewsStore and behaviors.user_index.
+      the targets : softmax(teacher scores / temperature) over the filled slots, 0 in the empty ones.
+      the loss    : the scorer's list_xent (xnrs_list_xent_fwd / _bwd: no copy of the listed rows) with the student's user
+                    vector divided by `temperature` (its logits are its scores / temperature; a bias cancels), minus the
+                    targets' entropy, which is constant in the student: KL per session, >= 0 up to rounding.
+
+    reduction 'mean' divides by the number of sessions with a filled slot.  rows: a (len(sessions), L) int32 tensor of table
+    rows skips the mining; return_lists=True returns (loss, rows) with the lists that were used -- one mining pass then
+    serves this loss and mined_negatives_loss(neg_rows=...) in the same step (the mining is what such a step costs most).
+    Raised before anything is encoded: everything mined_negatives_loss() refuses for the student; a temperature that is not
+    a finite number above 0; a pool outside [1, 1024]; a teacher of neither kind (CAUM: no user vector of its own and no
+    score_impressions)."""
+    import math
+    who = "distillation_loss()"
+    scorer, uidx = _refuse_before_encoding(student, behaviors, reduction, who, _list_xent_scorer, "soft-target loss over listed rows")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"{who}: temperature = {temperature!r}: a finite number above 0")
+    n_sessions = int(torch.as_tensor(sessions).numel())
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[0] != n_sessions:
+            raise ValueError(f"{who}: rows is a ({n_sessions}, L) int32 tensor, one list of table rows per session; got "
+                             f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    else:
+        if isinstance(pool, bool) or int(pool) != pool or not 1 <= int(pool) <= 1024:
+            raise ValueError(f"{who}: pool = {pool!r}: an integer in [1, 1024], the list lengths of topk_deep")
+        if getattr(scorer, "topk_deep", None) is None:
+            raise NotImplementedError(f"{who}: the scorer {type(scorer).__name__} has no topk_deep to list a pool with")
+    kind = _teacher_kind(teacher, who)
+    the_store = store if isinstance(store_or_table, (tuple, list)) else store_or_table
+    if the_store is None:
+        raise ValueError(f"{who}: a pre-encoded table comes with store= (its pad row and the history batcher's)")
+    t_uidx = None
+    if kind == "impressions" or getattr(teacher, "uses_user_index", False):
+        t_uidx = getattr(behaviors, "user_index", None)
+        if t_uidx is None:
+            raise ValueError(f"{who}: the teacher {type(teacher).__name__} needs the user index of every session (sessions "
+                             "without 'user_index': Behaviors.from_sessions keeps it when every session carries it)")
+    vecs, u, excl, _, win, pad_row = _encode_sessions(student, store_or_table, behaviors, sessions, l_hist, exclude_history,
+                                                      windows, store, uidx, who)
+    dev = vecs.device
+    sess = torch.as_tensor(sessions, dtype=torch.int64, device=dev).reshape(-1)
+    with torch.no_grad():
+        if rows is None:
+            kw = {} if win[0] is None else dict(win_lo=win[0], win_hi=win[1])
+            rows = scorer.topk_deep(vecs.detach(), u.detach(), int(pool), excl[0], excl[1], pad_row, **kw)[0]
+        filled = (rows >= 0) & (rows < vecs.shape[0]) & (rows != pad_row)
+        t = _teacher_scores(teacher, kind, the_store, behaviors, sess, l_hist, rows, teacher_table, t_uidx)
+        weights, entropy = soft_targets(t, filled, float(temperature))
+    xent, lse = _list_xent_scorer(scorer, who)(vecs, u * (1.0 / float(temperature)), rows, weights, pad_row)[:2]
+    loss = _reduce_per_user(xent - entropy, lse, reduction)
+    return (loss, rows) if return_lists else loss
+
+
 def _gather_rows(vecs: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
     """vecs[hist]: through the project's row gather when the table carries a gradient (its backward scatters on the HIP
     path), a plain index otherwise."""

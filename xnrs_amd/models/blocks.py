@@ -265,6 +265,14 @@ class DotScoring(nn.Module):
                                       "product only")
         return ops.list_loss(table, u, tgt_off, tgt_rows, neg_rows, pad_row)
 
+    def list_xent(self, table: torch.Tensor, u: torch.Tensor, rows, weights, pad_row: int = -1):
+        """The soft-target loss over the rows each user lists: the cross-entropy of the slot weights against the softmax of
+        the user's scores over the same slots (ops.list_xent) -> (loss, lse, slot_scores), differentiable in `table` and `u`."""
+        if self.normalize:
+            raise NotImplementedError("DotScoring.list_xent with normalize=True: the soft-target listed loss implements the "
+                                      "raw inner product only")
+        return ops.list_xent(table, u, rows, weights, pad_row)
+
 
 class BilinScoring(nn.Module):
     """Reference: scoring.py:41-66.  nn.Bilinear(E, E, 1, bias) registered as `bilin`; u:(B,1,E), c:(B,N,E) -> (B,N,1) =
@@ -332,6 +340,16 @@ class BilinScoring(nn.Module):
         E = self.bilin.weight.shape[-1]
         v = ops.linear(u.reshape(-1, E), self.bilin.weight[0].t())  # v_b = W[0]^T u_b
         return ops.list_loss(table, v, tgt_off, tgt_rows, neg_rows, pad_row, bias=self.bilin.bias)
+
+    def list_xent(self, table: torch.Tensor, u: torch.Tensor, rows, weights, pad_row: int = -1):
+        """As DotScoring.list_xent with the score u W[0] table[row] + bias: v = u W[0] through ops.linear, as in list_loss,
+        so that autograd reaches W and u; the bias is passed for the score bits and gets no gradient."""
+        if self.normalize:
+            raise NotImplementedError("BilinScoring.list_xent with normalize=True: the soft-target listed loss implements "
+                                      "the raw bilinear form only")
+        E = self.bilin.weight.shape[-1]
+        v = ops.linear(u.reshape(-1, E), self.bilin.weight[0].t())  # v_b = W[0]^T u_b
+        return ops.list_xent(table, v, rows, weights, pad_row, bias=self.bilin.bias)
 
 
 def _is_tanh(activation) -> bool:

@@ -83,6 +83,7 @@ class CAUMScoring(DotScoring):
     rank = None
     table_loss = None
     list_loss = None
+    list_xent = None
 
 
 class CAUMNewsEncoder(nn.Module):

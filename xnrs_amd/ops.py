@@ -963,6 +963,102 @@ def list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row: int = -1, bias=No
     return autograd.list_loss(table, up, tgt_off, tgt_rows, neg_rows, pad_row, bias)
 
 
+def _list_xent_check(table, up, rows, weights):
+    """What can be refused before anything touches the device: the table's shape, the lists and their weights."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError(f"news vectors: a (n_rows, E) table, got {tuple(getattr(table, 'shape', ()))}")
+    E = table.shape[1]
+    if not isinstance(up, torch.Tensor) or up.shape[-1:] != (E,):
+        raise RuntimeError(f"user vectors: (..., {E}) as the table's rows, got {tuple(getattr(up, 'shape', ()))}")
+    B = up.numel() // E
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[0] != B:
+        raise RuntimeError(f"row lists: a ({B}, L) int32 tensor, one list of rows per user; got "
+                           f"{tuple(getattr(rows, 'shape', ()))} {getattr(rows, 'dtype', type(rows))}")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(rows.shape):
+        raise RuntimeError(f"slot weights: a {tuple(rows.shape)} float32 tensor, one weight per slot; got "
+                           f"{tuple(getattr(weights, 'shape', ()))} {getattr(weights, 'dtype', type(weights))}")
+    if B * rows.shape[1] > 2 ** 31 - 1:
+        raise RuntimeError(f"row lists: {B} x {rows.shape[1]} slots, more than 2^31 - 1")
+    for t, what in ((rows, "row lists"), (weights, "slot weights")):
+        if t.device != table.device or not t.is_contiguous():
+            raise hip.XnrsHipError(f"{what} must be a contiguous tensor on {table.device}")
+
+
+def _list_xent_args(table, up, rows, weights, bias):
+    """The checked operands of xnrs_list_xent_fwd / _bwd -> (table, up, B, L, head, keep), as _list_loss_args."""
+    _list_xent_check(table, up, rows, weights)
+    table = hip.dev_f32(table, "news vectors")
+    n_rows, E = table.shape
+    up = hip.dev_f32(up, "user vectors").reshape(-1, E)
+    bias = None if bias is None else hip.dev_f32(bias, "score bias").reshape(-1)[:1]
+    B, L = up.shape[0], rows.shape[1]
+    head = (hip.ptr(table), n_rows, E, hip.ptr(up), hip.ptr(bias), B, hip.ptr(rows), hip.ptr(weights), L)
+    return table, up, B, L, head, (bias,)
+
+
+def list_xent_forward(table, up, rows, weights, pad_row: int = -1, bias=None):
+    """xnrs_list_xent_fwd -> (loss:(B,), lse:(B,), slot_scores:(B,L))."""
+    table, up, B, L, head, keep = _list_xent_args(table, up, rows, weights, bias)
+    dev = table.device
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    lse = torch.empty((B,), dtype=torch.float32, device=dev)
+    slot_scores = torch.empty((B, L), dtype=torch.float32, device=dev)
+    l = hip.lib()
+    nbytes = l.xnrs_list_xent_workspace_bytes(B, L, table.shape[1], 0)
+    ws = hip.workspace(dev, nbytes)
+    hip.check(l.xnrs_list_xent_fwd(*head, int(pad_row), hip.ptr(loss), hip.ptr(lse), hip.ptr(slot_scores), hip.ptr(ws), nbytes,
+                                   hip.stream_ptr(dev)), "xnrs_list_xent_fwd")
+    del keep  # (held until here)
+    return loss, lse, slot_scores
+
+
+def list_xent_order(n_rows: int, rows, slot_scores):
+    """The `order` operand of xnrs_list_xent_bwd: the B L slots stably sorted by row, the empty ones (NaN in slot_scores)
+    behind all others -- list_loss_order without queries."""
+    none = rows.new_zeros((0,))
+    return list_loss_order(n_rows, none, rows, slot_scores.new_zeros((0,)), slot_scores)
+
+
+def list_xent_backward(table, up, rows, weights, pad_row, bias, lse, slot_scores, g, want_d_up: bool = True,
+                       want_d_table: bool = True):
+    """xnrs_list_xent_bwd -> (d_up or None, d_table or None): a gradient that is not wanted is not computed (and without
+    d_table no order is sorted)."""
+    table, up, B, L, head, keep = _list_xent_args(table, up, rows, weights, bias)
+    dev = table.device
+    g = hip.dev_f32(g, "upstream gradient").reshape(-1)
+    if g.numel() != B or lse.numel() != B or tuple(slot_scores.shape) != (B, L):
+        raise RuntimeError(f"list xent backward: g and lse have one entry per user ({B}), slot_scores one per slot ({B}, {L}); "
+                           f"got {g.numel()}, {lse.numel()}, {tuple(slot_scores.shape)}")
+    if not (want_d_up or want_d_table):
+        return None, None
+    d_up = torch.empty_like(up) if want_d_up else None
+    d_table = torch.empty_like(table) if want_d_table else None
+    order = list_xent_order(table.shape[0], rows, slot_scores) if want_d_table else None
+    l = hip.lib()
+    nbytes = l.xnrs_list_xent_workspace_bytes(B, L, table.shape[1], int(want_d_table))
+    ws = hip.workspace(dev, nbytes)
+    hip.check(l.xnrs_list_xent_bwd(*head, int(pad_row), hip.ptr(lse), hip.ptr(slot_scores), hip.ptr(g), hip.ptr(order),
+                                   hip.ptr(d_up), hip.ptr(d_table), hip.ptr(ws), nbytes, hip.stream_ptr(dev)),
+              "xnrs_list_xent_bwd")
+    del keep  # (held until here)
+    return d_up, d_table
+
+
+def list_xent(table, up, rows, weights, pad_row: int = -1, bias=None):
+    """The soft-target listwise loss: the cross-entropy between the weights a caller gives the rows each user LISTS and the
+    softmax of the user's scores over the same slots (include/xnrs_hip.h: xnrs_list_xent_fwd) -> (loss:(B,), lse:(B,),
+    slot_scores:(B,L)).  rows:(B, L) int32, weights:(B, L) float32.  A slot is filled when its row is inside the table and
+    not pad_row; every other slot (the -1 fillers of topk_deep, foreign ids, the pad row) is empty: NaN in slot_scores, its
+    weight ignored.  A row listed twice is two slots.  loss[b] = sum over filled slots of w (lse[b] - s): with weights
+    that sum to 1 the cross-entropy of that distribution against softmax(s) (teacher scores: distillation; graded labels:
+    ListNet).  A user without a filled slot (lse -inf) or with all weights 0 has loss 0 and no gradient.  Differentiable
+    in `table` and `up` (a gradient that nobody asks for is not computed); weights, lse and slot_scores carry no gradient,
+    and neither does `bias`, which shifts every score of a user alike."""
+    from . import autograd
+    _list_xent_check(table, up, rows, weights)
+    return autograd.list_xent(table, up, rows, weights, pad_row, bias)
+
+
 MMR_REL = {"raw": hip._CONSTANTS["MMR_REL_RAW"], "minmax": hip._CONSTANTS["MMR_REL_MINMAX"]}  # include/xnrs_hip.h
 
 
