@@ -1,4 +1,4 @@
-"""The list launch of a dense encoder call, one pass spread over several workgroups (batch.hip dense_row_lists_kernel).
+"""The list launch of a dense encoder call, one pass spread over several workgroups (row_lists.hip dense_row_lists_kernel).
 
 A pass is cut into slices of 64 news, a workgroup each; a slice finds its place in the pass's live-row list by counting the
 live tokens of the news before it, and the workgroup of the pass's last slice writes the counts and the tile list.  The
@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 DEV = L.DEV
 D, A = L.D, L.A
 BM = 128      # tile height of the tile list (kernels.h LIVE_TILE_BM)
-SLICE = 64    # news per workgroup of the list launch (batch.hip DL_SLICE)
+SLICE = 64    # news per workgroup of the list launch (row_lists.hip DL_SLICE)
 ON = L.ON
 DENSE = L.DENSE
 

@@ -408,9 +408,9 @@ def test_compact_rows_kernel_over_three_rounds_of_1024_news(chunk):
 
 @pytest.mark.parametrize("tower", ["additive_only", "attention"])
 def test_row_list_kernels_for_short_titles_over_three_rounds_of_1024_news(tower):
-    """The same 2 100 news in one pass at S = 20 through compact_rows64_kernel<false> (the device-compacted encoder) and
-    compact_rows64_kernel<true> + list_live_tiles (the dense passes with their row lists on): lists on == lists off bit for
-    bit with the workspace filled with 0xFF bytes first; the compacted call within 2e-6 of it; both meet the fp64 oracle."""
+    """The same 2 100 news in one pass at S = 20 through compact_rows64_kernel (the device-compacted encoder) and
+    dense_row_lists_kernel + list_live_tiles (the dense passes with their row lists on; row_lists.hip): lists on == lists off
+    bit for bit with the workspace filled with 0xFF bytes first; the compacted call within 2e-6 of it; both meet the fp64 oracle."""
     n, S, h = 2100, 20, 2
     att = layers.MultiHeadAttention(h, PF_D) if tower == "attention" else None
     enc, sd = load(news_encoding.TextEncoder(pooler=layers.AdditiveAttention(PF_D, PF_A), p_dropout=0.0, out_features=PF_E,

@@ -41,7 +41,7 @@ its predicate tests -> where an ABI caller can reach it ("ws" = a region of the 
   tk_vec_ok (sweep.h: sweep_operands)      table / P, up rows through tk_load (sweep.h) / tl_load (table_loss.hip) | both, each on its own | top-k, rank,
       table loss.  Outputs, w, w1, bias: 4 bytes at a time.
   gru.hip:327                              w_hh, h0 (load_k4) | both, Hd % 4 | xnrs_gru_fwd*; the backward reads ws only
-  batch.hip:235 / 291 / 369                table / x and out rows | both, row width | xnrs_gather_rows, _dropout_rows, *_bf16
+  gather.hip:49 / 105 / 183                table / x and out rows | both, row width | xnrs_gather_rows, _dropout_rows, *_bf16
   personalized.hip:434                     d_table (zero_fill f32x4) | d_table | xnrs_embedding_grad_sparse
   caum.hip, scorers.hip, infonce.hip, pool_score.hip   no 8 / 16-byte global access (grep, confirmed by reading): one
       "all shifted" case each below, through the models that run them and the raw dot / InfoNCE / CSR / long-attention calls.

@@ -1,8 +1,8 @@
 // The library's own state and bookkeeping behind the C ABI (include/xnrs_hip.h): version, build id, error and status
 // strings, the development knobs, the forward-GEMM mode and the launch timer.  Every other extern "C" entry point sits
 // beside the code it drives: encoder_fwd.hip (the three forward pipelines, the fold), encoder_bwd.hip (training forward
-// and backward, linear backward), scorers.hip, infonce.hip, batch.hip, pool_score.hip / pool_bwd.hip (dot scoring),
-// personalized.hip; host.h holds what they share.
+// and backward, linear backward), scorers.hip, infonce.hip, batch.hip, gather.hip, row_lists.hip, pool_score.hip /
+// pool_bwd.hip (dot scoring), personalized.hip; host.h holds what they share.
 //
 // No entry point allocates device memory or synchronises: everything is enqueued on the caller's stream into the
 // caller's workspace (hipGraph-capturable) -- or, for the backward's weight gradients, on a side stream forked from and
@@ -12,7 +12,8 @@
 //     xnrs_reload_knobs): gemm_f32.hip;
 //   - the optional launch timer (xnrs_profile_*, mutex-guarded, off by default): here; host.h's ProfScope only tests its mask;
 //   - the backward's side stream and events, one set per device (mutex-guarded): encoder_bwd.hip;
-//   - the caller's sticky status word (xnrs_set_status_word): batch.hip.
+//   - the caller's sticky status word (xnrs_set_status_word): here, read by the launchers through status_word().
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -52,6 +53,25 @@ int64_t xnrs::prof_count(int stage, const int64_t* cnt, int which, int64_t host_
   if (hipStreamSynchronize(stream) != hipSuccess) return host_value;
   if (hipMemcpy(&v, cnt + which, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return host_value;
   return v;
+}
+
+// ---- the caller's sticky status word (kernels.h)
+// ONE word, on the device that was current when it was registered: a launch on another device gets nullptr (its kernels must
+// not be handed a pointer into this device's memory; their NaN outputs remain the signal there)
+static std::atomic<int32_t*> g_status_word{nullptr};
+static std::atomic<int> g_status_device{-1};
+int32_t* xnrs::status_word() {
+  int32_t* w = g_status_word.load(std::memory_order_relaxed);
+  if (!w) return nullptr;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != g_status_device.load(std::memory_order_relaxed)) return nullptr;
+  return w;
+}
+void xnrs::set_status_word(int32_t* w) {
+  int dev = -1;
+  (void)hipGetDevice(&dev);
+  g_status_device.store(w ? dev : -1, std::memory_order_relaxed);
+  g_status_word.store(w, std::memory_order_relaxed);
 }
 
 extern "C" {

@@ -472,7 +472,7 @@ __device__ __forceinline__ float drop_uniform(const Args& a, int64_t seq, int hd
   x ^= (uint32_t)(z >> 32);
   return (float)(x >> 8) * (1.0f / 16777216.0f);
 }
-// The input dropout of a tower (batch.hip: dropout_rows_kernel) draws from the same stream with ONE "head": the pair is
+// The input dropout of a tower (gather.hip: dropout_rows_kernel) draws from the same stream with ONE "head": the pair is
 // row i of the call, and element j < 2^32 of the row stands where the attention kernels pass query * S + key.
 struct DropRowsArgs {
   uint64_t seed;
@@ -676,7 +676,7 @@ hipError_t launch_collapse_mask(const float* m, const int32_t* gather_ids, float
 hipError_t launch_dot_scoring(const float* u, const float* c, float* r, int64_t B, int32_t C, int32_t E,
                               int32_t normalize, hipStream_t stream);
 
-// ---------------------------------------------------------------- device-side batch assembly / evaluation
+// ---------------------------------------------------------------- device-side batch assembly / evaluation (batch.hip)
 struct BatchArgs {
   const int64_t* sess;       // [B] session (impression) indices
   const int64_t* hist_off;   // CSR offsets [n_sess+1] and values (table rows) of the click histories
@@ -695,6 +695,14 @@ struct BatchArgs {
   int32_t* cand_sess_out;    // eval: [n_cand] impression index of every candidate
   float* targets_out;        // eval: [n_cand]
 };
+hipError_t launch_assemble_train(const BatchArgs& a, hipStream_t stream);
+hipError_t launch_assemble_eval(const BatchArgs& a, hipStream_t stream);
+hipError_t launch_score_csr(const float* vecs, const int32_t* rows, const int32_t* sess, const float* u, float* r, int64_t n,
+                            int E, int relu, hipStream_t stream);
+hipError_t launch_rank_metrics(const float* score, const float* target, const int64_t* off, float* out, int64_t B,
+                               hipStream_t stream);
+
+// ---------------------------------------------------------------- row gathers out of the news table (gather.hip)
 // out[i, :] = table[ids[i], :] for rows of row_floats floats (whole news blocks)
 hipError_t launch_gather_rows(const float* table, const int32_t* ids, float* out, int64_t n, int64_t row_floats,
                               hipStream_t stream);
@@ -705,38 +713,40 @@ hipError_t launch_gather_rows_bf16(const unsigned short* table, const int32_t* i
 // ... and with the towers' input dropout in the same launch: the keep mask of launch_dropout_rows for the same (seed, row, column)
 hipError_t launch_dropout_rows_bf16(const unsigned short* table, const int32_t* ids, float* out, int64_t n, int64_t row_elems, float p,
                                     uint64_t seed, const uint64_t* seed_dev, hipStream_t stream);
-hipError_t launch_poison(float* y, int64_t n, const int64_t* flags, int n_flags, int flag_stride, hipStream_t stream);
-// the caller's sticky device status word (xnrs_set_status_word; nullptr = none): kernels OR XNRS_STATUS_* bits into it when
-// they meet a violated precondition that no host code could check without a synchronisation
-int32_t* status_word();
-void set_status_word(int32_t* w);
-// live-row / kept-K|V-row lists + CSR offsets of every pass of `chunk` news, built on the device in one launch (batch.hip):
-// pass p writes row_off[p*(chunk+1) ..], the lists at [p*chunk*S ..], kv_block[p*chunk ..], counts[3*p ..]
+
+// ---------------------------------------------------------------- row lists from a token mask (row_lists.hip; its header
+// says which encoder route reads which list)
+// live-row / kept-K|V-row lists + CSR offsets of every pass of `chunk` news, built on the device in one launch
+// (compact_rows64_kernel for S <= 64, else compact_rows_kernel): pass p writes row_off[p*(chunk+1) ..], the lists at
+// [p*chunk*S ..], kv_block[p*chunk ..], counts[3*p ..]
 hipError_t launch_compact_rows(const float* mask, const int32_t* ids, int64_t n_news, int64_t chunk, int S, int64_t* row_off,
                                int32_t* live_src, int32_t* kv_src, int32_t* kv_block, int64_t* counts, hipStream_t stream);
-// the grad step's row lists built on the device (batch.hip): live[<= n_seq*L] unmasked token rows, kv[<= n_seq*L] all token
-// rows of the sequences with at least one unmasked token, both in row order; *_src (nullable, with ids): the same tokens'
-// rows in the gathered table; counts[0] = live rows, counts[1] = kv rows; cnt_scratch: int32 [n_seq]
+// NaN over y[0 .. n) -- and XNRS_STATUS_NONBINARY_MASK into the status word -- if one of the n_flags flags (flag_stride
+// apart: counts[3*p + 2] of launch_compact_rows) is set
+hipError_t launch_poison(float* y, int64_t n, const int64_t* flags, int n_flags, int flag_stride, hipStream_t stream);
+// the grad step's row lists built on the device (row_counts_kernel + row_lists_kernel): live[<= n_seq*L] unmasked token rows,
+// kv[<= n_seq*L] all token rows of the sequences with at least one unmasked token, both in row order; *_src (nullable, with
+// ids): the same tokens' rows in the gathered table; counts[0] = live rows, counts[1] = kv rows; cnt_scratch: int32 [n_seq]
 hipError_t launch_build_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int L, int32_t* live, int32_t* live_src,
                                   int32_t* kv, int32_t* kv_src, int64_t* counts, int32_t* cnt_scratch, hipStream_t stream);
-// the live row tiles of every dense encoder pass of `chunk` sequences, built on the device in one launch (batch.hip): pass p
-// writes n_tiles[p] and its ascending tile list at tiles[p * live_tiles_cap(chunk, L, BM) ..]; alive: n_seq bytes of scratch
+// the live row tiles of every dense encoder pass of `chunk` sequences, built on the device in one launch (live_tiles_kernel):
+// pass p writes n_tiles[p] and its ascending tile list at tiles[p * live_tiles_cap(chunk, L, BM) ..]; alive: n_seq bytes of scratch
 constexpr int LIVE_TILE_BM = 128;  // the forward GEMM's main tile height (GemmArgs::live_tiles launches take that tile)
 inline int64_t live_tiles_cap(int64_t chunk, int L, int BM) { return (chunk * L + BM - 1) / BM; }
 hipError_t launch_live_tiles(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM, uint8_t* alive,
                              int64_t* n_tiles, int32_t* tiles, hipStream_t stream);
-// launch_live_tiles AND the live rows of every dense pass in ONE launch (L <= 64; batch.hip dense_row_lists_kernel): pass p
+// launch_live_tiles AND the live rows of every dense pass in ONE launch (L <= 64; dense_row_lists_kernel): pass p
 // writes counts[3 * p] = its unmasked token rows (mask != 0) and their ascending list at [p * chunk * L ..] -- live_loc in the
 // pass's own row space (news j of the pass, token s: j * L + s), live_src (written only with ids) as rows of the gathered table
 hipError_t launch_dense_row_lists(const float* mask, const int32_t* ids, int64_t n_seq, int64_t chunk, int L, int BM,
                                   int32_t* live_loc, int32_t* live_src, int64_t* counts, uint8_t* alive, int64_t* n_tiles,
                                   int32_t* tiles, hipStream_t stream);
-hipError_t launch_assemble_train(const BatchArgs& a, hipStream_t stream);
-hipError_t launch_assemble_eval(const BatchArgs& a, hipStream_t stream);
-hipError_t launch_score_csr(const float* vecs, const int32_t* rows, const int32_t* sess, const float* u, float* r, int64_t n,
-                            int E, int relu, hipStream_t stream);
-hipError_t launch_rank_metrics(const float* score, const float* target, const int64_t* off, float* out, int64_t B,
-                               hipStream_t stream);
+
+// ---------------------------------------------------------------- the caller's sticky device status word (api.hip)
+// (xnrs_set_status_word; nullptr = none): kernels OR XNRS_STATUS_* bits into it when they meet a violated precondition
+// that no host code could check without a synchronisation
+int32_t* status_word();
+void set_status_word(int32_t* w);
 
 // ---------------------------------------------------------------- bilinear / MLP scorers (scorers.hip; scoring.py:41-102)
 // one row-major block of a fixed-order column sum: out[j] = sum_r X[r * ld + j], j < ncol (out nullable: skipped)
